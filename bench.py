@@ -26,6 +26,10 @@ replay batches.  Contract: python bench.py --gpus N --steps K --warmup W  ->  ON
               SURVEY 8(d) per update over the measured update time against 8 TB/s.
               `traffic` is replayed from a committed --pmc measurement of the same command (`traffic_replayed`: true).
   cpu_baseline = the CPU oracle (oracle/drq_oracle.py, kind "port") on the host cores, rank 0, N=1 only.
+  --full    the measurements beside `value` (roofline, scaling_base, weak, n1_same_workload, the exposed exchange
+              wait, cpu_baseline) take runs of their own and are made only with --full; a plain run sets up, warms
+              up, times the K steps and prints the line.
+  --dump-outputs DIR  after the timed steps, what the last timed update computed, as .npy files (dump_outputs()).
 """
 import argparse
 import json
@@ -80,9 +84,15 @@ def parse_args(argv=None):
                     help="bf16: BASELINE configs[4] -- conv2..4 and the fc GEMMs of the update on the bf16 MFMA (fp32 "
                          "accumulation and storage).  New functionality, never the headline line: use with "
                          "--task humanoid_run --batch 2048")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip scaling_base / weak / n1_same_workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, scaling_base / weak / n1_same_workload, the exposed exchange wait and "
+                         "cpu_baseline (separate runs after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the metrics and parameters of the last timed update to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip roofline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip scaling_base / weak / n1_same_workload / the exposed exchange wait")
     ap.add_argument("--host-batch", action="store_true",
                     help="the replay iterator yields pinned HOST tensors (the reference boundary): every update "
                          "pays the H2D copy of its batch.  Reported for DESIGN.md section 6; never the headline value")
@@ -93,7 +103,10 @@ def parse_args(argv=None):
                          "materialises the batch first (the round-2 form)")
     ap.add_argument("--dp-schedule", action="store_true",
                     help="development: run the data-parallel schedule on a one-rank RCCL group (N=1 only)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -307,6 +320,8 @@ def main():
     main_run = Runner(task, B_local, B_global, dev, rank, world, use_dp, args.exchange, args.host_batch,
                       args.device_replay, args.dtype)
     res = main_run.run(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(main_run.agent, res["last_metrics"], args.dump_outputs)
     dt = res.pop("dt")
     out = {
         "metric": "agent updates/sec (batch=256, 9x84x84 obs)", "value": res["value"], "unit": "updates/s",
@@ -329,23 +344,24 @@ def main():
         out["exchange"] = {"mode": ex.mode, "choice_by_bucket_floats": {str(k): v for k, v in ex.choice.items()},
                            "measured_us_by_bucket_floats": {str(k): v for k, v in ex.timings_us.items()}}
 
-    if not args.no_roofline and args.dtype == "f32":
+    if args.full and not args.no_roofline and args.dtype == "f32":
         # every rank runs it (the updates inside carry the data-parallel collectives); rank 0 reports
         roof = roofline_conv(main_run.agent, B_local, main_run.it, main_run.step, A, F)
         roof["frac_whole_step"] = frac_whole
         main_run.agent.flush()
         if rank == 0:
             out["roofline"] = roof
-    elif not args.no_roofline:
+    elif args.full and not args.no_roofline:
         if rank == 0:
             out["roofline"] = roofline_hbm(main_run.agent, task, B_local, A, res["ms_per_step"], args.dtype)
-    if use_dp and world > 1 and not args.no_extras:
+    if args.full and use_dp and world > 1 and not args.no_extras:
         exposed = exposed_exchange_us(main_run)
         if rank == 0 and exposed is not None:
             out.setdefault("exchange", {})["exposed_us_per_update"] = exposed
     main_run.close()
 
-    extras = not (args.no_extras or args.host_batch or args.device_replay or args.dp_schedule or args.dtype != "f32")
+    extras = args.full and not (args.no_extras or args.host_batch or args.device_replay or args.dp_schedule
+                                or args.dtype != "f32")
     k2, w2 = max(20, args.steps // 2), max(5, args.warmup // 2)
     if extras and world == 1 and workload == "config2" and args.task is None:
         # first point of the configs[3] scaling curve, on the same box in the same run
@@ -374,7 +390,7 @@ def main():
                                        "steps": k2, "warmup": w2}
             r.close()
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(task, B_local)
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
@@ -384,6 +400,32 @@ def main():
             dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_MAX_ELEMS = 1 << 20          # per tensor; larger ones are written as a fixed, seeded sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(agent, metrics, out_dir):
+    """--dump-outputs: what the last timed update() handed its caller, so that two builds can be compared output for
+    output on the same inputs.  <metric>.npy: each metric update() returned (float64 scalar); <net>.<param>.npy: the
+    encoder, actor, critic and critic_target parameters that update left behind (float32).  A tensor of more than
+    DUMP_MAX_ELEMS elements (the 39200 x feature_dim trunk weights) is written as the elements at DUMP_MAX_ELEMS sorted
+    indices drawn with seed 0, the same indices in every run; about 35 MB in all at every task."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in metrics.items()}
+    for net in ("encoder", "actor", "critic", "critic_target"):
+        for k, t in getattr(agent, net).state_dict().items():
+            a = t.detach().float().cpu().numpy().ravel()
+            if a.size > DUMP_MAX_ELEMS:
+                a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+            arrays[f"{net}.{k}"] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernel_traffic(name="kernel_traffic.json"):
