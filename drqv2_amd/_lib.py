@@ -109,20 +109,15 @@ class DrqError(RuntimeError):
     pass
 
 
-def load(dev=False):
-    """Returns the loaded library; raises if it has not been built (python -m drqv2_amd.build).
-    dev=True (tools/ only, must be the first load of the process): the -DDRQ_DEV build with the timing ablations
-    and time-stamp hooks (python -m drqv2_amd.build --dev); the product path never asks for it."""
+def load():
+    """Returns the loaded library; raises if it has not been built (python -m drqv2_amd.build)."""
     global _lib
     if _lib is not None:
-        if dev and not hasattr(_lib, "drq_dev_conv_variant"):
-            raise DrqError("the product library is already loaded in this process; load(dev=True) must come first")
         return _lib
-    path = os.path.join(HERE, "libdrqv2_hip_dev.so") if dev else LIB_PATH
-    if not os.path.exists(path):
-        raise DrqError(f"{path} is missing: build it with `python -m drqv2_amd.build{' --dev' if dev else ''}` "
+    if not os.path.exists(LIB_PATH):
+        raise DrqError(f"{LIB_PATH} is missing: build it with `python -m drqv2_amd.build` "
                        "(hipcc --offload-arch=gfx950).  The DrQ-v2 update path has no fallback.")
-    lib = C.CDLL(path)
+    lib = C.CDLL(LIB_PATH)
     for name, (res, args) in PROTOTYPES.items():
         fn = getattr(lib, name)       # AttributeError = ABI mismatch, also loud
         fn.restype = res

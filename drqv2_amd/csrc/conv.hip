@@ -23,7 +23,6 @@
 // registers.  Partials: 4 waves -> LDS -> one record per workgroup -> fixed-order reduction kernel
 // (deterministic, no float atomics).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -38,18 +37,11 @@ struct ConvArgs {
   int nb;
   int relu;
   int wmode;           // 0 forward gather, 1 dgrad gather (transposed + flipped)
-  unsigned long long* stamps;   // development only (ABL & 4): per-wave s_memtime stamps, 32 per wave
 };
 
-#ifdef DRQ_DEV   // development build only (tools/): per-wave time stamps, see drq_dev_* at the end of the file
-unsigned long long* g_conv_stamps = nullptr;
-int g_conv_variant = -1;          // drq_dev_conv_variant overrides DRQ_CONV_VARIANT
-#endif
-
 // BLK = workgroups per CU the kernel is tuned for (8 waves each): 2 -> 4 waves/SIMD (<=128 VGPR)
-// ABL (development only): 1 = skip the input loads, 2 = skip the LDS weight reads, 3 = both (timing ablations)
 // MASK: the epilogue multiplies by (mask > 0) (dgrad through the ReLU of the layer below)
-template <int CIN, int HIN, int STRIDE, int BLK, int TPW, int ABL = 0, bool MASK = false>
+template <int CIN, int HIN, int STRIDE, int BLK, int TPW, bool MASK = false>
 __global__ __launch_bounds__(512, 2 * BLK) void conv3x3_kernel(ConvArgs a) {
   constexpr int CP = (CIN + 1) / 2;
   constexpr int NS = CP * 9;                 // MFMA steps per tile
@@ -61,24 +53,6 @@ __global__ __launch_bounds__(512, 2 * BLK) void conv3x3_kernel(ConvArgs a) {
 
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
-  unsigned long long* stamp = nullptr;
-  int nstamp = 0;
-  auto mark = [&]() {
-    if constexpr (ABL & 4) {
-      if (stamp && nstamp < 30 && lane == 0) stamp[nstamp] = __builtin_amdgcn_s_memtime();
-      ++nstamp;
-    }
-  };
-  if constexpr (ABL & 4) {
-    if (a.stamps) {
-      stamp = a.stamps + ((size_t)blockIdx.x * 8 + wid) * 32;
-      if (lane == 0) {
-        stamp[30] = __builtin_amdgcn_s_memrealtime();
-        stamp[31] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID, all 32 bits
-      }
-    }
-  }
-  mark();
   const int col = lane & 31;   // MFMA: A row (cout) for the weights, B column (pixel) for the input
   const int half = lane >> 5;  // k parity -> channel parity
 
@@ -109,7 +83,6 @@ __global__ __launch_bounds__(512, 2 * BLK) void conv3x3_kernel(ConvArgs a) {
   }
   if (threadIdx.x < 32) bl[threadIdx.x] = a.bias ? a.bias[threadIdx.x] : 0.f;
   __syncthreads();
-  mark();
 
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
@@ -143,12 +116,6 @@ __global__ __launch_bounds__(512, 2 * BLK) void conv3x3_kernel(ConvArgs a) {
     // (3x fewer vector-memory instructions than per-tap dword loads; the TA was the limiter)
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
-      if constexpr (ABL & 1) {
-        dst[ky * 3 + 0] = __uint_as_float(voff + cbase);
-        dst[ky * 3 + 1] = __uint_as_float(voff + ky);
-        dst[ky * 3 + 2] = __uint_as_float(cbase + ky);
-        continue;
-      }
       const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, cbase + ky * HIN * 4, 0);
       // (elements are copied to scalars first: __builtin_bit_cast on a vector-element lvalue
       //  reads element 0 for every index with this clang)
@@ -164,7 +131,7 @@ __global__ __launch_bounds__(512, 2 * BLK) void conv3x3_kernel(ConvArgs a) {
     const float* wp = wlane + c * (9 * WP);
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      const float wv = (ABL & 2) ? __uint_as_float((unsigned)(c * 9 + t) + lane) : wp[t * WP];
+      const float wv = wp[t * WP];
 #pragma unroll
       for (int j = 0; j < TPW; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, xv[j][t], acc[j], 0, 0, 0);
     }
@@ -280,15 +247,9 @@ __global__ __launch_bounds__(512, 2 * BLK) void conv3x3_kernel(ConvArgs a) {
       out_yoff[j] = yoff[j];
       voff[j] = nvoff[j];
     }
-    if constexpr (ABL & 8) mark();
   }
 #pragma unroll
   for (int j = 0; j < TPW; ++j) store_out(out[j], out_yoff[j]);   // the last tile of this wave
-  if constexpr (ABL & 4) {
-    __builtin_amdgcn_s_waitcnt(0);
-    mark();
-    if (stamp && lane == 0) stamp[29] = __builtin_amdgcn_s_memrealtime();
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -332,14 +293,8 @@ struct WgradGeom {
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-#ifdef DRQ_DEV
-unsigned long long* g_wgrad1_stamps = nullptr;
-#else
-constexpr unsigned long long* g_wgrad1_stamps = nullptr;
-#endif
-
-template <int CIN, int HIN, int STRIDE, bool STAMP = false>
-__global__ __launch_bounds__(256, 1) void conv3x3_wgrad_kernel(WgradArgs a, unsigned long long* stamps = nullptr) {
+template <int CIN, int HIN, int STRIDE>
+__global__ __launch_bounds__(256, 1) void conv3x3_wgrad_kernel(WgradArgs a) {
   using G = WgradGeom<CIN, HIN, STRIDE>;
   constexpr int HOUT = G::HOUT, KS = G::KS, XP = G::XP, DP = G::DP, NT = G::NT;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -349,19 +304,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_kernel(WgradArgs a, unsi
   const int half = lane >> 5;
   float* xs = smem + wid * G::WAVE_LDS;
   float* ds = xs + G::XS;
-  unsigned long long* stamp = nullptr;            // development only: 32 per wave; [30], [29] = wall clock start / end
-  int nstamp = 0;
-  if (STAMP) {
-    stamp = stamps + ((size_t)blockIdx.x * 4 + wid) * 32;
-    if (lane == 0) stamp[30] = __builtin_amdgcn_s_memrealtime();
-  }
-  auto mark = [&]() {
-    if (STAMP) {
-      if (nstamp < 28 && lane == 0) stamp[nstamp] = __builtin_amdgcn_s_memtime();
-      ++nstamp;
-    }
-  };
-  mark();
 
   // zero the wave-private tile once: pad columns must hold finite values (they meet dY == 0)
   if constexpr (G::WAVE_LDS % 4 == 0) {
@@ -455,15 +397,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_kernel(WgradArgs a, unsi
   };
 
   if (u0 < u1) issue_loads(u0);
-  mark();
   for (int u = u0; u < u1; ++u) {
-    mark();
     // (single wave: LDS operations of one wave complete in order, no barrier needed)
     write_lds();
-    if (STAMP) {                          // odd stamps: the staged row is in LDS (loads waited for, stores issued)
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-      mark();
-    }
     if (u + 1 < u1) issue_loads(u + 1);   // in flight under the MFMA loop below
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -482,9 +418,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_kernel(WgradArgs a, unsi
   }
 
   // ---- reduce the 4 waves of the block through LDS, one partial record per block
-  mark();
   __syncthreads();
-  mark();
   float* red = smem;   // [4][PART]  (fits: checked on the host)
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -495,172 +429,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_kernel(WgradArgs a, unsi
   float* out = a.part + (long)blockIdx.x * G::PART;
   for (int i = threadIdx.x; i < G::PART; i += 256)
     out[i] = (red[i] + red[G::PART + i]) + (red[2 * G::PART + i] + red[3 * G::PART + i]);
-  mark();
-  if (STAMP && lane == 0) {
-    stamp[29] = __builtin_amdgcn_s_memrealtime();
-    stamp[28] = (unsigned long long)nstamp;
-  }
-}
-
-// ---- wgrad v2: the four waves of a workgroup take four consecutive output rows of one sample and SHARE
-// the staged input rows (3+3*STRIDE rows instead of 12); the LDS footprint (<= 74 KB incl. the final
-// reduction) lets two workgroups live on a CU, so one workgroup's staging/barriers hide under the other's
-// MFMA loop.
-template <int CIN, int HIN, int STRIDE>
-struct Wgrad2Geom : WgradGeom<CIN, HIN, STRIDE> {
-  using G = WgradGeom<CIN, HIN, STRIDE>;
-  static constexpr int NR = 3 * STRIDE + 3;                    // input rows per group of 4 output rows
-  static constexpr int NG = (G::HOUT + 3) / 4;                 // groups per sample
-  static constexpr int XQ = (NR * G::XJ + 3) / 4;              // X load instructions per wave and group
-  static constexpr int XS2 = NR * CIN * G::XP;                 // floats of the shared input tile
-  static constexpr int TILE = XS2 + 4 * 32 * G::DP;            // + one dY row per wave
-  static constexpr int LDS_FLOATS = TILE > 2 * G::PART ? TILE : 2 * G::PART;
-};
-
-template <int CIN, int HIN, int STRIDE>
-__global__ __launch_bounds__(256, 2) void conv3x3_wgrad2_kernel(WgradArgs a) {
-  using G = Wgrad2Geom<CIN, HIN, STRIDE>;
-  constexpr int HOUT = G::HOUT, KS = G::KS, XP = G::XP, DP = G::DP, NT = G::NT;
-  constexpr int XJ = G::XJ, DJ = G::DJ, XRPI = G::XRPI, DRPI = G::DRPI, NR = G::NR, XQ = G::XQ;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int col = lane & 31;
-  const int half = lane >> 5;
-  float* xs = smem;
-  float* ds = smem + G::XS2 + wid * 32 * DP;
-
-  // pad columns must hold finite values (they meet dY == 0): zero the tile once
-  for (int i = threadIdx.x; i < G::TILE; i += 256) smem[i] = 0.f;
-
-  int bbase;   // B operand: X[pixel][column], rows of this wave start at input row wid*STRIDE of the tile
-  if (G::SMALL) {
-    const int ci = col < CIN * 3 ? col / 3 : 0;
-    const int kx = col < CIN * 3 ? col % 3 : 0;
-    bbase = (wid * STRIDE * CIN + ci) * XP + kx + half * STRIDE;
-  } else {
-    bbase = (wid * STRIDE * CIN + (col < CIN ? col : 0)) * XP + half * STRIDE;
-  }
-  const int abase = col * DP + half;   // A operand: dY[cout][pixel]
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  float bsum = 0.f;
-
-  const int ngroups = a.nb * G::NG;
-  const int g0 = (int)((long)ngroups * blockIdx.x / gridDim.x);
-  const int g1 = (int)((long)ngroups * (blockIdx.x + 1) / gridDim.x);
-
-  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, 0x00020000);
-  const int xr = lane / G::XPAIRS, xpr = lane - xr * G::XPAIRS;      // xr >= XRPI: idle lane
-  const int dr = lane / G::DPAIRS, dpr = lane - dr * G::DPAIRS;
-  const bool xact = xr < XRPI, dact = dr < DRPI;
-  const int xg_lane = (xr * HIN * HIN + 2 * xpr) * 4;                // global byte offsets (lane part)
-  const int dg_lane = (int)(dr * a.dy_cs + 2 * dpr) * 4;
-  const int xl_lane = xr * XP + 2 * xpr;                             // LDS float offsets (lane part)
-  const int dl_lane = dr * DP + 2 * dpr;
-  const bool d_last_odd = (HOUT & 1) && dpr == G::DPAIRS - 1;
-
-  u32x2 rx[XQ], rd[DJ];
-  // instruction q of this wave covers tile row (q*4+wid) / XJ and channel block (q*4+wid) % XJ
-  auto issue_loads = [&](int g) {
-    const int b = g / G::NG;
-    const int oy0 = (g - b * G::NG) * 4;
-    const int xbase = ((b * CIN * HIN + oy0 * STRIDE) * HIN) * 4;
-#pragma unroll
-    for (int q = 0; q < XQ; ++q) {
-      const int it = q * 4 + wid;
-      const int trow = it / XJ, j = it - trow * XJ;
-      const bool ok = xact && it < NR * XJ && j * XRPI + xr < CIN && oy0 * STRIDE + trow < HIN;
-      const int voff = ok ? xbase + xg_lane + (j * XRPI * HIN * HIN + trow * HIN) * 4 : 0x7ffffff0;
-      rx[q] = __builtin_amdgcn_raw_buffer_load_b64(xrsrc, voff, 0, 0);
-    }
-    const int oy = oy0 + wid;
-    const int dbase = (int)(a.dy_off + (long)b * a.dy_bs + (long)oy * a.dy_rs) * 4;
-#pragma unroll
-    for (int j = 0; j < DJ; ++j) {
-      const bool ok = dact && j * DRPI + dr < 32 && oy < HOUT;
-      const int voff = ok ? dbase + dg_lane + (int)(j * DRPI * a.dy_cs) * 4 : 0x7ffffff0;
-      rd[j] = __builtin_amdgcn_raw_buffer_load_b64(drsrc, voff, 0, 0);
-    }
-  };
-  auto write_lds = [&]() {
-#pragma unroll
-    for (int q = 0; q < XQ; ++q) {
-      const int it = q * 4 + wid;
-      const int trow = it / XJ, j = it - trow * XJ;
-      if (xact && it < NR * XJ && j * XRPI + xr < CIN)
-        *reinterpret_cast<u32x2*>(xs + (trow * CIN + j * XRPI) * XP + xl_lane) = rx[q];
-    }
-#pragma unroll
-    for (int j = 0; j < DJ; ++j)
-      if (dact && j * DRPI + dr < 32) {
-        u32x2 v = rd[j];
-        if (d_last_odd) v[1] = 0u;      // column HOUT of an odd row must stay zero (it pairs with the pad pixel)
-        *reinterpret_cast<u32x2*>(ds + j * DRPI * DP + dl_lane) = v;
-      }
-  };
-
-  __syncthreads();                       // tile zeroed
-  for (int g = g0; g < g1; ++g) {
-    // no cross-group register prefetch (144 accumulators leave no room at 2 waves/SIMD): the load latency
-    // of this workgroup is covered by the MFMA loop of the other workgroup on the CU
-    issue_loads(g);
-    write_lds();
-    __syncthreads();                     // tile of group g complete
-    const int oy = (g % G::NG) * 4 + wid;
-    if (oy < HOUT) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const float av = ds[abase + 2 * s];
-        bsum += av;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const int off = G::SMALL ? (t * CIN * XP + 2 * s * STRIDE)
-                                   : ((t / 3) * CIN * XP + (t % 3) + 2 * s * STRIDE);
-          const float bv = xs[bbase + off];
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();                     // every wave done reading the tile
-  }
-
-  // ---- 4 waves -> 1 record, two rounds through LDS (2 records = 74 KB), fixed order
-  float* red = smem;
-  auto put = [&](int slot) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) red[slot * G::PART + t * 1024 + r * 64 + lane] = acc[t][r];
-    red[slot * G::PART + NT * 1024 + lane] = bsum;
-  };
-  auto add = [&](int slot) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] += red[slot * G::PART + t * 1024 + r * 64 + lane];
-    bsum += red[slot * G::PART + NT * 1024 + lane];
-  };
-  if (wid >= 2) put(wid - 2);
-  __syncthreads();
-  if (wid < 2) add(wid);                 // wave0 += wave2, wave1 += wave3
-  __syncthreads();
-  if (wid == 1) put(0);
-  __syncthreads();
-  if (wid == 0) {
-    add(0);
-    float* out = a.part + (long)blockIdx.x * G::PART;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) out[t * 1024 + r * 64 + lane] = acc[t][r];
-    out[NT * 1024 + lane] = bsum;
-  }
 }
 
 // ---- wgrad v3 (stride 1, 32 input channels): wave-private ROLLING tile.  Consecutive output rows of a sample
@@ -670,12 +438,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad2_kernel(WgradArgs a) {
 // 7 steps later, into the ring slot / dY buffer the loop does not read), so staging hides under the MFMAs
 // although the wave is alone on its SIMD.  A disabled load gets a zero-length buffer descriptor (returns 0)
 // instead of being branched around (branches would force vmcnt(0) waits).
-#ifdef DRQ_DEV
-unsigned long long* g_wgrad_stamps = nullptr;
-#else
-constexpr unsigned long long* g_wgrad_stamps = nullptr;
-#endif
-
 // The k-step loop is written for a wave that is alone on its SIMD.  Measured there (tools/mfma_issue_probe.hip):
 // every VALU instruction between the MFMAs costs ~5 cycles of matrix-pipe time (LDS and scalar instructions cost
 // ~1), so the loop keeps the vector ALU out of the staging path altogether: all per-row / per-piece address
@@ -683,8 +445,8 @@ constexpr unsigned long long* g_wgrad_stamps = nullptr;
 // count advanced by scalar adds, which also keeps the hardware range check exact), the per-lane parts of the
 // global and LDS addresses are loop invariants, and lanes that have nothing to load mirror a neighbour (same
 // address, same value, same LDS destination) instead of being masked.
-template <int HIN, bool STAMP = false>
-__global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a, unsigned long long* stamps = nullptr) {
+template <int HIN>
+__global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a) {
   constexpr int CIN = 32;
   using G = WgradGeom<CIN, HIN, 1>;
   constexpr int HOUT = G::HOUT, KS = G::KS, XP = G::XP, DP = G::DP, NT = 9;
@@ -701,19 +463,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a, uns
   const int half = lane >> 5;
   float* ring = smem + wid * WAVE;
   float* dyb = ring + 4 * RS;
-  unsigned long long* stamp = nullptr;            // development only: 32 per wave; [30], [29] = wall clock start / end
-  int nstamp = 0;
-  if (STAMP) {
-    stamp = stamps + ((size_t)blockIdx.x * 4 + wid) * 32;
-    if (lane == 0) stamp[30] = __builtin_amdgcn_s_memrealtime();
-  }
-  auto mark = [&]() {
-    if (STAMP) {
-      if (nstamp < 28 && lane == 0) stamp[nstamp] = __builtin_amdgcn_s_memtime();
-      ++nstamp;
-    }
-  };
-  mark();
   auto zero_fill = [&]() {                        // pad columns stay finite / zero
     float4* r4 = reinterpret_cast<float4*>(ring);
 #pragma unroll 4
@@ -803,9 +552,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a, uns
   } else {
     zero_fill();
   }
-  mark();
   for (int u = u0; u < u1; ++u) {
-    mark();
     const int b = u / HOUT, oy = u - b * HOUT;
     const bool has_next = u + 1 < u1;
     const bool same = has_next && oy + 1 < HOUT;          // next row belongs to the same sample
@@ -906,9 +653,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a, uns
   }
 
   // ---- reduce the 4 waves of the block through LDS, one partial record per block
-  mark();
   __syncthreads();
-  mark();
   float* red = smem;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -923,11 +668,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a, uns
     const float4 p = r4[i], q = r4[G::PART / 4 + i], v = r4[2 * (G::PART / 4) + i], w = r4[3 * (G::PART / 4) + i];
     out[i] = make_float4((p.x + q.x) + (v.x + w.x), (p.y + q.y) + (v.y + w.y), (p.z + q.z) + (v.z + w.z),
                          (p.w + q.w) + (v.w + w.w));
-  }
-  mark();
-  if (STAMP && lane == 0) {
-    stamp[29] = __builtin_amdgcn_s_memrealtime();
-    stamp[28] = (unsigned long long)nstamp;
   }
 }
 
@@ -1014,7 +754,7 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_reduce_multi_kernel(Reduce
   }
 }
 
-template <int CIN, int HIN, int STRIDE, int BLK, int TPW, int ABL = 0, bool MASK = false>
+template <int CIN, int HIN, int STRIDE, int BLK, int TPW, bool MASK = false>
 int launch_conv_v(const ConvArgs& a, hipStream_t st) {
   constexpr int HOUT = (HIN - 3) / STRIDE + 1;
   const long ntiles = ((long)a.nb * HOUT * HOUT + 31) / 32;
@@ -1030,8 +770,7 @@ int launch_conv_v(const ConvArgs& a, hipStream_t st) {
   constexpr int static_lds = NS * 73 * 4 + 32 * 4;
   constexpr int want = 160 * 1024 / (BLK + 1) + 1024;
   const int pad = want > static_lds ? ((want - static_lds + 255) & ~255) : 0;
-  hipLaunchKernelGGL((conv3x3_kernel<CIN, HIN, STRIDE, BLK, TPW, ABL, MASK>), dim3((unsigned)blocks), dim3(512), pad, st,
-                     a);
+  hipLaunchKernelGGL((conv3x3_kernel<CIN, HIN, STRIDE, BLK, TPW, MASK>), dim3((unsigned)blocks), dim3(512), pad, st, a);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }
@@ -1039,70 +778,26 @@ int launch_conv_v(const ConvArgs& a, hipStream_t st) {
 template <int CIN, int HIN, int STRIDE>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
   if (a.mask) {
-    if constexpr (CIN == 32) return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 0, true>(a, st);
+    if constexpr (CIN == 32) return launch_conv_v<CIN, HIN, STRIDE, 2, 1, true>(a, st);
     else return DRQ_EARG;
   }
-#ifdef DRQ_DEV
-  // DRQ_CONV_VARIANT / drq_dev_conv_variant: timing ablations of the forward kernel.  Development build only
-  // (tools/conv_ab.py, tools/conv_stamps.py): variants 6-8 skip loads and compute garbage on purpose.
-  if (g_conv_variant < 0) {
-    const char* e = getenv("DRQ_CONV_VARIANT");
-    g_conv_variant = e ? atoi(e) : 0;
-  }
-  switch (g_conv_variant) {
-    case 1: return launch_conv_v<CIN, HIN, STRIDE, 2, 2>(a, st);        // 2 tiles per wave share each weight read
-    case 2: return launch_conv_v<CIN, HIN, STRIDE, 1, 2>(a, st);
-    case 4: return launch_conv_v<CIN, HIN, STRIDE, 1, 4>(a, st);        // 1 workgroup/CU, 4 accumulator chains/wave
-    case 6: return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 1>(a, st);     // no input loads
-    case 7: return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 2>(a, st);     // no LDS weight reads
-    case 8: return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 3>(a, st);     // neither: MFMA + epilogue only
-    case 10: case 11: case 12: {                                        // + per-wave time stamps
-      ConvArgs b = a;
-      b.stamps = g_conv_stamps;
-      if (g_conv_variant == 10) return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 4>(b, st);        // start/end only
-      if (g_conv_variant == 11) return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 12>(b, st);       // + every tile
-      return launch_conv_v<CIN, HIN, STRIDE, 2, 1, 7>(b, st);                                  // MFMA only, start/end
-    }
-    default: break;
-  }
-#endif
   return launch_conv_v<CIN, HIN, STRIDE, 2, 1>(a, st);
 }
 
-// 1 = rolling-tile kernel (conv2..4), the product path.  The development build can select 2 (block-shared input
-// rows, measured slower) through DRQ_WGRAD_VARIANT.
-inline int wgrad_variant() {
-#ifdef DRQ_DEV
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DRQ_WGRAD_VARIANT");
-    v = e ? atoi(e) : 1;
-  }
-  return v;
-#else
-  return 1;
-#endif
-}
-
-// defer: run only the partial-sum kernel (records in ws, their count in *nblocks_out); the caller reduces several
-// layers with one launch of conv3x3_wgrad_reduce_multi_kernel
+// conv1 (9 -> 32, stride 2) runs conv3x3_wgrad_kernel, conv2..4 (32 -> 32, stride 1) the rolling-tile
+// conv3x3_wgrad3_kernel.  defer: run only the partial-sum kernel (records in ws, their count in *nblocks_out); the
+// caller reduces several layers with one launch of conv3x3_wgrad_reduce_multi_kernel
 template <int CIN, int HIN, int STRIDE>
 int launch_wgrad(const WgradArgs& a0, float* dw, float* db, float* ws, size_t ws_bytes, hipStream_t st,
                  bool defer = false, int* nblocks_out = nullptr) {
   using G = WgradGeom<CIN, HIN, STRIDE>;
-  using G2 = Wgrad2Geom<CIN, HIN, STRIDE>;
-  static_assert(4 * G::WAVE_LDS * 4 <= 160 * 1024, "LDS tile too large");
   static_assert(4 * G::PART * 4 <= 160 * 1024, "reduction tile too large");
-  static_assert(G2::LDS_FLOATS * 4 <= 80 * 1024, "two workgroups per CU need <= 80 KB each");
   static_assert(G::PART % 64 == 0, "record size");
-  const bool v2 = wgrad_variant() == 2;
-  constexpr int lds1 = (4 * G::WAVE_LDS > 4 * G::PART) ? 4 * G::WAVE_LDS : 4 * G::PART;
-  const int lds_floats = v2 ? G2::LDS_FLOATS : lds1;
-  const long units = v2 ? (long)a0.nb * G2::NG : ((long)a0.nb * G::HOUT + 3) / 4;
+  const long units = ((long)a0.nb * G::HOUT + 3) / 4;
   // conv1 (SMALL): 63 MFMAs per output row against 38 staging loads + LDS writes that the wave cannot overlap with
   // its own MFMAs; its tile is 15 KB per wave and it needs 180 VGPRs, so two workgroups share a CU and one's staging
   // runs under the other's MFMAs
-  long blocks = ((v2 || G::SMALL) ? 2L : 1L) * drq_num_cus();
+  long blocks = (G::SMALL ? 2L : 1L) * drq_num_cus();
   if (blocks > units) blocks = units;
   if (blocks < 1) blocks = 1;
   if ((size_t)blocks * G::PART * sizeof(float) > ws_bytes) return DRQ_EWS;
@@ -1111,60 +806,28 @@ int launch_wgrad(const WgradArgs& a0, float* dw, float* db, float* ws, size_t ws
   a.part = ws;
   static bool attr_set_dev[kMaxDevices] = {};
   bool& attr_set = attr_set_dev[drq_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_kernel<CIN, HIN, STRIDE>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds1 * 4);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv3x3_wgrad2_kernel<CIN, HIN, STRIDE>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, G2::LDS_FLOATS * 4);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   if constexpr (STRIDE == 1 && CIN == 32) {
-    if (wgrad_variant() == 1) {          // default: rolling-tile kernel
-      constexpr int wave3 = 4 * CIN * G::XP + 2 * 32 * G::DP + 128;
-      constexpr int lds3 = (4 * wave3 > 4 * G::PART) ? 4 * wave3 : 4 * G::PART;
-      static_assert(lds3 * 4 <= 160 * 1024, "rolling tile too large");
-      static bool attr3_dev[kMaxDevices] = {};
-      bool& attr3 = attr3_dev[drq_device()];
-      if (!attr3) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad3_kernel<HIN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds3 * 4);
-        if (e != hipSuccess) return (int)e;
-        attr3 = true;
-      }
-      if (HIN == 41 && g_wgrad_stamps) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad3_kernel<41, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds3 * 4);
-        WgradArgs as = a;
-#ifdef DRQ_DEV
-        if (getenv("DRQ_WGRAD_NOLOAD")) as.x_bytes = as.dy_bytes = 0;     // every load out of range: no memory traffic
-#endif
-        hipLaunchKernelGGL((conv3x3_wgrad3_kernel<41, true>), dim3((unsigned)blocks), dim3(256), lds3 * 4, st, as,
-                           g_wgrad_stamps);
-      } else
-      hipLaunchKernelGGL((conv3x3_wgrad3_kernel<HIN>), dim3((unsigned)blocks), dim3(256), lds3 * 4, st, a,
-                         (unsigned long long*)nullptr);
-      DRQ_LAUNCH_CHECK();
-      if (nblocks_out) *nblocks_out = (int)blocks;
-      if (defer) return DRQ_OK;
-      hipLaunchKernelGGL((conv3x3_wgrad_reduce_kernel<CIN, G::SMALL>), dim3(G::PART / 64), dim3(1024), 0, st,
-                         (const float*)ws, (int)blocks, dw, db);
-      DRQ_LAUNCH_CHECK();
-      return DRQ_OK;
+    constexpr int wave3 = 4 * CIN * G::XP + 2 * 32 * G::DP + 128;
+    constexpr int lds3 = (4 * wave3 > 4 * G::PART) ? 4 * wave3 : 4 * G::PART;
+    static_assert(lds3 * 4 <= 160 * 1024, "rolling tile too large");
+    if (!attr_set) {
+      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad3_kernel<HIN>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds3 * 4);
+      if (e != hipSuccess) return (int)e;
+      attr_set = true;
     }
+    hipLaunchKernelGGL((conv3x3_wgrad3_kernel<HIN>), dim3((unsigned)blocks), dim3(256), lds3 * 4, st, a);
+  } else {
+    static_assert(4 * G::WAVE_LDS * 4 <= 160 * 1024, "LDS tile too large");
+    constexpr int lds1 = (4 * G::WAVE_LDS > 4 * G::PART) ? 4 * G::WAVE_LDS : 4 * G::PART;
+    if (!attr_set) {
+      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_kernel<CIN, HIN, STRIDE>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds1 * 4);
+      if (e != hipSuccess) return (int)e;
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((conv3x3_wgrad_kernel<CIN, HIN, STRIDE>), dim3((unsigned)blocks), dim3(256), lds1 * 4, st, a);
   }
-  if (v2)
-    hipLaunchKernelGGL((conv3x3_wgrad2_kernel<CIN, HIN, STRIDE>), dim3((unsigned)blocks), dim3(256), lds_floats * 4,
-                       st, a);
-  else if (CIN == 9 && g_wgrad1_stamps) {
-    (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_kernel<9, 84, 2, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_floats * 4);
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<9, 84, 2, true>), dim3((unsigned)blocks), dim3(256), lds_floats * 4, st, a,
-                       g_wgrad1_stamps);
-  } else
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<CIN, HIN, STRIDE>), dim3((unsigned)blocks), dim3(256), lds_floats * 4,
-                       st, a, (unsigned long long*)nullptr);
   DRQ_LAUNCH_CHECK();
   if (nblocks_out) *nblocks_out = (int)blocks;
   if (defer) return DRQ_OK;
@@ -1221,16 +884,6 @@ int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* n
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-#ifdef DRQ_DEV
-// development hooks (libdrqv2_hip_dev.so only, never in the product library): device buffer of 32 u64 per wave
-#pragma GCC visibility push(default)
-void drq_dev_conv_stamps(void* p) { g_conv_stamps = (unsigned long long*)p; }
-void drq_dev_wgrad_stamps(void* p) { g_wgrad_stamps = (unsigned long long*)p; }
-void drq_dev_wgrad1_stamps(void* p) { g_wgrad1_stamps = (unsigned long long*)p; }
-void drq_dev_conv_variant(int v) { g_conv_variant = v; }
-#pragma GCC visibility pop
-#endif
-
 // y = relu?(conv3x3(x, w) + bias); x [nb][cin][hin][hin], y written with the given strides.
 DRQ_API int drq_conv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int nb, int cin, int hin,
                     int stride, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
@@ -1239,7 +892,7 @@ DRQ_API int drq_conv3x3_fwd(const float* x, const float* w, const float* bias, f
   if (xb >= (1ull << 31)) return DRQ_EARG;
   const size_t yb = (size_t)nb * y_bs * 4;
   if (yb >= (1ull << 31) || y_off < 0 || y_bs <= 0) return DRQ_EARG;
-  ConvArgs a{x, w, bias, nullptr, y, y_bs, y_cs, y_rs, y_off, (unsigned)xb, (unsigned)yb, 0u, nb, relu, 0, nullptr};
+  ConvArgs a{x, w, bias, nullptr, y, y_bs, y_cs, y_rs, y_off, (unsigned)xb, (unsigned)yb, 0u, nb, relu, 0};
   if (cin == 9 && hin == 84 && stride == 2) return launch_conv<9, 84, 2>(a, st);
   if (cin == 32 && stride == 1) {
     if (hin == 41) return launch_conv<32, 41, 1>(a, st);
@@ -1261,7 +914,7 @@ DRQ_API int drq_conv3x3_dgrad(const float* dy_pad, const float* w, const float* 
   const size_t mb = (size_t)nb * 32 * (hout + 2) * (hout + 2) * 4;
   if (yb >= (1ull << 31) || dx_off < 0 || dx_bs <= 0) return DRQ_EARG;
   ConvArgs a{dy_pad, w, nullptr, mask, dx, dx_bs, dx_cs, dx_rs, dx_off, (unsigned)xb, (unsigned)yb, (unsigned)mb,
-             nb, 0, 1, nullptr};
+             nb, 0, 1};
   if (hp == 39) return launch_conv<32, 39, 1>(a, st);
   if (hp == 41) return launch_conv<32, 41, 1>(a, st);
   if (hp == 43) return launch_conv<32, 43, 1>(a, st);

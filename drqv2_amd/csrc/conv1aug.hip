@@ -12,21 +12,15 @@
 //            A operand (this lane's 45 weight values) held in registers for the whole kernel.
 // Two workgroups share a CU: one's stage 1 (memory) runs under the other's compute.  Stage 2 and stage 3 do NOT
 // overlap, although they come from different waves: on gfx950 the f32 MFMA and the f32 VALU share a SIMD's
-// datapath (ablations in tools/conv1aug_ab.py: augmentation alone 43 us, tiles alone 54 us, both 89 us; per-CU stamps
-// in tools/conv1aug_stamps.py show both workgroups resident all the time; staggering them changes nothing).
+// datapath (timing ablations: augmentation alone 43 us, tiles alone 54 us, both 89 us; per-CU time stamps show both
+// workgroups resident all the time; staggering them changes nothing.  The tools that measured this,
+// tools/conv1aug_ab.py and tools/conv1aug_stamps.py, are in git history, with the timing build they drove).
 // k order and accumulation order are those of conv3x3_kernel<9,84,2>: the results are bit-identical to the
 // unfused path (tests/test_hip_ops.py).
 #include "common.h"
 #include "wino_u.h"
-#include <stdio.h>
 
 namespace {
-
-#ifdef DRQ_DEV
-int g_conv1aug_variant = 0;
-int g_conv1aug_stagger = 1;
-unsigned long long* g_conv1aug_stamps = nullptr;
-#endif
 
 constexpr int H = 84, C = 9, PAD = 4, S = 92, HW = H * H;
 constexpr int HO = 41, PO = HO * HO;
@@ -67,7 +61,6 @@ struct Conv1AugArgs {
   const float* wino_w[3];
   float* wino_u;
   int n_rider;
-  unsigned long long* stamps;   // development build: [grid][4] = start, end (s_memrealtime), HW_ID, XCC_ID
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -88,15 +81,13 @@ __device__ __forceinline__ float div255(float v) {   // correctly rounded v / 25
   return __fmaf_rn(e, r, q);
 }
 
-// ABL (development build only, tools/conv1aug_ab.py): timing ablations -- 1 skips stage 3 (tiles), 2 skips stage 2
-// (augmentation), 4 skips the stage-2 global stores, 8 skips the LDS-DMA of the source rows
 // BF (the bf16 update path, DrqStep.bf16): stage 3 runs on v_mfma_f32_32x32x16_bf16 -- one MFMA per tap with k = 16
 // channel slots (9 real channels; lanes 0-31 supply channels 0-7, lanes 32-63 channel 8 and seven zero weights), the
 // operands rounded to bf16 as they are read from the fp32 LDS tile.  Stages 1 and 2 (and the stored encoder input)
 // are unchanged.  The bf16 matrix unit is separate from the f32 VALU datapath: here the two workgroups of a CU DO
 // overlap (one augments while the other multiplies).
 // YN (with BF): y is written as bf16 [frame][41][41][32 channels] (conv_bf16.hip's activation layout) instead of fp32 NCHW
-template <int ABL, bool BF = false, bool YN = false>
+template <bool BF = false, bool YN = false>
 __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1AugArgs a) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -120,13 +111,6 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
   const int units = 2 * a.n * NBAND;
   const int G = (int)gridDim.x - a.n_rider;
 
-#ifdef DRQ_DEV
-  if (a.stamps && tid == 0) {
-    a.stamps[4 * blockIdx.x + 0] = __builtin_amdgcn_s_memrealtime();
-    a.stamps[4 * blockIdx.x + 2] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-    a.stamps[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
-  }
-#endif
   if (tid < H) bg[tid] = a.base[tid];
   if (tid >= 128 && tid < 128 + MAXU) {                            // the host sizes the grid so that MAXU covers them
     const int k = tid - 128, uu = bid + k * G;
@@ -219,7 +203,7 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
       const int ch = rowid / SROWS, r = rowid - ch * SROWS;
       const int rr = r < q.nsrc ? r : q.nsrc - 1;
       const unsigned* g = reinterpret_cast<const unsigned*>(src + (long)ch * HW + (long)(q.sy_lo + rr) * H) + qd;
-      if constexpr (!(ABL & 8)) __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)(u8w + k * 64), 4, 0, 0);
+      __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)(u8w + k * 64), 4, 0, 0);
     }
   };
 
@@ -252,8 +236,8 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
     // column and the x shift is computed once per unit), channels go two at a time through the packed-f32
     // instructions (v_pk_mul/add/fma_f32: two IEEE operations per lane and issue slot, same roundings), and the
     // stores use a buffer descriptor with scalar channel offsets (no 64-bit address arithmetic per element).
-    if constexpr (!(ABL & 2)) {
-      const bool store = cur.f < a.n_store && !(ABL & 4);
+    {
+      const bool store = cur.f < a.n_store;
       const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(a.xaug + (long)cur.f * C * HW), 0, store ? (unsigned)(C * HW * 4) : 0u, 0x00020000);
       constexpr int RPP = NTHR / H;                            // rows per pass (the last NTHR - RPP*84 threads idle)
@@ -357,7 +341,7 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
         dst[ky * 3 + 2] = xc[ky * XPITCH + 1];
       }
     };
-    for (int tile = wid; tile < ((ABL & 1) || wid >= 4 ? 0 : ntiles); tile += 4) {
+    for (int tile = wid; tile < (wid >= 4 ? 0 : ntiles); tile += 4) {
       const int p0 = tile * 32 + col;
       const int p = p0 < npix ? p0 : npix - 1;
       const int oyl = p / HO, ox = p - oyl * HO;
@@ -419,21 +403,9 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
       }
     }
   }
-#ifdef DRQ_DEV
-  if (a.stamps && tid == 0) {
-    __builtin_amdgcn_s_waitcnt(0);
-    a.stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 }  // namespace
-
-#ifdef DRQ_DEV
-extern "C" DRQ_API void drq_dev_conv1aug_variant(int v) { g_conv1aug_variant = v; }
-extern "C" DRQ_API void drq_dev_conv1aug_stagger(int v) { g_conv1aug_stagger = v; }
-extern "C" DRQ_API void drq_dev_conv1aug_stamps(void* p) { g_conv1aug_stamps = (unsigned long long*)p; }
-#endif
 
 // C ABI (include/drqv2_hip.h): both views of the update through aug + conv1 in one launch.
 //   y [2n][32][41][41] = relu(conv1(aug(view)/255 - 0.5));  xaug [2n][9][84][84]: frames [0, n_store) are written.
@@ -454,33 +426,22 @@ int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, co
   a.fidx[0] = fidx0; a.fidx[1] = fidx1;
   a.shift[0] = shift; a.shift[1] = shift1;
   a.base = base_grid; a.w = w; a.bias = bias; a.xaug = xaug; a.y = y;
-  a.n = n; a.n_store = n_store; a.y_bytes = (unsigned)yb; a.stagger = 1; a.stamps = nullptr;
+  a.n = n; a.n_store = n_store; a.y_bytes = (unsigned)yb; a.stagger = 1;
   if (wino_w && wino_u) {
     for (int l = 0; l < 3; ++l) a.wino_w[l] = wino_w[l];
     a.wino_u = wino_u;
     a.n_rider = 6;
   }
-#ifdef DRQ_DEV
-  a.stagger = g_conv1aug_stagger;
-  a.stamps = g_conv1aug_stamps;
-#endif
   static bool attr_set_dev[kMaxDevices] = {};
   bool& attr_set = attr_set_dev[drq_device()];
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv1_aug_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute((const void*)conv1_aug_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        LDS_BYTES);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv1_aug_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      e = hipFuncSetAttribute((const void*)conv1_aug_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv1_aug_kernel<0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      e = hipFuncSetAttribute((const void*)conv1_aug_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               LDS_BYTES);
-#ifdef DRQ_DEV
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv1_aug_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv1_aug_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv1_aug_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv1_aug_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv1_aug_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-#endif
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
@@ -490,36 +451,9 @@ int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, co
   if (blocks > cap) blocks = cap;
   if (blocks * MAXU < units) blocks = (units + MAXU - 1) / MAXU;     // a workgroup's shift table holds MAXU units
   blocks += a.n_rider;
-#ifdef DRQ_DEV
-  {
-    static bool said = false;
-    if (!said) {
-      int nb = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv1_aug_kernel<0>, NTHR, LDS_BYTES);
-      fprintf(stderr, "conv1_aug_kernel: %d workgroups per CU by the occupancy query (LDS %d bytes), grid %ld\n", nb,
-              LDS_BYTES, blocks);
-      said = true;
-    }
-  }
-  if (bf_mma) {
-    if (bf_mma == 2) hipLaunchKernelGGL((conv1_aug_kernel<0, true, true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((conv1_aug_kernel<0, true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-    DRQ_LAUNCH_CHECK();
-    return DRQ_OK;
-  }
-  switch (g_conv1aug_variant) {
-    case 1: hipLaunchKernelGGL(conv1_aug_kernel<1>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a); break;
-    case 2: hipLaunchKernelGGL(conv1_aug_kernel<2>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a); break;
-    case 3: hipLaunchKernelGGL(conv1_aug_kernel<3>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a); break;
-    case 4: hipLaunchKernelGGL(conv1_aug_kernel<4>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a); break;
-    case 10: hipLaunchKernelGGL(conv1_aug_kernel<10>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a); break;
-    default: hipLaunchKernelGGL(conv1_aug_kernel<0>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-  }
-#else
-  if (bf_mma == 2) hipLaunchKernelGGL((conv1_aug_kernel<0, true, true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-  else if (bf_mma) hipLaunchKernelGGL((conv1_aug_kernel<0, true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-  else hipLaunchKernelGGL(conv1_aug_kernel<0>, dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-#endif
+  if (bf_mma == 2) hipLaunchKernelGGL((conv1_aug_kernel<true, true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
+  else if (bf_mma) hipLaunchKernelGGL((conv1_aug_kernel<true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
+  else hipLaunchKernelGGL((conv1_aug_kernel<false>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }

@@ -32,24 +32,15 @@ struct WinoArgs {
   int relu;
   int wmode;           // 0 forward gather, 1 dgrad gather (transposed + flipped)
   int stagger;         // start delay of the second wave of each SIMD, in units of 1024 clocks (see the kernel)
-  unsigned long long* stamps;   // development only (ABL & 8): 32 per wave
 };
 
 typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
 typedef float f32x2w __attribute__((ext_vector_type(2)));
 
-#ifdef DRQ_DEV
-int g_wino_variant = 0;   // drq_dev_wino_variant: timing ablations (tools/wino_bench.py)
-int g_wino_stagger = -1;  // drq_dev_wino_stagger: overrides kStagger
-unsigned long long* g_wino_stamps = nullptr;
-#endif
 constexpr int kStagger = 0;
 
-// ABL (development build only): 1 = no input transform (V = d), 2 = no output transform (position 0 is stored),
-// 4 = no patch loads; the results are wrong on purpose; 8 = per-wave s_memtime stamps (start, after the prologue,
-// after every unit; [29],[30] = s_memrealtime end / start, [31] = HW_ID)
-template <int HIN, bool MASK, bool RELU, int ABL = 0>
+template <int HIN, bool MASK, bool RELU>
 __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
 #pragma clang fp contract(off)
   constexpr int HOUT = HIN - 2;
@@ -61,25 +52,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  unsigned long long* stamp = nullptr;
-  int nstamp = 0;
-  auto mark = [&]() {
-    if constexpr (ABL & 8) {
-      if (stamp && nstamp < 28 && lane == 0) stamp[nstamp] = __builtin_amdgcn_s_memtime();
-      ++nstamp;
-    }
-  };
-  if constexpr (ABL & 8) {
-    if (a.stamps) {
-      stamp = a.stamps + ((size_t)blockIdx.x * 4 + wid) * 32;
-      if (lane == 0) {
-        stamp[30] = __builtin_amdgcn_s_memrealtime();
-        stamp[31] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-        stamp[28] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // XCC_ID
-      }
-    }
-  }
-  mark();
   const int tl = lane & 15;     // tile of the unit (B column / D column)
   const int kk = lane >> 4;     // input channel inside the k-step (A/B k index); D rows 4*kk + r
 
@@ -114,7 +86,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
       for (int q = 0; q < a.stagger; ++q) __builtin_amdgcn_s_sleep(16);
   }
 
-  mark();
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, a.y_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t mrs =
@@ -134,11 +105,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
     return (((b * 32 + kk) * HIN + 2 * ty) * HIN + 2 * tx) * 4;
   };
   auto load_patch_row = [&](float (&d)[16], int voff, int c, int i) {
-    if constexpr (ABL & 4) {
-      d[i * 4 + 0] = 1.0f + (float)(voff + c); d[i * 4 + 1] = 2.0f + (float)(voff + i);
-      d[i * 4 + 2] = 1.5f + (float)voff; d[i * 4 + 3] = (float)(c + i);
-      return;
-    }
     const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff, c * (4 * PLANE) + i * (HIN * 4), 0);
     const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];
     d[i * 4 + 0] = __uint_as_float(e0);
@@ -149,11 +115,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
   auto load_patch = [&](float (&d)[16], int voff, int c) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (ABL & 4) {
-        d[i * 4 + 0] = 1.0f + (float)(voff + c); d[i * 4 + 1] = 2.0f + (float)(voff + i);
-        d[i * 4 + 2] = 1.5f + (float)voff; d[i * 4 + 3] = (float)(c + i);
-        continue;
-      }
       const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff, c * (4 * PLANE) + i * (HIN * 4), 0);
       const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];
       d[i * 4 + 0] = __uint_as_float(e0);
@@ -235,10 +196,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
       float t[16];                           // B^T d
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if constexpr (ABL & 1) {
-          t[0 * 4 + j] = d[0 * 4 + j]; t[1 * 4 + j] = d[1 * 4 + j]; t[2 * 4 + j] = d[2 * 4 + j]; t[3 * 4 + j] = d[3 * 4 + j];
-          continue;
-        }
         t[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j];
         t[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j];
         t[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j];
@@ -250,10 +207,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
       float V[16];                           // (B^T d) B, all of it ahead of the MFMAs (no VALU->MFMA hazard per use)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if constexpr (ABL & 1) {
-          V[i * 4 + 0] = t[i * 4 + 0]; V[i * 4 + 1] = t[i * 4 + 1]; V[i * 4 + 2] = t[i * 4 + 2]; V[i * 4 + 3] = t[i * 4 + 3];
-          continue;
-        }
         V[i * 4 + 0] = t[i * 4 + 0] - t[i * 4 + 2];
         V[i * 4 + 1] = t[i * 4 + 1] + t[i * 4 + 2];
         V[i * 4 + 2] = t[i * 4 + 2] - t[i * 4 + 1];
@@ -303,13 +256,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
     }
     // ---- output transform Y = A^T M A, bias, ReLU / mask, stores
     {
-      if constexpr (ABL & 2) {               // every accumulator stays live although only four are stored
-#pragma unroll
-        for (int pos = 0; pos < 16; ++pos) {
-          if constexpr (HSEL != 1) asm volatile("" ::"v"(acc[pos][0]));
-          if constexpr (HSEL != 0) asm volatile("" ::"v"(acc[pos][1]));
-        }
-      }
       if constexpr (MASK && HSEL == 2) {     // ... the second half under the first half's transform arithmetic
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -328,14 +274,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
           for (int j = 0; j < 4; ++j) {
             const float m0 = acc[0 * 4 + j][h][r], m1 = acc[1 * 4 + j][h][r], m2 = acc[2 * 4 + j][h][r],
                         m3 = acc[3 * 4 + j][h][r];
-            s[0][j] = (ABL & 2) ? m0 : (m0 + m1) + m2;
-            s[1][j] = (ABL & 2) ? m0 + m3 : (m1 - m2) - m3;
+            s[0][j] = (m0 + m1) + m2;
+            s[1][j] = (m1 - m2) - m3;
           }
           const int co = (16 * h + r);       // + 4*kk rides in the lane's base offset
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            float y0 = (ABL & 2) ? s[i][0] : (s[i][0] + s[i][1]) + s[i][2];
-            float y1 = (ABL & 2) ? s[i][3] : (s[i][1] - s[i][2]) - s[i][3];
+            float y0 = (s[i][0] + s[i][1]) + s[i][2];
+            float y1 = (s[i][1] - s[i][2]) - s[i][3];
             if constexpr (RELU) {
               y0 = __builtin_fmaxf(y0, 0.f);
               y1 = __builtin_fmaxf(y1, 0.f);
@@ -353,16 +299,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
         }
     }
     voff = nvoff;
-    mark();
   };
   for (int i = 0; i < nfull; ++i) body(std::integral_constant<int, 2>{}, item_unit(i), item_unit(i + 1 < nitem ? i + 1 : i));
   if (has_half) {
     if (half_h == 0) body(std::integral_constant<int, 0>{}, half_unit, half_unit);
     else body(std::integral_constant<int, 1>{}, half_unit, half_unit);
-  }
-  if constexpr (ABL & 8) {
-    __builtin_amdgcn_s_waitcnt(0);
-    if (stamp && lane == 0) stamp[29] = __builtin_amdgcn_s_memrealtime();
   }
 }
 
@@ -370,30 +311,12 @@ template <int HIN>
 int launch_wino(const WinoArgs& a0, hipStream_t st) {
   WinoArgs a = a0;
   a.stagger = kStagger;
-#ifdef DRQ_DEV
-  if (g_wino_stagger >= 0) a.stagger = g_wino_stagger;
-#endif
   constexpr int HOUT = HIN - 2, TH = (HOUT + 1) / 2;
   const long nunit = ((long)a.nb * TH * TH + 15) / 16;
   long blocks = (nunit + 3) / 4;
   const long cap = 2L * drq_num_cus();
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-#ifdef DRQ_DEV
-  if (!a.mask && a.relu && g_wino_variant) {
-    switch (g_wino_variant) {
-      case 1: hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 1>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-      case 2: hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 2>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-      case 3: hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 3>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-      case 4: hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-      case 8: a.stamps = g_wino_stamps; hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 8>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-      case 15: a.stamps = g_wino_stamps; hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 15>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-      default: hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true, 7>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-    }
-    DRQ_LAUNCH_CHECK();
-    return DRQ_OK;
-  }
-#endif
   const dim3 g((unsigned)blocks), t(256);
   if (a.mask && a.relu) hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, true, true>), g, t, 0, st, a);
   else if (a.mask) hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, true, false>), g, t, 0, st, a);
@@ -405,12 +328,6 @@ int launch_wino(const WinoArgs& a0, hipStream_t st) {
 
 }  // namespace
 
-#ifdef DRQ_DEV
-extern "C" DRQ_API void drq_dev_wino_variant(int v) { g_wino_variant = v; }
-extern "C" DRQ_API void drq_dev_wino_stagger(int v) { g_wino_stagger = v; }
-extern "C" DRQ_API void drq_dev_wino_stamps(void* p) { g_wino_stamps = (unsigned long long*)p; }
-#endif
-
 // internal (step.hip): u_image = the layer's U image prepared by conv1_aug_kernel's rider for this update, or null
 int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,
                              int hin, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
@@ -418,7 +335,7 @@ int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_imag
   const size_t xb = (size_t)nb * 32 * hin * hin * 4;
   const size_t yb = (size_t)nb * y_bs * 4;
   if (xb >= (1ull << 31) || yb >= (1ull << 31) || y_off < 0 || y_bs <= 0) return DRQ_EARG;
-  WinoArgs a{x, w, u_image, bias, nullptr, y, (int)y_bs, (int)y_cs, (int)y_rs, (int)y_off, (unsigned)xb, (unsigned)yb, 0u, nb, relu, 0, 0, nullptr};
+  WinoArgs a{x, w, u_image, bias, nullptr, y, (int)y_bs, (int)y_cs, (int)y_rs, (int)y_off, (unsigned)xb, (unsigned)yb, 0u, nb, relu, 0, 0};
   if (hin == 41) return launch_wino<41>(a, st);
   if (hin == 39) return launch_wino<39>(a, st);
   if (hin == 37) return launch_wino<37>(a, st);
@@ -434,7 +351,7 @@ int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float*
   const size_t mb = (size_t)nb * 32 * (hout + 2) * (hout + 2) * 4;
   if (xb >= (1ull << 31) || yb >= (1ull << 31) || dx_off < 0 || dx_bs <= 0) return DRQ_EARG;
   WinoArgs a{dy_pad, w, u_image, nullptr, mask, dx, (int)dx_bs, (int)dx_cs, (int)dx_rs, (int)dx_off, (unsigned)xb, (unsigned)yb,
-             (unsigned)mb, nb, 0, 1, 0, nullptr};
+             (unsigned)mb, nb, 0, 1, 0};
   if (hp == 39) return launch_wino<39>(a, st);
   if (hp == 41) return launch_wino<41>(a, st);
   if (hp == 43) return launch_wino<43>(a, st);

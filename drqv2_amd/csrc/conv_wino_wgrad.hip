@@ -32,24 +32,9 @@ struct WWArgs {
 typedef unsigned u32x4q __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2q __attribute__((ext_vector_type(2)));
 
-#ifdef DRQ_DEV
-int g_ww_variant = 0;   // drq_dev_wgrad_wino_variant: timing ablations (tools/wino_ab.py)
-// drq_dev_wgrad_wino_stamps: 8 u64 per wave (s_memtime at start / first patches issued / loop done / image in LDS /
-// after the barrier / record written, then s_memrealtime start and end); tools/wwino_stamps.py
-__device__ unsigned long long* d_ww_stamps = nullptr;
-#define WW_MARK(k)                                                                                                     \
-  do {                                                                                                                 \
-    if (d_ww_stamps && lane == 0) d_ww_stamps[((size_t)bx * 4 + wid) * 8 + (k)] =                                       \
-        (k) >= 6 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();                                    \
-  } while (0)
-#else
-#define WW_MARK(k)
-#endif
-
-// ABL (development build only): 1 = no patch loads, 2 = no transforms (the raw patches are multiplied); wrong results
 // bx / nblk: the workgroup's index among the nblk workgroups that share this layer (a launch of its own: blockIdx.x /
 // gridDim.x; the three-layer launch below gives every layer a range of its grid)
-template <int HIN, int ABL = 0>
+template <int HIN>
 __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
 #pragma clang fp contract(off)
   constexpr int HOUT = HIN - 2;
@@ -59,8 +44,6 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
   extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][PART]
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ch = lane & 15, tq = lane >> 4;
-  WW_MARK(6);
-  WW_MARK(0);
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, 0x00020000);
   constexpr int kDrop = (int)0x80000000u;     // beyond num_records: the load returns 0
@@ -86,16 +69,6 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
   // two register sets of patches: the loads of step it+2 are issued while step it multiplies (one wave per SIMD has
   // nobody else to hide an HBM miss behind: one step = 64 MFMAs = 2048 matrix cycles is not always enough)
   auto load_item = [&](float (&Pdx)[2][16], float (&Pdy)[2][4], int xo, int dyo) {
-    if constexpr (ABL & 1) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Pdx[h][e] = 1.0f + (float)(xo + e);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Pdy[h][e] = 0.5f + (float)(dyo + e);
-      }
-      return;
-    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -119,16 +92,6 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
 
   // the k-th of the twelve load instructions of an item: 0..7 = x rows (h = k>>2, i = k&3), 8..11 = dY rows
   auto load_one = [&](float (&Pdx)[2][16], float (&Pdy)[2][4], int xo, int dyo, int k) {
-    if constexpr (ABL & 1) {
-      if (k < 8) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Pdx[k >> 2][(k & 3) * 4 + e] = 1.0f + (float)(xo + e + k);
-      } else {
-        Pdy[(k - 8) >> 1][((k - 8) & 1) * 2 + 0] = 0.5f + (float)(dyo + k);
-        Pdy[(k - 8) >> 1][((k - 8) & 1) * 2 + 1] = 0.25f + (float)(dyo + k);
-      }
-      return;
-    }
     if (k < 8) {
       const int h = k >> 2, i = k & 3;
       const u32x4q v = __builtin_amdgcn_raw_buffer_load_b128(xrs, xo, h * (16 * PLANE) + i * (HIN * 4), 0);
@@ -173,11 +136,6 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if constexpr (ABL & 2) {
-          V[h][i * 4 + 0] = Pdx[h][i * 4 + 0]; V[h][i * 4 + 1] = Pdx[h][i * 4 + 1];
-          V[h][i * 4 + 2] = Pdx[h][i * 4 + 2]; V[h][i * 4 + 3] = Pdx[h][i * 4 + 3];
-          continue;
-        }
         V[h][i * 4 + 0] = t[i * 4 + 0] - t[i * 4 + 2];
         V[h][i * 4 + 1] = t[i * 4 + 1] + t[i * 4 + 2];
         V[h][i * 4 + 2] = t[i * 4 + 2] - t[i * 4 + 1];
@@ -190,10 +148,6 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
       const float r[4][2] = {{y00, y01}, {y00 + y10, y01 + y11}, {y00 - y10, y01 - y11}, {y10, y11}};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if constexpr (ABL & 2) {
-          M[h][i * 4 + 0] = Pdy[h][0]; M[h][i * 4 + 1] = Pdy[h][1]; M[h][i * 4 + 2] = Pdy[h][2]; M[h][i * 4 + 3] = Pdy[h][3];
-          continue;
-        }
         M[h][i * 4 + 0] = r[i][0];
         M[h][i * 4 + 1] = r[i][0] + r[i][1];
         M[h][i * 4 + 2] = r[i][0] - r[i][1];
@@ -226,9 +180,7 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
     item_off(0, xo, dyo);
     load_item(dx0, dy0, xo, dyo);
   }
-  WW_MARK(1);
   for (int it = 0; it < total; ++it) step(dx0, dy0, it + 1);
-  WW_MARK(2);
 
   // ---- dg = G^T dU G per (cout, cin) -> this wave's image of the partial record in LDS
   // D register r of lane l: cout = 16*qa + 4*(l>>4) + r, cin = 16*qb + (l&15)
@@ -276,9 +228,7 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
       mine[9 * 1024 + 48 + ch] = 0.f;
     }
   }
-  WW_MARK(3);
   __syncthreads();
-  WW_MARK(4);
   float4* out = reinterpret_cast<float4*>(a.part + (long)bx * PART);
   const float4* r4 = reinterpret_cast<const float4*>(red);
   for (int i = threadIdx.x; i < PART / 4; i += 256) {
@@ -286,17 +236,12 @@ __device__ __forceinline__ void ww_body(const WWArgs& a, int bx, int nblk) {
     out[i] = make_float4((p.x + q.x) + (v.x + w.x), (p.y + q.y) + (v.y + w.y), (p.z + q.z) + (v.z + w.z),
                          (p.w + q.w) + (v.w + w.w));
   }
-#ifdef DRQ_DEV
-  if (d_ww_stamps) __builtin_amdgcn_s_waitcnt(0);
-#endif
-  WW_MARK(5);
-  WW_MARK(7);
 }
 
-template <int HIN, int ABL = 0>
+template <int HIN>
 __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_wino_kernel(WWArgs a) {
   const int G = (int)gridDim.x;   // XCD-aware order, see conv3x3_wgrad_wino3_kernel
-  ww_body<HIN, ABL>(a, (G & 7) ? (int)blockIdx.x : ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3), G);
+  ww_body<HIN>(a, (G & 7) ? (int)blockIdx.x : ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3), G);
 }
 
 // The three 32->32 layers of the encoder backward in ONE launch: layer l owns workgroups [beg[l], beg[l+1]) of the
@@ -335,19 +280,6 @@ int launch_ww(const WWArgs& a, int* nblocks, hipStream_t st) {
   const long steps = ((long)a.nb * TH * TH + 3) / 4;
   if (blocks * 4 > steps) blocks = (steps + 3) / 4;
   if (blocks < 1) blocks = 1;
-#ifdef DRQ_DEV
-  if (g_ww_variant) {
-    const void* fn = g_ww_variant == 1 ? (const void*)conv3x3_wgrad_wino_kernel<HIN, 1>
-                   : g_ww_variant == 2 ? (const void*)conv3x3_wgrad_wino_kernel<HIN, 2> : (const void*)conv3x3_wgrad_wino_kernel<HIN, 3>;
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (g_ww_variant == 1) hipLaunchKernelGGL((conv3x3_wgrad_wino_kernel<HIN, 1>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-    else if (g_ww_variant == 2) hipLaunchKernelGGL((conv3x3_wgrad_wino_kernel<HIN, 2>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_wino_kernel<HIN, 3>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-    DRQ_LAUNCH_CHECK();
-    *nblocks = (int)blocks;
-    return DRQ_OK;
-  }
-#endif
   hipLaunchKernelGGL((conv3x3_wgrad_wino_kernel<HIN>), dim3((unsigned)blocks), dim3(256), lds, st, a);
   DRQ_LAUNCH_CHECK();
   *nblocks = (int)blocks;
@@ -355,13 +287,6 @@ int launch_ww(const WWArgs& a, int* nblocks, hipStream_t st) {
 }
 
 }  // namespace
-
-#ifdef DRQ_DEV
-extern "C" DRQ_API void drq_dev_wgrad_wino_variant(int v) { g_ww_variant = v; }
-extern "C" DRQ_API void drq_dev_wgrad_wino_stamps(unsigned long long* p) {
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(d_ww_stamps), &p, sizeof(p));
-}
-#endif
 
 // internal (step.hip): conv2, conv3, conv4 (hin 41, 39, 37) in one launch; x[l], dy[l], part[l] and the dY strides per
 // layer; nblocks[l] = records written for layer l

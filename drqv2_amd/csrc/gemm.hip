@@ -764,12 +764,7 @@ int drq_gemm_batched_partial_any(int bf16, int nbatch, const float* const* A, lo
                                  long ldb, int b_kc, float* const* C, long ldc, int M, int N, int K,
                                  const float* const* bias, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st) {
   // the fp32 trunk forward (k-contiguous operands, N <= 64, long K) has its own kernel
-#ifdef DRQ_DEV
-  static const bool no_trunk = getenv("DRQ_NO_TRUNK_KERNEL") != nullptr;     // development build: A/B against the tiled GEMM
-#else
-  constexpr bool no_trunk = false;
-#endif
-  if (!bf16 && a_kc && b_kc && N <= 128 && K >= 4096 && ldc == N && !no_trunk) {
+  if (!bf16 && a_kc && b_kc && N <= 128 && K >= 4096 && ldc == N) {
     int sk = 1;
     const int rc = drq_trunk_fwd_partial(nbatch, A, lda, B, ldb, M, N, K, ws, ws_bytes, &sk, st);
     if (rc == DRQ_OK) {

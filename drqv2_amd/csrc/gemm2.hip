@@ -549,24 +549,13 @@ int drq_trunk_fwd_partial(int nbatch, const float* const* A, long lda, const flo
   // extra waves hide
   const int steps = K / 32, cus = drq_num_cus();
   const bool wide = N > 64;               // four column tiles per wave, one row tile
-#ifdef DRQ_DEV
-  static const char* const dbg = getenv("DRQ_TRUNK_DBG");       // development build only (tools/trunk_bench.py)
-#else
-  constexpr const char* dbg = nullptr;
-#endif
-  const bool force_tm2 = dbg && (atoi(dbg) & 4);
-  const bool tm2 = !wide && M % 64 == 0 && ((long)nbatch * (M / 32) * 4 >= 64 || force_tm2);
+  const bool tm2 = !wide && M % 64 == 0 && (long)nbatch * (M / 32) * 4 >= 64;
   const int rows = tm2 ? M / 64 : M / 32;
   int blocks_k = (cus + nbatch * rows - 1) / (nbatch * rows);
   if (blocks_k * 4 > steps) blocks_k = steps / 4;
   // small batches (one or two row tiles): the consumer (LayerNorm) sums the split-K records row by row, and beyond
   // ~64 records per element that sum costs more than the extra workgroups save here
   if (blocks_k > 64) blocks_k = 64;
-  if (dbg) {
-    const int d = atoi(dbg);
-    if (d & 1) g.a_bytes = g.b_bytes = 0;               // every load out of range: MFMA time only
-    if (d & 2) blocks_k *= 2;
-  }
   if (blocks_k < 2) return DRQ_EARG;      // a split count of 1 means "result in C" to the callers
   if ((size_t)nbatch * blocks_k * M * N * sizeof(float) > ws_bytes) return DRQ_EWS;
   const dim3 grid(blocks_k, rows, nbatch);

@@ -23,7 +23,6 @@
 // The weight gradient and the input gradient of one layer run as block ranges of ONE launch (gemm3_pair_kernel).
 #include "common.h"
 #include "../../include/drqv2_hip.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -44,7 +43,6 @@ struct G3Args {
   int M, N, K;
   int relu;
   unsigned a_bytes, b_bytes;
-  int dbg;                      // development build only: 1 = issue no copies, 2 = no barrier in the k loop
 };
 
 __device__ __forceinline__ int rowmap3(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
@@ -138,9 +136,6 @@ __device__ __forceinline__ void gemm3_body(const G3Args& g, int tile, int batch,
   // one 1-KiB piece (of the wave's JA + JB) of the copy of k-tile s into ring buffer `buf`; s >= nkt: zero records, the
   // copy is dropped by the range check (same instruction count in every iteration: the wait counts stay exact)
   auto dma_piece = [&](int s, int buf, int j) {
-#ifdef DRQ_DEV
-    if (g.dbg & 1) return;
-#endif
     const bool live = s < nkt;
     float* st = smem + buf * STAGE;
     if (j < JA) {
@@ -189,9 +184,6 @@ __device__ __forceinline__ void gemm3_body(const G3Args& g, int tile, int batch,
   int bnext = 1, bfill = NS - 1;                   // ring indices of tile t+1 and tile t+NS-1
   auto iter = [&](int t, const float (&a)[NM], const float (&b)[NM], float (&na)[NM], float (&nb)[NM]) {
     wait_vmcnt<Cfg::IPW*(NS - 3)>();
-#ifdef DRQ_DEV
-    if (!(g.dbg & 2))
-#endif
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -397,24 +389,6 @@ int drq_gemm3_fwd(int nbatch, const float* const* A, long lda, const float* cons
     if ((g.qw[b] != nullptr) != (g.qpart[b] != nullptr)) return DRQ_EARG;
   }
   const long t64 = (long)(M / 64) * (N / 64) * nbatch;
-#ifdef DRQ_DEV
-  static const char* const dbg = getenv("DRQ_G3_DBG");          // development build only (tools/gemm3_bench.py)
-  const int d = dbg ? atoi(dbg) : 0;
-  if (d & 1) g.a_bytes = g.b_bytes = 0;                         // every copy dropped: MFMA + LDS + barrier time only
-  g.dbg = d >> 4;
-  if (d & 2) {                                                  // deeper ring
-    if (nq_out) *nq_out = N / 64;
-    hipLaunchKernelGGL((gemm3_kernel<0, 2, 2, 1, 9>), dim3((M / 64) * (N / 64), 1, nbatch), dim3(256), 0, st, g);
-    DRQ_LAUNCH_CHECK();
-    return DRQ_OK;
-  }
-  if (d & 4) {                                                  // shallow ring
-    if (nq_out) *nq_out = N / 64;
-    hipLaunchKernelGGL((gemm3_kernel<0, 2, 2, 1, 4>), dim3((M / 64) * (N / 64), 1, nbatch), dim3(256), 0, st, g);
-    DRQ_LAUNCH_CHECK();
-    return DRQ_OK;
-  }
-#endif
   // enough 64x64 tiles to give every CU one: one sub-tile per wave; else 64x32 tiles with the k-steps of a k-tile
   // split over two wave groups (twice the workgroups, half the MFMAs per wave)
   if (t64 >= drq_num_cus()) {

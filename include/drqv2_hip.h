@@ -10,8 +10,7 @@
  *   - no allocation and no state that outlives a call, except two host-side caches indexed by the current HIP
  *     device: the CU count, and "dynamic-LDS attribute already set" flags of the weight-gradient kernels;
  *   - the library is built with -fvisibility=hidden: the functions declared here are ALL it exports
- *     (tests/test_cpu_interface.py checks both directions); development ablations and time-stamp hooks exist only
- *     in the -DDRQ_DEV build that tools/ makes for itself (drqv2_amd.build --dev -> libdrqv2_hip_dev.so);
+ *     (tests/test_cpu_interface.py checks both directions);
  *   - tensors are fp32 row-major / NCHW unless stated.
  */
 #ifndef DRQV2_HIP_H

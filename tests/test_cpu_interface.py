@@ -204,7 +204,7 @@ def test_c_abi_exports_every_declared_symbol():
     assert set(_lib.PROTOTYPES) == declared
     assert lib.drq_abi_version() == 7
     # ... and the other direction: the product library exports NOTHING named drq* beyond the header (internal helpers
-    # have hidden visibility; the development hooks drq_dev_* exist only in the -DDRQ_DEV build of tools/)
+    # have hidden visibility)
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True)
     exported = {ln.split()[-1] for ln in out.stdout.splitlines() if ln.strip()}

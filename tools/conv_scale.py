@@ -19,5 +19,5 @@ for nb in (128, 256, 512, 1024, 2048, 4096):
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / n
     fl = nb * 39 * 39 * 32 * 32 * 9 * 2
-    print(f"variant={os.environ.get('DRQ_CONV_VARIANT','0')} nb={nb:5d} {us:8.1f} us {fl/us/1e6:7.1f} TFLOP/s", flush=True)
+    print(f"nb={nb:5d} {us:8.1f} us {fl/us/1e6:7.1f} TFLOP/s", flush=True)
     del x

@@ -29,7 +29,7 @@ def timeit(fn, reps=50, warm=10):
 
 
 def main():
-    lib = _lib.load(dev=bool(os.environ.get('DRQ_G3_DBG')))
+    lib = _lib.load()
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     rn = lambda *s: torch.randn(*s, device=dev, generator=g)
@@ -37,8 +37,6 @@ def main():
     st = _stream()
     wsb = torch.empty(16 * 1024 * 1024, device=dev)
     shapes = ((4, 256), (2, 256), (1, 512), (4, 512), (2, 64), (4, 64), (2, 32))
-    if os.environ.get('DRQ_G3_DBG'):
-        shapes = ((4, 256), (4, 64), (2, 256))
     for n, M in shapes:
         xs = [rn(M, H) for _ in range(n)]
         ws = [rn(H, H) / 32 for _ in range(n)]

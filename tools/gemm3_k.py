@@ -7,7 +7,7 @@ from drqv2_amd import _lib
 from drqv2_amd.ops import _ptr_array, _stream
 from gemm3_bench import timeit
 
-lib = _lib.load(dev=bool(os.environ.get('DRQ_G3_DBG')))
+lib = _lib.load()
 dev = "cuda"
 st = _stream()
 n, M, N = 4, 256, 1024
