@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 import utils
-from drqv2_amd import _lib, ops
+from drqv2_amd import _lib, autograd, ops
 from drqv2_amd.engine import StepEngine, shard_bounds
 from torch.distributions.utils import _standard_normal
 
@@ -37,7 +37,8 @@ class RandomShiftsAug(nn.Module):
         n, c, h, w = x.size()
         assert h == w
         shift = self.draw(n, x.device, torch.float32)
-        return ops.random_shifts_aug(x.contiguous(), shift, self.pad)
+        # differentiable in a float frame (drqv2_amd.autograd: the input gradient runs on drq_aug_bwd_f32)
+        return autograd.random_shifts_aug(x.contiguous(), shift, self.pad)
 
 
 class Encoder(nn.Module):
@@ -52,26 +53,21 @@ class Encoder(nn.Module):
         self.apply(utils.weight_init)
 
     def forward(self, obs):
-        """obs: uint8 or float [B,C,84,84] on the GPU -> [B, 39200] (inference path, drqv2.py:63-67)."""
+        """obs: uint8 or float [B,C,84,84] on the GPU -> [B, 39200] (drqv2.py:63-67), differentiable in the conv
+        parameters and in a float obs (drqv2_amd.autograd.EncoderFn)."""
         if obs.dtype == torch.uint8:
             x = ops.u8_normalize(obs.contiguous())
         else:
             x = (obs.float() / 255.0 - 0.5).contiguous()
-        for li, i in enumerate((0, 2, 4, 6)):
-            conv = self.convnet[i]
-            x = ops.conv3x3_fwd(x, conv.weight.data, conv.bias.data, 2 if li == 0 else 1, relu=True)
-        return x.view(x.shape[0], -1)
+        return autograd.encoder(self, x)
 
 
 def _trunk(seq, obs):
-    z = ops.linear_fwd(obs.contiguous(), seq[0].weight.data, seq[0].bias.data)
-    return ops.ln_tanh_fwd(z, seq[1].weight.data, seq[1].bias.data, save=False)[0]
+    return autograd.trunk(seq, obs.contiguous())
 
 
-def _mlp3(seq, x):
-    x = ops.linear_fwd(x, seq[0].weight.data, seq[0].bias.data, relu=True)
-    x = ops.linear_fwd(x, seq[2].weight.data, seq[2].bias.data, relu=True)
-    return ops.linear_fwd(x, seq[4].weight.data, seq[4].bias.data)
+def _mlp3(seq, x, tanh_out=False):
+    return autograd.mlp3(seq, x, tanh_out)
 
 
 class Actor(nn.Module):
@@ -84,7 +80,7 @@ class Actor(nn.Module):
         self.apply(utils.weight_init)
 
     def forward(self, obs, std):
-        mu = ops.tanh(_mlp3(self.policy, _trunk(self.trunk, obs)))
+        mu = _mlp3(self.policy, _trunk(self.trunk, obs), tanh_out=True)
         return utils.TruncatedNormal(mu, torch.ones_like(mu) * std)
 
 

@@ -90,6 +90,10 @@ PROTOTYPES = {
     "drq_u8_normalize": (I, [P, P, L, P]),
     "drq_nstep_gather": (I, [P, P, P, P, P, I, I, L, I, F, P, P, P, P, P, P]),
     "drq_tanh": (I, [P, P, L, P]),
+    "drq_relu_mask_pad": (I, [P, P, P, L, I, I, P]),
+    "drq_conv1_dgrad": (I, [P, P, P, I, P]),
+    "drq_aug_bwd_f32": (I, [P, P, P, P, I, I, I, I, P]),
+    "drq_tanh_bwd": (I, [P, P, P, L, P]),
     "drq_param_layout": (I, [I, I, I, I, C.POINTER(L), I]),
     "drq_step_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_step_ws_offset": (L, [I, I, I, I, I, I]),

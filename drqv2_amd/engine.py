@@ -14,11 +14,20 @@ NETS = ("enc", "critic", "actor", "target")
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (defaults; drqv2.py:148-150) over one contiguous segment of the
     parameter arena.  `step()` is one fused launch; inside DrQV2Agent.update() the same kernel is
-    issued by the step library, which advances `t` through `begin_step()`."""
+    issued by the step library, which advances `t` through `begin_step()`.
 
-    def __init__(self, params, lr, seg_p, seg_g, seg_m, seg_v):
-        super().__init__(list(params), dict(lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False))
+    The reference's own loop -- `opt.zero_grad(); loss.backward(); opt.step()` over the modules' autograd
+    (drqv2_amd.autograd) -- works on the arenas: every parameter's `.grad` is a view of this segment of the gradient
+    arena, autograd accumulates into a defined `.grad` in place, zero_grad() clears the segment and step() reads it.
+    update() calls neither method (its kernels overwrite the segment), so it is unaffected by them."""
+
+    def __init__(self, params, lr, seg_p, seg_g, seg_m, seg_v, grad_views=None, flush=None):
+        params = list(params)
+        super().__init__(params, dict(lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False))
         self._p, self._g, self._m, self._v = seg_p, seg_g, seg_m, seg_v
+        # (parameter, its view of the gradient arena), parameters() order; flush: finishes deferred data-parallel steps
+        self._views = list(zip(params, grad_views)) if grad_views is not None else []
+        self._flush = flush
         self.t = 0
 
     @property
@@ -30,12 +39,39 @@ class FlatAdam(torch.optim.Optimizer):
         return self.t
 
     def zero_grad(self, set_to_none=True):
-        # gradients are overwritten (never accumulated) by the backward kernels
-        return None
+        """Zero the gradient segment for a following backward, after finishing any data-parallel step the last
+        update() deferred (it reads this segment).  `set_to_none` is accepted and ignored: the gradients stay views
+        of the arena (zeroed, not None), and a view a module's own `nn.Module.zero_grad()` dropped is re-attached.
+        update() does not need this call (its kernels overwrite the segment)."""
+        if self._flush is not None:
+            self._flush()
+        with torch.no_grad():
+            self._g.zero_()
+        for p, view in self._views:
+            if p.grad is not view:
+                p.grad = view
+
+    def _fold_grads(self):
+        """A parameter whose `.grad` is no longer its arena view (set to None by nn.Module.zero_grad() and then
+        assigned afresh by autograd, or replaced by the user) has its gradient copied into the arena -- None counts
+        as zero -- and the view re-attached."""
+        with torch.no_grad():
+            for p, view in self._views:
+                g = p.grad
+                if g is view:
+                    continue
+                if g is None:
+                    view.zero_()
+                elif not (g.data_ptr() == view.data_ptr() and g.shape == view.shape):
+                    view.copy_(g)
+                p.grad = view
 
     @torch.no_grad()
     def step(self, closure=None, gscale=1.0, tgt=None, tau=0.0):
+        """Adam over the segment with the gradients now in it (see _fold_grads).  Rank-local: with data parallelism
+        a backward of the user's own is not exchanged between the ranks (update() exchanges its own gradients)."""
         from . import ops
+        self._fold_grads()
         ops.adam_flat(self._p, self._g, self._m, self._v, self.lr, self.begin_step(), gscale, tgt, tau)
 
     # snapshot helpers (train.py:192-204 pickles the agent)
@@ -293,11 +329,13 @@ class StepEngine:
         self.adam_m = torch.zeros(total, device=dev, dtype=torch.float32)
         self.adam_v = torch.zeros(total, device=dev, dtype=torch.float32)
         self.modules = {"enc": encoder, "critic": critic, "actor": actor, "target": critic_target}
+        self._grad_views = {}     # net -> the gradient-arena views its parameters' .grad were set to
         for name, mod in self.modules.items():
             self._adopt(name, mod)
         seg = self.layout["seg"]
         mk = lambda n, mod: FlatAdam(mod.parameters(), lr, *(a[seg[n][0]:seg[n][1]] for a in
-                                                            (self.params, self.grads, self.adam_m, self.adam_v)))
+                                                            (self.params, self.grads, self.adam_m, self.adam_v)),
+                                     grad_views=self._grad_views[n], flush=self.flush)
         self.encoder_opt = mk("enc", encoder)
         self.actor_opt = mk("actor", actor)
         self.critic_opt = mk("critic", critic)
@@ -339,6 +377,7 @@ class StepEngine:
         offs = self.layout[name]
         plist = list(mod.parameters())
         assert len(plist) == len(offs), (name, len(plist), len(offs))
+        views = []
         with torch.no_grad():
             for p, off in zip(plist, offs):
                 n = p.numel()
@@ -347,6 +386,8 @@ class StepEngine:
                 p.data = view
                 if name != "target":
                     p.grad = self.grads[off:off + n].view(p.shape)
+                    views.append(p.grad)
+        self._grad_views[name] = views
         b, e = self.layout["seg"][name]
         mod._drq_segment = self.params[b:e]
 

@@ -118,8 +118,10 @@ def conv3x3_fwd(x, w, b, stride, relu=True, bf16=False, wino=False):
     return y
 
 
-def conv3x3_dgrad(dy_pad, w, mask, bf16=False, wino=False):
-    """dy_pad [nb,32,hout+4,hout+4] (zero border of 2) -> dx [nb,32,hout+2,hout+2] * (mask>0)."""
+def conv3x3_dgrad(dy_pad, w, mask, bf16=False, wino=False, pad_out=False):
+    """dy_pad [nb,32,hout+4,hout+4] (zero border of 2) -> dx [nb,32,hout+2,hout+2] * (mask>0).
+    pad_out (Winograd form): dx is returned in the same padded layout, [nb,32,hout+6,hout+6] with a zero border of 2,
+    ready to be the next (shallower) layer's dy_pad."""
     lib = _lib.load()
     _need(dy_pad, name="dy_pad"), _need(w, name="w")
     nb, _, hp, _ = dy_pad.shape
@@ -128,6 +130,14 @@ def conv3x3_dgrad(dy_pad, w, mask, bf16=False, wino=False):
     if mask is not None:
         _need(mask, name="mask")
         assert tuple(mask.shape) == (nb, 32, hin, hin)
+    if pad_out:
+        if not wino:
+            raise _lib.DrqError("conv3x3_dgrad: pad_out is implemented for the Winograd form")
+        hpi = hin + 4
+        dx = torch.zeros((nb, 32, hpi, hpi), device=dy_pad.device, dtype=torch.float32)
+        check(lib.drq_conv3x3_dgrad_wino(ptr(dy_pad), ptr(w), ptr(mask), ptr(dx), nb, hout, 32 * hpi * hpi, hpi * hpi, hpi,
+                                         2 * hpi + 2, _stream()), "drq_conv3x3_dgrad_wino")
+        return dx
     dx = torch.empty((nb, 32, hin, hin), device=dy_pad.device, dtype=torch.float32)
     if wino:
         check(lib.drq_conv3x3_dgrad_wino(ptr(dy_pad), ptr(w), ptr(mask), ptr(dx), nb, hout, 32 * hin * hin, hin * hin, hin,
@@ -142,8 +152,9 @@ def conv3x3_dgrad(dy_pad, w, mask, bf16=False, wino=False):
     return dx
 
 
-def conv3x3_wgrad(x, dy, stride, bf16=False, wino=False):
-    """x [nb,cin,hin,hin], dy [nb,32,hout,hout] (any strides with unit x-stride) -> dw, db."""
+def conv3x3_wgrad(x, dy, stride, bf16=False, wino=False, ws=None):
+    """x [nb,cin,hin,hin], dy [nb,32,hout,hout] (any strides with unit x-stride) -> dw, db.
+    ws: an fp32 workspace of at least drq_conv3x3_wgrad_ws_bytes() to use instead of a fresh one."""
     lib = _lib.load()
     _need(x, name="x")
     if not (dy.is_cuda and dy.dtype == torch.float32 and dy.stride(3) == 1):
@@ -152,7 +163,10 @@ def conv3x3_wgrad(x, dy, stride, bf16=False, wino=False):
     dw = torch.empty((32, cin, 3, 3), device=x.device, dtype=torch.float32)
     db = torch.empty((32,), device=x.device, dtype=torch.float32)
     nbytes = lib.drq_conv3x3_wgrad_ws_bytes()
-    ws = torch.empty((nbytes // 4,), device=x.device, dtype=torch.float32)
+    if ws is None:
+        ws = torch.empty((nbytes // 4,), device=x.device, dtype=torch.float32)
+    elif ws.numel() * 4 < nbytes:
+        raise _lib.DrqError("conv3x3_wgrad: workspace too small")
     if wino:        # dy must be the interior view of a buffer zero-padded by 2 (the kernel reads the padding as zeros)
         check(lib.drq_conv3x3_wgrad_wino(ptr(x), dy.data_ptr(), ptr(dw), ptr(db), nb, hin, dy.stride(0), dy.stride(1),
                                          dy.stride(2), 0, ptr(ws), nbytes, _stream()), "drq_conv3x3_wgrad_wino")
@@ -231,7 +245,8 @@ def conv3x3_wgrad_bf16_nhwc(x_nhwc, dy):
 
 
 def gemm(A, a_kc, B, b_kc, M, N, K, lda=None, ldb=None, bias=None, relu=False, aux=None, nbatch=1, a_bs=0,
-         b_bs=0, c_bs=None, bias_bs=0, aux_bs=0, tile=0, splitk=0, out=None, ldc=None):
+         b_bs=0, c_bs=None, bias_bs=0, aux_bs=0, tile=0, splitk=0, out=None, ldc=None, ws=None):
+    """ws: an fp32 split-K workspace to use (e.g. one kept across calls); None: a fresh 64 MB one."""
     lib = _lib.load()
     dev = A.device
     lda = lda if lda is not None else (K if a_kc else M)
@@ -240,7 +255,8 @@ def gemm(A, a_kc, B, b_kc, M, N, K, lda=None, ldb=None, bias=None, relu=False, a
     c_bs = c_bs if c_bs is not None else M * N
     if out is None:
         out = torch.empty((nbatch, M, N) if nbatch > 1 else (M, N), device=dev, dtype=torch.float32)
-    ws = torch.empty((16 * 1024 * 1024,), device=dev, dtype=torch.float32)
+    if ws is None:
+        ws = torch.empty((16 * 1024 * 1024,), device=dev, dtype=torch.float32)
     check(lib.drq_gemm_f32(ptr(A), lda, int(a_kc), ptr(B), ldb, int(b_kc), ptr(out), ldc, M, N, K, nbatch, a_bs, b_bs,
                            c_bs, ptr(bias), bias_bs, int(relu), ptr(aux), (aux.shape[-1] if aux is not None else 0),
                            aux_bs, 0, tile, splitk, ptr(ws), ws.numel() * 4, _stream()), "drq_gemm_f32")
@@ -316,6 +332,53 @@ def tanh(x):
     y = torch.empty_like(x)
     check(lib.drq_tanh(ptr(x), ptr(y), x.numel(), _stream()), "drq_tanh")
     return y
+
+
+def tanh_bwd(y, dy):
+    """dy * (1 - y^2): the gradient through y = tanh(x)."""
+    lib = _lib.load()
+    _need(y, name="y"), _need(dy, name="dy")
+    dx = torch.empty_like(y)
+    check(lib.drq_tanh_bwd(ptr(y), ptr(dy), ptr(dx), y.numel(), _stream()), "drq_tanh_bwd")
+    return dx
+
+
+def relu_mask_pad(dy, mask, pad=2):
+    """dy [n,c,h,h] -> [n,c,h+2pad,h+2pad]: dy where mask > 0 (mask None: all of it), zero elsewhere and on the border."""
+    lib = _lib.load()
+    _need(dy, name="dy")
+    n, c, h, _ = dy.shape
+    if mask is not None:
+        _need(mask, name="mask")
+        assert mask.shape == dy.shape
+    out = torch.empty((n, c, h + 2 * pad, h + 2 * pad), device=dy.device, dtype=torch.float32)
+    check(lib.drq_relu_mask_pad(ptr(dy), ptr(mask), ptr(out), n * c, h, pad, _stream()), "drq_relu_mask_pad")
+    return out
+
+
+def conv1_dgrad(dy_pad, w):
+    """dy_pad [nb,32,45,45] (conv1's pre-activation gradient, zero border of 2), w [32,9,3,3] -> dx [nb,9,84,84]."""
+    lib = _lib.load()
+    _need(dy_pad, name="dy_pad"), _need(w, name="w")
+    nb = dy_pad.shape[0]
+    if tuple(dy_pad.shape[1:]) != (32, 45, 45) or tuple(w.shape) != (32, 9, 3, 3):
+        raise _lib.DrqError("conv1_dgrad: dy_pad [nb,32,45,45] and w [32,9,3,3] required")
+    dx = torch.empty((nb, 9, 84, 84), device=dy_pad.device, dtype=torch.float32)
+    check(lib.drq_conv1_dgrad(ptr(dy_pad), ptr(w), ptr(dx), nb, _stream()), "drq_conv1_dgrad")
+    return dx
+
+
+def aug_bwd_f32(dy, shift, pad=4, base=None):
+    """Input gradient of random_shifts_aug on a float frame: dy [n,c,h,h], shift [n,2] / [n,1,1,2] -> dx."""
+    lib = _lib.load()
+    _need(dy, name="dy")
+    n, c, h, w = dy.shape
+    assert h == w
+    shift = _need(shift.reshape(n, 2), name="shift")
+    base = aug_base_grid(h, pad, dy.device) if base is None else _need(base, name="base")
+    dx = torch.empty_like(dy)
+    check(lib.drq_aug_bwd_f32(ptr(dy), ptr(shift), ptr(base), ptr(dx), n, c, h, pad, _stream()), "drq_aug_bwd_f32")
+    return dx
 
 
 def _ptr_array(ts):

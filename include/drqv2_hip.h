@@ -275,6 +275,23 @@ int drq_tanh(const float* x, float* y, long n, drq_stream_t stream);
 int drq_rng_draws(unsigned long long seed, unsigned long long offset, int n_shift, int n_noise, int range,
                   float* shift_obs, float* shift_next, float* noise_critic, float* noise_actor, drq_stream_t stream);
 
+/* ---- autograd of the modules (drqv2_amd/autograd.py: Encoder / Actor / Critic / RandomShiftsAug forwards as
+ * differentiable ops for user losses; update() does not use these).  Deterministic gather forms, no atomics.
+ * drq_relu_mask_pad: out [planes][h+2pad][h+2pad] = dy [planes][h][h] where mask > 0 (mask NULL: everywhere), zero
+ *   elsewhere and on the border -- the encoder output's gradient in the padded layout the conv gradients read.
+ * drq_conv1_dgrad: input gradient of the first encoder layer Conv2d(9,32,3,stride 2) (drqv2.py:55): dy_pad
+ *   [nb][32][45][45] = the pre-activation gradient [41][41] with a zero border of 2, w [32][9][3][3], dx [nb][9][84][84]
+ *   (8-byte aligned); row and column 83 receive no tap and are 0.
+ * drq_aug_bwd_f32: input gradient of drq_aug_fwd_f32 (RandomShiftsAug on a float frame): dy [n][c][hw][hw] -> dx, the
+ *   adjoint of the forward's bilinear taps with the forward's own fp32 weights; shift_xy / base_grid as there, shifts
+ *   integers in [0, 2*pad], pad <= 5.
+ * drq_tanh_bwd: dx = dy * (1 - y*y) for y = tanh(x) (the policy output, drqv2.py:89). */
+int drq_relu_mask_pad(const float* dy, const float* mask, float* out, long planes, int h, int pad, drq_stream_t stream);
+int drq_conv1_dgrad(const float* dy_pad, const float* w, float* dx, int nb, drq_stream_t stream);
+int drq_aug_bwd_f32(const float* dy, const float* shift_xy, const float* base_grid, float* dx, int n, int c, int hw,
+                    int pad, drq_stream_t stream);
+int drq_tanh_bwd(const float* y, const float* dy, float* dx, long n, drq_stream_t stream);
+
 /* ---- whole-step entry: DrQV2Agent.update (drqv2.py:230-262) ------------------------------------ */
 typedef struct {
   int B, global_B, C, A, F, H;
