@@ -106,6 +106,12 @@ PROTOTYPES = {
 WS_IDS = ["AUG", "ACT1", "ACT2", "ACT3", "FEAT", "Z_NEXT", "Z_OBS", "HA_T", "HA_C", "H_AN", "H_AO", "Q", "TQ",
           "DQ", "MU_O", "DY4", "DY3", "DY2", "DY1", "DZ_C", "DZ_A", "HA_C2", "P1", "P2", "C1", "C2"]
 
+# ids of drq_update_phase (the DRQ_PHASE_* enum of include/drqv2_hip.h, where each is described)
+PHASE_ALL, PHASE_CRITIC, PHASE_ACTOR, PHASE_OPT = -1, 0, 1, 2
+PHASE_ENCODE, PHASE_CRITIC_HEADS, PHASE_CONV_BACKWARD, PHASE_ACTOR_FORWARD, PHASE_ACTOR_BACKWARD = 3, 4, 5, 6, 7
+PHASE_ENCODER_OPT, PHASE_ACTOR_OPT = 8, 9
+PHASE_CRITIC_OPT, PHASE_ACTOR_LOSS, PHASE_POLYAK, PHASE_REDRAW = 10, 11, 12, 13
+
 _lib = None
 
 

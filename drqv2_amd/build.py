@@ -53,7 +53,8 @@ def build(force=False, verbose=True):
         if p.wait() != 0:
             raise RuntimeError(f"hipcc failed for {obj}")
         objs.append(obj)
-    # -z defs: an internal entry point declared with the wrong linkage fails here, not at dlopen on the GPU box
+    # -z defs: an internal launcher (csrc/internal.h, C++ linkage) whose definition drifted from its declaration has no
+    # symbol under the declared signature and fails here, not at dlopen on the GPU box
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

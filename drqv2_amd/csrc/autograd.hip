@@ -159,8 +159,6 @@ inline unsigned grid_cap(long n) {
 
 }  // namespace
 
-extern "C" {
-
 DRQ_API int drq_relu_mask_pad(const float* dy, const float* mask, float* out, long planes, int h, int pad,
                               hipStream_t st) {
   if (!dy || !out || planes <= 0 || h <= 0 || pad < 0) return DRQ_EARG;
@@ -198,5 +196,3 @@ DRQ_API int drq_tanh_bwd(const float* y, const float* dy, float* dx, long n, hip
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }
-
-}  // extern "C"

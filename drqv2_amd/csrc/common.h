@@ -4,8 +4,9 @@
 #include <stdint.h>
 
 // The library is built with -fvisibility=hidden: only the entry points declared in include/drqv2_hip.h carry
-// DRQ_API and are exported; everything else (kernels' host stubs, cross-file helpers) stays internal.
-#define DRQ_API __attribute__((visibility("default")))
+// DRQ_API, which exports them with C linkage; everything else (kernels' host stubs, the cross-file launchers of
+// internal.h) stays hidden and keeps C++ linkage.
+#define DRQ_API extern "C" __attribute__((visibility("default")))
 
 #define DRQ_OK 0
 #define DRQ_EARG (-1)      // bad argument / unsupported shape

@@ -23,6 +23,7 @@
 // registers.  Partials: 4 waves -> LDS -> one record per workgroup -> fixed-order reduction kernel
 // (deterministic, no float atomics).
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -839,10 +840,6 @@ int launch_wgrad(const WgradArgs& a0, float* dw, float* db, float* ws, size_t ws
 
 }  // namespace
 
-// conv_wino_wgrad.hip
-int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
-
 // ---- internal entry points of the step orchestration (step.hip): per-layer partial sums now, one reduction later
 int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, long dy_bs,
                               long dy_cs, long dy_rs, long dy_off, float* part, size_t part_bytes, int* nblocks,
@@ -882,8 +879,6 @@ int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* n
 // ------------------------------------------------------------------------------------------------
 // C ABI (declared in include/drqv2_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" {
-
 // y = relu?(conv3x3(x, w) + bias); x [nb][cin][hin][hin], y written with the given strides.
 DRQ_API int drq_conv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int nb, int cin, int hin,
                     int stride, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
@@ -955,5 +950,3 @@ DRQ_API int drq_conv3x3_wgrad_wino(const float* x, const float* dy, float* dw, f
 }
 
 DRQ_API size_t drq_conv3x3_wgrad_ws_bytes(void) { return (size_t)1024 * (9 * 1024 + 64) * sizeof(float); }
-
-}  // extern "C"

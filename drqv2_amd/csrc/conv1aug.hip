@@ -18,6 +18,7 @@
 // k order and accumulation order are those of conv3x3_kernel<9,84,2>: the results are bit-identical to the
 // unfused path (tests/test_hip_ops.py).
 #include "common.h"
+#include "internal.h"
 #include "wino_u.h"
 
 namespace {
@@ -458,8 +459,6 @@ int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, co
   return DRQ_OK;
 }
 
-extern "C" {
-
 DRQ_API int drq_conv1_aug_fwd(const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                               const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
                               int n_store, hipStream_t st) {
@@ -488,5 +487,3 @@ DRQ_API int drq_conv1_aug_fwd_bf16_nhwc(const uint8_t* obs, const float* shift, 
   return drq_conv1_aug_fwd_any(2, obs, shift, obs1, shift1, base_grid, w, bias, xaug, (float*)y_nhwc, n, n_store, st,
                                nullptr, nullptr, nullptr, nullptr);
 }
-
-}  // extern "C"

@@ -31,6 +31,7 @@
 // (round-to-nearest is monotone, so it commutes with ReLU and keeps the sign the mask tests); tests compare with LAY = 0.
 // LAY bits: 1 = input in that layout, 2 = output in that layout, 4 = mask in that layout.
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -524,10 +525,6 @@ int launch_wgrad_bf16(const WgradBfArgs& a0, float* ws, size_t ws_bytes, int* nb
 
 }  // namespace
 
-// conv.hip (internal): fixed-order reduction of the partial records of up to four layers
-int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* nblocks, const int* cin,
-                                   float* const* dw, float* const* db, hipStream_t st);
-
 // ---- internal (step.hip) and C ABI: the same launches with the bf16 channel-contiguous layout on some operands -----
 // x: bf16 [nb][hin][hin][32] when lay & 1, else fp32 NCHW; y: bf16 [nb][hout][hout][32] when lay & 2 (the strides are
 // ignored), else fp32 with the given strides
@@ -584,8 +581,6 @@ int drq_conv3x3_dgrad_bf16_lay(const void* dy_pad, const float* w, const void* m
 }
 
 // ---- C ABI (include/drqv2_hip.h), argument meaning as the fp32 entries of conv.hip ------------------------------
-extern "C" {
-
 DRQ_API int drq_conv3x3_fwd_bf16_nhwc(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
                                       int x_nhwc, int y_nhwc, hipStream_t st) {
   const int hout = hin - 2;
@@ -610,7 +605,6 @@ DRQ_API int drq_conv3x3_dgrad_bf16(const float* dy_pad, const float* w, const fl
   return drq_conv3x3_dgrad_bf16_lay(dy_pad, w, mask, dx, nb, hout, dx_bs, dx_cs, dx_rs, dx_off, 0, st);
 }
 
-}  // extern "C"
 
 // internal (step.hip): partial records only; one reduction launch serves all layers
 // lay bits: 1 = x is bf16 [nb][hin][hin][32] instead of fp32 NCHW; 2 = dy is the bf16 [nb][hin+2][hin+2][32] buffer
@@ -639,7 +633,7 @@ int drq_conv3x3_wgrad_partial_bf16(const float* x, const float* dy, int nb, int 
   return drq_conv3x3_wgrad_partial_bf16_lay(x, dy, nb, hin, dy_bs, dy_cs, dy_rs, dy_off, part, part_bytes, nblocks, 0, st);
 }
 
-extern "C" DRQ_API int drq_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw, float* db, int nb, int hin,
+DRQ_API int drq_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw, float* db, int nb, int hin,
                                               long dy_bs, long dy_cs, long dy_rs, long dy_off, float* ws, size_t ws_bytes,
                                               hipStream_t st) {
   if (!dw || !db || !ws) return DRQ_EARG;
@@ -652,7 +646,7 @@ extern "C" DRQ_API int drq_conv3x3_wgrad_bf16(const float* x, const float* dy, f
   return drq_conv3x3_wgrad_reduce_multi(1, parts, &nblk, cins, dws, dbs, st);
 }
 
-extern "C" DRQ_API int drq_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dy, float* dw, float* db, int nb, int hin,
+DRQ_API int drq_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dy, float* dw, float* db, int nb, int hin,
                                                    int dy_nhwc, long dy_bs, long dy_cs, long dy_rs, long dy_off, float* ws,
                                                    size_t ws_bytes, hipStream_t st) {
   if (!dw || !db || !ws) return DRQ_EARG;

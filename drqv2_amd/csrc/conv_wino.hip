@@ -14,6 +14,7 @@
 // transforms it in registers and feeds the 16 positions.  U = G g G^T is computed once per workgroup into LDS in
 // MFMA-lane order (one ds_read_b64 per position and k-step serves both cout halves).
 #include "common.h"
+#include "internal.h"
 #include "wino_u.h"
 #include <type_traits>
 
@@ -358,8 +359,6 @@ int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float*
   return DRQ_EARG;
 }
 
-extern "C" {
-
 // Same contract as drq_conv3x3_fwd (conv.hip) for cin = 32, stride 1, in Winograd form (rounding differs).
 DRQ_API int drq_conv3x3_fwd_wino(const float* x, const float* w, const float* bias, float* y, int nb, int hin, int relu,
                                  long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
@@ -371,5 +370,3 @@ DRQ_API int drq_conv3x3_dgrad_wino(const float* dy_pad, const float* w, const fl
                                    long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st) {
   return drq_conv3x3_dgrad_wino_pre(dy_pad, w, nullptr, mask, dx, nb, hout, dx_bs, dx_cs, dx_rs, dx_off, st);
 }
-
-}  // extern "C"

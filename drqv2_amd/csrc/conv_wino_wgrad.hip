@@ -17,6 +17,7 @@
 // writes ONE partial record in the format of conv3x3_wgrad3_kernel (conv.hip): the same fixed-order reduction kernel
 // finishes the job (deterministic, no float atomics).
 #include "common.h"
+#include "internal.h"
 
 namespace {
 

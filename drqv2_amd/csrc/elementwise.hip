@@ -5,6 +5,7 @@
 //   bias-gradient column sums, Adam (torch/optim/adam.py) with optional fused Polyak (utils.py:42-45).
 // All reductions are fixed-order (no float atomics): results are run-to-run bit-stable.
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -1166,24 +1167,6 @@ inline unsigned grid_for(long n, int block = 256) {
 
 }  // namespace
 
-extern "C" {
-
-int drq_ln_tanh_fwd_multi_ex(int n, const float* const* z, int ldz, const float* const* gamma,
-                             const float* const* beta, float* const* out, const int* ldo, float* const* xhat,
-                             float* const* rstd, int rows, int F, const float* const* tail, const int* tail_ld,
-                             int tail_n, hipStream_t st);
-int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
-                      float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B, float* sums_host,
-                      unsigned seq, hipStream_t st);
-int drq_ln_tanh_fwd_multi_part(int n, const float* const* z, int ldz, const float* const* gamma,
-                               const float* const* beta, float* const* out, const int* ldo, float* const* xhat,
-                               float* const* rstd, int rows, int F, const float* const* tail, const int* tail_ld,
-                               int tail_n, const float* part, const float* const* bias, int splitk, hipStream_t st);
-int drq_ln_tanh_bwd_part(const float* dh0, int ld0, const float* dh1, int ld1, const float* h, int ldh,
-                         const float* xhat, const float* rstd, const float* gamma, float* dz, float* dln,
-                         float* dgamma, float* dbeta, int rows, int F, const float* part, int splitk, int nprob,
-                         int ldp, hipStream_t st);
-
 DRQ_API int drq_aug_fwd(const uint8_t* obs, const float* shift_xy, const float* base_grid, float* out, int n, int c,
                 int hw, int pad, int fuse_norm, hipStream_t st) {
   if (!obs || !shift_xy || !base_grid || !out || n <= 0 || c <= 0 || hw <= 0 || pad < 0) return DRQ_EARG;
@@ -1285,7 +1268,6 @@ DRQ_API int drq_qout_fwd(int nz, const float* const* h, const float* const* w, c
   return DRQ_OK;
 }
 
-}  // extern "C"
 namespace {
 // 64 columns per workgroup below 1,024 rows, 16 beyond (see qout_bwd_kernel)
 void launch_qout_bwd(const QOutBwdArgs& a, int nz, size_t lds, hipStream_t st) {
@@ -1293,7 +1275,6 @@ void launch_qout_bwd(const QOutBwdArgs& a, int nz, size_t lds, hipStream_t st) {
   else hipLaunchKernelGGL(qout_bwd_kernel<64>, dim3((a.H + 63) / 64, nz), dim3(1024), lds, st, a);
 }
 }  // namespace
-extern "C" {
 
 // dh = (dq w^T) * (h > 0);  dw = dq^T h, db = sum dq when the dw/db arrays are given
 DRQ_API int drq_qout_bwd(int nz, const float* const* dq, const float* const* h, const float* const* w, float* const* dh,
@@ -1612,5 +1593,3 @@ DRQ_API int drq_fill(float* p, long n, float v, hipStream_t st) {
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }
-
-}  // extern "C"

@@ -12,6 +12,8 @@
 // conflict-free MFMA operand reads) -> MFMA.  Split-K writes dense partials; a second kernel sums them
 // in a fixed order (deterministic) and applies the epilogue.
 #include "common.h"
+#include "internal.h"
+#include "../../include/drqv2_hip.h"
 #include <type_traits>
 
 namespace {
@@ -607,22 +609,6 @@ int launch_bf16(const GemmArgs& g, bool v4, hipStream_t st) {
 
 }  // namespace
 
-// elementwise.hip (C ABI): out[n] = sum_m dy[m*ld + n]
-extern "C" int drq_colsum(const float* dy, long ld, long dy_bs, float* out, long out_bs, int M, int N, int nbatch,
-                          hipStream_t st);
-// skinny.hip
-int drq_skinny_dgrad(const float* dz, long lda, const float* w, long ldb, float* c, long ldc, int M, int N, int K,
-                     const float* aux, int ldaux, int scatter_hw, hipStream_t st);
-
-// gemm2.hip
-int drq_trunk_wgrad(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                    float* rowsum, hipStream_t st);
-int drq_trunk_fwd_partial(int nbatch, const float* const* A, long lda, const float* const* B, long ldb, int M, int N,
-                          int K, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st);
-int drq_gemm2(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb, int b_kc,
-              float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
-              const float* const* aux, int ldaux, float* const* rowsum, hipStream_t st);
-
 // bf16 != 0: the bf16-MFMA kernel for every shape (fp32 storage, operands rounded when staged); see gemm_bf16_kernel
 int drq_gemm_batched_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
                          int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
@@ -736,26 +722,23 @@ int drq_gemm_batched_any(int bf16, int nbatch, const float* const* A, long lda, 
   return tile == 2 ? dispatch<2, 2>(g, a_kc, b_kc, v4, st) : dispatch<1, 1>(g, a_kc, b_kc, v4, st);
 }
 
-extern "C" {
-
 // See include/drqv2_hip.h.  Host arrays of nbatch (<= 8) device pointers; bias/aux/rowsum arrays may be null.
 DRQ_API int drq_gemm_batched_f32(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
                          int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
                          const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int tile,
-                         int splitk, float* ws, size_t ws_bytes, hipStream_t st) {
+                         int splitk, float* ws, size_t ws_bytes, drq_stream_t stream) {
   return drq_gemm_batched_any(0, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, relu, aux, ldaux, rowsum,
-                              scatter_hw, tile, splitk, ws, ws_bytes, st);
+                              scatter_hw, tile, splitk, ws, ws_bytes, (hipStream_t)stream);
 }
 
 DRQ_API int drq_gemm_batched_bf16(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
                           int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
                           const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int splitk,
-                          float* ws, size_t ws_bytes, hipStream_t st) {
+                          float* ws, size_t ws_bytes, drq_stream_t stream) {
   return drq_gemm_batched_any(1, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, relu, aux, ldaux, rowsum,
-                              scatter_hw, 0, splitk, ws, ws_bytes, st);
+                              scatter_hw, 0, splitk, ws, ws_bytes, (hipStream_t)stream);
 }
 
-}  // extern "C"
 
 // internal (step.hip): the forward form with the split-K sum left to the caller, in either precision: a split-K
 // result stays in `ws` as partials [nbatch*splitk][M][N] (no bias, no epilogue) and *splitk_out says how many there
@@ -782,20 +765,18 @@ int drq_gemm_batched_partial_any(int bf16, int nbatch, const float* const* A, lo
   return rc;
 }
 
-extern "C" {
-
 DRQ_API int drq_gemm_batched_partial(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
                              int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias,
-                             float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st) {
+                             float* ws, size_t ws_bytes, int* splitk_out, drq_stream_t stream) {
   return drq_gemm_batched_partial_any(0, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, ws, ws_bytes,
-                                      splitk_out, st);
+                                      splitk_out, (hipStream_t)stream);
 }
 
 // strided-batch form of the same call
 DRQ_API int drq_gemm_f32(const float* A, long lda, int a_kc, const float* B, long ldb, int b_kc, float* C, long ldc,
                  int M, int N, int K, int nbatch, long a_bs, long b_bs, long c_bs, const float* bias, long bias_bs,
                  int relu, const float* aux, int ldaux, long aux_bs, int scatter_hw, int tile, int splitk,
-                 float* ws, size_t ws_bytes, hipStream_t st) {
+                 float* ws, size_t ws_bytes, drq_stream_t stream) {
   if (!A || !B || !C || nbatch <= 0 || nbatch > MAXB) return DRQ_EARG;
   const float *Ap[MAXB], *Bp[MAXB], *bp[MAXB], *xp[MAXB];
   float* Cp[MAXB];
@@ -805,7 +786,5 @@ DRQ_API int drq_gemm_f32(const float* A, long lda, int a_kc, const float* B, lon
     xp[b] = aux ? aux + b * aux_bs : nullptr;
   }
   return drq_gemm_batched_f32(nbatch, Ap, lda, a_kc, Bp, ldb, b_kc, Cp, ldc, M, N, K, bias ? bp : nullptr, relu,
-                              aux ? xp : nullptr, ldaux, nullptr, scatter_hw, tile, splitk, ws, ws_bytes, st);
+                              aux ? xp : nullptr, ldaux, nullptr, scatter_hw, tile, splitk, ws, ws_bytes, stream);
 }
-
-}  // extern "C"

@@ -21,6 +21,7 @@
 // that M*N/1024 tiles x 4 waves fill the chip.  Epilogue: bias, ReLU, ReLU mask, and the bias gradient of the
 // wgrad form (row sums of A).  drq_gemm_batched_f32 (gemm.hip) routes eligible calls here.
 #include "common.h"
+#include "internal.h"
 
 namespace {
 

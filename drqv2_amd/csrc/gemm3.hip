@@ -22,6 +22,7 @@
 // dx = (dy W) masked;  2 wgrad  dW = dy^T x with the bias gradient (row sums of dy^T) fused.
 // The weight gradient and the input gradient of one layer run as block ranges of ONE launch (gemm3_pair_kernel).
 #include "common.h"
+#include "internal.h"
 #include "../../include/drqv2_hip.h"
 
 namespace {
@@ -446,8 +447,6 @@ int drq_gemm3_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const f
   return DRQ_OK;
 }
 
-extern "C" {
-
 // See include/drqv2_hip.h
 DRQ_API int drq_mlp_fwd(int nbatch, const float* const* x, long ldx, const float* const* w, long ldw, float* const* y,
                         long ldy, int M, int N, int K, const float* const* bias, int relu, const float* const* qw,
@@ -471,5 +470,3 @@ DRQ_API int drq_mlp_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, c
   return drq_gemm3_wgrad_dgrad(nbatch, dy, lddy, x, ldx, dw, db, w, ldw, dx, lddx, mask, ldmask, Brows, Nout, Kin,
                                (hipStream_t)stream);
 }
-
-}  // extern "C"

@@ -1,0 +1,129 @@
+// Launchers called across the library's .hip files that are not part of the C ABI (include/drqv2_hip.h).
+// Every function here has C++ linkage and hidden visibility: the mangled name carries the signature, so a definition
+// that drifts from its declaration fails to compile in the defining file (which includes this header) or to link
+// (-z defs).  Grouped by defining file.
+#pragma once
+#include "common.h"
+
+// ---- elementwise.hip
+// LayerNorm+tanh of n problems; problem i may also copy tail_n (<= 64) columns of tail[i] behind its F outputs
+int drq_ln_tanh_fwd_multi_ex(int n, const float* const* z, int ldz, const float* const* gamma,
+                             const float* const* beta, float* const* out, const int* ldo, float* const* xhat,
+                             float* const* rstd, int rows, int F, const float* const* tail, const int* tail_ld,
+                             int tail_n, hipStream_t st);
+// ... that sums the split-K partials of drq_gemm_batched_partial
+int drq_ln_tanh_fwd_multi_part(int n, const float* const* z, int ldz, const float* const* gamma,
+                               const float* const* beta, float* const* out, const int* ldo, float* const* xhat,
+                               float* const* rstd, int rows, int F, const float* const* tail, const int* tail_ld,
+                               int tail_n, const float* part, const float* const* bias, int splitk, hipStream_t st);
+int drq_ln_tanh_bwd_part(const float* dh0, int ld0, const float* dh1, int ld1, const float* h, int ldh,
+                         const float* xhat, const float* rstd, const float* gamma, float* dz, float* dln,
+                         float* dgamma, float* dbeta, int rows, int F, const float* part, int splitk, int nprob,
+                         int ldp, hipStream_t st);
+int drq_ln_param_grad(const float* dln, const float* xhat, float* dgamma, float* dbeta, int rows, int F,
+                      hipStream_t st);
+int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+                    const float* discount, float inv_global_B, float* sums, const float* const* h,
+                    const float* const* w, float* const* dh, float* const* dw, float* const* db, int B, int H,
+                    hipStream_t st);
+int drq_qout_bwd_actor(const float* q1, const float* q2, const float* act, long lda, const float* mu, float std, int A,
+                       float inv_global_B, float* sums, float* sums_host, unsigned seq, const float* const* h,
+                       const float* const* w, float* const* dh, int B, int H, hipStream_t st);
+int drq_policy_out_fwd(const float* h2, const float* w, const float* b, float* p3, int rows, int H, int A,
+                       const float* noise, float std, float clip, int use_clip, int srow0, float* mu_out,
+                       float* a_out, long lda_out, const float* noise0, float* mu_out0, float* a_out0, long lda_out0,
+                       hipStream_t st);
+int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, const float* mu, const float* p2,
+                       const float* w, float* dp2, float* dw, float* db, int B, int H, int A, const float* part,
+                       int splitk, hipStream_t st);
+int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
+                      float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B, float* sums_host,
+                      unsigned seq, hipStream_t st);
+int drq_adam_flat2(float* p0, const float* g0, float* m0, float* v0, long n0, long step0, float* p1, const float* g1,
+                   float* m1, float* v1, long n1, long step1, double lr, float gscale, hipStream_t st);
+
+// ---- gemm.hip: either precision (bf16 != 0: bf16-MFMA kernel, fp32 storage)
+int drq_gemm_batched_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
+                         int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
+                         const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int tile,
+                         int splitk, float* ws, size_t ws_bytes, hipStream_t st);
+int drq_gemm_batched_partial_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B,
+                                 long ldb, int b_kc, float* const* C, long ldc, int M, int N, int K,
+                                 const float* const* bias, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st);
+
+// ---- skinny.hip
+int drq_skinny_dgrad(const float* dz, long lda, const float* w, long ldb, float* c, long ldc, int M, int N, int K,
+                     const float* aux, int ldaux, int scatter_hw, hipStream_t st);
+
+// ---- gemm2.hip
+int drq_trunk_wgrad(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
+                    float* rowsum, hipStream_t st);
+// the trunk weight gradient with the LayerNorm parameter gradients riding in the same launch
+int drq_trunk_wgrad_ln(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
+                       float* rowsum, const float* ln_dln, const float* ln_xhat, float* ln_dgamma, float* ln_dbeta,
+                       int ln_rows, int ln_F, hipStream_t st);
+int drq_trunk_fwd_partial(int nbatch, const float* const* A, long lda, const float* const* B, long ldb, int M, int N,
+                          int K, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st);
+int drq_gemm2(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb, int b_kc,
+              float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
+              const float* const* aux, int ldaux, float* const* rowsum, hipStream_t st);
+// weight gradient + input gradient of one hidden layer in one launch
+int drq_gemm2_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
+                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
+                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st);
+
+// ---- gemm3.hip: the hidden x hidden layers on the LDS-DMA ring kernel (DRQ_EARG = shape not eligible)
+int drq_gemm3_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx,
+                    long lddx, int M, int N, int K, const float* const* mask, int ldmask, hipStream_t st);
+int drq_gemm3_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
+                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
+                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st);
+
+// ---- rowblock.hip: LayerNorm+tanh fused with the first MLP layers; policy output layer + sample fused with the
+// target critic's first layers (DRQ_EARG = shape not eligible)
+int drq_lnl1_fwd(int njobs, const float* const* part, const float* const* z, const float* const* bias,
+                 const float* const* gamma, const float* const* beta, float* const* out, const int* ldo,
+                 float* const* xhat, float* const* rstd, const float* const* tail, const int* tail_ld, const int* tail_n,
+                 const int* rows, const int* nheads, const float* const* w, const float* const* b, float* const* y, int F,
+                 int H, int splitk, long slab, hipStream_t st);
+int drq_polout_l1_fwd(const float* p2, const float* w3, const float* b3, float* p3, int rows, int srow0, int H, int A,
+                      int F, float std, float clip, int use_clip, const float* noise_hi, float* mu_hi, float* ha_hi,
+                      long lda_hi, const float* noise_lo, float* mu_lo, float* ha_lo, long lda_lo, int nheads,
+                      const float* const* w, const float* const* b, float* const* y, hipStream_t st);
+
+// ---- conv1aug.hip: bf_mma selects the bf16-MFMA form of the layer's products
+int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
+                          const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
+                          int n_store, hipStream_t st, const float* const* wino_w, float* wino_u, const long* fidx0,
+                          const long* fidx1);
+
+// ---- conv_wino.hip: the Winograd kernels with the layer's U image prepared by conv1_aug_kernel's rider
+int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,
+                             int hin, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st);
+int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float* u_image, const float* mask, float* dx,
+                               int nb, int hout, long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st);
+
+// ---- conv_bf16.hip: the bf16 launches with activations in bf16 [frame][y][x][32] where the flags say so
+int drq_conv3x3_fwd_bf16_lay(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
+                             long y_bs, long y_cs, long y_rs, long y_off, int lay, hipStream_t st);
+int drq_conv3x3_dgrad_bf16_lay(const void* dy_pad, const float* w, const void* mask, void* dx, int nb, int hout,
+                               long dx_bs, long dx_cs, long dx_rs, long dx_off, int lay, hipStream_t st);
+int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
+                                       long dy_off, float* part, size_t part_bytes, int* nblocks, int lay,
+                                       hipStream_t st);
+int drq_conv3x3_wgrad_partial_bf16(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
+                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
+
+// ---- conv.hip: per-layer partial records; fixed-order reduction of the records of up to four layers
+int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, long dy_bs,
+                              long dy_cs, long dy_rs, long dy_off, float* part, size_t part_bytes, int* nblocks,
+                              hipStream_t st);
+int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* nblocks, const int* cin,
+                                   float* const* dw, float* const* db, hipStream_t st);
+
+// ---- conv_wino_wgrad.hip: the 32->32 layers' records in Winograd form (same format, same reduction)
+int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
+                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
+int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const long* dy_bs,
+                                    const long* dy_cs, const long* dy_rs, const long* dy_off, float* const* part,
+                                    size_t part_bytes, int* nblocks, hipStream_t st);

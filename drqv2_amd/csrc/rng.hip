@@ -47,8 +47,6 @@ __global__ __launch_bounds__(256) void rng_draws_kernel(RngArgs a) {
 
 }  // namespace
 
-extern "C" {
-
 // shift_obs / shift_next: n_shift floats each (= 2*B), values in [0, range); noise_critic / noise_actor: n_noise
 // floats each (= B*A).  (seed, offset) = the state of torch's CUDA generator BEFORE the draws; the caller advances the
 // generator's offset by 16 (four launches' worth) -- or by 8 when n_noise == 0: only the two shift draws are made (the
@@ -67,5 +65,3 @@ DRQ_API int drq_rng_draws(unsigned long long seed, unsigned long long offset, in
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }
-
-}  // extern "C"

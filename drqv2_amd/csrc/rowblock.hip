@@ -13,6 +13,7 @@
 //                  order) + tanh + sample -> for the next_obs rows the target critic's two first layers on [h, a']
 // The first-layer product is a k-ordered f32 fma chain per output (lane's k values 4V*q + V*kq + e, both operands).
 #include "common.h"
+#include "internal.h"
 #include "../../include/drqv2_hip.h"
 
 namespace {
@@ -545,8 +546,6 @@ int drq_polout_l1_fwd(const float* p2, const float* w3, const float* b3, float* 
   return DRQ_OK;
 }
 
-extern "C" {
-
 // See include/drqv2_hip.h
 DRQ_API int drq_ln_l1_fwd(int njobs, const float* const* part, const float* const* z, const float* const* bias,
                           const float* const* gamma, const float* const* beta, float* const* out, const int* ldo,
@@ -566,5 +565,3 @@ DRQ_API int drq_policy_out_l1_fwd(const float* p2, const float* w3, const float*
   return drq_polout_l1_fwd(p2, w3, b3, p3, rows, srow0, H, A, F, std, clip, use_clip, noise_hi, mu_hi, ha_hi, lda_hi,
                            noise_lo, mu_lo, ha_lo, lda_lo, nheads, w, b, y, (hipStream_t)stream);
 }
-
-}  // extern "C"

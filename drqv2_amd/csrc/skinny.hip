@@ -11,6 +11,7 @@
 // (The matching wgrad shape, dW = dz^T X, was tried the same way and only tied the generic kernel: 27 us,
 // bound by two half-filled rounds of workgroups rather than by memory; it stays on gemm.hip.)
 #include "common.h"
+#include "internal.h"
 
 namespace {
 

@@ -2,111 +2,8 @@
 // Host code only: sequences the kernels of conv.hip / gemm.hip / elementwise.hip over a caller-owned
 // workspace.  No allocation, no synchronisation, no global state.
 #include "common.h"
+#include "internal.h"
 #include "../../include/drqv2_hip.h"
-
-// elementwise.hip (internal): LayerNorm that sums the split-K partials of drq_gemm_batched_partial
-extern "C" int drq_ln_tanh_fwd_multi_part(int n, const float* const* z, int ldz, const float* const* gamma,
-                                          const float* const* beta, float* const* out, const int* ldo,
-                                          float* const* xhat, float* const* rstd, int rows, int F,
-                                          const float* const* tail, const int* tail_ld, int tail_n, const float* part,
-                                          const float* const* bias, int splitk, hipStream_t st);
-// elementwise.hip (internal)
-extern "C" int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
-                               const float* discount, float inv_global_B, float* sums, const float* const* h,
-                               const float* const* w, float* const* dh, float* const* dw, float* const* db, int B,
-                               int H, hipStream_t st);
-extern "C" int drq_qout_bwd_actor(const float* q1, const float* q2, const float* act, long lda, const float* mu, float std,
-                                    int A, float inv_global_B, float* sums, float* sums_host, unsigned seq,
-                                    const float* const* h, const float* const* w, float* const* dh, int B, int H,
-                                    hipStream_t st);
-extern "C" int drq_policy_out_fwd(const float* h2, const float* w, const float* b, float* p3, int rows, int H, int A,
-                                  const float* noise, float std, float clip, int use_clip, int srow0, float* mu_out,
-                                  float* a_out, long lda_out, const float* noise0, float* mu_out0, float* a_out0,
-                                  long lda_out0, hipStream_t st);
-extern "C" int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, const float* mu,
-                                  const float* p2, const float* w, float* dp2, float* dw, float* db, int B, int H,
-                                  int A, const float* part, int splitk, hipStream_t st);
-extern "C" int drq_ln_tanh_bwd_part(const float* dh0, int ld0, const float* dh1, int ld1, const float* h, int ldh,
-                                    const float* xhat, const float* rstd, const float* gamma, float* dz, float* dln,
-                                    float* dgamma, float* dbeta, int rows, int F, const float* part, int splitk,
-                                    int nprob, int ldp, hipStream_t st);
-extern "C" int drq_ln_tanh_fwd_multi_ex(int n, const float* const* z, int ldz, const float* const* gamma,
-                                        const float* const* beta, float* const* out, const int* ldo,
-                                        float* const* xhat, float* const* rstd, int rows, int F,
-                                        const float* const* tail, const int* tail_ld, int tail_n, hipStream_t st);
-extern "C" int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
-                                 float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B,
-                                 float* sums_host, unsigned seq, hipStream_t st);
-extern "C" int drq_adam_flat2(float* p0, const float* g0, float* m0, float* v0, long n0, long step0, float* p1,
-                              const float* g1, float* m1, float* v1, long n1, long step1, double lr, float gscale,
-                              hipStream_t st);
-// gemm.hip (internal): either precision (bf16 != 0: bf16-MFMA kernel, fp32 storage)
-int drq_gemm_batched_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
-                         int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
-                         const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int tile,
-                         int splitk, float* ws, size_t ws_bytes, hipStream_t st);
-int drq_gemm_batched_partial_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B,
-                                 long ldb, int b_kc, float* const* C, long ldc, int M, int N, int K,
-                                 const float* const* bias, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st);
-// conv1aug.hip (internal): bf_mma selects the bf16-MFMA form of the layer's products
-int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
-                          const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
-                          int n_store, hipStream_t st, const float* const* wino_w, float* wino_u, const long* fidx0,
-                          const long* fidx1);
-// conv_wino.hip (internal): the Winograd kernels with the layer's U image prepared by conv1_aug_kernel's rider
-int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,
-                             int hin, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st);
-int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float* u_image, const float* mask, float* dx,
-                               int nb, int hout, long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st);
-// gemm2.hip (internal): the trunk weight gradient with the LayerNorm parameter gradients riding in the same launch
-int drq_trunk_wgrad_ln(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                       float* rowsum, const float* ln_dln, const float* ln_xhat, float* ln_dgamma, float* ln_dbeta,
-                       int ln_rows, int ln_F, hipStream_t st);
-extern "C" int drq_ln_param_grad(const float* dln, const float* xhat, float* dgamma, float* dbeta, int rows, int F,
-                                 hipStream_t st);
-// gemm2.hip (internal): weight gradient + input gradient of one hidden layer in one launch
-int drq_gemm2_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
-                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
-                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st);
-// gemm3.hip (internal): the hidden x hidden layers on the LDS-DMA ring kernel (DRQ_EARG = shape not eligible)
-int drq_gemm3_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx,
-                    long lddx, int M, int N, int K, const float* const* mask, int ldmask, hipStream_t st);
-int drq_gemm3_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
-                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
-                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st);
-// rowblock.hip (internal): LayerNorm+tanh fused with the first MLP layers; policy output layer + sample fused with the
-// target critic's first layers (DRQ_EARG = shape not eligible)
-int drq_lnl1_fwd(int njobs, const float* const* part, const float* const* z, const float* const* bias,
-                 const float* const* gamma, const float* const* beta, float* const* out, const int* ldo,
-                 float* const* xhat, float* const* rstd, const float* const* tail, const int* tail_ld, const int* tail_n,
-                 const int* rows, const int* nheads, const float* const* w, const float* const* b, float* const* y, int F,
-                 int H, int splitk, long slab, hipStream_t st);
-int drq_polout_l1_fwd(const float* p2, const float* w3, const float* b3, float* p3, int rows, int srow0, int H, int A,
-                      int F, float std, float clip, int use_clip, const float* noise_hi, float* mu_hi, float* ha_hi,
-                      long lda_hi, const float* noise_lo, float* mu_lo, float* ha_lo, long lda_lo, int nheads,
-                      const float* const* w, const float* const* b, float* const* y, hipStream_t st);
-// conv_bf16.hip (internal): the bf16 launches with activations in bf16 [frame][y][x][32] where the flags say so
-int drq_conv3x3_fwd_bf16_lay(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
-                             long y_bs, long y_cs, long y_rs, long y_off, int lay, hipStream_t st);
-int drq_conv3x3_dgrad_bf16_lay(const void* dy_pad, const float* w, const void* mask, void* dx, int nb, int hout,
-                               long dx_bs, long dx_cs, long dx_rs, long dx_off, int lay, hipStream_t st);
-int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                       long dy_off, float* part, size_t part_bytes, int* nblocks, int lay,
-                                       hipStream_t st);
-int drq_conv3x3_wgrad_partial_bf16(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
-// conv.hip (internal)
-int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, long dy_bs,
-                              long dy_cs, long dy_rs, long dy_off, float* part, size_t part_bytes, int* nblocks,
-                              hipStream_t st);
-// conv_wino_wgrad.hip (internal): the 32->32 layers' records in Winograd form (same format, same reduction)
-int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
-int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const long* dy_bs,
-                                    const long* dy_cs, const long* dy_rs, const long* dy_off, float* const* part,
-                                    size_t part_bytes, int* nblocks, hipStream_t st);
-int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* nblocks, const int* cin,
-                                   float* const* dw, float* const* db, hipStream_t st);
 
 namespace {
 
@@ -120,13 +17,16 @@ struct HeadOff {
   long trunk_w, trunk_b, ln_g, ln_b;
   long w[2][3], b[2][3];
 };
+enum { SEG_ENC, SEG_CRITIC, SEG_ACTOR, SEG_TARGET };
 struct ParamLayout {
   long enc_w[4], enc_b[4];
   HeadOff critic, actor, target;
-  long seg[8];   // enc, critic, actor, target [beg,end)
+  long seg[8];   // [beg,end) of SEG_ENC, SEG_CRITIC, SEG_ACTOR, SEG_TARGET
   long total;
   long flat[50];
   int nflat;
+  long seg_beg(int net) const { return seg[2 * net]; }
+  long seg_len(int net) const { return seg[2 * net + 1] - seg[2 * net]; }
 };
 
 ParamLayout param_layout(int C, int A, int F, int H) {
@@ -181,6 +81,9 @@ struct WsLayout {
   long off[64];
   long total;
 };
+// split-K partials: the widest user is the trunk forward (2 nets x B x F x splits) and the
+// H x H weight gradients; 64 MiB covers every shape the step issues (checked per call).
+constexpr long kGemmWsFloats = 16L * 1024 * 1024;
 enum {
   W_AUG = DRQ_WS_AUG, W_ACT1 = DRQ_WS_ACT1, W_ACT2 = DRQ_WS_ACT2, W_ACT3 = DRQ_WS_ACT3, W_FEAT = DRQ_WS_FEAT,
   W_Z_NEXT = DRQ_WS_Z_NEXT, W_Z_OBS = DRQ_WS_Z_OBS, W_HA_T = DRQ_WS_HA_T, W_HA_C = DRQ_WS_HA_C,
@@ -251,9 +154,7 @@ WsLayout ws_layout(int B, int C, int A, int F, int H) {
   take(W_DP1, (long)B * H);
   take(W_DH_A, (long)B * F);
   take(W_DA, 2L * B * A);
-  // split-K partials: the widest user is the trunk forward (2 nets x B x F x splits) and the
-  // H x H weight gradients; 64 MiB covers every shape the step issues (checked per call).
-  take(W_GEMM_WS, 16L * 1024 * 1024);
+  take(W_GEMM_WS, kGemmWsFloats);
   take(W_CONV_WS, (long)(drq_conv3x3_wgrad_ws_bytes() / sizeof(float)));
   take(W_WINO_U, 6L * 16384);
   w.total = off;
@@ -275,9 +176,9 @@ struct Ctx {
   // launch of the backward (drq_qout_bwd_actor) instead of a launch of its own.  A host that exchanges the metric
   // sums between the two phases calls them separately and keeps the separate loss launch.
   bool fuse_actor_loss = false;
-  bool actor_loss_fused() const {
-    return fuse_actor_loss && ((size_t)s->B + 5 * 1024 + 16) * 4 <= 60 * 1024;
-  }
+  // B rows fit the LDS of the Q-output backward kernels that compute a loss as well (drq_qout_bwd_td / _actor)
+  bool qout_loss_fits_lds() const { return ((size_t)s->B + 5 * 1024 + 16) * 4 <= 60 * 1024; }
+  bool actor_loss_fused() const { return fuse_actor_loss && qout_loss_fits_lds(); }
   // row-local stages fused with the first MLP layers (rowblock.hip): fp32, shapes its kernels take
   bool fuse_rows() const {
     // measured (tools/ab_flags.py, same process, interleaved): cheetah_run B=256 1021.9 us fused against 1024.2, but
@@ -288,7 +189,7 @@ struct Ctx {
            s->A % 2 == 0 && s->H % 256 == 0;
   }
   bool use_gemm3() const { return !(s->flags & DRQ_STEP_NO_GEMM3) && !s->bf16; }
-  // timing pair k of DrqStep.timing_events (bench.py's roofline), recorded when the host asked for that many
+  // slot idx of DrqStep.timing_events (bench.py's roofline), recorded when the host asked for that many
   int stamp(int idx) const {
     if (s->timing_events && idx < s->timing_n && hipEventRecord((hipEvent_t)s->timing_events[idx], st) != hipSuccess)
       return DRQ_EARG;
@@ -304,8 +205,14 @@ struct Ctx {
   // ... and so are the gradients that pass between the encoder's input-gradient launches (DY3, DY2: zero-padded by 2);
   // DY4 (written by the trunk's masked scatter) and DY1 (read by conv1's fp32 weight gradient) stay fp32
   bool grads16() const { return acts16() && !(s->flags & DRQ_STEP_BF16_FP32_GRADS); }
+  // torch.optim.Adam.step over one network's segment; target >= 0: Polyak of the stepped segment into that one, fused
+  int adam_segment(int net, long step, int target = -1) const {
+    const long o = P.seg_beg(net);
+    return drq_adam_flat(p(o), g(o), s->adam_m + o, s->adam_v + o, P.seg_len(net), s->lr, step, s->gscale,
+                         target >= 0 ? p(P.seg_beg(target)) : nullptr, target >= 0 ? s->tau : 0.0, st);
+  }
   float* gemm_ws() const { return ws(W_GEMM_WS); }
-  size_t gemm_ws_bytes() const { return (size_t)16 * 1024 * 1024 * sizeof(float); }
+  size_t gemm_ws_bytes() const { return (size_t)kGemmWsFloats * sizeof(float); }
 
   // n problems  y_i = act(x_i W_i^T + b_i)
   int fwd(int n, const float* const* x, long ldx, const float* const* w, const float* const* b, float* const* y,
@@ -370,15 +277,15 @@ struct Ctx {
 };
 
 // x == nullptr: a1 already holds the first layer's output (fused aug + conv1), start at layer 2
+// timed: the update's pass, which stamps timing slots 0 and 1 around conv2 (drq_act_forward's pass does not)
 int encoder_forward(const Ctx& c, const float* x, int nb, float* a1, float* a2, float* a3, float* a4,
                     bool timed = false) {
   const ParamLayout& P = c.P;
   float* outs[4] = {a1, a2, a3, a4};
   const float* in = x ? x : a1;
-  void* const* ev = (timed && c.s->timing_n >= 2) ? c.s->timing_events : nullptr;
   for (int l = x ? 0 : 1; l < 4; ++l) {
     const int hin = kEncH[l], hout = kEncH[l + 1];
-    if (ev && l == 1 && hipEventRecord((hipEvent_t)ev[0], c.st) != hipSuccess) return DRQ_EARG;
+    if (timed && l == 1) CK(c.stamp(0));
     if (c.bf16() && l > 0)
       CK(drq_conv3x3_fwd_bf16_lay(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, hin, 1, 32L * hout * hout,
                                   (long)hout * hout, hout, 0, (x == nullptr && c.acts16()) ? (l < 3 ? 3 : 1) : 0, c.st));
@@ -388,9 +295,9 @@ int encoder_forward(const Ctx& c, const float* x, int nb, float* a1, float* a2, 
                                   c.p(P.enc_b[l]), outs[l], nb, hin, 1, 32L * hout * hout, (long)hout * hout, hout, 0,
                                   c.st));
     else
-    CK(drq_conv3x3_fwd(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, l == 0 ? c.s->C : 32, hin, l == 0 ? 2 : 1,
-                       1, 32L * hout * hout, (long)hout * hout, hout, 0, c.st));
-    if (ev && l == 1 && hipEventRecord((hipEvent_t)ev[1], c.st) != hipSuccess) return DRQ_EARG;
+      CK(drq_conv3x3_fwd(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, l == 0 ? c.s->C : 32, hin, l == 0 ? 2 : 1,
+                         1, 32L * hout * hout, (long)hout * hout, hout, 0, c.st));
+    if (timed && l == 1) CK(c.stamp(1));
     in = outs[l];
   }
   return 0;
@@ -459,12 +366,11 @@ int q_forward(const Ctx& c, int nn, const HeadOff* const* nets, const float* con
 // phase 3: augmentation + encoder forward (reads encoder weights only)
 int phase_encode(const Ctx& c) {
   const DrqStep* s = c.s;
-  const int B = s->B, C = s->C;
+  const int B = s->B;
   hipStream_t st = c.st;
   float* aug = c.ws(W_AUG);
   // aug (drqv2.py:241-242) + /255-0.5 (:64) + conv1 (:55) in one kernel that reads the uint8 frames once; rows
   // [0,B) = obs, [B,2B) = next_obs.  Only the obs view's encoder input is kept (conv1's weight gradient reads it).
-  (void)C;
   // riders of the same launch: the Winograd images of the conv2..4 weights for this update's forward and backward
   const float* wino_w[3] = {c.p(c.P.enc_w[1]), c.p(c.P.enc_w[2]), c.p(c.P.enc_w[3])};
   CK(drq_conv1_aug_fwd_any(c.acts16() ? 2 : c.bf16(), s->obs, s->shift_obs, s->next_obs, s->shift_next, s->base_grid,
@@ -530,10 +436,10 @@ int phase_critic_heads(const Ctx& c) {
       else if (rc != DRQ_EARG) return rc;
     }
     if (!rows_fused) {
-    CK(drq_ln_tanh_fwd_multi_part(4, zz, F, gm, bt, out, ldo, xh, rs, B, F, with_tail ? tail : nullptr,
-                                  with_tail ? tld : nullptr, with_tail ? A : 0, sk > 1 ? c.gemm_ws() : nullptr, b, sk,
-                                  st));
-    if (!with_tail) CK(drq_copy_cols(s->action, A, c.ws(W_HA_C) + F, FA, B, A, st));
+      CK(drq_ln_tanh_fwd_multi_part(4, zz, F, gm, bt, out, ldo, xh, rs, B, F, with_tail ? tail : nullptr,
+                                    with_tail ? tld : nullptr, with_tail ? A : 0, sk > 1 ? c.gemm_ws() : nullptr, b,
+                                    sk, st));
+      if (!with_tail) CK(drq_copy_cols(s->action, A, c.ws(W_HA_C) + F, FA, B, A, st));
     }
   }
   // policy MLP once on the 2B stacked rows
@@ -554,12 +460,12 @@ int phase_critic_heads(const Ctx& c) {
                          bt2, yt, st));
     q_l1_done = true;
   } else {
-  bool did0 = false;
-  CK(policy_forward(c, hrows, 2 * B, c.ws(W_P1), c.ws(W_P2), c.ws(W_P3), B, s->noise_critic, c.ws(W_HA_T) + F, FA,
-                    s->noise_actor, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, &did0));
-  if (!did0)
-    CK(drq_trunc_normal_sample(c.ws(W_P3), s->noise_actor, s->std, s->clip, 1, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, B,
-                               A, st));
+    bool did0 = false;
+    CK(policy_forward(c, hrows, 2 * B, c.ws(W_P1), c.ws(W_P2), c.ws(W_P3), B, s->noise_critic, c.ws(W_HA_T) + F, FA,
+                      s->noise_actor, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, &did0));
+    if (!did0)
+      CK(drq_trunc_normal_sample(c.ws(W_P3), s->noise_actor, s->std, s->clip, 1, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA,
+                                 B, A, st));
   }
 
   // y = r + d*min Q_target(next, a')   (:184-186);  critic(obs, action) (:188)
@@ -590,7 +496,7 @@ int phase_critic_heads(const Ctx& c) {
           *gb2[2] = {c.g(cr.b[0][2]), c.g(cr.b[1][2])};
     // TD target + twin MSE (:185-189) and layer 3 (hidden -> 1) backward in one pass: dq never leaves the chip,
     // sums[0..4] come from the same launch
-    if (((size_t)B + 5 * 1024 + 16) * 4 <= 60 * 1024) {
+    if (c.qout_loss_fits_lds()) {
       CK(drq_qout_bwd_td(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, invB, s->sums,
                          c2c, w2, dc2, gw2, gb2, B, H, st));
     } else {
@@ -660,17 +566,17 @@ int phase_conv_backward(const Ctx& c) {
     }
     if (l >= 1) {
       const int hpi = hin + 4;   // padded size of the next (shallower) gradient buffer
-      void* const* ev = s->timing_n >= 4 ? s->timing_events : nullptr;
-      if (ev && l == 2 && hipEventRecord((hipEvent_t)ev[2], st) != hipSuccess) return DRQ_EARG;
+      if (l == 2) CK(c.stamp(2));
       if (c.bf16())
         CK(drq_conv3x3_dgrad_bf16_lay(dy, c.p(P.enc_w[l]), c.ws(actid[l]), c.ws(dyid[l - 1]), B, hout, 32L * hpi * hpi,
                                       (long)hpi * hpi, hpi, 2L * hpi + 2,
                                       (c.acts16() ? 4 : 0) | (c.grads16() && l < 3 ? 1 : 0) | (c.grads16() && l > 1 ? 2 : 0),
                                       st));
       else
-      CK(drq_conv3x3_dgrad_wino_pre(dy, c.p(P.enc_w[l]), c.ws(W_WINO_U) + (2L * (l - 1) + 1) * 16384, c.ws(actid[l]),
-                                    c.ws(dyid[l - 1]), B, hout, 32L * hpi * hpi, (long)hpi * hpi, hpi, 2L * hpi + 2, st));
-      if (ev && l == 2 && hipEventRecord((hipEvent_t)ev[3], st) != hipSuccess) return DRQ_EARG;
+        CK(drq_conv3x3_dgrad_wino_pre(dy, c.p(P.enc_w[l]), c.ws(W_WINO_U) + (2L * (l - 1) + 1) * 16384, c.ws(actid[l]),
+                                      c.ws(dyid[l - 1]), B, hout, 32L * hpi * hpi, (long)hpi * hpi, hpi, 2L * hpi + 2,
+                                      st));
+      if (l == 2) CK(c.stamp(3));
     }
   }
   if (merged) {
@@ -732,9 +638,7 @@ int phase_actor_forward(const Ctx& c, bool with_opt = true) {
   float* feat_obs = c.ws(W_FEAT);
   const HeadOff& cr = P.critic;
 
-  if (with_opt)
-  CK(drq_adam_flat(c.p(P.seg[2]), c.g(P.seg[2]), s->adam_m + P.seg[2], s->adam_v + P.seg[2], P.seg[3] - P.seg[2],
-                   s->lr, s->step_critic, s->gscale, c.p(P.seg[6]), s->tau, st));
+  if (with_opt) CK(c.adam_segment(SEG_CRITIC, s->step_critic, SEG_TARGET));
   bool q_l1_done = false;
   CK(c.stamp(8));
 
@@ -763,8 +667,8 @@ int phase_actor_forward(const Ctx& c, bool with_opt = true) {
       else if (rc != DRQ_EARG) return rc;
     }
     if (!q_l1_done)
-    CK(drq_ln_tanh_fwd_multi_part(1, zz, F, gm, bt, out, ldo, nullptr, nullptr, B, F, nullptr, nullptr, 0,
-                                  sk > 1 ? c.gemm_ws() : nullptr, b, sk, st));
+      CK(drq_ln_tanh_fwd_multi_part(1, zz, F, gm, bt, out, ldo, nullptr, nullptr, B, F, nullptr, nullptr, 0,
+                                    sk > 1 ? c.gemm_ws() : nullptr, b, sk, st));
   }
   {
     const HeadOff* nets[1] = {&cr};
@@ -850,19 +754,24 @@ int phase_actor_backward(const Ctx& c) {
   return 0;
 }
 
-// ---- phase 2 = phases 8, 9 ------------------------------------------------------------------------
-int phase_encoder_opt(const Ctx& c) {   // encoder_opt.step() (:202)
+// ---- phase 2 = phases 8, 9 in one launch ---------------------------------------------------------
+int phase_both_opt(const Ctx& c) {      // encoder_opt.step() (:202) and actor_opt.step() (:221)
   const DrqStep* s = c.s;
   const ParamLayout& P = c.P;
-  return drq_adam_flat(c.p(P.seg[0]), c.g(P.seg[0]), s->adam_m + P.seg[0], s->adam_v + P.seg[0], P.seg[1] - P.seg[0],
-                       s->lr, s->step_enc, s->gscale, nullptr, 0.0, c.st);
+  const long e = P.seg_beg(SEG_ENC), a = P.seg_beg(SEG_ACTOR);
+  return drq_adam_flat2(c.p(e), c.g(e), s->adam_m + e, s->adam_v + e, P.seg_len(SEG_ENC), s->step_enc, c.p(a), c.g(a),
+                        s->adam_m + a, s->adam_v + a, P.seg_len(SEG_ACTOR), s->step_actor, s->lr, s->gscale, c.st);
 }
 
-int phase_actor_opt(const Ctx& c) {     // actor_opt.step() (:221)
-  const DrqStep* s = c.s;
-  const ParamLayout& P = c.P;
-  return drq_adam_flat(c.p(P.seg[4]), c.g(P.seg[4]), s->adam_m + P.seg[4], s->adam_v + P.seg[4], P.seg[5] - P.seg[4],
-                       s->lr, s->step_actor, s->gscale, nullptr, 0.0, c.st);
+// does a drq_update_phase call with id `phase` run the piece `part`?  The composite ids are spelled out here and
+// nowhere else; DRQ_PHASE_OPT is a piece of its own (phases 8 and 9 in one launch), which DRQ_PHASE_ALL ends with
+bool runs(int phase, int part) {
+  switch (phase) {
+    case DRQ_PHASE_ALL: return (part >= DRQ_PHASE_ENCODE && part <= DRQ_PHASE_ACTOR_BACKWARD) || part == DRQ_PHASE_OPT;
+    case DRQ_PHASE_CRITIC: return part >= DRQ_PHASE_ENCODE && part <= DRQ_PHASE_CONV_BACKWARD;
+    case DRQ_PHASE_ACTOR: return part == DRQ_PHASE_ACTOR_FORWARD || part == DRQ_PHASE_ACTOR_BACKWARD;
+    default: return phase == part;
+  }
 }
 
 int check_step(const DrqStep* s) {
@@ -877,8 +786,6 @@ int check_step(const DrqStep* s) {
 }
 
 }  // namespace
-
-extern "C" {
 
 DRQ_API int drq_abi_version(void) { return 7; }
 
@@ -908,40 +815,31 @@ DRQ_API int drq_update_phase(const DrqStep* s, int phase) {
       !s->noise_critic || !s->noise_actor || !s->base_grid || !s->grads || !s->adam_m || !s->adam_v || !s->sums)
     return DRQ_EARG;
   Ctx c{s, param_layout(s->C, s->A, s->F, s->H), ws_layout(s->B, s->C, s->A, s->F, s->H), (hipStream_t)s->stream};
-  if (phase < -1 || phase > 13) return DRQ_EARG;
-  c.fuse_actor_loss = phase == -1 || phase == 1;
-  if (phase == 3 || phase == 0 || phase == -1) CK(phase_encode(c));
-  if (phase == 4 || phase == 0 || phase == -1) {
+  if (phase < DRQ_PHASE_ALL || phase > DRQ_PHASE_REDRAW) return DRQ_EARG;
+  c.fuse_actor_loss = phase == DRQ_PHASE_ALL || phase == DRQ_PHASE_ACTOR;
+  if (runs(phase, DRQ_PHASE_ENCODE)) CK(phase_encode(c));
+  if (runs(phase, DRQ_PHASE_CRITIC_HEADS)) {
     CK(c.stamp(6));
     CK(phase_critic_heads(c));
     CK(c.stamp(7));
   }
-  if (phase == 5 || phase == 0 || phase == -1) CK(phase_conv_backward(c));
-  if (phase == 6 || phase == 1 || phase == -1) CK(phase_actor_forward(c));
-  if (phase == 7 || phase == 1 || phase == -1) {
+  if (runs(phase, DRQ_PHASE_CONV_BACKWARD)) CK(phase_conv_backward(c));
+  if (runs(phase, DRQ_PHASE_ACTOR_FORWARD)) CK(phase_actor_forward(c));
+  if (runs(phase, DRQ_PHASE_ACTOR_BACKWARD)) {
     CK(phase_actor_backward(c));
     CK(c.stamp(9));
   }
-  if (phase == 2 || phase == -1) {          // both optimiser steps in one launch
-    const ParamLayout& P = c.P;
-    CK(drq_adam_flat2(c.p(P.seg[0]), c.g(P.seg[0]), s->adam_m + P.seg[0], s->adam_v + P.seg[0], P.seg[1] - P.seg[0],
-                      s->step_enc, c.p(P.seg[4]), c.g(P.seg[4]), s->adam_m + P.seg[4], s->adam_v + P.seg[4],
-                      P.seg[5] - P.seg[4], s->step_actor, s->lr, s->gscale, c.st));
-  }
-  if (phase == 8) CK(phase_encoder_opt(c));
-  if (phase == 9) CK(phase_actor_opt(c));
+  if (runs(phase, DRQ_PHASE_OPT)) CK(phase_both_opt(c));
+  if (runs(phase, DRQ_PHASE_ENCODER_OPT)) CK(c.adam_segment(SEG_ENC, s->step_enc));      // encoder_opt.step() (:202)
+  if (runs(phase, DRQ_PHASE_ACTOR_OPT)) CK(c.adam_segment(SEG_ACTOR, s->step_actor));    // actor_opt.step() (:221)
   // the reference's method boundaries (DrQV2Agent.update_critic / update_actor, drqv2.py:177-228) cut phase 6 apart:
-  if (phase == 10) {                        // critic_opt.step() alone (:201), no Polyak
-    const ParamLayout& P = c.P;
-    CK(drq_adam_flat(c.p(P.seg[2]), c.g(P.seg[2]), s->adam_m + P.seg[2], s->adam_v + P.seg[2], P.seg[3] - P.seg[2], s->lr,
-                     s->step_critic, s->gscale, nullptr, 0.0, c.st));
-  }
-  if (phase == 11) CK(phase_actor_forward(c, false));   // actor loss through the (already stepped) critic (:210-216)
-  if (phase == 12) {                        // utils.soft_update_params(critic, critic_target, tau) (:259-260)
-    const ParamLayout& P = c.P;
-    CK(drq_ema_flat(c.p(P.seg[2]), c.p(P.seg[6]), P.seg[3] - P.seg[2], s->tau, c.st));
-  }
-  if (phase == 13) {                        // the actor update's own draw (:210-211) from the stored policy output
+  // critic_opt.step() alone (:201), no Polyak
+  if (runs(phase, DRQ_PHASE_CRITIC_OPT)) CK(c.adam_segment(SEG_CRITIC, s->step_critic));
+  // actor loss through the (already stepped) critic (:210-216)
+  if (runs(phase, DRQ_PHASE_ACTOR_LOSS)) CK(phase_actor_forward(c, false));
+  if (runs(phase, DRQ_PHASE_POLYAK))        // utils.soft_update_params(critic, critic_target, tau) (:259-260)
+    CK(drq_ema_flat(c.p(c.P.seg_beg(SEG_CRITIC)), c.p(c.P.seg_beg(SEG_TARGET)), c.P.seg_len(SEG_CRITIC), s->tau, c.st));
+  if (runs(phase, DRQ_PHASE_REDRAW)) {      // the actor update's own draw (:210-211) from the stored policy output
     const int F = s->F, A = s->A, FA = F + A;
     CK(drq_trunc_normal_sample(c.ws(W_P3), s->noise_actor, s->std, s->clip, 1, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, s->B,
                                A, c.st));
@@ -958,7 +856,7 @@ DRQ_API int drq_act_forward(const DrqStep* s, const uint8_t* obs, int n, float* 
   if (!obs || !mu_out || n <= 0 || n > 2 * s->B) return DRQ_EARG;
   Ctx c{s, param_layout(s->C, s->A, s->F, s->H), ws_layout(s->B, s->C, s->A, s->F, s->H), (hipStream_t)s->stream};
   const ParamLayout& P = c.P;
-  const int F = s->F, H = s->H, A = s->A;
+  const int F = s->F, A = s->A;
   CK(drq_u8_normalize(obs, c.ws(W_AUG), (long)n * s->C * 84 * 84, c.st));
   CK(encoder_forward(c, c.ws(W_AUG), n, c.ws(W_ACT1), c.ws(W_ACT2), c.ws(W_ACT3), c.ws(W_FEAT)));
   const HeadOff& a = P.actor;
@@ -970,8 +868,5 @@ DRQ_API int drq_act_forward(const DrqStep* s, const uint8_t* obs, int n, float* 
   }
   CK(drq_ln_tanh_fwd(c.ws(W_Z4), F, c.p(a.ln_g), c.p(a.ln_b), c.ws(W_HROWS), F, nullptr, nullptr, n, F, c.st));
   CK(policy_forward(c, c.ws(W_HROWS), n, c.ws(W_P1), c.ws(W_P2), c.ws(W_P3)));
-  (void)H;
   return drq_tanh(c.ws(W_P3), mu_out, (long)n * A, c.st);
 }
-
-}  // extern "C"

@@ -566,7 +566,7 @@ class StepEngine:
         if desc is not None:                                    # replicated step (the sharded one came with the exchange)
             if self.device.type == "cuda":
                 desc.stream = self._stream()
-            self._phase(desc, 8)
+            self._phase(desc, _lib.PHASE_ENCODER_OPT)
         del keep
 
     def flush(self):
@@ -582,7 +582,7 @@ class StepEngine:
         if desc is not None:
             if self.device.type == "cuda":
                 desc.stream = self._stream()
-            self._phase(desc, 9)
+            self._phase(desc, _lib.PHASE_ACTOR_OPT)
         del keep
 
     # ---- the step ------------------------------------------------------------------------
@@ -654,7 +654,7 @@ class StepEngine:
         d.noise_critic, d.noise_actor = ptr(noise_critic), ptr(noise_actor)
         if self.pg is None:
             self._throttle(steps[2] & 0xFFFFFFFF)
-            self._phase(d, -1)
+            self._phase(d, _lib.PHASE_ALL)
             self._last_seq = steps[2] & 0xFFFFFFFF
         else:
             # overlapped schedule.  Every exchange is a SUM of gradients already scaled by
@@ -670,9 +670,9 @@ class StepEngine:
                 torch.cuda.current_stream(self.device).wait_stream(self._side)
                 self._side_busy = False
             self.flush_encoder()                                # previous update's Adam(encoder)
-            self._phase(d, 3)                                   # aug + encoder forward: no actor weights yet
+            self._phase(d, _lib.PHASE_ENCODE)                   # aug + encoder forward: no actor weights yet
             self.flush()                                        # previous update's Adam(actor), reduce done by now
-            self._phase(d, 4)                                   # critic loss, backward to the encoder output
+            self._phase(d, _lib.PHASE_CRITIC_HEADS)             # critic loss, backward to the encoder output
             ex = self.exchange
             z_critic = ex is not None and ex.sharded(c1 - c0)
             if z_critic:     # gradient slices -> Adam on the owned slice -> stepped parameters back, beside phase 5
@@ -680,10 +680,11 @@ class StepEngine:
                                           d.lr, steps[0])
             else:
                 w_critic = self._allreduce_async(self.grads[c0:c1])  # 16.7 MB, under the encoder backward
-            self._phase(d, 5)
+            self._phase(d, _lib.PHASE_CONV_BACKWARD)
             self._wait(w_critic, "critic_grads")
             # phase 6 = critic_opt.step() + Polyak + the actor loss; with the sharded step already done: Polyak + loss
-            ph6 = (lambda: (self._phase(d, 12), self._phase(d, 11))) if z_critic else (lambda: self._phase(d, 6))
+            ph6 = ((lambda: (self._phase(d, _lib.PHASE_POLYAK), self._phase(d, _lib.PHASE_ACTOR_LOSS))) if z_critic
+                   else (lambda: self._phase(d, _lib.PHASE_ACTOR_FORWARD)))
             if not self.global_metrics:
                 # metrics of THIS rank's shard (means over its rows): published by phase 6 itself, no exchange
                 d.sums_host = ptr(self.sums_host) if mirror else None
@@ -707,7 +708,7 @@ class StepEngine:
                 else:
                     self._allreduce_async(self.sums).wait()
                     self._last_seq = None
-            self._phase(d, 7)                                   # actor backward
+            self._phase(d, _lib.PHASE_ACTOR_BACKWARD)           # actor backward
             # encoder (0.1 MB) and actor (12.3 MB) gradients: reduced under the next update's encoder forward
             def hand_over(b, e, step_no):
                 if ex is not None and ex.sharded(e - b):        # the optimiser step travels with the exchange
@@ -742,7 +743,7 @@ class StepEngine:
         for f in ("action", "reward", "discount", "noise_critic", "noise_actor"):
             setattr(d, f, ptr(shift_obs))
         self._manual = {"d": d, "keep": [obs, next_obs, shift_obs, shift_next], "B": B, "stage": "encoded"}
-        self._phase(d, 3)
+        self._phase(d, _lib.PHASE_ENCODE)
         feat = self.ws_view("FEAT", B, (2 * B, 39200))
         return feat[:B], feat[B:]
 
@@ -762,7 +763,7 @@ class StepEngine:
         d.action, d.reward, d.discount = ptr(action), ptr(reward), ptr(discount)
         d.noise_critic, d.noise_actor = ptr(noise_critic), ptr(noise_critic)   # the actor's draw comes with update_actor
         d.stream = self._stream()
-        for k in (4, 5, 10, 8):
+        for k in (_lib.PHASE_CRITIC_HEADS, _lib.PHASE_CONV_BACKWARD, _lib.PHASE_CRITIC_OPT, _lib.PHASE_ENCODER_OPT):
             self._phase(d, k)
         m["stage"] = "critic"
         return self.sums
@@ -775,7 +776,7 @@ class StepEngine:
         m["keep"].append(noise_actor)
         d.noise_actor = ptr(noise_actor)
         d.stream = self._stream()
-        for k in (13, 11, 7, 9):
+        for k in (_lib.PHASE_REDRAW, _lib.PHASE_ACTOR_LOSS, _lib.PHASE_ACTOR_BACKWARD, _lib.PHASE_ACTOR_OPT):
             self._phase(d, k)
         self._last_seq = None
         self._manual = None

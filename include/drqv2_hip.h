@@ -344,7 +344,7 @@ typedef struct {
                               * heads of the critic update: trunks .. trunk input gradient); [8],[9] phases 6-7 without
                               * the critic's optimiser step (the heads of the actor update).  Pairs beyond timing_n
                               * are not recorded. */
-  int timing_n;              /* entries of timing_events (0, 4, 6, 8 or 10) */
+  int timing_n;              /* entries of timing_events: 0, 4, 6, 8 or 10; other values are not supported */
   const int64_t* obs_index;      /* optional (both or neither): the batch is NOT materialised -- `obs` / `next_obs` are */
   const int64_t* next_obs_index; /* stores of frames (a device replay ring, [slots][C][84][84] u8) and row b of the batch
                               * is frame obs_index[b] of `obs` / next_obs_index[b] of `next_obs` (replay_buffer.py:152-153:
@@ -389,25 +389,33 @@ enum {
   DRQ_WS_NBUF_PUBLIC
 };
 
-/* One update = phases 3..9 in this order (phase -1 runs them all: single GPU):
- *   3  aug + encoder forward (drqv2.py:241-246)         reads the encoder weights only
- *   4  trunks, policy, Q heads, TD loss, backward down to the encoder output (:180-200)
- *      leaves ALL critic gradients and sums[0..4]; first reader of the actor weights
- *   5  encoder backward                                  leaves the encoder gradients
- *   6  Adam(critic) + Polyak (:201,:259-260), actor loss through the updated critic (:210-216)
- *      leaves sums[5..6]; publishes sums to sums_host when that is set
- *   7  actor backward (:218-220)                         leaves the actor gradients
- *   8  Adam(encoder) (:202)   commutes to here: phases 6/7 work on features encoded before it (:255)
- *   9  Adam(actor) (:221)
- * Composite ids kept for callers that exchange at coarser points: 0 = 3,4,5; 1 = 6,7; 2 = 8,9.
+/* One update = phases 3..9 in this order (phase -1, DRQ_PHASE_ALL, runs them all: single GPU):
+ *   3  ENCODE          aug + encoder forward (drqv2.py:241-246)         reads the encoder weights only
+ *   4  CRITIC_HEADS    trunks, policy, Q heads, TD loss, backward down to the encoder output (:180-200)
+ *                      leaves ALL critic gradients and sums[0..4]; first reader of the actor weights
+ *   5  CONV_BACKWARD   encoder backward                                  leaves the encoder gradients
+ *   6  ACTOR_FORWARD   Adam(critic) + Polyak (:201,:259-260), actor loss through the updated critic (:210-216)
+ *                      leaves sums[5..6]; publishes sums to sums_host when that is set
+ *   7  ACTOR_BACKWARD  actor backward (:218-220)                         leaves the actor gradients
+ *   8  ENCODER_OPT     Adam(encoder) (:202)   commutes to here: phases 6/7 work on features encoded before it (:255)
+ *   9  ACTOR_OPT       Adam(actor) (:221)
+ * Composite ids kept for callers that exchange at coarser points: 0 (CRITIC) = 3,4,5; 1 (ACTOR) = 6,7; 2 (OPT) = 8,9
+ * in one launch.
  * For hosts that follow the reference's METHOD boundaries (DrQV2Agent.update_critic / update_actor, drqv2.py:177-228)
- * phase 6 is also available in pieces: 10 = Adam(critic) alone (no Polyak), 11 = the actor loss of phase 6 without the
- * optimiser step, 12 = Polyak alone (utils.soft_update_params), 13 = re-draw the actor update's action from the policy
- * output stored by phase 4 with s->noise_actor (update_critic does not know that draw yet).  update_critic = 4, 5, 10, 8;
- * update_actor = 13, 11, 7, 9; results equal phase -1 bit for bit (tests/test_hip_step.py).
+ * phase 6 is also available in pieces: 10 (CRITIC_OPT) = Adam(critic) alone (no Polyak), 11 (ACTOR_LOSS) = the actor
+ * loss of phase 6 without the optimiser step, 12 (POLYAK) = Polyak alone (utils.soft_update_params), 13 (REDRAW) =
+ * re-draw the actor update's action from the policy output stored by phase 4 with s->noise_actor (update_critic does
+ * not know that draw yet).  update_critic = 4, 5, 10, 8; update_actor = 13, 11, 7, 9; results equal phase -1 bit for
+ * bit (tests/test_hip_step.py).
  * A data-parallel host SUM-all-reduces the critic gradients while 5 runs, the encoder gradients while 6/7 run,
  * the metric sums after 6 and the actor gradients after 7; 8 may be deferred until the next update's phase 3
  * and 9 until its phase 4 (or drq_act_forward), so both exchanges overlap compute. */
+enum {
+  DRQ_PHASE_ALL = -1, DRQ_PHASE_CRITIC = 0, DRQ_PHASE_ACTOR = 1, DRQ_PHASE_OPT = 2,
+  DRQ_PHASE_ENCODE = 3, DRQ_PHASE_CRITIC_HEADS = 4, DRQ_PHASE_CONV_BACKWARD = 5, DRQ_PHASE_ACTOR_FORWARD = 6,
+  DRQ_PHASE_ACTOR_BACKWARD = 7, DRQ_PHASE_ENCODER_OPT = 8, DRQ_PHASE_ACTOR_OPT = 9,
+  DRQ_PHASE_CRITIC_OPT = 10, DRQ_PHASE_ACTOR_LOSS = 11, DRQ_PHASE_POLYAK = 12, DRQ_PHASE_REDRAW = 13
+};
 int drq_update_phase(const DrqStep* s, int phase);
 
 /* sums[0..7] -> sums_host[0..7], then seq -> slot 8 with system-scope release (see DrqStep.sums_host); for hosts
