@@ -172,6 +172,36 @@ class DrQV2Agent:
                 action.uniform_(-1.0, 1.0)
         return action.cpu().numpy()[0]
 
+    def act_batch(self, obs, step, eval_mode):
+        """act() for n observations at once (new: vectorised environments, parallel evaluation episodes, frames that
+        already live on the GPU): the body of drqv2.py:164-175 without unsqueeze(0) / [0], on the inference launches of
+        csrc/act.hip (drq_act_batch).
+        obs: uint8 [n, C, 84, 84] -- numpy array, host tensor, or tensor on the agent's device.
+        Returns float32 [n, A]: a tensor on the agent's device if obs was one (nothing waits for the GPU), otherwise a
+        numpy array.
+        The generator is consumed as the reference's body would on a batch: when not eval_mode ONE
+        _standard_normal((n, A)) draw (TruncatedNormal.sample), then, while step < num_expl_steps, uniform_(-1, 1) over
+        the [n, A] result; for n = 1 exactly what act() consumes.  Up to StepEngine.ACT_FUSED_MAX_ROWS frames the call
+        does not touch the step workspace and may sit between encode() and update_critic(); larger batches go through
+        act()'s kernels in chunks and must not (StepEngine.act_batch_forward)."""
+        if str(self.device).startswith("cpu"):
+            raise _lib.DrqError("DrQV2Agent.update/act need the GPU: the HIP path has no CPU fallback")
+        on_device = isinstance(obs, torch.Tensor) and obs.is_cuda
+        if not on_device:
+            obs = torch.as_tensor(obs).to(self.device)
+        if obs.dim() != 4:
+            raise _lib.DrqError(f"act_batch(): frames of shape (n, C, 84, 84) required, got {tuple(obs.shape)}")
+        eng = self._engine
+        if eval_mode:
+            action = eng.act_batch_forward(obs.contiguous())
+        else:
+            stddev = utils.schedule(self.stddev_schedule, step)
+            noise = _standard_normal((obs.shape[0], eng.A), dtype=torch.float32, device=eng.device)   # utils.py:119
+            action = eng.act_batch_forward(obs.contiguous(), noise, stddev)
+            if step < self.num_expl_steps:
+                action.uniform_(-1.0, 1.0)
+        return action if on_device else action.cpu().numpy()
+
     # ---- data parallel (new: one process per GPU, RCCL all-reduce of the flat gradient arenas) ---
     def enable_data_parallel(self, process_group=None, batch_is_global=True, global_metrics=False,
                              exchange="allreduce"):

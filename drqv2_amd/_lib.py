@@ -99,6 +99,8 @@ PROTOTYPES = {
     "drq_step_ws_offset": (L, [I, I, I, I, I, I]),
     "drq_update_phase": (I, [C.POINTER(DrqStep), I]),
     "drq_act_forward": (I, [C.POINTER(DrqStep), P, I, P]),
+    "drq_act_ws_bytes": (SZ, [I, I, I, I, I]),
+    "drq_act_batch": (I, [P, I, I, I, I, P, I, P, F, P, P, P, SZ, P]),
     "drq_publish_sums": (I, [P, P, C.c_uint, P]),
     "drq_rng_draws": (I, [C.c_uint64, C.c_uint64, I, I, I, P, P, P, P, P]),
 }

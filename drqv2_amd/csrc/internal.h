@@ -114,6 +114,19 @@ int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, in
 int drq_conv3x3_wgrad_partial_bf16(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
                                    long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
 
+// ---- act.hip: batched policy inference on launches of its own (drq_act_batch; the C entry lives in step.hip beside
+// the parameter layout).  ws holds drq_act_batch_ws_floats(n, F, H) floats; no state, no counter.
+constexpr int kActMaxRows = 256;
+struct ActWeights {
+  const float *enc_w[4], *enc_b[4];
+  const float *trunk_w, *trunk_b, *ln_g, *ln_b;
+  const float *w[3], *b[3];   // policy MLP
+};
+bool drq_act_batch_supported(int n, int C, int A, int F, int H);
+long drq_act_batch_ws_floats(int n, int F, int H);
+int drq_act_batch_launch(const ActWeights& p, int A, int F, int H, const uint8_t* obs, int n, const float* noise,
+                         float std, float* mu_out, float* action_out, float* ws, hipStream_t st);
+
 // ---- conv.hip: per-layer partial records; fixed-order reduction of the records of up to four layers
 int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, long dy_bs,
                               long dy_cs, long dy_rs, long dy_off, float* part, size_t part_bytes, int* nblocks,

@@ -870,3 +870,33 @@ DRQ_API int drq_act_forward(const DrqStep* s, const uint8_t* obs, int n, float* 
   CK(policy_forward(c, c.ws(W_HROWS), n, c.ws(W_P1), c.ws(W_P2), c.ws(W_P3)));
   return drq_tanh(c.ws(W_P3), mu_out, (long)n * A, c.st);
 }
+
+DRQ_API size_t drq_act_ws_bytes(int n_max, int C, int A, int F, int H) {
+  if (!drq_act_batch_supported(n_max, C, A, F, H)) return 0;
+  return (size_t)drq_act_batch_ws_floats(n_max, F, H) * sizeof(float);
+}
+
+DRQ_API int drq_act_batch(const float* params, int C, int A, int F, int H, const uint8_t* obs, int n,
+                          const float* noise, float std, float* mu_out, float* action_out, void* ws, size_t ws_bytes,
+                          drq_stream_t stream) {
+  if (!params || !obs || !action_out || !ws) return DRQ_EARG;
+  if (!drq_act_batch_supported(n, C, A, F, H)) return DRQ_EARG;
+  if (ws_bytes < drq_act_ws_bytes(n, C, A, F, H)) return DRQ_EWS;
+  const ParamLayout P = param_layout(C, A, F, H);
+  const HeadOff& a = P.actor;
+  ActWeights w{};
+  for (int l = 0; l < 4; ++l) {
+    w.enc_w[l] = params + P.enc_w[l];
+    w.enc_b[l] = params + P.enc_b[l];
+  }
+  w.trunk_w = params + a.trunk_w;
+  w.trunk_b = params + a.trunk_b;
+  w.ln_g = params + a.ln_g;
+  w.ln_b = params + a.ln_b;
+  for (int l = 0; l < 3; ++l) {
+    w.w[l] = params + a.w[0][l];
+    w.b[l] = params + a.b[0][l];
+  }
+  return drq_act_batch_launch(w, A, F, H, obs, n, noise, std, mu_out, action_out, static_cast<float*>(ws),
+                              (hipStream_t)stream);
+}

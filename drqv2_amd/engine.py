@@ -341,6 +341,7 @@ class StepEngine:
         self.critic_opt = mk("critic", critic)
         self._ws = None
         self._ws_B = None
+        self._act_ws = None       # scratch of act_batch_forward's fused path (never the step workspace), grown on demand
         self._base = None
         self.sums = torch.zeros(8, device=dev, dtype=torch.float32)
         # pinned host mirror of the metric sums (DrqStep.sums_host): slot 8 = sequence word of the update
@@ -865,3 +866,49 @@ class StepEngine:
         with torch.cuda.device(self.device):
             check(lib.drq_act_forward(ctypes.byref(d), ptr(obs_u8), n, ptr(mu)), "drq_act_forward")
         return mu
+
+    # rows up to which act_batch_forward runs the inference launches of csrc/act.hip (drq_act_batch); above it the batch
+    # goes through drq_act_forward, whose kernels are built for batches of hundreds.  Measured on an MI355X
+    # (tools/act_bench.py, profiles/act_batch_bench.txt; device-event us per call, fused against act_forward): n = 1
+    # 53.8 / 76.0, n = 4 60.7 / 81.2, n = 16 129.2 / 86.7, n = 64 258.4 / 111.6 -- the crossover lies between 4 and 16
+    # rows and nothing in between was measured, so the constant is the largest n with a measured win.  The library
+    # itself takes up to 256 rows (tests and tools raise the constant on an instance to reach them).
+    ACT_FUSED_MAX_ROWS = 4
+
+    def act_batch_forward(self, obs_u8, noise=None, std=1.0):
+        """obs u8 [n,C,84,84] on the GPU -> action [n,A] (device, nothing waits): mu when noise is None, else
+        clamp(mu + noise*std, +-(1-1e-6)) with noise float32 [n,A] (TruncatedNormal.sample(clip=None)).
+        n <= ACT_FUSED_MAX_ROWS: six launches of their own in a scratch buffer of their own -- the step workspace is not
+        touched, so the call may sit between encode() and update_critic().  Larger n is routed through act_forward in
+        chunks; that path runs in the STEP workspace like act() and must not sit inside an update."""
+        if obs_u8.dtype != torch.uint8 or not obs_u8.is_cuda or obs_u8.device != self.device:
+            raise _lib.DrqError(f"act_batch(): uint8 frames on {self.device} required, got {obs_u8.dtype} on "
+                                f"{obs_u8.device}")
+        if obs_u8.dim() != 4 or tuple(obs_u8.shape[1:]) != (self.C, 84, 84) or obs_u8.shape[0] < 1:
+            raise _lib.DrqError(f"act_batch(): frames of shape (n >= 1, {self.C}, 84, 84) required, got "
+                                f"{tuple(obs_u8.shape)}")
+        if not obs_u8.is_contiguous():
+            raise _lib.DrqError("act_batch(): contiguous frames required")
+        n = obs_u8.shape[0]
+        if noise is not None and (noise.dtype != torch.float32 or noise.device != self.device
+                                  or tuple(noise.shape) != (n, self.A) or not noise.is_contiguous()):
+            raise _lib.DrqError(f"act_batch(): noise must be contiguous float32 {(n, self.A)} on {self.device}")
+        self.flush()
+        lib = _lib.load()
+        need = lib.drq_act_ws_bytes(n, self.C, self.A, self.F, self.H) if n <= self.ACT_FUSED_MAX_ROWS else 0
+        if need > 0:
+            if self._act_ws is None or self._act_ws.numel() * 4 < need:
+                self._act_ws = None
+                self._act_ws = torch.zeros(need // 4, device=self.device, dtype=torch.float32)
+            action = torch.empty((n, self.A), device=self.device, dtype=torch.float32)
+            with torch.cuda.device(self.device):
+                check(lib.drq_act_batch(ptr(self.params), self.C, self.A, self.F, self.H, ptr(obs_u8), n, ptr(noise),
+                                        float(std), None, ptr(action), ptr(self._act_ws), self._act_ws.numel() * 4,
+                                        self._stream()), "drq_act_batch")
+            return action
+        cap = 2 * self._ws_B if self._ws_B is not None else n        # drq_act_forward takes <= 2*B rows
+        mu = torch.cat([self.act_forward(obs_u8[i:i + cap]) for i in range(0, n, cap)])
+        if noise is None:
+            return mu
+        lim = 1.0 - 1e-6
+        return (mu + noise * float(std)).clamp_(-lim, lim)

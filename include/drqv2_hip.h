@@ -426,6 +426,21 @@ int drq_publish_sums(const float* sums, float* sums_host, unsigned seq, drq_stre
  * (n <= 2*B; uses s->params, s->ws, s->stream only; must not run between the phases of an update). */
 int drq_act_forward(const DrqStep* s, const uint8_t* obs, int n, float* mu_out);
 
+/* ---- batched policy inference on launches of its own (csrc/act.hip): the body of DrQV2Agent.act (drqv2.py:164-175)
+ * for n frame stacks at once, without unsqueeze(0) / [0].  obs u8 [n][C][84][84] -> obs/255 - 0.5 (:64) -> the four
+ * Conv2d+ReLU (:55-59) -> flatten (:66) -> actor trunk Linear + LayerNorm + tanh (:74-75) -> policy MLP (:77-81) ->
+ * tanh = mu [n][A] (:88-89); action_out [n][A] = mu (noise == NULL: dist.mean, :169) or clamp(mu + noise*std,
+ * +-(1 - 1e-6)) with noise [n][A] the caller's standard-normal draw (dist.sample(clip=None), :171, utils.py:112-126).
+ * The :173-174 uniform_ override stays with the caller.  fp32 throughout; six kernel launches for any n; the weights
+ * are read from `params` (the arena of drq_param_layout) as they are when the launches run, nothing is cached between
+ * calls.  Domain: C = 9, 1 <= n <= 256, 0 < F <= 256, any A, H >= 1; anything else is DRQ_EARG before any launch.
+ * ws: drq_act_ws_bytes(n_max, ...) bytes (0 = unsupported dimensions) serve every n <= n_max; a ws_bytes smaller than
+ * drq_act_ws_bytes(n, ...) is DRQ_EWS.  It is scratch only: no counter or state lives in it, and it is never the step
+ * workspace, so a call may sit between the phases of an update.  mu_out may be NULL. */
+size_t drq_act_ws_bytes(int n_max, int C, int A, int F, int H);
+int drq_act_batch(const float* params, int C, int A, int F, int H, const uint8_t* obs, int n, const float* noise,
+                  float std, float* mu_out, float* action_out, void* ws, size_t ws_bytes, drq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
