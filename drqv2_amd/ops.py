@@ -8,6 +8,14 @@ from ._lib import check, ptr
 ENC_H = (84, 41, 39, 37, 35)
 
 
+def _alloc(shape, dtype, device, kind="out"):
+    """Every result and workspace of this module comes from here (tests swap it for poisoned, guarded memory).
+    kind: "out" = a result the launch writes in full, "ws" = scratch, "zero" = a zeroed buffer it writes partly."""
+    if kind == "zero":
+        return torch.zeros(shape, device=device, dtype=dtype)
+    return torch.empty(shape, device=device, dtype=dtype)
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -38,7 +46,7 @@ def random_shifts_aug(x, shift, pad=4, base=None, fuse_norm=False):
     assert h == w
     shift = _need(shift.reshape(n, 2), name="shift")
     base = aug_base_grid(h, pad, x.device) if base is None else _need(base, name="base")
-    out = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
+    out = _alloc((n, c, h, w), torch.float32, x.device)
     if x.dtype == torch.uint8:
         _need(x, torch.uint8, "obs")
         check(lib.drq_aug_fwd(ptr(x), ptr(shift), ptr(base), ptr(out), n, c, h, pad, int(fuse_norm), _stream()),
@@ -65,9 +73,9 @@ def conv1_aug_fwd(obs, shift, obs1, shift1, w, b, n_store=None, base=None, bf16=
     shift, shift1 = _need(shift.reshape(n, 2), name="shift"), _need(shift1.reshape(n, 2), name="shift1")
     base = aug_base_grid(84, 4, obs.device) if base is None else _need(base, name="base")
     n_store = n if n_store is None else n_store
-    y = (torch.empty((2 * n, 41, 41, 32), device=obs.device, dtype=torch.bfloat16) if y_nhwc else
-         torch.empty((2 * n, 32, 41, 41), device=obs.device, dtype=torch.float32))
-    xaug = torch.zeros((2 * n, 9, 84, 84), device=obs.device, dtype=torch.float32)
+    y = (_alloc((2 * n, 41, 41, 32), torch.bfloat16, obs.device) if y_nhwc else
+         _alloc((2 * n, 32, 41, 41), torch.float32, obs.device))
+    xaug = _alloc((2 * n, 9, 84, 84), torch.float32, obs.device, "zero")
     if y_nhwc and not bf16:
         raise _lib.DrqError("conv1_aug_fwd: the channel-contiguous bf16 output belongs to the bf16 form")
     fn = lib.drq_conv1_aug_fwd_bf16_nhwc if y_nhwc else lib.drq_conv1_aug_fwd_bf16 if bf16 else lib.drq_conv1_aug_fwd
@@ -83,8 +91,8 @@ def conv1_aug_fwd_indexed(frames, idx, shift, frames1, idx1, shift1, w, b, n_sto
     shift, shift1 = _need(shift.reshape(n, 2), name="shift"), _need(shift1.reshape(n, 2), name="shift1")
     base = aug_base_grid(84, 4, frames.device) if base is None else _need(base, name="base")
     n_store = n if n_store is None else n_store
-    y = torch.empty((2 * n, 32, 41, 41), device=frames.device, dtype=torch.float32)
-    xaug = torch.zeros((2 * n, 9, 84, 84), device=frames.device, dtype=torch.float32)
+    y = _alloc((2 * n, 32, 41, 41), torch.float32, frames.device)
+    xaug = _alloc((2 * n, 9, 84, 84), torch.float32, frames.device, "zero")
     check(lib.drq_conv1_aug_fwd_indexed(ptr(frames), ptr(idx), ptr(shift), ptr(frames1), ptr(idx1), ptr(shift1), ptr(base),
                                         ptr(_need(w, name="w")), ptr(_need(b, name="b")), ptr(xaug), ptr(y), n, n_store,
                                         _stream()), "drq_conv1_aug_fwd_indexed")
@@ -94,7 +102,7 @@ def conv1_aug_fwd_indexed(frames, idx, shift, frames1, idx1, shift1, w, b, n_sto
 def u8_normalize(x):
     lib = _lib.load()
     _need(x, torch.uint8, "obs")
-    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    y = _alloc(x.shape, torch.float32, x.device)
     check(lib.drq_u8_normalize(ptr(x), ptr(y), x.numel(), _stream()), "drq_u8_normalize")
     return y
 
@@ -104,7 +112,7 @@ def conv3x3_fwd(x, w, b, stride, relu=True, bf16=False, wino=False):
     _need(x, name="x"), _need(w, name="w"), _need(b, name="b")
     nb, cin, hin, _ = x.shape
     hout = (hin - 3) // stride + 1
-    y = torch.empty((nb, 32, hout, hout), device=x.device, dtype=torch.float32)
+    y = _alloc((nb, 32, hout, hout), torch.float32, x.device)
     if wino:
         check(lib.drq_conv3x3_fwd_wino(ptr(x), ptr(w), ptr(b), ptr(y), nb, hin, int(relu), 32 * hout * hout, hout * hout,
                                        hout, 0, _stream()), "drq_conv3x3_fwd_wino")
@@ -134,11 +142,11 @@ def conv3x3_dgrad(dy_pad, w, mask, bf16=False, wino=False, pad_out=False):
         if not wino:
             raise _lib.DrqError("conv3x3_dgrad: pad_out is implemented for the Winograd form")
         hpi = hin + 4
-        dx = torch.zeros((nb, 32, hpi, hpi), device=dy_pad.device, dtype=torch.float32)
+        dx = _alloc((nb, 32, hpi, hpi), torch.float32, dy_pad.device, "zero")
         check(lib.drq_conv3x3_dgrad_wino(ptr(dy_pad), ptr(w), ptr(mask), ptr(dx), nb, hout, 32 * hpi * hpi, hpi * hpi, hpi,
                                          2 * hpi + 2, _stream()), "drq_conv3x3_dgrad_wino")
         return dx
-    dx = torch.empty((nb, 32, hin, hin), device=dy_pad.device, dtype=torch.float32)
+    dx = _alloc((nb, 32, hin, hin), torch.float32, dy_pad.device)
     if wino:
         check(lib.drq_conv3x3_dgrad_wino(ptr(dy_pad), ptr(w), ptr(mask), ptr(dx), nb, hout, 32 * hin * hin, hin * hin, hin,
                                          0, _stream()), "drq_conv3x3_dgrad_wino")
@@ -160,11 +168,11 @@ def conv3x3_wgrad(x, dy, stride, bf16=False, wino=False, ws=None):
     if not (dy.is_cuda and dy.dtype == torch.float32 and dy.stride(3) == 1):
         raise _lib.DrqError("dy: GPU fp32 with unit innermost stride required")
     nb, cin, hin, _ = x.shape
-    dw = torch.empty((32, cin, 3, 3), device=x.device, dtype=torch.float32)
-    db = torch.empty((32,), device=x.device, dtype=torch.float32)
+    dw = _alloc((32, cin, 3, 3), torch.float32, x.device)
+    db = _alloc((32,), torch.float32, x.device)
     nbytes = lib.drq_conv3x3_wgrad_ws_bytes()
     if ws is None:
-        ws = torch.empty((nbytes // 4,), device=x.device, dtype=torch.float32)
+        ws = _alloc((nbytes // 4,), torch.float32, x.device, "ws")
     elif ws.numel() * 4 < nbytes:
         raise _lib.DrqError("conv3x3_wgrad: workspace too small")
     if wino:        # dy must be the interior view of a buffer zero-padded by 2 (the kernel reads the padding as zeros)
@@ -198,8 +206,8 @@ def conv3x3_fwd_bf16_nhwc(x, w, b, relu=True, y_nhwc=True):
     hin = x.shape[1] if x_nhwc else x.shape[2]
     hout = hin - 2
     assert x.is_cuda and x.is_contiguous() and (x.shape[3] == 32 if x_nhwc else x.shape[1] == 32)
-    y = (torch.empty((nb, hout, hout, 32), device=x.device, dtype=torch.bfloat16) if y_nhwc else
-         torch.empty((nb, 32, hout, hout), device=x.device, dtype=torch.float32))
+    y = (_alloc((nb, hout, hout, 32), torch.bfloat16, x.device) if y_nhwc else
+         _alloc((nb, 32, hout, hout), torch.float32, x.device))
     check(lib.drq_conv3x3_fwd_bf16_nhwc(ptr(x), ptr(w), ptr(b), ptr(y), nb, hin, int(relu), int(x_nhwc), int(y_nhwc),
                                         _stream()), "drq_conv3x3_fwd_bf16_nhwc")
     return y
@@ -217,8 +225,8 @@ def conv3x3_dgrad_bf16_nhwc(dy_pad, w, mask_nhwc, dx_nhwc=False):
     hin = hout + 2
     assert dy_pad.is_cuda and dy_pad.is_contiguous()
     assert mask_nhwc.dtype == torch.bfloat16 and tuple(mask_nhwc.shape) == (nb, hin, hin, 32) and mask_nhwc.is_contiguous()
-    dx = (torch.zeros((nb, hin + 4, hin + 4, 32), device=dy_pad.device, dtype=torch.bfloat16) if dx_nhwc else
-          torch.empty((nb, 32, hin, hin), device=dy_pad.device, dtype=torch.float32))
+    dx = (_alloc((nb, hin + 4, hin + 4, 32), torch.bfloat16, dy_pad.device, "zero") if dx_nhwc else
+          _alloc((nb, 32, hin, hin), torch.float32, dy_pad.device))
     check(lib.drq_conv3x3_dgrad_bf16_nhwc(ptr(dy_pad), ptr(w), ptr(mask_nhwc), ptr(dx), nb, hout, int(dy_nhwc), int(dx_nhwc),
                                           32 * hin * hin, hin * hin, hin, 0, _stream()), "drq_conv3x3_dgrad_bf16_nhwc")
     return dx
@@ -229,10 +237,10 @@ def conv3x3_wgrad_bf16_nhwc(x_nhwc, dy):
     lib = _lib.load()
     nb, hin, _, _ = x_nhwc.shape
     assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.is_contiguous() and x_nhwc.shape[3] == 32
-    dw = torch.empty((32, 32, 3, 3), device=dy.device, dtype=torch.float32)
-    db = torch.empty((32,), device=dy.device, dtype=torch.float32)
+    dw = _alloc((32, 32, 3, 3), torch.float32, dy.device)
+    db = _alloc((32,), torch.float32, dy.device)
     nbytes = lib.drq_conv3x3_wgrad_ws_bytes()
-    ws = torch.empty((nbytes // 4,), device=dy.device, dtype=torch.float32)
+    ws = _alloc((nbytes // 4,), torch.float32, dy.device, "ws")
     if dy.dtype == torch.bfloat16:
         assert tuple(dy.shape) == (nb, hin + 2, hin + 2, 32) and dy.is_contiguous()
         check(lib.drq_conv3x3_wgrad_bf16_nhwc(ptr(x_nhwc), ptr(dy), ptr(dw), ptr(db), nb, hin, 1, 0, 0, 0, 0, ptr(ws), nbytes,
@@ -254,9 +262,9 @@ def gemm(A, a_kc, B, b_kc, M, N, K, lda=None, ldb=None, bias=None, relu=False, a
     ldc = ldc if ldc is not None else N
     c_bs = c_bs if c_bs is not None else M * N
     if out is None:
-        out = torch.empty((nbatch, M, N) if nbatch > 1 else (M, N), device=dev, dtype=torch.float32)
+        out = _alloc((nbatch, M, N) if nbatch > 1 else (M, N), torch.float32, dev)
     if ws is None:
-        ws = torch.empty((16 * 1024 * 1024,), device=dev, dtype=torch.float32)
+        ws = _alloc((16 * 1024 * 1024,), torch.float32, dev, "ws")
     check(lib.drq_gemm_f32(ptr(A), lda, int(a_kc), ptr(B), ldb, int(b_kc), ptr(out), ldc, M, N, K, nbatch, a_bs, b_bs,
                            c_bs, ptr(bias), bias_bs, int(relu), ptr(aux), (aux.shape[-1] if aux is not None else 0),
                            aux_bs, 0, tile, splitk, ptr(ws), ws.numel() * 4, _stream()), "drq_gemm_f32")
@@ -280,7 +288,7 @@ def linear_wgrad(dy, x, **kw):
     K = x.shape[1]
     dw = gemm(dy, False, x, False, N, K, Brows, lda=N, ldb=K, **kw)
     lib = _lib.load()
-    db = torch.empty((N,), device=dy.device, dtype=torch.float32)
+    db = _alloc((N,), torch.float32, dy.device)
     check(lib.drq_colsum(ptr(dy), N, 0, ptr(db), 0, Brows, N, 1, _stream()), "drq_colsum")
     return dw, db
 
@@ -288,9 +296,9 @@ def linear_wgrad(dy, x, **kw):
 def ln_tanh_fwd(z, gamma, beta, save=True):
     lib = _lib.load()
     rows, F = z.shape
-    out = torch.empty_like(z)
-    xhat = torch.empty_like(z) if save else None
-    rstd = torch.empty((rows,), device=z.device, dtype=torch.float32) if save else None
+    out = _alloc(z.shape, z.dtype, z.device)
+    xhat = _alloc(z.shape, z.dtype, z.device) if save else None
+    rstd = _alloc((rows,), torch.float32, z.device) if save else None
     check(lib.drq_ln_tanh_fwd(ptr(z), F, ptr(gamma), ptr(beta), ptr(out), F, ptr(xhat), ptr(rstd), rows, F, _stream()),
           "drq_ln_tanh_fwd")
     return out, xhat, rstd
@@ -299,8 +307,8 @@ def ln_tanh_fwd(z, gamma, beta, save=True):
 def ln_tanh_bwd(dh, h, xhat, rstd, gamma):
     lib = _lib.load()
     rows, F = dh.shape
-    dz, dln = torch.empty_like(dh), torch.empty_like(dh)
-    dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
+    dz, dln = _alloc(dh.shape, dh.dtype, dh.device), _alloc(dh.shape, dh.dtype, dh.device)
+    dg, db = _alloc(gamma.shape, gamma.dtype, gamma.device), _alloc(gamma.shape, gamma.dtype, gamma.device)
     check(lib.drq_ln_tanh_bwd(ptr(dh), F, None, 0, ptr(h), F, ptr(xhat), ptr(rstd), ptr(gamma), ptr(dz), ptr(dln),
                               ptr(dg), ptr(db), rows, F, _stream()), "drq_ln_tanh_bwd")
     return dz, dg, db
@@ -309,7 +317,7 @@ def ln_tanh_bwd(dh, h, xhat, rstd, gamma):
 def trunc_normal_sample(pre_tanh, noise, std, clip):
     lib = _lib.load()
     B, A = pre_tanh.shape
-    mu, a = torch.empty_like(pre_tanh), torch.empty_like(pre_tanh)
+    mu, a = (_alloc(pre_tanh.shape, pre_tanh.dtype, pre_tanh.device) for _ in range(2))
     check(lib.drq_trunc_normal_sample(ptr(pre_tanh), ptr(noise), float(std), float(clip if clip is not None else 0.0),
                                       int(clip is not None), ptr(mu), ptr(a), A, B, A, _stream()),
           "drq_trunc_normal_sample")
@@ -329,7 +337,7 @@ def ema_flat(p, t, tau):
 
 def tanh(x):
     lib = _lib.load()
-    y = torch.empty_like(x)
+    y = _alloc(x.shape, x.dtype, x.device)
     check(lib.drq_tanh(ptr(x), ptr(y), x.numel(), _stream()), "drq_tanh")
     return y
 
@@ -338,7 +346,7 @@ def tanh_bwd(y, dy):
     """dy * (1 - y^2): the gradient through y = tanh(x)."""
     lib = _lib.load()
     _need(y, name="y"), _need(dy, name="dy")
-    dx = torch.empty_like(y)
+    dx = _alloc(y.shape, y.dtype, y.device)
     check(lib.drq_tanh_bwd(ptr(y), ptr(dy), ptr(dx), y.numel(), _stream()), "drq_tanh_bwd")
     return dx
 
@@ -351,7 +359,7 @@ def relu_mask_pad(dy, mask, pad=2):
     if mask is not None:
         _need(mask, name="mask")
         assert mask.shape == dy.shape
-    out = torch.empty((n, c, h + 2 * pad, h + 2 * pad), device=dy.device, dtype=torch.float32)
+    out = _alloc((n, c, h + 2 * pad, h + 2 * pad), torch.float32, dy.device)
     check(lib.drq_relu_mask_pad(ptr(dy), ptr(mask), ptr(out), n * c, h, pad, _stream()), "drq_relu_mask_pad")
     return out
 
@@ -363,7 +371,7 @@ def conv1_dgrad(dy_pad, w):
     nb = dy_pad.shape[0]
     if tuple(dy_pad.shape[1:]) != (32, 45, 45) or tuple(w.shape) != (32, 9, 3, 3):
         raise _lib.DrqError("conv1_dgrad: dy_pad [nb,32,45,45] and w [32,9,3,3] required")
-    dx = torch.empty((nb, 9, 84, 84), device=dy_pad.device, dtype=torch.float32)
+    dx = _alloc((nb, 9, 84, 84), torch.float32, dy_pad.device)
     check(lib.drq_conv1_dgrad(ptr(dy_pad), ptr(w), ptr(dx), nb, _stream()), "drq_conv1_dgrad")
     return dx
 
@@ -376,7 +384,7 @@ def aug_bwd_f32(dy, shift, pad=4, base=None):
     assert h == w
     shift = _need(shift.reshape(n, 2), name="shift")
     base = aug_base_grid(h, pad, dy.device) if base is None else _need(base, name="base")
-    dx = torch.empty_like(dy)
+    dx = _alloc(dy.shape, dy.dtype, dy.device)
     check(lib.drq_aug_bwd_f32(ptr(dy), ptr(shift), ptr(base), ptr(dx), n, c, h, pad, _stream()), "drq_aug_bwd_f32")
     return dx
 
@@ -395,9 +403,9 @@ def gemm_batched(As, a_kc, Bs, b_kc, M, N, K, lda, ldb, biases=None, relu=False,
     n = len(As)
     dev = As[0].device
     if Cs is None:
-        Cs = [torch.empty((M, N), device=dev, dtype=torch.float32) for _ in range(n)]
-    rs = [torch.empty((M,), device=dev, dtype=torch.float32) for _ in range(n)] if rowsum else None
-    ws = torch.empty((16 * 1024 * 1024,), device=dev, dtype=torch.float32)
+        Cs = [_alloc((M, N), torch.float32, dev) for _ in range(n)]
+    rs = [_alloc((M,), torch.float32, dev) for _ in range(n)] if rowsum else None
+    ws = _alloc((16 * 1024 * 1024,), torch.float32, dev, "ws")
     if bf16:
         check(lib.drq_gemm_batched_bf16(n, _ptr_array(As), lda, int(a_kc), _ptr_array(Bs), ldb, int(b_kc), _ptr_array(Cs),
                                         N, M, N, K, _ptr_array(biases) if biases else None, int(relu),
@@ -420,8 +428,8 @@ def gemm_batched_partial(As, Bs, M, N, K, lda, ldb):
     lib = _lib.load()
     n = len(As)
     dev = As[0].device
-    Cs = [torch.zeros((M, N), device=dev, dtype=torch.float32) for _ in range(n)]
-    ws = torch.zeros((16 * 1024 * 1024,), device=dev, dtype=torch.float32)
+    Cs = [_alloc((M, N), torch.float32, dev, "zero") for _ in range(n)]
+    ws = _alloc((16 * 1024 * 1024,), torch.float32, dev, "zero")
     sk = ctypes.c_int(0)
     check(lib.drq_gemm_batched_partial(n, _ptr_array(As), lda, 1, _ptr_array(Bs), ldb, 1, _ptr_array(Cs), N, M, N, K, None, ptr(ws),
              ws.numel() * 4, ctypes.byref(sk), _stream()), "drq_gemm_batched_partial")
@@ -434,7 +442,7 @@ def gemm_batched_partial(As, Bs, M, N, K, lda, ldb):
 def qout_fwd(hs, ws_, bs):
     lib = _lib.load()
     B, H = hs[0].shape
-    qs = [torch.empty((B,), device=hs[0].device, dtype=torch.float32) for _ in hs]
+    qs = [_alloc((B,), torch.float32, hs[0].device) for _ in hs]
     check(lib.drq_qout_fwd(len(hs), _ptr_array(hs), _ptr_array(ws_), _ptr_array(bs), _ptr_array(qs), B, H, _stream()),
           "drq_qout_fwd")
     return qs
@@ -444,9 +452,9 @@ def qout_bwd(dqs, hs, ws_, want_wgrad=True):
     lib = _lib.load()
     B, H = hs[0].shape
     dev = hs[0].device
-    dhs = [torch.empty((B, H), device=dev, dtype=torch.float32) for _ in hs]
-    dws = [torch.empty((H,), device=dev, dtype=torch.float32) for _ in hs] if want_wgrad else None
-    dbs = [torch.empty((1,), device=dev, dtype=torch.float32) for _ in hs] if want_wgrad else None
+    dhs = [_alloc((B, H), torch.float32, dev) for _ in hs]
+    dws = [_alloc((H,), torch.float32, dev) for _ in hs] if want_wgrad else None
+    dbs = [_alloc((1,), torch.float32, dev) for _ in hs] if want_wgrad else None
     check(lib.drq_qout_bwd(len(hs), _ptr_array(dqs), _ptr_array(hs), _ptr_array(ws_), _ptr_array(dhs),
                            _ptr_array(dws) if dws else None, _ptr_array(dbs) if dbs else None, B, H, _stream()),
           "drq_qout_bwd")
@@ -461,8 +469,8 @@ def mlp_fwd(xs, ws_, bs, relu=True, qws=None):
     M, K = xs[0].shape
     N = ws_[0].shape[0]
     dev = xs[0].device
-    ys = [torch.empty((M, N), device=dev, dtype=torch.float32) for _ in xs]
-    qps = [torch.zeros((M, N // 32), device=dev, dtype=torch.float32) for _ in xs] if qws else None
+    ys = [_alloc((M, N), torch.float32, dev) for _ in xs]
+    qps = [_alloc((M, N // 32), torch.float32, dev, "zero") for _ in xs] if qws else None
     nq = ctypes.c_int(0)
     check(lib.drq_mlp_fwd(len(xs), _ptr_array(xs), xs[0].stride(0), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(ys), N,
                           M, N, K, _ptr_array(bs) if bs else None, int(relu), _ptr_array(qws) if qws else None,
@@ -476,7 +484,7 @@ def mlp_dgrad(dys, ws_, masks=None):
     lib = _lib.load()
     M, K = dys[0].shape
     N = ws_[0].shape[1]
-    dxs = [torch.empty((M, N), device=dys[0].device, dtype=torch.float32) for _ in dys]
+    dxs = [_alloc((M, N), torch.float32, dys[0].device) for _ in dys]
     check(lib.drq_mlp_dgrad(len(dys), _ptr_array(dys), dys[0].stride(0), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(dxs),
                             N, M, N, K, _ptr_array(masks) if masks else None, (masks[0].stride(0) if masks else 0),
                             _stream()), "drq_mlp_dgrad")
@@ -489,9 +497,9 @@ def mlp_wgrad_dgrad(dys, xs, ws_, masks=None):
     Brows, Nout = dys[0].shape
     Kin = xs[0].shape[1]
     dev = dys[0].device
-    dws = [torch.empty((Nout, Kin), device=dev, dtype=torch.float32) for _ in dys]
-    dbs = [torch.empty((Nout,), device=dev, dtype=torch.float32) for _ in dys]
-    dxs = [torch.empty((Brows, Kin), device=dev, dtype=torch.float32) for _ in dys]
+    dws = [_alloc((Nout, Kin), torch.float32, dev) for _ in dys]
+    dbs = [_alloc((Nout,), torch.float32, dev) for _ in dys]
+    dxs = [_alloc((Brows, Kin), torch.float32, dev) for _ in dys]
     check(lib.drq_mlp_wgrad_dgrad(len(dys), _ptr_array(dys), dys[0].stride(0), _ptr_array(xs), xs[0].stride(0),
                                   _ptr_array(dws), _ptr_array(dbs), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(dxs),
                                   Kin, _ptr_array(masks) if masks else None, (masks[0].stride(0) if masks else 0),
@@ -514,11 +522,11 @@ def ln_l1_fwd(jobs, F, H, splitk=0, slab=0):
         r = j["rows"]
         t = j.get("tail")
         n_t = t.shape[1] if t is not None else 0
-        o = torch.zeros((r, F + n_t), device=dev, dtype=torch.float32)
-        xh = torch.empty((r, F), device=dev, dtype=torch.float32) if j.get("save", True) else None
-        rs = torch.empty((r,), device=dev, dtype=torch.float32) if j.get("save", True) else None
+        o = _alloc((r, F + n_t), torch.float32, dev, "zero")
+        xh = _alloc((r, F), torch.float32, dev) if j.get("save", True) else None
+        rs = _alloc((r,), torch.float32, dev) if j.get("save", True) else None
         heads = j.get("heads", [])
-        ys = [torch.empty((r, H), device=dev, dtype=torch.float32) for _ in heads]
+        ys = [_alloc((r, H), torch.float32, dev) for _ in heads]
         res.append(dict(out=o, xhat=xh, rstd=rs, ys=ys))
         part.append(j.get("part")); z.append(j.get("z")); bias.append(j.get("bias"))
         gamma.append(j["gamma"]); beta.append(j["beta"]); out.append(o); ldo.append(F + n_t)
@@ -543,10 +551,10 @@ def policy_out_l1_fwd(p2, w3, b3, srow0, F, std, clip, noise_hi, ha_hi, noise_lo
     rows, H = p2.shape
     A = w3.shape[0]
     dev = p2.device
-    p3 = torch.empty((rows, A), device=dev, dtype=torch.float32)
-    mu_hi = torch.empty((rows - srow0, A), device=dev, dtype=torch.float32)
-    mu_lo = torch.empty((srow0, A), device=dev, dtype=torch.float32) if noise_lo is not None else None
-    ys = [torch.empty((rows - srow0, H), device=dev, dtype=torch.float32) for _ in (heads or [])]
+    p3 = _alloc((rows, A), torch.float32, dev)
+    mu_hi = _alloc((rows - srow0, A), torch.float32, dev)
+    mu_lo = _alloc((srow0, A), torch.float32, dev) if noise_lo is not None else None
+    ys = [_alloc((rows - srow0, H), torch.float32, dev) for _ in (heads or [])]
     check(lib.drq_policy_out_l1_fwd(ptr(p2), ptr(w3), ptr(b3), ptr(p3), rows, srow0, H, A, F, float(std),
                                     float(clip if clip is not None else 0.0), int(clip is not None), ptr(noise_hi),
                                     ptr(mu_hi), ptr(ha_hi), ha_hi.stride(0), ptr(noise_lo), ptr(mu_lo), ptr(ha_lo),

@@ -5,6 +5,9 @@ and must stay within the stated distance (2e-2 normwise, measured 2-4e-3) of the
 import pytest
 import torch
 
+from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned, guarded outputs and workspaces in the op tests;
+#                                                       the whole-update tests allocate nothing through drqv2_amd.ops)
+
 pytestmark = pytest.mark.gpu
 
 

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from drqv2_amd import synth
+from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned, guarded outputs and workspaces in every op test)
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")

@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned, guarded outputs and workspaces in every op test)
+
 pytestmark = pytest.mark.gpu
 
 
