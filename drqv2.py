@@ -8,7 +8,8 @@ Reference: /root/reference/drqv2.py.  Parity contract (tests/):
   * update() issues the four random draws of the reference in its order (drqv2.py:34-38 twice,
     utils.py:119 twice) and runs aug -> encoder -> critic step -> actor step -> target update in
     hand-written HIP kernels; there is no PyTorch/CPU fallback for that path;
-  * metrics: the same 8 keys as python floats when use_tb, {} on gated-off steps.
+  * metrics: the same 8 keys as python floats when use_tb, {} on gated-off steps;
+  * set_behavior_cloning(alpha) (new, not in the reference): DrQ+BC, the TD3+BC actor loss fused into update().
 """
 import math
 
@@ -149,8 +150,40 @@ class DrQV2Agent:
                 "bf16": "bf16", "bfloat16": "bf16", torch.bfloat16: "bf16"}.get(dtype)
         if name is None:
             raise ValueError(f"compute dtype {dtype!r}: 'fp32' or 'bf16'")
+        if name == "bf16" and self._engine.bc_alpha is not None:
+            raise _lib.DrqError(self._engine._BC_BF16)
         self._engine.bf16 = name == "bf16"
         return self
+
+    def set_behavior_cloning(self, alpha):
+        """DrQ+BC for offline training from a fixed dataset (TD3+BC on the DrQ-v2 actor step; new functionality, the
+        reference has no such loss).  alpha=None (default) is the plain update.  With alpha > 0 the critic step is
+        unchanged and the actor step, on the same sample a (fourth draw, gradient straight through to mu), minimises
+            -lambda * mean_i Qmin_i + mean_{i,j} (a - a_beh)^2,   lambda = alpha / mean_i |Qmin_i|  (no gradient),
+        a_beh being the batch's `action`; the arithmetic runs in the BC forms of the actor-step kernels
+        (include/drqv2_hip.h), launch for launch.  Metrics gain "actor_bc_loss" and "actor_bc_lambda"; "actor_loss" is
+        the total.  Single GPU only."""
+        if alpha is not None:
+            try:
+                ok = not isinstance(alpha, bool) and math.isfinite(float(alpha)) and float(alpha) > 0.0
+                with np.errstate(over="ignore"):
+                    ok = ok and 0.0 < float(np.float32(alpha)) < float("inf")      # the kernels take it as fp32
+            except (TypeError, ValueError, OverflowError):
+                ok = False
+            if not ok:
+                raise ValueError(f"behaviour-cloning alpha {alpha!r}: None or a finite float > 0")
+            alpha = float(alpha)
+        self._engine.set_behavior_cloning(alpha)
+        return self
+
+    def _bc_metrics(self, metrics, q_sum, sq_sum, abs_sum, inv):
+        """actor_loss (the total), actor_bc_loss, actor_bc_lambda from the sums the BC loss kernel leaves: q_sum = sum -Qmin
+        (slot 5), sq_sum = sum (a - a_beh)^2 (slot 9), abs_sum = sum |Qmin| (slot 10); floats or 0-d tensors."""
+        lam = self._engine.bc_alpha / (abs_sum * inv)
+        bc = sq_sum * (inv / self._engine.A)
+        metrics["actor_loss"] = lam * (q_sum * inv) + bc
+        metrics["actor_bc_loss"] = bc
+        metrics["actor_bc_lambda"] = lam
 
     def train(self, training=True):
         self.training = training
@@ -274,6 +307,9 @@ class DrQV2Agent:
                 metrics[k] = vals[i]
             metrics["actor_ent"] = torch.tensor(A * (0.5 + 0.5 * math.log(2 * math.pi) + math.log(stddev)),
                                                 dtype=torch.float32)
+            if eng.bc_alpha is not None:
+                bc = eng.bc_sums.clone()     # like vals: the buffer is overwritten by the next update
+                self._bc_metrics(metrics, sums[5], bc[0], bc[1], inv)
         elif self.use_tb:
             s = eng.read_sums()          # the single device->host wait of the update
             # data parallel without global_metrics: the sums cover this rank's rows only
@@ -286,6 +322,8 @@ class DrQV2Agent:
             metrics["actor_loss"] = s[5] * inv
             metrics["actor_logprob"] = s[6] * inv
             metrics["actor_ent"] = A * (0.5 + 0.5 * math.log(2 * math.pi) + math.log(stddev))
+            if eng.bc_alpha is not None:
+                self._bc_metrics(metrics, s[5], *eng.read_bc_sums(), inv)
         return metrics
 
     # ---- the update in the reference's pieces (drqv2.py:177-228, :241-246) -----------------------------------------
@@ -335,6 +373,8 @@ class DrQV2Agent:
             metrics["actor_loss"] = s[5] * inv
             metrics["actor_logprob"] = s[6] * inv
             metrics["actor_ent"] = A * (0.5 + 0.5 * math.log(2 * math.pi) + math.log(stddev))
+            if self._engine.bc_alpha is not None:
+                self._bc_metrics(metrics, s[5], *self._engine.bc_sums.tolist(), inv)
         return metrics
 
     # ---- snapshots: train.py:192-204 pickles the whole agent --------------------------------
@@ -411,7 +451,8 @@ class DrQV2Agent:
         return {"init": self._init_kwargs, "training": self.training,
                 "encoder": cpu(self.encoder.state_dict()), "actor": cpu(self.actor.state_dict()),
                 "critic": cpu(self.critic.state_dict()), "critic_target": cpu(self.critic_target.state_dict()),
-                "opt": {n: getattr(self, n).export_state() for n in ("encoder_opt", "actor_opt", "critic_opt")}}
+                "opt": {n: getattr(self, n).export_state() for n in ("encoder_opt", "actor_opt", "critic_opt")},
+                "bc_alpha": self._engine.bc_alpha}
 
     def _load_reference_state(self, st):
         """`st` is the __dict__ of an agent pickled by the REFERENCE's class (train.py:192-198 pickles the object and
@@ -463,4 +504,5 @@ class DrQV2Agent:
         self.critic_target.load_state_dict(st["critic_target"])
         for n, s in st["opt"].items():
             getattr(self, n).import_state(s)
+        self.set_behavior_cloning(st.get("bc_alpha"))      # absent in snapshots written before DrQ+BC: off
         self.train(st["training"])

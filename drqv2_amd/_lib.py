@@ -82,6 +82,10 @@ PROTOTYPES = {
     "drq_td_mse": (I, [P, P, P, P, P, P, P, P, P, I, F, P]),
     "drq_actor_loss": (I, [P, P, P, L, P, F, P, P, P, I, I, F, P]),
     "drq_actor_dmu": (I, [P, P, L, I, P, P, I, I, P]),
+    "drq_actor_loss_bc": (I, [P, P, P, L, P, L, P, F, F, P, P, P, I, I, F, P]),
+    "drq_qout_bwd_actor_bc": (I, [P, P, P, L, P, L, P, F, F, I, F, P, P, P, P, I, I, P]),
+    "drq_actor_dmu_bc": (I, [P, P, L, I, P, P, L, P, L, F, P, I, I, P]),
+    "drq_policy_out_bwd_bc": (I, [P, P, L, I, P, P, L, P, L, F, P, P, P, P, P, I, I, I, P, I, P]),
     "drq_adam_flat": (I, [P, P, P, P, L, D, L, F, P, D, P]),
     "drq_ema_flat": (I, [P, P, L, D, P]),
     "drq_sum_slices": (I, [P, L, I, P, L, P]),
@@ -98,6 +102,7 @@ PROTOTYPES = {
     "drq_step_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_step_ws_offset": (L, [I, I, I, I, I, I]),
     "drq_update_phase": (I, [C.POINTER(DrqStep), I]),
+    "drq_update_phase_bc": (I, [C.POINTER(DrqStep), I, F]),
     "drq_act_forward": (I, [C.POINTER(DrqStep), P, I, P]),
     "drq_act_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_act_batch": (I, [P, I, I, I, I, P, I, P, F, P, P, P, SZ, P]),

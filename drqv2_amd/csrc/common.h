@@ -61,4 +61,11 @@ __device__ __forceinline__ void drq_publish_mirror(float* host, const float (&v)
   __hip_atomic_store(reinterpret_cast<unsigned*>(host + 8), seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   asm volatile("" ::: "memory");
 }
+// DrQ+BC: the two sums of the BC actor loss travel in slots 9 and 10, ahead of the sequence word like the other eight
+__device__ __forceinline__ void drq_publish_mirror_bc(float* host, const float (&v)[8], float bc_sq, float abs_q,
+                                                      unsigned seq) {
+  __hip_atomic_store(host + 9, bc_sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(host + 10, abs_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  drq_publish_mirror(host, v, seq);
+}
 #endif

@@ -572,6 +572,112 @@ __global__ void actor_dmu_kernel(const float* dha1, const float* dha2, long ld, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// DrQ+BC (TD3+BC on the DrQ-v2 actor; new functionality, the reference has no such loss):
+//   lambda = alpha / mean_i |min(q1,q2)_i|   (a constant of the backward),   bc = mean_{i,j} (a - a_beh)^2,
+//   L = -lambda mean_i min(q1,q2)_i + bc;   dq_k[i] = -lambda / B_global on the smaller head (ties split),
+//   dmu = da_1 + da_2 + 2 (a - a_beh) / (B_global A).
+// lambda needs the sum of |min(q1,q2)| over the whole batch before any dq exists.  Every workgroup that needs it adds
+// the B values itself, in ONE order whatever its size, so that every workgroup of every kernel form gets the same bits:
+// chain t (t < 256) adds rows t, t + 256, ... in that order (16 rows requested per round trip), a wave adds its 64
+// chains (wave_sum), the four wave sums are added in index order.  Called by all threads of a workgroup of >= 256;
+// scratch = 4 floats of LDS that nobody writes again before the caller's next barrier.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float bc_abs_qmin_sum(const float* q1, const float* q2, int B, float* scratch) {
+  if (threadIdx.x < 256) {
+    float t = 0.f;
+    for (int m0 = threadIdx.x; m0 < B; m0 += 16 * 256) {
+      float x[16], y[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int m = min(m0 + 256 * u, B - 1);
+        x[u] = q1[m];
+        y[u] = q2[m];
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (m0 + 256 * u < B) t += fabsf(fminf(x[u], y[u]));
+    }
+    t = wave_sum(t);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = t;
+  }
+  __syncthreads();
+  return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
+}
+
+// -lambda / B_global from that sum: the one place the scale of dq is formed (both loss kernels call it)
+__device__ __forceinline__ float bc_dq_scale(float alpha, int B, float sum_abs, float invB) {
+  const float lambda = alpha * (float)B / sum_abs;
+  return -(lambda * invB);
+}
+
+// actor_loss_kernel with the BC terms.  sums[5], sums[6] as there (sums[5] stays sum -min(q1,q2): the host forms the
+// loss from it), sums[9] = sum (a - a_beh)^2 over [B][A], sums[10] = sum |min(q1,q2)|; the mirror gets slots 9, 10 too.
+__global__ void actor_loss_bc_kernel(const float* q1, const float* q2, const float* a, long lda, const float* abeh,
+                                     long ldb, const float* mu, float std, float alpha, float* dq1, float* dq2,
+                                     float* sums, int B, int A, float invB, float* sums_host, unsigned seq) {
+  __shared__ float sm[4][256];
+  __shared__ float sc[4];
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  const float log_std = logf(std);
+  const float c = 0.91893853320467274178f;   // log(sqrt(2*pi))
+  const float var2 = 2.f * std * std;
+  const float sabs = bc_abs_qmin_sum(q1, q2, B, sc);
+  const float g = bc_dq_scale(alpha, B, sabs, invB);
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const float x = q1[b], y = q2[b];
+    s[0] += -fminf(x, y);
+    dq1[b] = x < y ? g : (x == y ? 0.5f * g : 0.f);
+    dq2[b] = y < x ? g : (x == y ? 0.5f * g : 0.f);
+  }
+  const int nel = B * A;
+  for (int e0 = threadIdx.x; e0 < nel; e0 += 4 * 256) {
+    float av[4], mv[4], bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + u * 256 < nel ? e0 + u * 256 : nel - 1;
+      const int m = e / A, jj = e - m * A;
+      av[u] = a[(long)m * lda + jj];
+      bv[u] = abeh[(long)m * ldb + jj];
+      mv[u] = mu[e];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (e0 + u * 256 < nel) {
+        const float d = av[u] - mv[u];
+        s[1] += -(d * d) / var2 - log_std - c;
+        const float e = av[u] - bv[u];
+        s[2] += e * e;
+      }
+  }
+  block_sum4(s, sm);
+  if (threadIdx.x == 0) {
+    sums[5] = s[0];
+    sums[6] = s[1];
+    sums[9] = s[2];
+    sums[10] = sabs;
+    if (sums_host) {
+      float v8[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v8[i] = i == 5 ? s[0] : (i == 6 ? s[1] : sums[i]);
+      drq_publish_mirror_bc(sums_host, v8, s[2], sabs, seq);
+    }
+  }
+}
+
+// actor_dmu_kernel with the BC pull: dpre = (da1 + da2 + bc_scale (a - a_beh)) (1 - mu^2), bc_scale = 2 / (B_global A)
+__global__ void actor_dmu_bc_kernel(const float* dha1, const float* dha2, long ld, int col0, const float* mu,
+                                    const float* act, long lda, const float* abeh, long ldb, float bc_scale,
+                                    float* dpre, int B, int A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * A) return;
+  const int b = i / A, j = i - b * A;
+  const float da = dha1[(long)b * ld + col0 + j] + dha2[(long)b * ld + col0 + j];
+  const float dm = __fmaf_rn(act[(long)b * lda + j] - abeh[(long)b * ldb + j], bc_scale, da);
+  const float m = mu[i];
+  dpre[i] = dm * (1.f - m * m);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam defaults) over a flat arena, rounding sequence of torch's CPU kernels
 // (oracle/drq_oracle.py:adam_step), optional fused Polyak update of a target arena.
 // ------------------------------------------------------------------------------------------------
@@ -751,6 +857,10 @@ struct QOutBwdArgs {
   float std;
   float* sums_host;
   unsigned seq;
+  // BC form of td == 2 (qout_bwd_kernel<CW, true>): the behavioural action [B][ldb] and alpha
+  const float* abeh;
+  long ldb;
+  float alpha;
 };
 
 // Workgroup = 64 columns x 16 row groups (1024 threads).  The per-row scalars dq[B] go to LDS once; the only global
@@ -759,7 +869,8 @@ struct QOutBwdArgs {
 // (16 workgroups per head at hidden_dim 1024); at batch 2,048 that left 32 workgroups walking 2,048 rows each (60 us per
 // launch): 16 columns x 64 row groups gives four times as many (drq_qout_bwd_cw).  The row-group sums are added in
 // the same fixed order either way (deterministic); the two shapes group them differently (rounding-level).
-template <int CW>
+// BC (td == 2 only): the DrQ+BC actor loss, see bc_abs_qmin_sum; BC = false compiles to the kernel as it was.
+template <int CW, bool BC>
 __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
   constexpr int NRG = 1024 / CW;
   extern __shared__ float dql[];            // [B] then NRG x CW + 64 floats of reduction scratch
@@ -778,12 +889,35 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
   float hv0[16];
 #pragma unroll
   for (int u = 0; u < 16; ++u) hv0[u] = h[(long)min(rg + NRG * u, a.B - 1) * a.H + nc];
+  float bc_sabs = 0.f;   // BC: sum |min(q1,q2)| over the batch, the same bits in every workgroup
   if (a.td == 2) {
     const float *qz = z == 0 ? a.q1 : a.q2, *qo = z == 0 ? a.q2 : a.q1;
-    const float g = -a.invB;
-    for (int m = threadIdx.x; m < a.B; m += 1024) {
-      const float x = qz[m], y = qo[m];
-      dql[m] = x < y ? g : (x == y ? 0.5f * g : 0.f);
+    if constexpr (BC) {
+      // the Q values of this thread's first four rows are requested before the batch sum, like hv0: only the scale waits
+      float xq[4], yq[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int m = min((int)threadIdx.x + 1024 * u, a.B - 1);
+        xq[u] = qz[m];
+        yq[u] = qo[m];
+      }
+      bc_sabs = bc_abs_qmin_sum(a.q1, a.q2, a.B, sb);
+      const float g = bc_dq_scale(a.alpha, a.B, bc_sabs, a.invB);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int m = threadIdx.x + 1024 * u;
+        if (m < a.B) dql[m] = xq[u] < yq[u] ? g : (xq[u] == yq[u] ? 0.5f * g : 0.f);
+      }
+      for (int m = threadIdx.x + 4096; m < a.B; m += 1024) {
+        const float x = qz[m], y = qo[m];
+        dql[m] = x < y ? g : (x == y ? 0.5f * g : 0.f);
+      }
+    } else {
+      const float g = -a.invB;
+      for (int m = threadIdx.x; m < a.B; m += 1024) {
+        const float x = qz[m], y = qo[m];
+        dql[m] = x < y ? g : (x == y ? 0.5f * g : 0.f);
+      }
     }
   } else if (a.td) {
     const float* qz = z == 0 ? a.q1 : a.q2;
@@ -832,7 +966,7 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
   // metric sums of the actor loss: workgroup (0, 0), the same fixed tree; then the host mirror
   if (a.td == 2 && blockIdx.x == 0 && z == 0) {
     __syncthreads();
-    float v[2] = {0.f, 0.f};
+    float v[3] = {0.f, 0.f, 0.f};   // v[2] (BC): sum (a - a_beh)^2, element by element like the log-probabilities
     const float log_std = logf(a.std);
     const float c0 = 0.91893853320467274178f;   // log(sqrt(2*pi))
     const float var2 = 2.f * a.std * a.std;
@@ -843,28 +977,35 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
     // the grouping differs from a row-by-row sum at rounding level.
     const int nel = a.B * a.A;
     for (int e0 = threadIdx.x; e0 < nel; e0 += 4 * 1024) {
-      float av[4], mv[4];
+      float av[4], mv[4], bv[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int e = e0 + u * 1024 < nel ? e0 + u * 1024 : nel - 1;
         const int m = e / a.A, jj = e - m * a.A;
         av[u] = a.act[(long)m * a.lda + jj];
         mv[u] = a.mu[e];
+        if constexpr (BC) bv[u] = a.abeh[(long)m * a.ldb + jj];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         if (e0 + u * 1024 < nel) {
           const float d = av[u] - mv[u];
           v[1] += -(d * d) / var2 - log_std - c0;
+          if constexpr (BC) {
+            const float e = av[u] - bv[u];
+            v[2] += e * e;
+          }
         }
     }
     s[threadIdx.x] = v[0];
     s[1024 + threadIdx.x] = v[1];
+    if constexpr (BC) s[2048 + threadIdx.x] = v[2];
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
       if ((int)threadIdx.x < o) {
         s[threadIdx.x] += s[threadIdx.x + o];
         s[1024 + threadIdx.x] += s[1024 + threadIdx.x + o];
+        if constexpr (BC) s[2048 + threadIdx.x] += s[2048 + threadIdx.x + o];
       }
       __syncthreads();
     }
@@ -872,11 +1013,16 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
       const float s5 = s[0], s6 = s[1024];
       a.sums[5] = s5;
       a.sums[6] = s6;
+      if constexpr (BC) {
+        a.sums[9] = s[2048];
+        a.sums[10] = bc_sabs;
+      }
       if (a.sums_host) {   // metrics mirror (DrqStep.sums_host): all eight sums, then the sequence word
         float v8[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) v8[i] = i == 5 ? s5 : (i == 6 ? s6 : a.sums[i]);
-        drq_publish_mirror(a.sums_host, v8, a.seq);
+        if constexpr (BC) drq_publish_mirror_bc(a.sums_host, v8, s[2048], bc_sabs, a.seq);
+        else drq_publish_mirror(a.sums_host, v8, a.seq);
       }
     }
   }
@@ -1059,6 +1205,12 @@ struct PolBwdArgs {
   int B, H, A;
   const float* part;    // optional: da1/da2 as split-K partials [2*splitk][B][A] of the two dgrad GEMMs
   int splitk;
+  // BC form (policy_out_bwd_kernel<.., true>): dmu also gets bc_scale (act - abeh), see actor_dmu_bc_kernel
+  const float* act;     // [B][lda] the sampled action
+  long lda;
+  const float* abeh;    // [B][ldb] the behavioural action
+  long ldb;
+  float bc_scale;
 };
 
 constexpr int kPolMaxA = 32;
@@ -1067,7 +1219,8 @@ constexpr int kPolMaxA = 32;
 // the only global stream in the row loop is p2, up to 16 rows of it in flight per thread.  CW = 16 (64 workgroups at
 // hidden_dim 1024) is what the update uses: with 64 columns the launch kept 16 CUs busy with 2*A FMAs per row and
 // thread -- 14.6 us at A = 6, 40 us at A = 21 (batch 256), 47 us at A = 12 (batch 512); CW = 64 remains for tiny H.
-template <int AMAX, int CW>    // AMAX: action_dim rounded up to 8 / 16 / 32 (the per-output loops are unrolled over it)
+// AMAX: action_dim rounded up to 8 / 16 / 32 (the per-output loops are unrolled over it); BC: the DrQ+BC pull in dmu
+template <int AMAX, int CW, bool BC>
 __global__ __launch_bounds__(1024) void policy_out_bwd_kernel(PolBwdArgs a) {
   constexpr int NRG = 1024 / CW;
   extern __shared__ float dpre[];           // [B][A], then 4 x NRG x CW = 4096 floats of reduction scratch
@@ -1083,6 +1236,8 @@ __global__ __launch_bounds__(1024) void policy_out_bwd_kernel(PolBwdArgs a) {
   for (int i = threadIdx.x; i < a.B * a.A; i += 1024) {
     const int m = i / a.A, j = i - m * a.A;
     const float mv = a.mu[i];
+    float pull = 0.f;
+    if constexpr (BC) pull = a.act[(long)m * a.lda + j] - a.abeh[(long)m * a.ldb + j];
     float d1, d2;
     if (a.part) {
       const long slab = (long)a.B * a.A;
@@ -1092,7 +1247,8 @@ __global__ __launch_bounds__(1024) void policy_out_bwd_kernel(PolBwdArgs a) {
       d1 = a.da1[(long)m * a.ld + a.col0 + j];
       d2 = a.da2[(long)m * a.ld + a.col0 + j];
     }
-    dpre[i] = (d1 + d2) * (1.f - mv * mv);
+    if constexpr (BC) dpre[i] = __fmaf_rn(pull, a.bc_scale, d1 + d2) * (1.f - mv * mv);
+    else dpre[i] = (d1 + d2) * (1.f - mv * mv);
   }
   float wn[AMAX], acc[AMAX];
 #pragma unroll
@@ -1270,9 +1426,26 @@ DRQ_API int drq_qout_fwd(int nz, const float* const* h, const float* const* w, c
 
 namespace {
 // 64 columns per workgroup below 1,024 rows, 16 beyond (see qout_bwd_kernel)
+template <bool BC = false>
 void launch_qout_bwd(const QOutBwdArgs& a, int nz, size_t lds, hipStream_t st) {
-  if (a.B >= 1024) hipLaunchKernelGGL(qout_bwd_kernel<16>, dim3((a.H + 15) / 16, nz), dim3(1024), lds, st, a);
-  else hipLaunchKernelGGL(qout_bwd_kernel<64>, dim3((a.H + 63) / 64, nz), dim3(1024), lds, st, a);
+  if (a.B >= 1024) hipLaunchKernelGGL((qout_bwd_kernel<16, BC>), dim3((a.H + 15) / 16, nz), dim3(1024), lds, st, a);
+  else hipLaunchKernelGGL((qout_bwd_kernel<64, BC>), dim3((a.H + 63) / 64, nz), dim3(1024), lds, st, a);
+}
+
+template <bool BC>
+void launch_policy_out_bwd(const PolBwdArgs& a, size_t lds, hipStream_t st) {
+  const int H = a.H, A = a.A;
+  if (H >= 256) {          // 16 columns per workgroup
+    const dim3 g((H + 15) / 16);
+    if (A <= 8) hipLaunchKernelGGL((policy_out_bwd_kernel<8, 16, BC>), g, dim3(1024), lds, st, a);
+    else if (A <= 16) hipLaunchKernelGGL((policy_out_bwd_kernel<16, 16, BC>), g, dim3(1024), lds, st, a);
+    else hipLaunchKernelGGL((policy_out_bwd_kernel<32, 16, BC>), g, dim3(1024), lds, st, a);
+  } else {
+    const dim3 g((H + 63) / 64);
+    if (A <= 8) hipLaunchKernelGGL((policy_out_bwd_kernel<8, 64, BC>), g, dim3(1024), lds, st, a);
+    else if (A <= 16) hipLaunchKernelGGL((policy_out_bwd_kernel<16, 64, BC>), g, dim3(1024), lds, st, a);
+    else hipLaunchKernelGGL((policy_out_bwd_kernel<32, 64, BC>), g, dim3(1024), lds, st, a);
+  }
 }
 }  // namespace
 
@@ -1339,6 +1512,38 @@ int drq_qout_bwd_actor(const float* q1, const float* q2, const float* act, long 
   launch_qout_bwd(a, 2, lds, st);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
+}
+
+// internal (step.hip): drq_qout_bwd_actor_bc that also publishes to the host mirror (slots 0..7, 9, 10, then 8)
+int drq_qout_bwd_actor_bc_ex(const float* q1, const float* q2, const float* act, long lda, const float* a_beh, long ldb,
+                             const float* mu, float std, float alpha, int A, float inv_global_B, float* sums,
+                             float* sums_host, unsigned seq, const float* const* h, const float* const* w,
+                             float* const* dh, int B, int H, hipStream_t st) {
+  if (!q1 || !q2 || !act || !a_beh || !mu || !sums || !h || !w || !dh || B <= 0 || H <= 0 || A <= 0 || lda < A ||
+      ldb < A || !(alpha > 0.f))
+    return DRQ_EARG;
+  QOutBwdArgs a{};
+  for (int z = 0; z < 2; ++z) {
+    if (!h[z] || !w[z] || !dh[z]) return DRQ_EARG;
+    a.h[z] = h[z]; a.w[z] = w[z]; a.dh[z] = dh[z];
+  }
+  a.B = B; a.H = H;
+  a.td = 2; a.q1 = q1; a.q2 = q2; a.invB = inv_global_B; a.sums = sums;
+  a.act = act; a.lda = lda; a.mu = mu; a.A = A; a.std = std; a.sums_host = sums_host; a.seq = seq;
+  a.abeh = a_beh; a.ldb = ldb; a.alpha = alpha;
+  const size_t lds = ((size_t)B + 5 * 1024 + 64) * sizeof(float);
+  if (lds > 60 * 1024) return DRQ_EARG;
+  launch_qout_bwd<true>(a, 2, lds, st);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_qout_bwd_actor_bc(const float* q1, const float* q2, const float* act, long lda, const float* a_beh,
+                                  long ldb, const float* mu, float std, float alpha, int A, float inv_global_B,
+                                  float* sums, const float* const* h, const float* const* w, float* const* dh, int B,
+                                  int H, hipStream_t st) {
+  return drq_qout_bwd_actor_bc_ex(q1, q2, act, lda, a_beh, ldb, mu, std, alpha, A, inv_global_B, sums, nullptr, 0u, h, w,
+                                  dh, B, H, st);
 }
 
 // n (<= 4) LayerNorm+tanh problems of the same (rows, F) in one launch
@@ -1433,17 +1638,24 @@ int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, co
   const size_t lds = ((size_t)B * A + 4 * 16 * 64) * sizeof(float);
   if (lds > 60 * 1024) return DRQ_EARG;
   PolBwdArgs a{da1, da2, ld, col0, mu, p2, w, dp2, dw, db, B, H, A, part, splitk};
-  if (H >= 256) {          // 16 columns per workgroup
-    const dim3 g((H + 15) / 16);
-    if (A <= 8) hipLaunchKernelGGL((policy_out_bwd_kernel<8, 16>), g, dim3(1024), lds, st, a);
-    else if (A <= 16) hipLaunchKernelGGL((policy_out_bwd_kernel<16, 16>), g, dim3(1024), lds, st, a);
-    else hipLaunchKernelGGL((policy_out_bwd_kernel<32, 16>), g, dim3(1024), lds, st, a);
-  } else {
-    const dim3 g((H + 63) / 64);
-    if (A <= 8) hipLaunchKernelGGL((policy_out_bwd_kernel<8, 64>), g, dim3(1024), lds, st, a);
-    else if (A <= 16) hipLaunchKernelGGL((policy_out_bwd_kernel<16, 64>), g, dim3(1024), lds, st, a);
-    else hipLaunchKernelGGL((policy_out_bwd_kernel<32, 64>), g, dim3(1024), lds, st, a);
-  }
+  launch_policy_out_bwd<false>(a, lds, st);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+// the same with the DrQ+BC pull in dmu (see actor_dmu_bc_kernel): act [B][lda], a_beh [B][ldb]
+DRQ_API int drq_policy_out_bwd_bc(const float* da1, const float* da2, long ld, int col0, const float* mu,
+                                  const float* act, long lda, const float* a_beh, long ldb, float bc_scale,
+                                  const float* p2, const float* w, float* dp2, float* dw, float* db, int B, int H, int A,
+                                  const float* part, int splitk, hipStream_t st) {
+  if (((!da1 || !da2) && !part) || !mu || !act || !a_beh || !p2 || !w || !dp2 || !dw || !db || B <= 0 || H <= 0 ||
+      A <= 0 || A > kPolMaxA || lda < A || ldb < A)
+    return DRQ_EARG;
+  if (part && splitk < 1) return DRQ_EARG;
+  const size_t lds = ((size_t)B * A + 4 * 16 * 64) * sizeof(float);
+  if (lds > 60 * 1024) return DRQ_EARG;
+  PolBwdArgs a{da1, da2, ld, col0, mu, p2, w, dp2, dw, db, B, H, A, part, splitk, act, lda, a_beh, ldb, bc_scale};
+  launch_policy_out_bwd<true>(a, lds, st);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }
@@ -1479,6 +1691,36 @@ int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda
 DRQ_API int drq_actor_loss(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
                    float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B, hipStream_t st) {
   return drq_actor_loss_ex(q1, q2, a, lda, mu, std, dq1, dq2, sums, B, A, inv_global_B, nullptr, 0u, st);
+}
+
+// internal form used by the step: also publishes to the host mirror (slots 0..7, 9, 10, then 8)
+int drq_actor_loss_bc_ex(const float* q1, const float* q2, const float* a, long lda, const float* a_beh, long ldb,
+                         const float* mu, float std, float alpha, float* dq1, float* dq2, float* sums, int B, int A,
+                         float inv_global_B, float* sums_host, unsigned seq, hipStream_t st) {
+  if (!q1 || !q2 || !a || !a_beh || !mu || !dq1 || !dq2 || !sums || B <= 0 || A <= 0 || lda < A || ldb < A ||
+      !(alpha > 0.f))
+    return DRQ_EARG;
+  hipLaunchKernelGGL(actor_loss_bc_kernel, dim3(1), dim3(256), 0, st, q1, q2, a, lda, a_beh, ldb, mu, std, alpha, dq1,
+                     dq2, sums, B, A, inv_global_B, sums_host, seq);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_actor_loss_bc(const float* q1, const float* q2, const float* a, long lda, const float* a_beh, long ldb,
+                              const float* mu, float std, float alpha, float* dq1, float* dq2, float* sums, int B, int A,
+                              float inv_global_B, hipStream_t st) {
+  return drq_actor_loss_bc_ex(q1, q2, a, lda, a_beh, ldb, mu, std, alpha, dq1, dq2, sums, B, A, inv_global_B, nullptr, 0u,
+                              st);
+}
+
+DRQ_API int drq_actor_dmu_bc(const float* dha1, const float* dha2, long ld, int col0, const float* mu, const float* act,
+                             long lda, const float* a_beh, long ldb, float bc_scale, float* dpre, int B, int A,
+                             hipStream_t st) {
+  if (!dha1 || !dha2 || !mu || !act || !a_beh || !dpre || B <= 0 || A <= 0 || lda < A || ldb < A) return DRQ_EARG;
+  hipLaunchKernelGGL(actor_dmu_bc_kernel, dim3((B * A + 255) / 256), dim3(256), 0, st, dha1, dha2, ld, col0, mu, act, lda,
+                     a_beh, ldb, bc_scale, dpre, B, A);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
 }
 
 DRQ_API int drq_actor_dmu(const float* dha1, const float* dha2, long ld, int col0, const float* mu, float* dpre, int B,

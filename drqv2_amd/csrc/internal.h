@@ -39,6 +39,14 @@ int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, co
 int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
                       float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B, float* sums_host,
                       unsigned seq, hipStream_t st);
+// DrQ+BC forms of the two loss launches that also publish to the host mirror (the C entries pass no mirror)
+int drq_actor_loss_bc_ex(const float* q1, const float* q2, const float* a, long lda, const float* a_beh, long ldb,
+                         const float* mu, float std, float alpha, float* dq1, float* dq2, float* sums, int B, int A,
+                         float inv_global_B, float* sums_host, unsigned seq, hipStream_t st);
+int drq_qout_bwd_actor_bc_ex(const float* q1, const float* q2, const float* act, long lda, const float* a_beh, long ldb,
+                             const float* mu, float std, float alpha, int A, float inv_global_B, float* sums,
+                             float* sums_host, unsigned seq, const float* const* h, const float* const* w,
+                             float* const* dh, int B, int H, hipStream_t st);
 int drq_adam_flat2(float* p0, const float* g0, float* m0, float* v0, long n0, long step0, float* p1, const float* g1,
                    float* m1, float* v1, long n1, long step1, double lr, float gscale, hipStream_t st);
 

@@ -176,6 +176,13 @@ struct Ctx {
   // launch of the backward (drq_qout_bwd_actor) instead of a launch of its own.  A host that exchanges the metric
   // sums between the two phases calls them separately and keeps the separate loss launch.
   bool fuse_actor_loss = false;
+  // DrQ+BC (drq_update_phase_bc): alpha > 0 swaps the actor loss and the policy output backward for their BC forms;
+  // 0 = the launches and arguments of the plain update.  a_beh is the action the critic loss consumed: phase 4 copied
+  // it into the action columns of HA_C, which nothing writes again before the next update's phase 4.
+  float bc_alpha = 0.f;
+  bool bc() const { return bc_alpha > 0.f; }
+  const float* a_beh() const { return ws(W_HA_C) + s->F; }
+  float bc_scale() const { return 2.0f / ((float)s->global_B * (float)s->A); }
   // B rows fit the LDS of the Q-output backward kernels that compute a loss as well (drq_qout_bwd_td / _actor)
   bool qout_loss_fits_lds() const { return ((size_t)s->B + 5 * 1024 + 16) * 4 <= 60 * 1024; }
   bool actor_loss_fused() const { return fuse_actor_loss && qout_loss_fits_lds(); }
@@ -678,7 +685,11 @@ int phase_actor_forward(const Ctx& c, bool with_opt = true) {
   }
   const float invB = 1.0f / (float)s->global_B;
   // the loss kernel also publishes the eight sums to the host mirror when one is given
-  if (!c.actor_loss_fused())
+  if (!c.actor_loss_fused() && c.bc())
+    CK(drq_actor_loss_bc_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.a_beh(), FA, c.ws(W_MU_O), s->std,
+                            c.bc_alpha, c.ws(W_DQ), c.ws(W_DQ) + B, s->sums, B, A, invB, s->sums_host,
+                            (unsigned)s->step_actor, st));
+  else if (!c.actor_loss_fused())
     CK(drq_actor_loss_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.ws(W_MU_O), s->std, c.ws(W_DQ),
                          c.ws(W_DQ) + B, s->sums, B, A, invB, s->sums_host, (unsigned)s->step_actor, st));
   return 0;
@@ -706,7 +717,11 @@ int phase_actor_backward(const Ctx& c) {
     const float *w0a[2] = {c.p(cr.w[0][0]) + F, c.p(cr.w[1][0]) + F}, *w1[2] = {c.p(cr.w[0][1]), c.p(cr.w[1][1])},
                 *w2[2] = {c.p(cr.w[0][2]), c.p(cr.w[1][2])};
     float* da[2] = {c.ws(W_DA), c.ws(W_DA) + (long)B * A};
-    if (c.actor_loss_fused())
+    if (c.actor_loss_fused() && c.bc())
+      CK(drq_qout_bwd_actor_bc_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.a_beh(), FA, c.ws(W_MU_O), s->std,
+                                  c.bc_alpha, A, 1.0f / (float)s->global_B, s->sums, s->sums_host,
+                                  (unsigned)s->step_actor, t2, w2, dc2, B, H, st));
+    else if (c.actor_loss_fused())
       CK(drq_qout_bwd_actor(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.ws(W_MU_O), s->std, A,
                             1.0f / (float)s->global_B, s->sums, s->sums_host, (unsigned)s->step_actor, t2, w2, dc2, B, H,
                             st));
@@ -722,7 +737,11 @@ int phase_actor_backward(const Ctx& c) {
       CK(c.dgrad(2, dc1c, H, w0a, FA, da, A, B, A, H, nullptr, 0));
   }
 
-  if (!fused_head) CK(drq_actor_dmu(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), c.ws(W_DPRE), B, A, st));
+  if (!fused_head && c.bc())
+    CK(drq_actor_dmu_bc(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, c.a_beh(), FA,
+                        c.bc_scale(), c.ws(W_DPRE), B, A, st));
+  else if (!fused_head)
+    CK(drq_actor_dmu(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), c.ws(W_DPRE), B, A, st));
 
   // policy MLP backward (rows [0,B) of the stacked activations are the obs rows)
   int sk_dh = 1;
@@ -733,7 +752,11 @@ int phase_actor_backward(const Ctx& c) {
     const float *w0[1] = {c.p(ac.w[0][0])}, *w1[1] = {c.p(ac.w[0][1])}, *w2[1] = {c.p(ac.w[0][2])};
     float *gw0[1] = {c.g(ac.w[0][0])}, *gw1[1] = {c.g(ac.w[0][1])}, *gw2[1] = {c.g(ac.w[0][2])};
     float *gb0[1] = {c.g(ac.b[0][0])}, *gb1[1] = {c.g(ac.b[0][1])}, *gb2[1] = {c.g(ac.b[0][2])};
-    if (fused_head) {
+    if (fused_head && c.bc()) {
+      CK(drq_policy_out_bwd_bc(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, c.a_beh(),
+                               FA, c.bc_scale(), p2[0], w2[0], dp2[0], gw2[0], gb2[0], B, H, A,
+                               sk_da > 1 ? c.gemm_ws() : nullptr, sk_da, st));
+    } else if (fused_head) {
       CK(drq_policy_out_bwd(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), p2[0], w2[0], dp2[0], gw2[0],
                             gb2[0], B, H, A, sk_da > 1 ? c.gemm_ws() : nullptr, sk_da, st));
     } else {
@@ -809,7 +832,8 @@ DRQ_API long drq_step_ws_offset(int B, int C, int A, int F, int H, int id) {
   return ws_layout(B, C, A, F, H).off[id];
 }
 
-DRQ_API int drq_update_phase(const DrqStep* s, int phase) {
+namespace {
+int update_phase(const DrqStep* s, int phase, float bc_alpha) {
   CK(check_step(s));
   if (!s->obs || !s->next_obs || !s->action || !s->reward || !s->discount || !s->shift_obs || !s->shift_next ||
       !s->noise_critic || !s->noise_actor || !s->base_grid || !s->grads || !s->adam_m || !s->adam_v || !s->sums)
@@ -817,6 +841,7 @@ DRQ_API int drq_update_phase(const DrqStep* s, int phase) {
   Ctx c{s, param_layout(s->C, s->A, s->F, s->H), ws_layout(s->B, s->C, s->A, s->F, s->H), (hipStream_t)s->stream};
   if (phase < DRQ_PHASE_ALL || phase > DRQ_PHASE_REDRAW) return DRQ_EARG;
   c.fuse_actor_loss = phase == DRQ_PHASE_ALL || phase == DRQ_PHASE_ACTOR;
+  c.bc_alpha = bc_alpha;
   if (runs(phase, DRQ_PHASE_ENCODE)) CK(phase_encode(c));
   if (runs(phase, DRQ_PHASE_CRITIC_HEADS)) {
     CK(c.stamp(6));
@@ -845,6 +870,15 @@ DRQ_API int drq_update_phase(const DrqStep* s, int phase) {
                                A, c.st));
   }
   return 0;
+}
+}  // namespace
+
+DRQ_API int drq_update_phase(const DrqStep* s, int phase) { return update_phase(s, phase, 0.f); }
+
+DRQ_API int drq_update_phase_bc(const DrqStep* s, int phase, float bc_alpha) {
+  // single GPU only: lambda needs the GLOBAL sum of |min(q1,q2)| before any gradient exists
+  if (!(bc_alpha > 0.f) || bc_alpha > 3.0e38f || (s && s->global_B != s->B)) return DRQ_EARG;
+  return update_phase(s, phase, bc_alpha);
 }
 
 DRQ_API int drq_publish_sums(const float* sums, float* sums_host, unsigned seq, drq_stream_t stream) {

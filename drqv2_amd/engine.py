@@ -343,7 +343,13 @@ class StepEngine:
         self._ws_B = None
         self._act_ws = None       # scratch of act_batch_forward's fused path (never the step workspace), grown on demand
         self._base = None
-        self.sums = torch.zeros(8, device=dev, dtype=torch.float32)
+        # sixteen floats behind DrqStep.sums: the eight metric sums every caller sees (self.sums), and in slots 9 and 10
+        # the two sums of the DrQ+BC actor loss (self.bc_sums: sum (a - a_beh)^2, sum |min(q1,q2)|); the host mirror
+        # below has the same layout
+        self._sums_all = torch.zeros(16, device=dev, dtype=torch.float32)
+        self.sums = self._sums_all[:8]
+        self.bc_sums = self._sums_all[9:11]
+        self.bc_alpha = None      # DrQ+BC (set_behavior_cloning): None = the plain actor loss
         # pinned host mirror of the metric sums (DrqStep.sums_host): slot 8 = sequence word of the update
         self.sums_host = torch.zeros(16, dtype=torch.float32).pin_memory() if dev.type == "cuda" else None
         self._sums_seq = self.sums_host[8:9].view(torch.int32) if self.sums_host is not None else None
@@ -419,11 +425,35 @@ class StepEngine:
             self._base = aug_base_grid(84, 4, self.device)
         return self._base
 
+    # ---- DrQ+BC --------------------------------------------------------------------------
+    _BC_DP = ("behaviour cloning and data parallelism cannot be combined: lambda = alpha / mean|Qmin| needs the GLOBAL "
+              "sum of |Qmin| before any gradient exists, a third dependent exchange per update that is not built")
+
+    _BC_BF16 = ("behaviour cloning with the bf16 compute dtype is not covered by a test against the bf16 bounds yet and is "
+                "refused: use set_compute_dtype('fp32')")
+
+    def set_behavior_cloning(self, alpha):
+        """alpha: None (the plain actor loss) or a validated float > 0 (DrQ+BC, drq_update_phase_bc)."""
+        if alpha is not None and self.pg is not None:
+            raise _lib.DrqError(self._BC_DP)
+        if alpha is not None and self.bf16:
+            raise _lib.DrqError(self._BC_BF16)
+        self.bc_alpha = alpha
+
+    def read_bc_sums(self):
+        """(sum (a - a_beh)^2, sum |min(q1,q2)|) of the last BC update as Python floats; call it after read_sums(), which
+        waits for the update's sums: the mirror's slots 9 and 10 are written before its sequence word."""
+        if self._last_seq is None:
+            return self.bc_sums.tolist()
+        return self.sums_host[9:11].tolist()
+
     # ---- data parallel -------------------------------------------------------------------
     def enable_data_parallel(self, process_group=None, global_metrics=False, exchange="allreduce"):
         """exchange: how the gradient buckets are summed over the ranks (GradExchange): "allreduce", "direct" or
         "auto" (measures both on the real bucket sizes now and keeps the faster)."""
         import torch.distributed as dist
+        if self.bc_alpha is not None:
+            raise _lib.DrqError(self._BC_DP)
         self.global_metrics = bool(global_metrics)
         self.pg = process_group if process_group is not None else dist.group.WORLD
         self.world = dist.get_world_size(self.pg)
@@ -535,7 +565,10 @@ class StepEngine:
         # the library launches on the CURRENT HIP device: make that the agent's (an agent on cuda:1 in a process
         # whose current device is 0 would otherwise launch device-1 pointers on device 0)
         with torch.cuda.device(self.device):
-            check(_lib.load().drq_update_phase(ctypes.byref(desc), k), f"drq_update_phase({k})")
+            if self.bc_alpha is not None:
+                check(_lib.load().drq_update_phase_bc(ctypes.byref(desc), k, self.bc_alpha), f"drq_update_phase_bc({k})")
+            else:
+                check(_lib.load().drq_update_phase(ctypes.byref(desc), k), f"drq_update_phase({k})")
 
     def _wait(self, work, name):
         """work.wait() (the current stream waits for the exchange); with profile_exchange the wait is bracketed by two

@@ -237,6 +237,40 @@ int drq_actor_loss(const float* q1, const float* q2, const float* a, long lda, c
 int drq_actor_dmu(const float* dha1, const float* dha2, long ld, int col0, const float* mu, float* dpre, int B,
                   int A, drq_stream_t stream);
 
+/* ---- DrQ+BC: the actor loss of TD3+BC on DrQ-v2's actor step (offline training from a fixed dataset).  New
+ * functionality: the reference has no such loss; these definitions are the contract.  With a the sample of
+ * drqv2.py:210-211 (its gradient passes straight through to mu), a_beh the batch's action and Qmin = min(Q1, Q2)(a):
+ *   lambda = alpha / mean_i |Qmin_i|  (a constant of the backward, no epsilon),  bc = mean over [B][A] of (a - a_beh)^2,
+ *   loss = -lambda mean_i Qmin_i + bc;  dq_k[i] = -lambda * inv_global_B on the head that holds the minimum (ties split
+ *   as in the plain loss);  dmu = da_1 + da_2 + bc_scale (a - a_beh), bc_scale = 2 / (B_global A);  dpre = dmu (1 - mu^2).
+ * lambda needs sum |Qmin| over the whole batch before any dq: every workgroup that needs it adds the B values itself in
+ * one fixed order, so all workgroups of all four entries and all runs see the same bits.  Single GPU: B is the global batch.
+ * `sums` holds at least 11 floats: sums[5] = sum -Qmin and sums[6] = sum log_prob as the plain loss leaves them,
+ * sums[9] = sum (a - a_beh)^2, sums[10] = sum |Qmin|; slots 7 and 8 are not written.  a [B][lda], a_beh [B][ldb].
+ * The loss as a launch of its own (BC form of the plain loss entry above), and as the first launch of the actor
+ * backward: the twin Q output layer's input gradient dh[k] = (dq_k w[k]) * (h[k] > 0) with dq never stored, h / w / dh
+ * host arrays of two device pointers ([B][H], [H], [B][H]); (B + 5184) floats of LDS, else DRQ_EARG. */
+int drq_actor_loss_bc(const float* q1, const float* q2, const float* a, long lda, const float* a_beh, long ldb,
+                      const float* mu, float std, float alpha, float* dq1, float* dq2, float* sums, int B, int A,
+                      float inv_global_B, drq_stream_t stream);
+int drq_qout_bwd_actor_bc(const float* q1, const float* q2, const float* act, long lda, const float* a_beh, long ldb,
+                          const float* mu, float std, float alpha, int A, float inv_global_B, float* sums,
+                          const float* const* h, const float* const* w, float* const* dh, int B, int H,
+                          drq_stream_t stream);
+/* The policy output layer's backward with the BC pull in dmu, in the two shapes the update uses.  The elementwise form
+ * (BC form of the dmu entry above) writes dpre [B][A].  The fused form (A <= 32, (B A + 4096) floats of LDS) computes dpre
+ * in LDS and from it dp2 [B][H] = (dpre w) * (p2 > 0), dw [A][H] = dpre^T p2, db [A] = column sums of dpre, for the layer
+ * Linear(H, A) with weight w [A][H] and post-ReLU input p2 [B][H]; da1 / da2 are read as columns [col0, col0 + A) of
+ * [B][ld] buffers or, when `part` is given, as the sums of splitk partial records [2 splitk][B][A] of the two
+ * input-gradient GEMMs (head 1's records first). */
+int drq_actor_dmu_bc(const float* dha1, const float* dha2, long ld, int col0, const float* mu, const float* act,
+                     long lda, const float* a_beh, long ldb, float bc_scale, float* dpre, int B, int A,
+                     drq_stream_t stream);
+int drq_policy_out_bwd_bc(const float* da1, const float* da2, long ld, int col0, const float* mu, const float* act,
+                          long lda, const float* a_beh, long ldb, float bc_scale, const float* p2, const float* w,
+                          float* dp2, float* dw, float* db, int B, int H, int A, const float* part, int splitk,
+                          drq_stream_t stream);
+
 /* ---- torch.optim.Adam.step (drqv2.py:148-150,201-202,221; defaults) over a flat arena; optional fused
  * utils.soft_update_params (utils.py:42-45) into tgt.  g is multiplied by gscale first (1 = exact). */
 int drq_adam_flat(float* p, const float* g, float* m, float* v, long n, double lr, long step, float gscale,
@@ -311,7 +345,7 @@ typedef struct {
   float* adam_v;
   float* ws;                 /* drq_step_ws_bytes(), zero-initialised once */
   size_t ws_bytes;
-  float* sums;               /* [8] local partial sums of the metrics */
+  float* sums;               /* [8] local partial sums of the metrics ([11] for drq_update_phase_bc) */
   double lr, tau;
   float std, clip;
   long step_critic, step_enc, step_actor; /* 1-based Adam step numbers of THIS update */
@@ -417,6 +451,13 @@ enum {
   DRQ_PHASE_CRITIC_OPT = 10, DRQ_PHASE_ACTOR_LOSS = 11, DRQ_PHASE_POLYAK = 12, DRQ_PHASE_REDRAW = 13
 };
 int drq_update_phase(const DrqStep* s, int phase);
+/* The same update with the DrQ+BC actor loss (see the BC entries above), alpha finite and > 0: the critic step is
+ * unchanged bit for bit; phases 6 / 11 and 7 issue the BC forms of the loss and of the policy output backward in place
+ * of the plain ones, launch for launch.  a_beh is s->action as phase 4 consumed it (the copy phase 4 left in the
+ * workspace is read, so the caller's tensor need not outlive phase 4).  s->sums must hold 11 floats (slots 9 and 10, see
+ * above); with s->sums_host set those two are published in slots 9 and 10 before the sequence word.  Single GPU only:
+ * global_B != B is DRQ_EARG.  The descriptor is unchanged, so callers of the plain entry are not affected. */
+int drq_update_phase_bc(const DrqStep* s, int phase, float bc_alpha);
 
 /* sums[0..7] -> sums_host[0..7], then seq -> slot 8 with system-scope release (see DrqStep.sums_host); for hosts
  * that reduce the sums themselves before publishing them. */
