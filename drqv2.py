@@ -268,6 +268,10 @@ class DrQV2Agent:
 
         batch = next(replay_iter)
         frames = getattr(batch, "frames", None)      # drqv2_amd.replay.IndexedBatch: obs / next_obs are indices into it
+        # prioritized replay (drqv2_amd.replay.PrioritizedBatch, or any batch type of the caller's with this attribute):
+        # float32 [B] on the device, the critic loss becomes mean_i w_i (Q - y)_i^2 per head (StepEngine.update)
+        weights = getattr(batch, "weights", None)
+        wkw = {} if weights is None else {"loss_weights": weights}
         obs, action, reward, discount, next_obs = utils.to_torch(batch, self.device)
         eng = self._engine
         A = eng.A
@@ -287,12 +291,17 @@ class DrQV2Agent:
         if frames is not None:
             sums = eng.update(frames, f32(action_l), f32(reward_l).view(-1), f32(discount_l).view(-1), frames, f32(sh_o),
                               f32(sh_n), f32(n_c), f32(n_a), stddev, self.stddev_clip, self.critic_target_tau,
-                              B_global=n_global, obs_index=obs_l.contiguous(), next_obs_index=next_l.contiguous())
+                              B_global=n_global, obs_index=obs_l.contiguous(), next_obs_index=next_l.contiguous(), **wkw)
         else:
             sums = eng.update(obs_l.contiguous(), f32(action_l), f32(reward_l).view(-1), f32(discount_l).view(-1),
                               next_l.contiguous(), f32(sh_o), f32(sh_n), f32(n_c), f32(n_a), stddev, self.stddev_clip,
-                              self.critic_target_tau, B_global=n_global)
+                              self.critic_target_tau, B_global=n_global, **wkw)
 
+        # the per-sample |TD error| of this update goes back into the store's priorities, in stream order (no host wait)
+        # and before the iterator below places new episodes and draws again
+        renew = getattr(batch, "update_priorities", None) if weights is not None else None
+        if renew is not None:
+            renew(eng.last_td_abs)
         # the update is queued: the next batch's host work goes here, beside the GPU (drqv2_amd.replay.BatchIterator)
         ahead = getattr(replay_iter, "prefetch", None)
         if ahead is not None:
@@ -342,7 +351,8 @@ class DrQV2Agent:
     def update_critic(self, obs, action, reward, discount, next_obs, step):
         """drqv2.py:177-204.  obs / next_obs: the features encode() returned for this batch.  Issues the critic loss, its
         backward through the encoder, critic_opt.step() and encoder_opt.step(); consumes the reference's third draw
-        (utils.py:119).  `step` must be the step encode() was called with (the stddev schedule is evaluated there)."""
+        (utils.py:119).  `step` must be the step encode() was called with (the stddev schedule is evaluated there).
+        Always the unweighted loss: the importance weights of prioritized replay go through update() only."""
         metrics = dict()
         f32 = lambda t: torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
         n = obs.shape[0]

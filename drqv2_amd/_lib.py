@@ -80,6 +80,7 @@ PROTOTYPES = {
     "drq_trunc_normal_sample": (I, [P, P, F, F, I, P, P, L, I, I, P]),
     "drq_copy_cols": (I, [P, I, P, L, I, I, P]),
     "drq_td_mse": (I, [P, P, P, P, P, P, P, P, P, I, F, P]),
+    "drq_td_mse_w": (I, [P, P, P, P, P, P, P, P, P, P, P, I, F, P]),
     "drq_actor_loss": (I, [P, P, P, L, P, F, P, P, P, I, I, F, P]),
     "drq_actor_dmu": (I, [P, P, L, I, P, P, I, I, P]),
     "drq_actor_loss_bc": (I, [P, P, P, L, P, L, P, F, F, P, P, P, I, I, F, P]),
@@ -94,6 +95,9 @@ PROTOTYPES = {
     "drq_u8_normalize": (I, [P, P, L, P]),
     "drq_nstep_gather": (I, [P, P, P, P, P, I, I, L, I, F, P, P, P, P, P, P]),
     "drq_tanh": (I, [P, P, L, P]),
+    "drq_per_fill": (I, [P, L, L, L, I, P]),
+    "drq_per_sample": (I, [P, L, P, I, I, L, D, P, P, P]),
+    "drq_per_update": (I, [P, L, P, P, I, D, D, P]),
     "drq_relu_mask_pad": (I, [P, P, P, L, I, I, P]),
     "drq_conv1_dgrad": (I, [P, P, P, I, P]),
     "drq_aug_bwd_f32": (I, [P, P, P, P, I, I, I, I, P]),
@@ -103,6 +107,7 @@ PROTOTYPES = {
     "drq_step_ws_offset": (L, [I, I, I, I, I, I]),
     "drq_update_phase": (I, [C.POINTER(DrqStep), I]),
     "drq_update_phase_bc": (I, [C.POINTER(DrqStep), I, F]),
+    "drq_update_phase_per": (I, [C.POINTER(DrqStep), I, P, P]),
     "drq_act_forward": (I, [C.POINTER(DrqStep), P, I, P]),
     "drq_act_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_act_batch": (I, [P, I, I, I, I, P, I, P, F, P, P, P, SZ, P]),

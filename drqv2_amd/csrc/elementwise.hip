@@ -478,22 +478,34 @@ __device__ __forceinline__ void block_sum4(float (&v)[4], float (*sm)[256]) {
 // TD target + twin MSE (drqv2.py:185-189).  Single block.  invB = 1/global batch.
 // sums[0..4] = sum reward, sum target_q, sum q1, sum q2, sum (q1-y)^2+(q2-y)^2  (un-normalised: the
 // data-parallel path adds them across ranks before dividing).
+// PW (prioritized replay, drq_td_mse_w): row b carries the importance weight w[b].  dq_k is the plain expression
+// multiplied by w[b] LAST, so that w == 1 gives the plain bits; sums[4] adds w (e1^2 + e2^2); sums[0..3] stay
+// unweighted; td_abs[b] = (|e1| + |e2|) / 2, unweighted, is what the priorities are made of.
 // ------------------------------------------------------------------------------------------------
+template <bool PW>
 __global__ void td_loss_kernel(const float* tq1, const float* tq2, const float* q1, const float* q2,
                                const float* reward, const float* discount, float* dq1, float* dq2, float* sums,
-                               int B, float invB) {
+                               int B, float invB, const float* w, float* td_abs) {
   __shared__ float sm[4][256];
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   float sr = 0.f;
   for (int b = threadIdx.x; b < B; b += 256) {
     const float y = reward[b] + discount[b] * fminf(tq1[b], tq2[b]);
     const float e1 = q1[b] - y, e2 = q2[b] - y;
-    dq1[b] = 2.f * e1 * invB;
-    dq2[b] = 2.f * e2 * invB;
+    if constexpr (PW) {
+      const float wb = w[b];
+      dq1[b] = (2.f * e1 * invB) * wb;
+      dq2[b] = (2.f * e2 * invB) * wb;
+      td_abs[b] = 0.5f * (fabsf(e1) + fabsf(e2));
+    } else {
+      dq1[b] = 2.f * e1 * invB;
+      dq2[b] = 2.f * e2 * invB;
+    }
     s[0] += y;
     s[1] += q1[b];
     s[2] += q2[b];
-    s[3] += e1 * e1 + e2 * e2;
+    if constexpr (PW) s[3] += w[b] * (e1 * e1 + e2 * e2);
+    else s[3] += e1 * e1 + e2 * e2;
     sr += reward[b];
   }
   block_sum4(s, sm);
@@ -861,6 +873,10 @@ struct QOutBwdArgs {
   const float* abeh;
   long ldb;
   float alpha;
+  // weighted form of td == 1 (qout_bwd_kernel<CW, false, true>, prioritized replay): the importance weights [B] and
+  // the per-sample error (|q1 - y| + |q2 - y|) / 2 [B] that workgroup (0, 0) leaves beside the sums
+  const float* isw;
+  float* td_abs;
 };
 
 // Workgroup = 64 columns x 16 row groups (1024 threads).  The per-row scalars dq[B] go to LDS once; the only global
@@ -870,7 +886,8 @@ struct QOutBwdArgs {
 // launch): 16 columns x 64 row groups gives four times as many (drq_qout_bwd_cw).  The row-group sums are added in
 // the same fixed order either way (deterministic); the two shapes group them differently (rounding-level).
 // BC (td == 2 only): the DrQ+BC actor loss, see bc_abs_qmin_sum; BC = false compiles to the kernel as it was.
-template <int CW, bool BC>
+// PW (td == 1 only): the TD loss weighted per row (td_loss_kernel<true>'s arithmetic); PW = false likewise.
+template <int CW, bool BC, bool PW>
 __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
   constexpr int NRG = 1024 / CW;
   extern __shared__ float dql[];            // [B] then NRG x CW + 64 floats of reduction scratch
@@ -923,7 +940,8 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
     const float* qz = z == 0 ? a.q1 : a.q2;
     for (int m = threadIdx.x; m < a.B; m += 1024) {
       const float y = a.reward[m] + a.discount[m] * fminf(a.tq1[m], a.tq2[m]);
-      dql[m] = 2.f * (qz[m] - y) * a.invB;
+      if constexpr (PW) dql[m] = (2.f * (qz[m] - y) * a.invB) * a.isw[m];
+      else dql[m] = 2.f * (qz[m] - y) * a.invB;
     }
   } else {
     const float* dq = a.dq[z];
@@ -1034,7 +1052,12 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
       const float r = a.reward[m];
       const float y = r + a.discount[m] * fminf(a.tq1[m], a.tq2[m]);
       const float e1 = a.q1[m] - y, e2 = a.q2[m] - y;
-      v[0] += r; v[1] += y; v[2] += a.q1[m]; v[3] += a.q2[m]; v[4] += e1 * e1 + e2 * e2;
+      if constexpr (PW) {
+        v[0] += r; v[1] += y; v[2] += a.q1[m]; v[3] += a.q2[m]; v[4] += a.isw[m] * (e1 * e1 + e2 * e2);
+        a.td_abs[m] = 0.5f * (fabsf(e1) + fabsf(e2));
+      } else {
+        v[0] += r; v[1] += y; v[2] += a.q1[m]; v[3] += a.q2[m]; v[4] += e1 * e1 + e2 * e2;
+      }
     }
     // one tree for the five sums (scratch: 5 x 1024 floats behind dq)
 #pragma unroll
@@ -1426,10 +1449,10 @@ DRQ_API int drq_qout_fwd(int nz, const float* const* h, const float* const* w, c
 
 namespace {
 // 64 columns per workgroup below 1,024 rows, 16 beyond (see qout_bwd_kernel)
-template <bool BC = false>
+template <bool BC = false, bool PW = false>
 void launch_qout_bwd(const QOutBwdArgs& a, int nz, size_t lds, hipStream_t st) {
-  if (a.B >= 1024) hipLaunchKernelGGL((qout_bwd_kernel<16, BC>), dim3((a.H + 15) / 16, nz), dim3(1024), lds, st, a);
-  else hipLaunchKernelGGL((qout_bwd_kernel<64, BC>), dim3((a.H + 63) / 64, nz), dim3(1024), lds, st, a);
+  if (a.B >= 1024) hipLaunchKernelGGL((qout_bwd_kernel<16, BC, PW>), dim3((a.H + 15) / 16, nz), dim3(1024), lds, st, a);
+  else hipLaunchKernelGGL((qout_bwd_kernel<64, BC, PW>), dim3((a.H + 63) / 64, nz), dim3(1024), lds, st, a);
 }
 
 template <bool BC>
@@ -1470,12 +1493,15 @@ DRQ_API int drq_qout_bwd(int nz, const float* const* dq, const float* const* h, 
 
 // internal (step.hip): the twin-Q output layer backward with the TD loss (drq_td_mse) computed inside it:
 // dq1/dq2 never exist in memory, sums[0..4] are written by the same launch
-int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+namespace {
+template <bool PW>
+int qout_bwd_td_any(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
                     const float* discount, float inv_global_B, float* sums, const float* const* h,
                     const float* const* w, float* const* dh, float* const* dw, float* const* db, int B, int H,
-                    hipStream_t st) {
+                    const float* is_weight, float* td_abs, hipStream_t st) {
   if (!tq1 || !tq2 || !q1 || !q2 || !reward || !discount || !sums || !h || !w || !dh || B <= 0 || H <= 0)
     return DRQ_EARG;
+  if (PW && (!is_weight || !td_abs)) return DRQ_EARG;
   QOutBwdArgs a{};
   for (int z = 0; z < 2; ++z) {
     if (!h[z] || !w[z] || !dh[z]) return DRQ_EARG;
@@ -1486,11 +1512,31 @@ int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const f
   a.B = B; a.H = H;
   a.td = 1; a.tq1 = tq1; a.tq2 = tq2; a.q1 = q1; a.q2 = q2; a.reward = reward; a.discount = discount;
   a.invB = inv_global_B; a.sums = sums;
+  a.isw = is_weight; a.td_abs = td_abs;
   const size_t lds = ((size_t)B + 5 * 1024 + 64) * sizeof(float);      // the sums tree of workgroup (0,0) needs 5 x 1024
   if (lds > 60 * 1024) return DRQ_EARG;
-  launch_qout_bwd(a, 2, lds, st);
+  launch_qout_bwd<false, PW>(a, 2, lds, st);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
+}
+}  // namespace
+
+int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+                    const float* discount, float inv_global_B, float* sums, const float* const* h,
+                    const float* const* w, float* const* dh, float* const* dw, float* const* db, int B, int H,
+                    hipStream_t st) {
+  return qout_bwd_td_any<false>(tq1, tq2, q1, q2, reward, discount, inv_global_B, sums, h, w, dh, dw, db, B, H, nullptr,
+                                nullptr, st);
+}
+
+// internal (step.hip): the same launch with the loss weighted per row (prioritized replay): dq_k[i] carries
+// is_weight[i], sums[4] is the weighted sum, td_abs[i] = (|q1 - y| + |q2 - y|) / 2 is written by workgroup (0, 0)
+int drq_qout_bwd_td_w(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+                      const float* discount, const float* is_weight, float inv_global_B, float* sums, float* td_abs,
+                      const float* const* h, const float* const* w, float* const* dh, float* const* dw,
+                      float* const* db, int B, int H, hipStream_t st) {
+  return qout_bwd_td_any<true>(tq1, tq2, q1, q2, reward, discount, inv_global_B, sums, h, w, dh, dw, db, B, H, is_weight,
+                               td_abs, st);
 }
 
 // internal (step.hip, single-GPU schedule): the same backward (input gradient only) with the actor loss (drq_actor_loss)
@@ -1671,8 +1717,19 @@ DRQ_API int drq_td_mse(const float* tq1, const float* tq2, const float* q1, cons
                const float* discount, float* dq1, float* dq2, float* sums, int B, float inv_global_B,
                hipStream_t st) {
   if (!tq1 || !tq2 || !q1 || !q2 || !reward || !discount || !dq1 || !dq2 || !sums || B <= 0) return DRQ_EARG;
-  hipLaunchKernelGGL(td_loss_kernel, dim3(1), dim3(256), 0, st, tq1, tq2, q1, q2, reward, discount, dq1, dq2, sums, B,
-                     inv_global_B);
+  hipLaunchKernelGGL(td_loss_kernel<false>, dim3(1), dim3(256), 0, st, tq1, tq2, q1, q2, reward, discount, dq1, dq2,
+                     sums, B, inv_global_B, nullptr, nullptr);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_td_mse_w(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+                         const float* discount, const float* w, float* dq1, float* dq2, float* td_abs, float* sums,
+                         int B, float inv_global_B, hipStream_t st) {
+  if (!tq1 || !tq2 || !q1 || !q2 || !reward || !discount || !w || !dq1 || !dq2 || !td_abs || !sums || B <= 0)
+    return DRQ_EARG;
+  hipLaunchKernelGGL(td_loss_kernel<true>, dim3(1), dim3(256), 0, st, tq1, tq2, q1, q2, reward, discount, dq1, dq2,
+                     sums, B, inv_global_B, w, td_abs);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }

@@ -26,6 +26,11 @@ int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const f
                     const float* discount, float inv_global_B, float* sums, const float* const* h,
                     const float* const* w, float* const* dh, float* const* dw, float* const* db, int B, int H,
                     hipStream_t st);
+// ... with the loss weighted per row (prioritized replay, drq_td_mse_w's arithmetic); also leaves td_abs [B]
+int drq_qout_bwd_td_w(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+                      const float* discount, const float* is_weight, float inv_global_B, float* sums, float* td_abs,
+                      const float* const* h, const float* const* w, float* const* dh, float* const* dw,
+                      float* const* db, int B, int H, hipStream_t st);
 int drq_qout_bwd_actor(const float* q1, const float* q2, const float* act, long lda, const float* mu, float std, int A,
                        float inv_global_B, float* sums, float* sums_host, unsigned seq, const float* const* h,
                        const float* const* w, float* const* dh, int B, int H, hipStream_t st);

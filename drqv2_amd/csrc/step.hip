@@ -183,6 +183,11 @@ struct Ctx {
   bool bc() const { return bc_alpha > 0.f; }
   const float* a_beh() const { return ws(W_HA_C) + s->F; }
   float bc_scale() const { return 2.0f / ((float)s->global_B * (float)s->A); }
+  // prioritized replay (drq_update_phase_per): the critic loss weighted per row by is_weight [B]; phase 4 also leaves
+  // the per-sample error in td_abs [B].  Null = the launches and arguments of the plain update.
+  const float* is_weight = nullptr;
+  float* td_abs = nullptr;
+  bool per() const { return is_weight != nullptr; }
   // B rows fit the LDS of the Q-output backward kernels that compute a loss as well (drq_qout_bwd_td / _actor)
   bool qout_loss_fits_lds() const { return ((size_t)s->B + 5 * 1024 + 16) * 4 <= 60 * 1024; }
   bool actor_loss_fused() const { return fuse_actor_loss && qout_loss_fits_lds(); }
@@ -503,12 +508,21 @@ int phase_critic_heads(const Ctx& c) {
           *gb2[2] = {c.g(cr.b[0][2]), c.g(cr.b[1][2])};
     // TD target + twin MSE (:185-189) and layer 3 (hidden -> 1) backward in one pass: dq never leaves the chip,
     // sums[0..4] come from the same launch
-    if (c.qout_loss_fits_lds()) {
+    if (c.qout_loss_fits_lds() && c.per()) {
+      CK(drq_qout_bwd_td_w(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, c.is_weight,
+                           invB, s->sums, c.td_abs, c2c, w2, dc2, gw2, gb2, B, H, st));
+    } else if (c.qout_loss_fits_lds()) {
       CK(drq_qout_bwd_td(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, invB, s->sums,
                          c2c, w2, dc2, gw2, gb2, B, H, st));
     } else {
-      CK(drq_td_mse(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, c.ws(W_DQ),
-                    c.ws(W_DQ) + B, s->sums, B, invB, st));
+      // beyond 10,224 rows only: update() takes 4,096 at most, so neither form of this route runs from the Python side
+      // (a C caller's batch can reach it); drq_td_mse_w is tested as an op
+      if (c.per())
+        CK(drq_td_mse_w(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, c.is_weight,
+                        c.ws(W_DQ), c.ws(W_DQ) + B, c.td_abs, s->sums, B, invB, st));
+      else
+        CK(drq_td_mse(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, c.ws(W_DQ),
+                      c.ws(W_DQ) + B, s->sums, B, invB, st));
       CK(drq_qout_bwd(2, dq, c2c, w2, dc2, gw2, gb2, B, H, st));
     }
     // layer 2
@@ -833,7 +847,7 @@ DRQ_API long drq_step_ws_offset(int B, int C, int A, int F, int H, int id) {
 }
 
 namespace {
-int update_phase(const DrqStep* s, int phase, float bc_alpha) {
+int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_weight = nullptr, float* td_abs = nullptr) {
   CK(check_step(s));
   if (!s->obs || !s->next_obs || !s->action || !s->reward || !s->discount || !s->shift_obs || !s->shift_next ||
       !s->noise_critic || !s->noise_actor || !s->base_grid || !s->grads || !s->adam_m || !s->adam_v || !s->sums)
@@ -842,6 +856,8 @@ int update_phase(const DrqStep* s, int phase, float bc_alpha) {
   if (phase < DRQ_PHASE_ALL || phase > DRQ_PHASE_REDRAW) return DRQ_EARG;
   c.fuse_actor_loss = phase == DRQ_PHASE_ALL || phase == DRQ_PHASE_ACTOR;
   c.bc_alpha = bc_alpha;
+  c.is_weight = is_weight;
+  c.td_abs = td_abs;
   if (runs(phase, DRQ_PHASE_ENCODE)) CK(phase_encode(c));
   if (runs(phase, DRQ_PHASE_CRITIC_HEADS)) {
     CK(c.stamp(6));
@@ -879,6 +895,12 @@ DRQ_API int drq_update_phase_bc(const DrqStep* s, int phase, float bc_alpha) {
   // single GPU only: lambda needs the GLOBAL sum of |min(q1,q2)| before any gradient exists
   if (!(bc_alpha > 0.f) || bc_alpha > 3.0e38f || (s && s->global_B != s->B)) return DRQ_EARG;
   return update_phase(s, phase, bc_alpha);
+}
+
+DRQ_API int drq_update_phase_per(const DrqStep* s, int phase, const float* is_weight, float* td_abs) {
+  // single GPU only: the weights of a data-parallel batch would need a normalisation over all ranks' rows
+  if (!is_weight || !td_abs || (s && s->global_B != s->B)) return DRQ_EARG;
+  return update_phase(s, phase, 0.f, is_weight, td_abs);
 }
 
 DRQ_API int drq_publish_sums(const float* sums, float* sums_host, unsigned seq, drq_stream_t stream) {

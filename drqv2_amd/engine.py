@@ -377,6 +377,8 @@ class StepEngine:
         self.fused_rng = True     # the update's four draws in one launch (rng_draws); None/False: torch's own four calls
         self._rng_ok = None       # verdict of _rng_selftest
         self._rng_bufs = None
+        self._td_bufs = None      # (B, four td_abs buffers used in turn, next slot): weighted updates (loss_weights)
+        self.last_td_abs = None   # the per-sample |TD error| [B] the last weighted update leaves (device, stream order)
 
     # ---- arenas --------------------------------------------------------------------------
     def _adopt(self, name, mod):
@@ -439,6 +441,35 @@ class StepEngine:
         if alpha is not None and self.bf16:
             raise _lib.DrqError(self._BC_BF16)
         self.bc_alpha = alpha
+
+    # ---- prioritized replay: the critic loss weighted per sample --------------------------------
+    _PER_DP = ("per-sample loss weights and data parallelism cannot be combined: prioritized replay over several ranks "
+               "needs per-rank stores and a normalisation of the weights over the global batch, which is not built")
+    _PER_BF16 = ("per-sample loss weights with the bf16 compute dtype are not covered by a test against the bf16 bounds "
+                 "and are refused: use set_compute_dtype('fp32')")
+    _PER_BC = ("per-sample loss weights and behaviour cloning cannot be combined: the two forms of the update are "
+               "separate entries of the library (drq_update_phase_per / drq_update_phase_bc)")
+
+    def _loss_weights(self, w, B):
+        """validates update()'s loss_weights and returns (weights, the td_abs buffer of this update)"""
+        if self.pg is not None:
+            raise _lib.DrqError(self._PER_DP)
+        if self.bf16:
+            raise _lib.DrqError(self._PER_BF16)
+        if self.bc_alpha is not None:
+            raise _lib.DrqError(self._PER_BC)
+        if (not torch.is_tensor(w) or w.dtype != torch.float32 or w.device != self.device or tuple(w.shape) != (B,)
+                or not w.is_contiguous()):
+            what = f"{w.dtype} {tuple(w.shape)} on {w.device}" if torch.is_tensor(w) else type(w).__name__
+            raise _lib.DrqError(f"update(): loss weights must be a contiguous float32 tensor of shape ({B},) on "
+                                f"{self.device}, got {what}")
+        if self._td_bufs is None or self._td_bufs[0] != B:
+            # four buffers used in turn: at most two updates are queued behind the running one (_throttle), and the
+            # priority launch that reads a buffer is queued right behind its update
+            self._td_bufs = [B, [torch.zeros(B, device=self.device, dtype=torch.float32) for _ in range(4)], 0]
+        td = self._td_bufs[1][self._td_bufs[2]]
+        self._td_bufs[2] = (self._td_bufs[2] + 1) & 3
+        return w, td
 
     def read_bc_sums(self):
         """(sum (a - a_beh)^2, sum |min(q1,q2)|) of the last BC update as Python floats; call it after read_sums(), which
@@ -561,11 +592,14 @@ class StepEngine:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _phase(self, desc, k):
+    def _phase(self, desc, k, per=None):
         # the library launches on the CURRENT HIP device: make that the agent's (an agent on cuda:1 in a process
         # whose current device is 0 would otherwise launch device-1 pointers on device 0)
         with torch.cuda.device(self.device):
-            if self.bc_alpha is not None:
+            if per is not None:         # (loss weights, td_abs): the weighted critic loss (_loss_weights)
+                check(_lib.load().drq_update_phase_per(ctypes.byref(desc), k, ptr(per[0]), ptr(per[1])),
+                      f"drq_update_phase_per({k})")
+            elif self.bc_alpha is not None:
                 check(_lib.load().drq_update_phase_bc(ctypes.byref(desc), k, self.bc_alpha), f"drq_update_phase_bc({k})")
             else:
                 check(_lib.load().drq_update_phase(ctypes.byref(desc), k), f"drq_update_phase({k})")
@@ -652,8 +686,10 @@ class StepEngine:
         return d
 
     def update(self, obs, action, reward, discount, next_obs, shift_obs, shift_next, noise_critic, noise_actor, std,
-               clip, tau, B_global=None, obs_index=None, next_obs_index=None):
+               clip, tau, B_global=None, obs_index=None, next_obs_index=None, loss_weights=None):
         """All tensors are this rank's shard, on the GPU.  Returns the 8-float sums tensor (device).
+        loss_weights (float32 [B], device): the critic loss weighted per sample (prioritized replay,
+        drq_update_phase_per); the per-sample |TD error| is left in self.last_td_abs.  Single GPU, fp32, no BC.
         obs_index / next_obs_index (int64 [B], device): the batch is not materialised -- obs / next_obs are frame stores
         ([slots, C*84*84] or [slots, C, 84, 84] uint8) and row b is frame index[b] (DrqStep.obs_index)."""
         indexed = obs_index is not None
@@ -677,10 +713,11 @@ class StepEngine:
                                 f"buffer with 32-bit byte offsets, which holds up to {self.MAX_BATCH} rows "
                                 "(2B x 32 x 41 x 41 floats < 2 GiB): split the batch over more GPUs")
         B_global = B * self.world if B_global is None else B_global
+        per = self._loss_weights(loss_weights, B) if loss_weights is not None else None      # before any state moves
         steps = (self.critic_opt.begin_step(), self.encoder_opt.begin_step(), self.actor_opt.begin_step())
         d = self.make_desc(B, B_global, std, clip, tau, steps)
         keep = (obs, action, reward, discount, next_obs, shift_obs, shift_next, noise_critic, noise_actor, obs_index,
-                next_obs_index)
+                next_obs_index, per)
         d.obs, d.next_obs = ptr(obs), ptr(next_obs)
         d.obs_index, d.next_obs_index = ptr(obs_index), ptr(next_obs_index)
         d.action, d.reward, d.discount = ptr(action), ptr(reward), ptr(discount)
@@ -688,7 +725,8 @@ class StepEngine:
         d.noise_critic, d.noise_actor = ptr(noise_critic), ptr(noise_actor)
         if self.pg is None:
             self._throttle(steps[2] & 0xFFFFFFFF)
-            self._phase(d, _lib.PHASE_ALL)
+            self._phase(d, _lib.PHASE_ALL, per)
+            self.last_td_abs = per[1] if per is not None else None
             self._last_seq = steps[2] & 0xFFFFFFFF
         else:
             # overlapped schedule.  Every exchange is a SUM of gradients already scaled by

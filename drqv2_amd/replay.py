@@ -11,6 +11,13 @@ drops the OLDEST whole episodes until the new one fits (`_store_episode`, :100-1
 uniformly, then `idx` uniformly in [1, len - nstep + 1] (:145-150).  Not kept: the on-disk npz files and the
 worker processes (their per-worker RNG streams are not reproducible in the reference either); index draws come
 from one numpy RandomState, vectorised over the batch.
+
+Prioritized replay (new: `priority_alpha`; the reference samples uniformly).  Proportional prioritization (Schaul et
+al. 2016): position i is drawn with probability p_i^alpha / sum_k p_k^alpha, stratified over the batch, and carries the
+importance weight (N P(i))^-beta / max_batch.  The priorities live in a sum tree in HBM (csrc/per.hip, the layout is in
+include/drqv2_hip.h); a draw is one launch (drq_per_sample) whose positions never leave the device, the new priorities
+|TD error| come out of the update's own loss launch and go back into the tree with one more (drq_per_update).  The
+host only counts: which slots can be drawn, how many there are, how many episodes have been placed.
 """
 import numpy as np
 import torch
@@ -37,6 +44,31 @@ class IndexedBatch(tuple):
         return (self.frames[obs_idx].view(shp), action, reward, discount, self.frames[next_idx].view(shp))
 
 
+class PrioritizedBatch:
+    """What a prioritized DeviceReplay yields: the batch of the store's form -- an IndexedBatch (indexed=True) or the
+    materialised 5-tuple -- that also carries `weights` (float32 [B] on the device: the importance weights, largest 1)
+    and `update_priorities(td_abs)`.  DrQV2Agent.update() reads both: the weights go into the critic loss, the
+    per-sample TD errors the loss launch leaves come back through update_priorities, all in stream order."""
+
+    def _per(self, store, pos, weights):
+        self.weights, self._store, self._pos, self._stamp = weights, store, pos, store._placements
+        return self
+
+    def update_priorities(self, td_abs):
+        """td_abs: float32 [B] on the device, the |TD error| of every row -> leaf = (td_abs + eps)^alpha.  Nothing is
+        written if the store has placed an episode since this batch was drawn: a position of this batch may then lie
+        in a newer episode, whose fresh priority must not be overwritten with an error of the evicted one."""
+        self._store._update_priorities(self, td_abs)
+
+
+class _PrioritizedTuple(PrioritizedBatch, tuple):
+    pass
+
+
+class _PrioritizedIndexed(PrioritizedBatch, IndexedBatch):
+    pass
+
+
 class BatchIterator:
     """Endless iterator over device batches with one batch of look-ahead: DrQV2Agent.update() calls prefetch() right
     after it has queued its kernels, so the next batch's host work (index draw, upload, gather launch) happens while the
@@ -60,7 +92,17 @@ class BatchIterator:
 
 
 class DeviceReplay:
-    def __init__(self, capacity_steps, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=False):
+    def __init__(self, capacity_steps, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=False,
+                 priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
+        """priority_alpha: None = uniform sampling (no tree is allocated, the draws from the RandomState are what they
+        were); a float in (0, 1] = proportional prioritized replay, sample() yields PrioritizedBatch objects.
+        priority_beta is a plain attribute, read at every draw: the training loop may anneal it towards 1.
+        priority_eps (> 0) keeps a transition with zero error drawable.  The order that keeps every priority update
+        valid is the one DrQV2Agent.update() and the loader's iterator follow: update, then update_priorities, then
+        add_episode, then the next draw; a batch that is overtaken by an add writes no priorities (PrioritizedBatch).
+        replay_buffer.make_replay_loader keeps that order by handing a prioritized store its finished episodes when the
+        loader's iterator draws next, not when they finish: sample() called on the store directly does not see an
+        episode the iterator has not taken over yet."""
         self.device = torch.device(device)
         self.obs_shape = tuple(int(s) for s in obs_shape)
         self.frame_bytes = int(np.prod(self.obs_shape))
@@ -83,6 +125,24 @@ class DeviceReplay:
         # reference's loader yields
         self.indexed = bool(indexed)
         self._ibufs = {}
+        self.priority_alpha = None
+        self.priority_beta, self.priority_eps = float(priority_beta), float(priority_eps)
+        self._placements = 0        # episodes placed so far: what a PrioritizedBatch compares before it writes priorities
+        self.n_valid = 0            # drawable positions (prioritized store)
+        self.tree = None
+        if priority_alpha is not None:
+            a = float(priority_alpha)
+            if isinstance(priority_alpha, bool) or not (0.0 < a <= 1.0):
+                raise ValueError(f"priority_alpha {priority_alpha!r}: None or a float in (0, 1]")
+            if not (self.priority_beta >= 0.0) or not (0.0 < self.priority_eps < float("inf")):
+                raise ValueError("priority_beta must be >= 0 and priority_eps > 0")
+            if self.device.type != "cuda":
+                raise _lib.DrqError("prioritized replay keeps its sum tree on the GPU: the HIP path has no CPU fallback")
+            self.priority_alpha = a
+            self.tree_leaves = 1 << max(0, self.capacity - 1).bit_length()      # smallest power of two >= capacity
+            self.tree = torch.zeros(2 * self.tree_leaves, dtype=torch.float64, device=dev)
+            self.tree[0] = 1.0      # running maximum leaf: what a new episode's positions start at
+            self._pbufs = {}
 
     # ---- storage -------------------------------------------------------------------------
     def __len__(self):
@@ -91,14 +151,35 @@ class DeviceReplay:
 
     def _place(self, n):
         """slot range for an episode of n steps: contiguous, wrapping to slot 0 when the tail is too short;
-        evicts every stored episode the range overlaps (they are the oldest ones)."""
+        evicts every stored episode the range overlaps (they are the oldest ones).  Returns (start, the evicted
+        episodes as [start, steps])."""
         if n > self.capacity:
             raise ValueError(f"episode of {n} steps exceeds the store ({self.capacity})")
         start = self._head if self._head + n <= self.capacity else 0
         end = start + n
-        self.episodes = [e for e in self.episodes if e[0] + e[1] <= start or e[0] >= end]
+        clear = lambda e: e[0] + e[1] <= start or e[0] >= end
+        evicted = [e for e in self.episodes if not clear(e)]
+        self.episodes = [e for e in self.episodes if clear(e)]
         self._head = end
-        return start
+        return start, evicted
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _fill(self, lo, hi, mode):
+        with torch.cuda.device(self.device):       # the library launches on the current HIP device
+            check(_lib.load().drq_per_fill(ptr(self.tree), self.tree_leaves, lo, hi, mode, self._stream()), "drq_per_fill")
+
+    def _place_priorities(self, start, n, evicted):
+        """the tree after an episode of n steps went to `start`: every slot of the evicted episodes (also the part the
+        new one does not cover) and of the new one's range is 0, then the drawable positions start+1 .. start+n-nstep
+        (draw_positions' range) get the running maximum"""
+        for s, m in evicted:
+            self._fill(s, s + m, 0)
+        self._fill(start, start + n, 0)
+        if n - 1 >= self.nstep:
+            self._fill(start + 1, start + n - self.nstep + 1, 1)
+        self.n_valid = sum(m - self.nstep for _, m in self.episodes if m - 1 >= self.nstep)
 
     def add_episode(self, episode):
         """episode: dict of numpy arrays like the reference's npz (observation [T+1,...] uint8, action [T+1,A],
@@ -107,7 +188,7 @@ class DeviceReplay:
         n = obs.shape[0]
         if obs.dtype != np.uint8 or int(np.prod(obs.shape[1:])) != self.frame_bytes:
             raise ValueError("observation must be uint8 frames of the configured shape")
-        start = self._place(n)
+        start, evicted = self._place(n)
         sl = slice(start, start + n)
         dev = self.device
         self.frames[sl].copy_(torch.from_numpy(obs.reshape(n, self.frame_bytes)), non_blocking=False)
@@ -115,6 +196,9 @@ class DeviceReplay:
         self.reward[sl].copy_(torch.from_numpy(np.asarray(episode["reward"], np.float32).reshape(n)))
         self.discount[sl].copy_(torch.from_numpy(np.asarray(episode["discount"], np.float32).reshape(n)))
         self.episodes.append([start, n])
+        self._placements += 1
+        if self.tree is not None:
+            self._place_priorities(start, n, evicted)
         return start
 
     # ---- sampling ------------------------------------------------------------------------
@@ -186,7 +270,58 @@ class DeviceReplay:
                                    None, torch.cuda.current_stream().cuda_stream), "drq_nstep_gather")
         return IndexedBatch(self.frames, idx[0], act, rew, disc, idx[1])
 
+    def sample_prioritized(self, batch_size):
+        """One stratified draw on the device: u ~ U[0,1)^B from the store's RandomState (one random_sample call per
+        batch) -> drq_per_sample -> drq_nstep_gather on the device positions.  Returns a PrioritizedBatch."""
+        if self.n_valid <= 0:
+            raise _lib.DrqError("replay: no stored episode is at least nstep long")
+        lib = _lib.load()
+        B = int(batch_size)
+        bufs = self._pbufs.get(B)
+        if bufs is None:
+            dev = self.device
+            # four sets used in turn, like gather_indexed's (and for its reason: the pinned u row of a set is
+            # overwritten by the host when batch k+4 is drawn); a set also holds the weights of its batch and, for
+            # indexed batches, their action / reward / discount rows (materialised ones use gather()'s buffers)
+            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
+                          f(B), torch.empty((B,), dtype=torch.float64).pin_memory(),
+                          (f(B, self.A), f(B, 1), f(B, 1)) if self.indexed else None)
+            bufs = [mk(), mk(), mk(), mk(), 0]
+            self._pbufs = {B: bufs}
+        idx, u, w, host, rows = bufs[bufs[4]]
+        bufs[4] = (bufs[4] + 1) & 3
+        host.numpy()[:] = self.rng.random_sample(B)
+        u.copy_(host, non_blocking=True)
+        with torch.cuda.device(self.device):
+            check(lib.drq_per_sample(ptr(self.tree), self.tree_leaves, ptr(u), B, self.nstep, self.n_valid,
+                                     float(self.priority_beta), ptr(idx), ptr(w), self._stream()), "drq_per_sample")
+            if self.indexed:
+                act, rew, disc = rows
+                check(lib.drq_nstep_gather(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
+                                           ptr(idx[2]), B, self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act),
+                                           ptr(rew), ptr(disc), None, self._stream()), "drq_nstep_gather")
+        if self.indexed:
+            batch = _PrioritizedIndexed(self.frames, idx[0], act, rew, disc, idx[1])
+        else:
+            batch = _PrioritizedTuple(self.gather(idx[2]))
+        return batch._per(self, idx[2], w)
+
+    def _update_priorities(self, batch, td_abs):
+        if batch._stamp != self._placements:
+            return                      # an episode was placed since the draw: see PrioritizedBatch.update_priorities
+        pos = batch._pos
+        B = pos.numel()
+        if (not torch.is_tensor(td_abs) or td_abs.dtype != torch.float32 or td_abs.device != pos.device
+                or td_abs.numel() != B or not td_abs.is_contiguous()):
+            raise _lib.DrqError(f"update_priorities(): contiguous float32 [{B}] on {pos.device} required")
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_per_update(ptr(self.tree), self.tree_leaves, ptr(pos), ptr(td_abs), B, self.priority_alpha,
+                                             self.priority_eps, self._stream()), "drq_per_update")
+
     def sample(self, batch_size):
+        if self.tree is not None:
+            return self.sample_prioritized(batch_size)
         pos = self.draw_positions(batch_size)
         return self.gather_indexed(pos) if self.indexed else self.gather(pos)
 

@@ -231,6 +231,14 @@ int drq_copy_cols(const float* src, int ld_src, float* dst, long ld_dst, int B, 
 int drq_td_mse(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
                const float* discount, float* dq1, float* dq2, float* sums, int B, float inv_global_B,
                drq_stream_t stream);
+/* The same loss with a weight per row (prioritized replay; new functionality, these definitions are the contract).
+ * With w [B] and y as above:  critic_loss = mean_i w_i (q1_i - y_i)^2 + mean_i w_i (q2_i - y_i)^2,
+ *   dq_k[i] = (2 (q_k,i - y_i) inv_global_B) w_i   -- multiplied by w_i LAST: w_i == 1.0f gives drq_td_mse's bits --
+ *   td_abs[i] = (|q1_i - y_i| + |q2_i - y_i|) / 2  (unweighted: what the priorities are made of),
+ *   sums[4] = sum_i w_i ((q1_i-y_i)^2 + (q2_i-y_i)^2);  sums[0..3] are unweighted, as drq_td_mse leaves them. */
+int drq_td_mse_w(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
+                 const float* discount, const float* w, float* dq1, float* dq2, float* td_abs, float* sums, int B,
+                 float inv_global_B, drq_stream_t stream);
 /* ---- update_actor loss (drqv2.py:212-216,225): sums[5] = sum -min(q1,q2), sums[6] = sum log_prob */
 int drq_actor_loss(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
                    float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B, drq_stream_t stream);
@@ -299,6 +307,36 @@ int drq_nstep_gather(const uint8_t* frames, const float* action, const float* re
                      const long* pos, int B, int A, long frame_bytes, int nstep, float gamma, uint8_t* obs,
                      float* act_out, float* rew_out, float* disc_out, uint8_t* next_obs, drq_stream_t stream);
 int drq_tanh(const float* x, float* y, long n, drq_stream_t stream);
+
+/* ---- proportional prioritized replay (Schaul et al. 2016) on the store above.  New functionality: the reference's
+ * replay is uniform; these definitions are the contract.
+ * `tree` is double [2 L], L the smallest power of two >= the store's slots: node 1 is the root, the children of node k
+ * are 2k and 2k+1, the leaf of slot s is tree[L + s].  Every inner node holds exactly tree[2k] + tree[2k+1]: it is always
+ * recomputed from its children, never adjusted by a difference.  tree[0] is the largest leaf value a priority update
+ * ever wrote (the caller initialises it, to 1.0).  A leaf is 0 for a slot that must not be drawn, p^alpha otherwise.
+ * Each entry is one launch of one workgroup, plain loads and stores, no atomics; the caller orders them on one stream.
+ *
+ * drq_per_fill: the leaves of slots [lo, hi) become 0 (mode 0) or tree[0] (mode 1: a new episode's drawable
+ *   positions), then every ancestor of the range is rebuilt; no other node is touched.  lo == hi: nothing, DRQ_OK.
+ *   DRQ_EARG: null tree, L no power of two, not 0 <= lo <= hi <= L, another mode.
+ * drq_per_sample: B stratified draws.  u is double [B] in [0, 1); row i aims at the mass (i + u[i]) / B * tree[1] and
+ *   descends from the root: at node k with left = tree[2k], right = tree[2k+1] it goes left if
+ *   (m < left && left > 0) || right == 0, else m -= left and it goes right.  While the root is positive this never ends
+ *   on a zero leaf.  idx_out is int64 [3][B] = pos - 1, pos + nstep - 1, pos (obs frame, next_obs frame, transition:
+ *   row 2 is drq_nstep_gather's `pos`).  weight_out is float [B] = (n_valid leaf / tree[1])^(-beta) divided by the largest
+ *   such value of the batch, evaluated in double and rounded once; the largest weight is exactly 1.  n_valid is the
+ *   caller's count of drawable positions.  A root of 0 must be refused by the caller BEFORE the launch.
+ *   DRQ_EARG: null pointers, B <= 0, L no power of two, nstep <= 0, n_valid <= 0, beta < 0.
+ * drq_per_update: leaf[pos[i]] = pow((double)td_abs[i] + eps, alpha) for pos int64 [B] and td_abs float [B], both on the
+ *   device (a NaN or negative td_abs counts as 0, an infinite one as FLT_MAX).  Where one position occurs in several
+ *   rows the row with the HIGHEST index wins, on every run.  Positions outside [0, L) are skipped.  Then the ancestors
+ *   are rebuilt and tree[0] = max(tree[0], the leaves written).  Any B.
+ *   DRQ_EARG: null pointers, B <= 0, L no power of two, alpha <= 0, eps < 0. */
+int drq_per_fill(double* tree, long L, long lo, long hi, int mode, drq_stream_t stream);
+int drq_per_sample(const double* tree, long L, const double* u, int B, int nstep, long n_valid, double beta,
+                   long* idx_out, float* weight_out, drq_stream_t stream);
+int drq_per_update(double* tree, long L, const long* pos, const float* td_abs, int B, double alpha, double eps,
+                   drq_stream_t stream);
 
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
@@ -458,6 +496,13 @@ int drq_update_phase(const DrqStep* s, int phase);
  * above); with s->sums_host set those two are published in slots 9 and 10 before the sequence word.  Single GPU only:
  * global_B != B is DRQ_EARG.  The descriptor is unchanged, so callers of the plain entry are not affected. */
 int drq_update_phase_bc(const DrqStep* s, int phase, float bc_alpha);
+/* The same update with the critic loss weighted per row (prioritized replay; drq_td_mse_w's definitions): is_weight is
+ * float [B] on the device, td_abs float [B] receives the per-sample error in phase 4.  Same phases as drq_update_phase,
+ * the launches are those of the plain update one for one: the weighted loss is a compile-time form of the same two
+ * loss launches (fused into the Q output backward, or drq_td_mse_w in front of it).  sums[4] is the weighted sum; the
+ * other sums and the actor step are the plain update's; weights of 1.0f give the plain update bit for bit.
+ * DRQ_EARG: null is_weight / td_abs, or global_B != B (single GPU only).  The descriptor is unchanged. */
+int drq_update_phase_per(const DrqStep* s, int phase, const float* is_weight, float* td_abs);
 
 /* sums[0..7] -> sums_host[0..7], then seq -> slot 8 with system-scope release (see DrqStep.sums_host); for hosts
  * that reduce the sums themselves before publishing them. */

@@ -112,7 +112,10 @@ class ReplayBufferStorage:
         if ent["save_snapshot"]:                      # replay_buffer.py:69-78 (same file name, same content)
             ts = datetime.datetime.now().strftime("%Y%m%dT%H%M%S")
             save_episode(episode, pathlib.Path(self._replay_dir) / f"{ts}_{eps_idx}_{eps_len}.npz")
-        if ent["store"] is not None:
+        # a prioritized store takes the episode when the iterator draws next (_Loader): the batch the iterator has drawn
+        # ahead is consumed first and its priorities are written before an episode is placed (the order update ->
+        # priorities -> adds -> next draw, drqv2_amd.replay.PrioritizedBatch.update_priorities)
+        if ent["store"] is not None and ent["store"].priority_alpha is None:
             ent["store"].add_episode(episode)
         else:
             ent["pending"].append(episode)
@@ -138,9 +141,15 @@ class _Loader:
 
 
 def make_replay_loader(replay_dir, max_size, batch_size, num_workers, save_snapshot, nstep, discount, device=None,
-                       obs_shape=None, action_dim=None, seed=None, indexed=False):
+                       obs_shape=None, action_dim=None, seed=None, indexed=False, priority_alpha=None, priority_beta=0.4,
+                       priority_eps=1e-6):
     """Same positional signature as the reference (replay_buffer.py:173-190).  The observation / action shapes
-    come from the data_specs the storage of the same replay_dir was built with (or from the keyword arguments)."""
+    come from the data_specs the storage of the same replay_dir was built with (or from the keyword arguments).
+    priority_alpha (None: uniform): proportional prioritized replay, see drqv2_amd.replay.DeviceReplay; episodes
+    reloaded on a resume start at the running maximum priority of 1.  A prioritized store receives the episodes the
+    storage finishes when the loader's iterator draws next (so that the batch drawn ahead is consumed and its priorities
+    written first), not at once: until then they are not in the store, and store.sample() called directly does not
+    see them."""
     ent = _entry(replay_dir)
     if ent["specs"] is not None:
         by_name = {s.name: s for s in ent["specs"]}
@@ -155,7 +164,8 @@ def make_replay_loader(replay_dir, max_size, batch_size, num_workers, save_snaps
         seed = int(np.random.get_state()[1][0])          # what the reference's _worker_init_fn seeds from
     # indexed=True: the iterator yields drqv2_amd.replay.IndexedBatch objects (frames stay in the store, the update's first
     # kernel gathers them): what DrQV2Agent.update() consumes fastest; False: plain device tensors like the reference's
-    ent["store"] = DeviceReplay(capacity, obs_shape, action_dim, nstep, discount, device, seed=seed, indexed=indexed)
+    ent["store"] = DeviceReplay(capacity, obs_shape, action_dim, nstep, discount, device, seed=seed, indexed=indexed,
+                                priority_alpha=priority_alpha, priority_beta=priority_beta, priority_eps=priority_eps)
     ent["save_snapshot"] = bool(save_snapshot)
     # resume: the newest episodes on disk that fit max_size (replay_buffer.py:120-140 walks them newest first),
     # added oldest first so that eviction order stays chronological
