@@ -98,6 +98,8 @@ PROTOTYPES = {
     "drq_per_fill": (I, [P, L, L, L, I, P]),
     "drq_per_sample": (I, [P, L, P, I, I, L, D, P, P, P]),
     "drq_per_update": (I, [P, L, P, P, I, D, D, P]),
+    "drq_vec_add": (I, [P, P, P, P, P, L, L, I, L, L, P, P, P, P, P, P]),
+    "drq_vec_sample": (I, [P, P, P, P, L, L, I, L, L, L, P, I, I, I, F, P, P, P, P, P, P, P, P, P]),
     "drq_relu_mask_pad": (I, [P, P, P, L, I, I, P]),
     "drq_conv1_dgrad": (I, [P, P, P, I, P]),
     "drq_aug_bwd_f32": (I, [P, P, P, P, I, I, I, I, P]),

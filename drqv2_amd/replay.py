@@ -18,6 +18,10 @@ importance weight (N P(i))^-beta / max_batch.  The priorities live in a sum tree
 include/drqv2_hip.h); a draw is one launch (drq_per_sample) whose positions never leave the device, the new priorities
 |TD error| come out of the update's own loss launch and go back into the tree with one more (drq_per_update).  The
 host only counts: which slots can be drawn, how many there are, how many episodes have been placed.
+
+Vectorised collection (new: VecDeviceReplay, csrc/vecreplay.hip).  N environments stepped in lockstep write one row per
+step into a ring, straight from device tensors; episode boundaries are flags on the device, an n-step window ends at
+one, and the batches are the IndexedBatch above.  The episode store and everything it does are unchanged.
 """
 import numpy as np
 import torch
@@ -324,6 +328,172 @@ class DeviceReplay:
             return self.sample_prioritized(batch_size)
         pos = self.draw_positions(batch_size)
         return self.gather_indexed(pos) if self.indexed else self.gather(pos)
+
+    def __iter__(self):
+        return BatchIterator(lambda: self.sample(self.batch_size))
+
+    batch_size = 256
+
+
+class VecDeviceReplay:
+    """Step-major device store for N environments stepped in lockstep (new; the contract is in include/drqv2_hip.h,
+    "step-major replay"): add() writes one row -- the observation after the step and the action, reward and discount that
+    led to it, for all N environments -- with one launch (drq_vec_add), sample() draws, windows and indexes a batch with
+    one more (drq_vec_sample).  Device tensors go in and come out; nothing here waits for the GPU or reads a flag back:
+    episode boundaries are the `first` flags of the rows (1 = the dummy reset transition of a new episode, like index 0 of
+    an episode file), an n-step window that meets one simply ends there (`last_steps` tells how long each window was).
+
+    A ring of `rows` rows.  With T rows added the drawable ones are lo .. hi, hi = T - nstep and
+    lo = max(1, T - rows + 1 + guard_rows): an IndexedBatch stays valid while fewer than `guard_rows` rows are added
+    between its draw and the update that consumes it (the iterator's one batch of look-ahead needs 1).
+    Every environment must hold a non-reset row among the drawable ones; a batch row drawn from one that does not comes
+    out with steps 0, reward 0 and discount 0.  Not here: prioritized sampling, episode files / resume, rows for a subset
+    of the environments."""
+
+    K = 4       # candidates per batch row (the columns of the u table)
+
+    def __init__(self, rows, num_envs, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=True,
+                 guard_rows=8):
+        self.device = torch.device(device)
+        self.obs_shape = tuple(int(s) for s in obs_shape)
+        self.frame_bytes = int(np.prod(self.obs_shape))
+        self.R, self.N, self.A = int(rows), int(num_envs), int(action_dim)
+        self.nstep, self.gamma, self.guard_rows = int(nstep), float(discount), int(guard_rows)
+        if self.frame_bytes <= 0 or self.frame_bytes % 16:
+            raise ValueError("frame size must be a multiple of 16 bytes")
+        if self.N < 1 or self.A < 1 or self.nstep < 1 or self.guard_rows < 0:
+            raise ValueError("num_envs, action_dim and nstep must be >= 1, guard_rows >= 0")
+        if self.R < self.nstep + self.guard_rows + 2:
+            raise ValueError(f"rows {self.R}: at least nstep + guard_rows + 2 = {self.nstep + self.guard_rows + 2}")
+        dev, S = self.device, self.R * self.N
+        self.frames = torch.empty((S, self.frame_bytes), dtype=torch.uint8, device=dev)
+        self.action = torch.zeros((S, self.A), dtype=torch.float32, device=dev)
+        self.reward = torch.zeros((S,), dtype=torch.float32, device=dev)
+        self.discount = torch.ones((S,), dtype=torch.float32, device=dev)
+        self.first = torch.ones((S,), dtype=torch.uint8, device=dev)
+        self.T = 0                  # rows added
+        self.rng = np.random.RandomState(seed)
+        self.indexed = bool(indexed)
+        self.last_steps = None      # int32 [B] on the device: the window length of every row of the newest batch
+        self.last_index = None      # int64 [3][B] on the device: its obs, next_obs and transition slots
+        self._stage = None          # pinned + device staging of one row, for host inputs
+        self._bufs = {}
+        self._frames_out = {}
+
+    # ---- storage -------------------------------------------------------------------------
+    def bounds(self):
+        """(lo, hi): the drawable rows; hi < lo while there are none"""
+        return max(1, self.T - self.R + 1 + self.guard_rows), self.T - self.nstep
+
+    def __len__(self):
+        """drawable transitions, reset rows included: rows x environments"""
+        lo, hi = self.bounds()
+        return max(0, hi - lo + 1) * self.N
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _row(self, x, name, shapes, dtypes):
+        """one argument of add() as a contiguous tensor of its storage type, checked; still where the caller has it"""
+        t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+        if not torch.is_tensor(t):
+            raise ValueError(f"add(): {name} must be a numpy array or a tensor")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"add(): {name} of shape {shapes[0]} required, got {tuple(t.shape)}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"add(): {name} must be {dtypes[0]}, got {t.dtype}")
+        if t.device.type != "cpu" and t.device != self._device_index():
+            raise ValueError(f"add(): {name} is on {t.device}, the store on {self.device}")
+        if t.dtype != dtypes[0]:
+            t = t.to(dtypes[0])     # float64 / bool of the same device: a cast, no wait
+        return t.contiguous()
+
+    def _device_index(self):
+        d = self.device
+        if d.type == "cuda" and d.index is None:
+            return torch.device("cuda", torch.cuda.current_device())
+        return d
+
+    def _staged(self, k, t):
+        """a host tensor -> the device, through the pinned buffer of argument k: a blocking copy, like add_episode's"""
+        if self._stage is None:
+            N, A, fb, dev = self.N, self.A, self.frame_bytes, self.device
+            mk = lambda shape, dt: (torch.empty(shape, dtype=dt).pin_memory(), torch.empty(shape, dtype=dt, device=dev))
+            self._stage = [mk((N, fb), torch.uint8), mk((N, A), torch.float32), mk((N,), torch.float32),
+                           mk((N,), torch.float32), mk((N,), torch.uint8)]
+        pin, dv = self._stage[k]
+        pin.copy_(t.reshape(pin.shape))
+        dv.copy_(pin, non_blocking=False)
+        return dv
+
+    def add(self, obs, action, reward, discount, first=None):
+        """One row for all N environments: obs uint8 [N, *obs_shape] (the observation after the step), action [N, A],
+        reward and discount [N] or [N, 1] (float32; float64 is cast), first bool / uint8 [N] (True = this row is the reset
+        row of a new episode: obs is its first observation, the other three are dummies; None = no environment was
+        reset).  Row 0 is a reset row for every environment whatever `first` says.  Tensors on the store's device are
+        handed to the launch as they are and nothing waits; numpy arrays and host tensors are staged with a blocking
+        copy."""
+        N, f32 = self.N, (torch.float32, torch.float64)
+        args = [self._row(obs, "obs", [(N,) + self.obs_shape, (N, self.frame_bytes)], (torch.uint8,)),
+                self._row(action, "action", [(N, self.A)], f32),
+                self._row(reward, "reward", [(N,), (N, 1)], f32),
+                self._row(discount, "discount", [(N,), (N, 1)], f32),
+                None if first is None else self._row(first, "first", [(N,)], (torch.uint8, torch.bool))]
+        if self.device.type != "cuda":
+            raise _lib.DrqError("the step-major replay lives on the GPU: the HIP path has no CPU fallback")
+        with torch.cuda.device(self.device):
+            src = [t if t is None or t.is_cuda else self._staged(k, t) for k, t in enumerate(args)]
+            check(_lib.load().drq_vec_add(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
+                                          ptr(self.first), self.R, N, self.A, self.frame_bytes, self.T, *(ptr(t) for t in src),
+                                          self._stream()), "drq_vec_add")
+            for t in src:           # a caller's tensor may be freed right after add(): the launch still reads it
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream())
+        self.T += 1
+
+    # ---- sampling ------------------------------------------------------------------------
+    def sample(self, batch_size):
+        """IndexedBatch (indexed=True: the frames stay in the ring) or the materialised 5-tuple of the reference's loader,
+        shaped like DeviceReplay's.  One random_sample((B, K)) call on the store's RandomState per batch."""
+        if self.device.type != "cuda":
+            raise _lib.DrqError("the step-major replay lives on the GPU: the HIP path has no CPU fallback")
+        lo, hi = self.bounds()
+        if hi < lo:
+            raise _lib.DrqError(f"replay: {self.T} rows added, no drawable row yet (nstep {self.nstep})")
+        B, K, dev = int(batch_size), self.K, self.device
+        bufs = self._bufs.get(B)
+        if bufs is None:
+            # four sets used in turn, like DeviceReplay.gather_indexed's and for its reason: the pinned u table of a set
+            # is overwritten by the host when batch k+4 is drawn, and its upload must have run by then
+            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
+                          torch.empty((B,), dtype=torch.int32, device=dev),
+                          torch.empty((B, K), dtype=torch.float64, device=dev),
+                          torch.empty((B, K), dtype=torch.float64).pin_memory())
+            bufs = [mk(), mk(), mk(), mk(), 0]
+            self._bufs = {B: bufs}
+        idx, act, rew, disc, steps, u, host = bufs[bufs[4]]
+        bufs[4] = (bufs[4] + 1) & 3
+        host.numpy()[:] = self.rng.random_sample((B, K))
+        u.copy_(host, non_blocking=True)
+        obs = nxt = None
+        if not self.indexed:
+            out = self._frames_out.get(B)
+            if out is None:         # one batch size at a time, reused every call (DeviceReplay.gather's buffers)
+                out = tuple(torch.empty((B, self.frame_bytes), dtype=torch.uint8, device=dev) for _ in range(2))
+                self._frames_out = {B: out}
+            obs, nxt = out
+        with torch.cuda.device(dev):
+            check(_lib.load().drq_vec_sample(ptr(self.first), ptr(self.action), ptr(self.reward), ptr(self.discount), self.R,
+                                             self.N, self.A, self.frame_bytes, lo, hi, ptr(u), B, K, self.nstep, self.gamma,
+                                             ptr(idx), ptr(act), ptr(rew), ptr(disc), ptr(steps),
+                                             None if self.indexed else ptr(self.frames), ptr(obs), ptr(nxt), self._stream()),
+                  "drq_vec_sample")
+        self.last_steps, self.last_index = steps, idx
+        if self.indexed:
+            return IndexedBatch(self.frames, idx[0], act, rew, disc, idx[1])
+        shp = (B,) + self.obs_shape
+        return obs.view(shp), act, rew, disc, nxt.view(shp)
 
     def __iter__(self):
         return BatchIterator(lambda: self.sample(self.batch_size))

@@ -338,6 +338,48 @@ int drq_per_sample(const double* tree, long L, const double* u, int B, int nstep
 int drq_per_update(double* tree, long L, const long* pos, const float* td_abs, int B, double alpha, double eps,
                    drq_stream_t stream);
 
+/* ---- step-major replay for vectorised environments.  New functionality: the reference stores whole episodes of one
+ * environment; these definitions are the contract.
+ * A ring of R rows x N environments.  Absolute row numbers t = 0, 1, 2, ... count the rows added; row t of environment e
+ * lives in slot (t mod R) * N + e of
+ *   frames u8 [R N][frame_bytes] (frame_bytes % 16 == 0), action f32 [R N][A], reward f32 [R N], discount f32 [R N],
+ *   first u8 [R N].
+ * Row t holds the observation after step t and the action, reward and discount that led to it (the reference's episode
+ * layout, replay_buffer.py:76-98).  first == 1 marks the dummy reset transition of a new episode (index 0 of an episode
+ * file); row 0 always is one.  The transition at (t, e), first[t, e] == 0: obs = frame (t-1, e), action = action[t, e],
+ * and the n-step window accumulates over rows t, t+1, ... in the reference's float32 order (reward += discount * r;
+ * discount *= d * gamma; one rounding per operation, drq_nstep_gather's arithmetic) but stops early, after k < nstep
+ * steps, at the first i > 0 with first[t+i, e] == 1; next_obs = frame (t+k-1, e), steps = k.  A window no reset cuts is
+ * replay_buffer.py:142-160 on that environment's episode, a cut one the same with nstep = k, both bit for bit.
+ * Drawable rows are lo <= t <= hi, chosen by the caller: with T rows added, hi = T - nstep (the head never cuts a
+ * window) and lo = max(1, T - R + 1 + guard_rows) (row t-1 is still in the ring, and guard_rows more rows may be added
+ * before a batch whose frames travel as indices is consumed).
+ *
+ * drq_vec_add: one launch writes row t mod R of the five arrays from device sources for all N environments: src_obs u8
+ *   [N][frame_bytes] (16-byte aligned, like frames), src_action [N][A], src_reward [N], src_discount [N], src_first u8 [N]
+ *   (non-zero = reset; NULL = all 0).  t == 0 stores first = 1 for every environment whatever src_first says.
+ *   DRQ_EARG, nothing written: null pointers (but src_first), R, N, A <= 0, frame_bytes <= 0 or % 16 != 0, t < 0,
+ *   misaligned frames / src_obs.
+ * drq_vec_sample: one launch draws B transitions.  u is double [B][K] in [0, 1): with M = (hi - lo + 1) N, candidate j
+ *   of batch row b is c = min((long)(u[b][j] M), M - 1), t = lo + c / N, e = c % N.  The first candidate that is no
+ *   reset row is taken; if all K are reset rows, candidate 0 is walked cyclically through t+1 .. hi, lo .. t-1 of its
+ *   environment to the first row that is none.  idx_out int64 [3][B] = the slots of (t-1, e), (t+k-1, e), (t, e): obs
+ *   frame, next_obs frame, transition.  act_out [B][A], rew_out [B], disc_out [B], steps_out int32 [B] = k.  If the
+ *   environment of candidate 0 has no drawable row at all (a violated precondition) the row gets steps = 0, reward = 0,
+ *   discount = 0, all three indices and the action row those of candidate 0's slot; nothing is read out of range.
+ *   frames / obs_out / next_obs_out: all NULL (the frames stay in the store) or all given: obs_out, next_obs_out u8
+ *   [B][frame_bytes] receive frames[idx_out[0][b]], frames[idx_out[1][b]].
+ *   DRQ_EARG, nothing written: null required pointers, R, N, A, B, K, nstep <= 0, frame_bytes <= 0 or % 16 != 0, lo < 1,
+ *   hi < lo, hi - lo + 1 + nstep > R (rows lo-1 .. hi+nstep-1 must be distinct ring rows), some but not all of frames /
+ *   obs_out / next_obs_out, one of them misaligned. */
+int drq_vec_add(uint8_t* frames, float* action, float* reward, float* discount, uint8_t* first, long R, long N, int A,
+                long frame_bytes, long t, const uint8_t* src_obs, const float* src_action, const float* src_reward,
+                const float* src_discount, const uint8_t* src_first, drq_stream_t stream);
+int drq_vec_sample(const uint8_t* first, const float* action, const float* reward, const float* discount, long R, long N,
+                   int A, long frame_bytes, long lo, long hi, const double* u, int B, int K, int nstep, float gamma,
+                   long* idx_out, float* act_out, float* rew_out, float* disc_out, int* steps_out, const uint8_t* frames,
+                   uint8_t* obs_out, uint8_t* next_obs_out, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,

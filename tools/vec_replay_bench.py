@@ -1,0 +1,169 @@
+"""Collection cost of N lockstep environments at cheetah_run shapes (frames 9x84x84, A=6, nstep 3, batch 256), one process:
+
+  vec       VecDeviceReplay: store.add(<device tensors of one step of all N>) + store.sample(256) per environment step
+  episode   the same rows through the episode store, as a user of a batched GPU simulator has to feed it today: every
+            step's tensors are copied to the host (.cpu(): one synchronisation per step), kept in per-environment lists,
+            and every --episode-len steps the N finished episodes go in through DeviceReplay.add_episode (host arrays ->
+            four blocking copies each); DeviceReplay.sample(256) per environment step
+
+for N = 16 / 256 / 1024, then update() at batch 256 (feature_dim 50, hidden_dim 1024) fed by each store's look-ahead
+iterator, alternated inside every repeat: the ring with one add() of N = 16 rows in front of every update, the episode
+store as tools/per_bench.py's uniform path feeds it.
+
+Two figures per line (measuring-on-mi355x, section 4): device-event time = median over the iterations of an event pair
+around ONE iteration; host wall = a perf_counter window over all iterations of a repeat that ends in a synchronise,
+per iteration.  The episode path synchronises by itself, so only its host wall is meaningful; it is reported alone.
+The inputs of a step come from a pool of four pre-generated device rows; nothing is allocated inside a timed window
+except what the stores allocate themselves.
+
+  python tools/vec_replay_bench.py [--steps 2000] [--repeats 3] [--episode-len 16] [--episodes 3] [--envs 16,256,1024] [--updates 200]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import drqv2  # noqa: E402
+from drqv2_amd import synth  # noqa: E402
+from drqv2_amd.replay import DeviceReplay, VecDeviceReplay  # noqa: E402
+
+OBS = (9, 84, 84)
+A, NSTEP, B = 6, 3, 256
+SLOTS = 65536                       # both stores hold this many steps: 4.2 GB of frames each
+
+
+def pool_rows(N, n=4):
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N)
+    return [(torch.randint(0, 256, (N,) + OBS, dtype=torch.uint8, device="cuda", generator=g),
+             torch.rand(N, A, device="cuda", generator=g) * 2 - 1, torch.rand(N, device="cuda", generator=g),
+             torch.ones(N, device="cuda")) for _ in range(n)]
+
+
+def timed(fn, n):
+    """(median device-event us of one call, host wall us per call) over n calls"""
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i, (e0, e1) in enumerate(pairs):
+        e0.record()
+        fn(i)
+        e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / n
+    return 1e3 * sorted(e0.elapsed_time(e1) for e0, e1 in pairs)[n // 2], 1e6 * wall
+
+
+def spread(v):
+    v = sorted(v)
+    return f"{v[len(v) // 2]:9.1f} us [{v[0]:.1f} .. {v[-1]:.1f}]"
+
+
+def collection(N, args):
+    rows = pool_rows(N)
+    vec = VecDeviceReplay(max(32, SLOTS // N), N, OBS, A, NSTEP, 0.99, "cuda", seed=1)
+    epi = DeviceReplay(SLOTS, OBS, A, NSTEP, 0.99, "cuda", seed=1, indexed=True)
+    first = torch.zeros(N, dtype=torch.bool, device="cuda")
+    L = args.episode_len
+    held = []
+
+    def vec_step(i):
+        vec.add(*rows[i & 3], first)
+        vec.sample(B)
+
+    def epi_step(i):
+        held.append(tuple(t.cpu().numpy() for t in rows[i & 3]))          # the per-step trip to the host
+        if len(held) == L + 1:
+            cols = [np.stack(c) for c in zip(*held)]                      # [L+1][N]...
+            for e in range(N):
+                epi.add_episode({"observation": cols[0][:, e], "action": cols[1][:, e], "reward": cols[2][:, e],
+                                 "discount": cols[3][:, e]})
+            del held[:]
+        if epi.episodes:
+            epi.sample(B)
+
+    for i in range(NSTEP + 1):                                            # warm-up: both stores become drawable
+        vec.add(*rows[i & 3], first)
+    for i in range(20):
+        vec_step(i)
+    for i in range(L + 2):
+        epi_step(i)
+    del held[:]
+    n_epi = args.episodes * (L + 1)                                       # whole episodes: every add_episode is inside
+    res = {"vec_dev": [], "vec_wall": [], "epi_wall": []}
+    for _ in range(args.repeats):
+        d, w = timed(vec_step, args.steps)
+        res["vec_dev"].append(d)
+        res["vec_wall"].append(w)
+        res["epi_wall"].append(timed(epi_step, n_epi)[1])
+    print(f"N={N:5d}  vec     add()+sample({B}) per environment step: device-event {spread(res['vec_dev'])}   host wall "
+          f"{spread(res['vec_wall'])}   ({args.steps} steps x {args.repeats})", flush=True)
+    print(f"N={N:5d}  episode .cpu() + add_episode every {L} steps + sample({B}), per environment step: host wall "
+          f"{spread(res['epi_wall'])}   ({n_epi} steps x {args.repeats})", flush=True)
+    mid = args.repeats // 2
+    print(f"N={N:5d}  episode / vec (host wall): {sorted(res['epi_wall'])[mid] / sorted(res['vec_wall'])[mid]:.1f}", flush=True)
+
+
+def updates(args):
+    N, Fd, H = 16, 50, 1024
+    torch.manual_seed(0)
+    ag = drqv2.DrQV2Agent(OBS, (A,), "cuda", 1e-4, Fd, H, 0.01, 2000, 1, "linear(1.0,0.1,500000)", 0.3, False)
+    enc, actor, critic = synth.make_weights(9, A, Fd, H, 0)
+    ag.encoder.load_state_dict(enc)
+    ag.actor.load_state_dict(actor)
+    ag.critic.load_state_dict(critic)
+    ag.critic_target.load_state_dict(critic)
+    rows = pool_rows(N)
+    first = torch.zeros(N, dtype=torch.bool, device="cuda")
+    vec = VecDeviceReplay(SLOTS // N, N, OBS, A, NSTEP, 0.99, "cuda", seed=1)
+    epi = DeviceReplay(SLOTS, OBS, A, NSTEP, 0.99, "cuda", seed=1, indexed=True)
+    for i in range(200):
+        vec.add(*rows[i & 3], first)
+    r = np.random.RandomState(0)
+    for e in range(8):
+        epi.add_episode({"observation": r.randint(0, 256, (501,) + OBS).astype(np.uint8),
+                         "action": r.uniform(-1, 1, (501, A)).astype(np.float32),
+                         "reward": r.rand(501, 1).astype(np.float32), "discount": np.ones((501, 1), np.float32)})
+    vec.batch_size = epi.batch_size = B
+    it_vec, it_epi = iter(vec), iter(epi)
+
+    def vec_update(i):
+        vec.add(*rows[i & 3], first)
+        ag.update(it_vec, i)
+
+    paths = {"vec (add + update)": vec_update, "episode (update)": lambda i: ag.update(it_epi, i)}
+    for fn in paths.values():
+        for i in range(20):
+            fn(i)
+    res = {k: [] for k in paths}
+    for _ in range(args.repeats):
+        for k, fn in paths.items():
+            res[k].append(timed(fn, args.updates))
+    for k, v in res.items():
+        print(f"update B={B} fed by {k:20s}: device-event {spread([x[0] for x in v])}   host wall "
+              f"{spread([x[1] for x in v])}   ({args.updates} updates x {args.repeats}, alternated)", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--episodes", type=int, default=3, help="episode lengths per repeat of the episode path")
+    ap.add_argument("--updates", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--episode-len", type=int, default=16)
+    ap.add_argument("--envs", default="16,256,1024")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    for N in (int(x) for x in args.envs.split(",")):
+        collection(N, args)
+        torch.cuda.empty_cache()
+    updates(args)
+
+
+if __name__ == "__main__":
+    main()
