@@ -10,44 +10,15 @@
 // Nothing here talks to another workgroup; that would need agent scope.  Plain C++, vector stores, no atomics.
 // An inner node is always recomputed as tree[2k] + tree[2k+1], never adjusted by a difference: it cannot drift.
 #include "common.h"
+#include "per_tree.h"
 #include "../../include/drqv2_hip.h"
 
 namespace {
-
-constexpr int kPerThreads = 1024;
-
-inline bool pow2(long x) { return x > 0 && (x & (x - 1)) == 0; }
-
-// tree[k] = tree[2k] + tree[2k+1] for the ancestors of the leaf nodes [a, b], level by level up to the root
-__device__ __forceinline__ void per_rebuild_range(double* tree, long a, long b) {
-  while (a > 1) {
-    a >>= 1;
-    b >>= 1;
-    __syncthreads();
-    for (long k = a + threadIdx.x; k <= b; k += kPerThreads) tree[k] = tree[2 * k] + tree[2 * k + 1];
-  }
-}
 
 __global__ __launch_bounds__(kPerThreads) void per_fill_kernel(double* tree, long L, long lo, long hi, int mode) {
   const double v = mode ? tree[0] : 0.0;
   for (long s = lo + threadIdx.x; s < hi; s += kPerThreads) tree[L + s] = v;
   per_rebuild_range(tree, L + lo, L + hi - 1);
-}
-
-// block-wide maximum of non-negative doubles; every thread gets it
-__device__ __forceinline__ double per_block_max(double v, double* sm) {
-  __syncthreads();
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kPerThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + o]);
-    __syncthreads();
-  }
-  return sm[0];
-}
-
-__device__ __forceinline__ double per_weight(double leaf, double total, double n_valid, double beta) {
-  return pow(n_valid * leaf / total, -beta);
 }
 
 __global__ __launch_bounds__(kPerThreads) void per_sample_kernel(const double* tree, long L, const double* u, int B,
@@ -105,11 +76,7 @@ __global__ __launch_bounds__(kPerThreads) void per_update_kernel(double* tree, l
         if (j0 + jj > i && sp[jj] == my) win = false;
     }
     if (win) {
-      // a NaN or negative error counts as 0, an infinite one as the largest float: the root stays finite
-      double t = (double)td_abs[i];
-      if (!(t >= 0.0)) t = 0.0;
-      t = fmin(t, 3.4028234663852886e38);
-      const double v = pow(t + eps, alpha);
+      const double v = per_priority(td_abs[i], alpha, eps);
       tree[L + my] = v;
       vmax = fmax(vmax, v);
     }

@@ -21,7 +21,8 @@ host only counts: which slots can be drawn, how many there are, how many episode
 
 Vectorised collection (new: VecDeviceReplay, csrc/vecreplay.hip).  N environments stepped in lockstep write one row per
 step into a ring, straight from device tensors; episode boundaries are flags on the device, an n-step window ends at
-one, and the batches are the IndexedBatch above.  The episode store and everything it does are unchanged.
+one, and the batches are the IndexedBatch above.  The episode store and everything it does are unchanged.  With
+`priority_alpha` the ring carries the same sum tree over its slots, kept and drawn from entirely on the device.
 """
 import numpy as np
 import torch
@@ -71,6 +72,20 @@ class _PrioritizedTuple(PrioritizedBatch, tuple):
 
 class _PrioritizedIndexed(PrioritizedBatch, IndexedBatch):
     pass
+
+
+class _PrioritizedRing(_PrioritizedIndexed):
+    """What a prioritized VecDeviceReplay yields.  The stamp is the number of rows the ring held at the draw."""
+
+    def _per(self, store, pos, weights):
+        self.weights, self._store, self._pos, self._stamp = weights, store, pos, store.T
+        return self
+
+    def update_priorities(self, td_abs):
+        """td_abs: float32 [B] on the device -> leaf = (td_abs + eps)^alpha for every row whose position is still
+        drawable (one launch checks that on the device).  Nothing is written if `guard_rows` or more rows were added
+        since the draw: the batch's slots may then hold other transitions."""
+        self._store._update_priorities(self, td_abs)
 
 
 class BatchIterator:
@@ -347,13 +362,26 @@ class VecDeviceReplay:
     lo = max(1, T - rows + 1 + guard_rows): an IndexedBatch stays valid while fewer than `guard_rows` rows are added
     between its draw and the update that consumes it (the iterator's one batch of look-ahead needs 1).
     Every environment must hold a non-reset row among the drawable ones; a batch row drawn from one that does not comes
-    out with steps 0, reward 0 and discount 0.  Not here: prioritized sampling, episode files / resume, rows for a subset
-    of the environments."""
+    out with steps 0, reward 0 and discount 0.  Not here: episode files / resume, rows for a subset of the environments.
+
+    Prioritized sampling (`priority_alpha`, indexed batches only): a sum tree over the ring's slots in HBM, laid out and
+    drawn from like DeviceReplay's (csrc/per.hip), maintained without the host ever reading a flag.  A leaf is positive
+    exactly for the drawable, non-reset transitions.  add() makes a second launch (drq_vec_per_advance): the row that
+    became drawable starts at the largest priority ever written (1 before any update), its reset rows and the row
+    that stopped being drawable at 0.  sample() is one launch (drq_vec_per_sample) instead of drq_vec_sample: B
+    stratified draws from one random_sample(B) call, the windows and n-step sums of the uniform draw, and the weights
+    (n P(i))^-beta / max_batch with the nominal n = len(self) -- it cancels against the maximum.  The batch is a
+    PrioritizedBatch; its update_priorities(td_abs) is one launch (drq_vec_per_update) that writes only positions that
+    are still drawable, and nothing at all once `guard_rows` rows were added since the draw (so guard_rows >= 1 is
+    needed for priorities to be renewed at all).  If every drawable row is a reset row the tree is empty, which the host
+    cannot know: the batch then consists of steps-0 rows on slot(lo, 0) with weight 1."""
 
     K = 4       # candidates per batch row (the columns of the u table)
 
     def __init__(self, rows, num_envs, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=True,
-                 guard_rows=8):
+                 guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
+        """priority_alpha, priority_beta, priority_eps: as DeviceReplay's.  None = uniform sampling: no tree is
+        allocated and every draw and launch is what it was.  priority_beta is a plain attribute, read at every draw."""
         self.device = torch.device(device)
         self.obs_shape = tuple(int(s) for s in obs_shape)
         self.frame_bytes = int(np.prod(self.obs_shape))
@@ -379,6 +407,24 @@ class VecDeviceReplay:
         self._stage = None          # pinned + device staging of one row, for host inputs
         self._bufs = {}
         self._frames_out = {}
+        self.priority_alpha = None
+        self.priority_beta, self.priority_eps = float(priority_beta), float(priority_eps)
+        self.tree = None
+        if priority_alpha is not None:
+            a = float(priority_alpha)
+            if isinstance(priority_alpha, bool) or not (0.0 < a <= 1.0):
+                raise ValueError(f"priority_alpha {priority_alpha!r}: None or a float in (0, 1]")
+            if not (self.priority_beta >= 0.0) or not (0.0 < self.priority_eps < float("inf")):
+                raise ValueError("priority_beta must be >= 0 and priority_eps > 0")
+            if not self.indexed:
+                raise ValueError("prioritized sampling on the ring yields indexed batches: indexed=True required")
+            if self.device.type != "cuda":
+                raise _lib.DrqError("prioritized replay keeps its sum tree on the GPU: the HIP path has no CPU fallback")
+            self.priority_alpha = a
+            self.tree_leaves = 1 << max(0, S - 1).bit_length()      # smallest power of two >= rows * num_envs
+            self.tree = torch.zeros(2 * self.tree_leaves, dtype=torch.float64, device=dev)
+            self.tree[0] = 1.0      # running maximum leaf: what a row that becomes drawable starts at
+            self._pbufs = {}
 
     # ---- storage -------------------------------------------------------------------------
     def bounds(self):
@@ -449,7 +495,15 @@ class VecDeviceReplay:
             for t in src:           # a caller's tensor may be freed right after add(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())
-        self.T += 1
+            self.T += 1
+            if self.tree is not None:
+                # hi and lo move by at most one row per add: the new hi enters (its flags were written nstep - 1 adds
+                # ago, on this stream), the old lo leaves
+                lo, hi = self.bounds()
+                enter, leave = (hi if hi >= lo else -1), (lo - 1 if lo >= 2 else -1)
+                if enter >= 0 or leave >= 0:
+                    check(_lib.load().drq_vec_per_advance(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, N,
+                                                          self.T, enter, leave, self._stream()), "drq_vec_per_advance")
 
     # ---- sampling ------------------------------------------------------------------------
     def sample(self, batch_size):
@@ -460,6 +514,8 @@ class VecDeviceReplay:
         lo, hi = self.bounds()
         if hi < lo:
             raise _lib.DrqError(f"replay: {self.T} rows added, no drawable row yet (nstep {self.nstep})")
+        if self.tree is not None:
+            return self._sample_prioritized(int(batch_size), lo, hi)
         B, K, dev = int(batch_size), self.K, self.device
         bufs = self._bufs.get(B)
         if bufs is None:
@@ -494,6 +550,47 @@ class VecDeviceReplay:
             return IndexedBatch(self.frames, idx[0], act, rew, disc, idx[1])
         shp = (B,) + self.obs_shape
         return obs.view(shp), act, rew, disc, nxt.view(shp)
+
+    def _sample_prioritized(self, B, lo, hi):
+        """One stratified draw on the device: u ~ U[0,1)^B from the store's RandomState (one random_sample call per
+        batch) -> drq_vec_per_sample.  Returns a PrioritizedBatch that is an IndexedBatch."""
+        dev = self.device
+        bufs = self._pbufs.get(B)
+        if bufs is None:
+            # four sets used in turn, like sample()'s and for its reason
+            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
+                          torch.empty((B,), dtype=torch.int32, device=dev), f(B),
+                          torch.empty((B,), dtype=torch.float64, device=dev),
+                          torch.empty((B,), dtype=torch.float64).pin_memory())
+            bufs = [mk(), mk(), mk(), mk(), 0]
+            self._pbufs = {B: bufs}
+        idx, act, rew, disc, steps, w, u, host = bufs[bufs[4]]
+        bufs[4] = (bufs[4] + 1) & 3
+        host.numpy()[:] = self.rng.random_sample(B)
+        u.copy_(host, non_blocking=True)
+        with torch.cuda.device(dev):
+            check(_lib.load().drq_vec_per_sample(ptr(self.tree), self.tree_leaves, ptr(self.first), ptr(self.action),
+                                                 ptr(self.reward), ptr(self.discount), self.R, self.N, self.A, self.T, lo, hi,
+                                                 ptr(u), B, self.nstep, self.gamma, float(self.priority_beta), ptr(idx),
+                                                 ptr(act), ptr(rew), ptr(disc), ptr(steps), ptr(w), self._stream()),
+                  "drq_vec_per_sample")
+        self.last_steps, self.last_index = steps, idx
+        return _PrioritizedRing(self.frames, idx[0], act, rew, disc, idx[1])._per(self, idx[2], w)
+
+    def _update_priorities(self, batch, td_abs):
+        if self.T - batch._stamp >= self.guard_rows:
+            return                      # the batch's slots may hold other transitions: see _PrioritizedRing
+        pos = batch._pos
+        B = pos.numel()
+        if (not torch.is_tensor(td_abs) or td_abs.dtype != torch.float32 or td_abs.device != pos.device
+                or td_abs.numel() != B or not td_abs.is_contiguous()):
+            raise _lib.DrqError(f"update_priorities(): contiguous float32 [{B}] on {pos.device} required")
+        lo, hi = self.bounds()
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_per_update(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N, self.T,
+                                                 lo, hi, ptr(pos), ptr(td_abs), B, self.priority_alpha, self.priority_eps,
+                                                 self._stream()), "drq_vec_per_update")
 
     def __iter__(self):
         return BatchIterator(lambda: self.sample(self.batch_size))

@@ -380,6 +380,53 @@ int drq_vec_sample(const uint8_t* first, const float* action, const float* rewar
                    long* idx_out, float* act_out, float* rew_out, float* disc_out, int* steps_out, const uint8_t* frames,
                    uint8_t* obs_out, uint8_t* next_obs_out, drq_stream_t stream);
 
+/* ---- prioritized step-major replay: proportional prioritization (the definitions of "proportional prioritized replay"
+ * above) on the ring of "step-major replay".  New functionality; these definitions are the contract.
+ * `tree` is the sum tree of drq_per_*: double [2 L], L the smallest power of two >= R N, the leaf of slot s at tree[L + s],
+ * every inner node recomputed as tree[2k] + tree[2k+1], never adjusted; tree[0] the largest leaf a priority update ever
+ * wrote (the caller initialises it to 1.0, and every leaf to 0).  T is the number of rows added so far, lo .. hi the
+ * drawable rows (hi = T - nstep, lo = max(1, T - R + 1 + guard_rows)).  Ring row r holds the absolute row
+ * t(r) = T-1 - ((T-1-r) mod R); a slot p is DRAWABLE if 0 <= p < R N, lo <= t(p / N) <= hi and first[p] == 0.
+ * Invariant the caller keeps by calling drq_vec_per_advance after every drq_vec_add: a leaf is > 0 iff its slot is
+ * drawable (eps > 0); every other leaf -- the padding above R N, guard rows, head rows, reset rows -- is exactly 0.
+ * Each entry is one launch of one workgroup of 1,024 threads, plain loads and stores, no atomics; the caller orders
+ * them, and drq_vec_add, on one stream.  Any N and any B.
+ *
+ * drq_vec_per_advance: an add moves hi and lo by at most one row.  enter_t = the absolute row that became drawable (the
+ *   new hi, if hi >= lo), leave_t = the one that stopped being (the old lo, if lo advanced), -1 = none; the caller knows
+ *   both from T, R, nstep and guard_rows alone.  The N leaves of row enter_t become first ? 0 : tree[0] (the flags were
+ *   written by the drq_vec_add of that row, nstep - 1 adds earlier), those of row leave_t 0, and the ancestors of both
+ *   ranges are recomputed.  Both -1: DRQ_OK without a launch.
+ *   DRQ_EARG: null pointers, L no power of two or < R N, R, N, T <= 0, enter_t / leave_t outside [-1, T) or no longer in
+ *   the ring (< T - R), enter_t == leave_t >= 0.
+ * drq_vec_per_sample: B stratified draws, u double [B] in [0, 1): drq_per_sample's descent, verbatim, to a slot p;
+ *   e = p % N, t = t(p / N); from there drq_vec_sample's outputs for the transition (t, e): the window k cut at the
+ *   first reset row, idx_out int64 [3][B] = the slots of (t-1, e), (t+k-1, e), (t, e), act_out [B][A], rew_out, disc_out
+ *   [B] in the same float32 operation order, steps_out int32 [B] = k.  weight_out float [B] =
+ *   (n leaf / tree[1])^(-beta) divided by the largest such value of the batch (evaluated in double, rounded once, the
+ *   largest exactly 1), n = (hi - lo + 1) N: the nominal count, reset rows included -- it cancels against the maximum,
+ *   so no count of the valid positions is needed.  The tree is not written.  An empty tree (tree[1] == 0: every
+ *   drawable row is a reset row, which the host cannot know) gives every batch row all three indices and the action row
+ *   of slot(lo, 0), steps = 0, reward = 0, discount = 0, weight = 1; so does a row whose descent ends on a slot that is
+ *   not drawable (a broken invariant).  Nothing is read out of range, no NaN.
+ *   DRQ_EARG, nothing written: null pointers, L no power of two or < R N, R, N, A, B, nstep <= 0, beta < 0, lo < 1,
+ *   hi < lo, hi - lo + 1 + nstep > R, hi + nstep > T, lo - 1 < T - R.
+ * drq_vec_per_update: leaf[pos[i]] = pow(clamp(td_abs[i]) + eps, alpha) as drq_per_update (NaN / negative -> 0,
+ *   inf -> FLT_MAX; the row with the HIGHEST index of a repeated position wins), but ONLY where pos[i] is drawable at
+ *   the time of the call: a row that is not writes nothing and does not count for tree[0].  Then the ancestors of every
+ *   pos[i] in [0, L) are recomputed (those of a skipped row get the sums they held) and tree[0] = max(tree[0], the
+ *   leaves written).  The caller drops a whole batch once its slots may have been overwritten (guard_rows rows added).
+ *   DRQ_EARG: null pointers, L no power of two or < R N, R, N, B <= 0, alpha <= 0, eps < 0, lo < 1, hi < lo,
+ *   hi - lo + 2 > R, hi + 1 > T, lo - 1 < T - R. */
+int drq_vec_per_advance(double* tree, long L, const uint8_t* first, long R, long N, long T, long enter_t, long leave_t,
+                        drq_stream_t stream);
+int drq_vec_per_sample(const double* tree, long L, const uint8_t* first, const float* action, const float* reward,
+                       const float* discount, long R, long N, int A, long T, long lo, long hi, const double* u, int B,
+                       int nstep, float gamma, double beta, long* idx_out, float* act_out, float* rew_out,
+                       float* disc_out, int* steps_out, float* weight_out, drq_stream_t stream);
+int drq_vec_per_update(double* tree, long L, const uint8_t* first, long R, long N, long T, long lo, long hi,
+                       const long* pos, const float* td_abs, int B, double alpha, double eps, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,

@@ -17,6 +17,15 @@ The inputs of a step come from a pool of four pre-generated device rows; nothing
 except what the stores allocate themselves.
 
   python tools/vec_replay_bench.py [--steps 2000] [--repeats 3] [--episode-len 16] [--episodes 3] [--envs 16,256,1024] [--updates 200]
+
+--priority-alpha 0.6 measures prioritized sampling on the ring instead (VecDeviceReplay(priority_alpha=...)): for every N
+two rings of the same shape, uniform and prioritized, alternated inside every repeat of the same process -- add() +
+sample(256) per environment step (prioritized: drq_vec_add + drq_vec_per_advance, then drq_vec_per_sample in place of
+drq_vec_sample), and update() with one add() of N rows in front of it (prioritized: the weighted loss and one
+drq_vec_per_update more).  Same steps, updates, repeats and the same two figures per line as above.  No environment is
+ever reset here, so every drawable slot carries a priority.
+
+  python tools/vec_replay_bench.py --priority-alpha 0.6 [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--updates 200]
 """
 import argparse
 import os
@@ -108,8 +117,8 @@ def collection(N, args):
     print(f"N={N:5d}  episode / vec (host wall): {sorted(res['epi_wall'])[mid] / sorted(res['vec_wall'])[mid]:.1f}", flush=True)
 
 
-def updates(args):
-    N, Fd, H = 16, 50, 1024
+def make_agent():
+    Fd, H = 50, 1024
     torch.manual_seed(0)
     ag = drqv2.DrQV2Agent(OBS, (A,), "cuda", 1e-4, Fd, H, 0.01, 2000, 1, "linear(1.0,0.1,500000)", 0.3, False)
     enc, actor, critic = synth.make_weights(9, A, Fd, H, 0)
@@ -117,6 +126,54 @@ def updates(args):
     ag.actor.load_state_dict(actor)
     ag.critic.load_state_dict(critic)
     ag.critic_target.load_state_dict(critic)
+    return ag
+
+
+def prioritized(N, args, ag):
+    """uniform ring against prioritized ring at N environments: collection steps, then updates, alternated per repeat"""
+    rows = pool_rows(N)
+    first = torch.zeros(N, dtype=torch.bool, device="cuda")
+    mk = lambda alpha: VecDeviceReplay(max(32, SLOTS // N), N, OBS, A, NSTEP, 0.99, "cuda", seed=1, priority_alpha=alpha)
+    rings = {"uniform": mk(None), "prioritized": mk(args.priority_alpha)}
+    its = {}
+    for k, ring in rings.items():
+        ring.batch_size = B
+        for i in range(NSTEP + 1 + 20):
+            ring.add(*rows[i & 3], first)
+        its[k] = iter(ring)
+
+    def step(ring):
+        def fn(i):
+            ring.add(*rows[i & 3], first)
+            ring.sample(B)
+        return fn
+
+    def update(k):
+        def fn(i):
+            rings[k].add(*rows[i & 3], first)
+            ag.update(its[k], i)
+        return fn
+
+    for k in rings:
+        for i in range(20):
+            step(rings[k])(i)
+            update(k)(i)
+    res = {(what, k): [] for what in ("step", "update") for k in rings}
+    for _ in range(args.repeats):
+        for k in rings:
+            res["step", k].append(timed(step(rings[k]), args.steps))
+        for k in rings:
+            res["update", k].append(timed(update(k), args.updates))
+    for (what, k), v in res.items():
+        label = f"add()+sample({B}) per environment step" if what == "step" else f"add() + update B={B}"
+        n = args.steps if what == "step" else args.updates
+        print(f"N={N:5d}  {k:11s} ring  {label}: device-event {spread([x[0] for x in v])}   host wall "
+              f"{spread([x[1] for x in v])}   ({n} x {args.repeats}, alternated)", flush=True)
+
+
+def updates(args):
+    N = 16
+    ag = make_agent()
     rows = pool_rows(N)
     first = torch.zeros(N, dtype=torch.bool, device="cuda")
     vec = VecDeviceReplay(SLOTS // N, N, OBS, A, NSTEP, 0.99, "cuda", seed=1)
@@ -156,9 +213,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--episode-len", type=int, default=16)
     ap.add_argument("--envs", default="16,256,1024")
+    ap.add_argument("--priority-alpha", type=float, default=None,
+                    help="measure the uniform ring against the prioritized one instead of against the episode store")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    if args.priority_alpha is not None:
+        ag = make_agent()
+        for N in (int(x) for x in args.envs.split(",")):
+            prioritized(N, args, ag)
+            torch.cuda.empty_cache()
+        return
     for N in (int(x) for x in args.envs.split(",")):
         collection(N, args)
         torch.cuda.empty_cache()
