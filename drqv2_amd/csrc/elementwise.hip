@@ -6,6 +6,7 @@
 // All reductions are fixed-order (no float atomics): results are run-to-run bit-stable.
 #include "common.h"
 #include "internal.h"
+#include "replay_device.h"
 
 namespace {
 
@@ -1077,7 +1078,8 @@ __global__ __launch_bounds__(1024) void qout_bwd_kernel(QOutBwdArgs a) {
 // ------------------------------------------------------------------------------------------------
 // Replay sampling on the device (replay_buffer.py:142-160): batch row b is transition pos[b] of a flat store of
 // steps (episodes contiguous): obs = frame[pos-1], next_obs = frame[pos+nstep-1], action = action[pos], and the
-// n-step return in the reference's float32 order:  reward += discount*r[pos+i];  discount *= d[pos+i]*gamma.
+// n-step return in the reference's float32 order:  reward += discount*r[pos+i];  discount *= d[pos+i]*gamma
+// (nstep_sum, replay_device.h).
 // blockIdx.y = 0 / 1: obs / next_obs frame copy (16-byte pieces); blockIdx.y = 2: the scalars of 256 rows.
 // ------------------------------------------------------------------------------------------------
 struct NstepArgs {
@@ -1097,7 +1099,6 @@ struct NstepArgs {
 };
 
 __global__ void nstep_gather_kernel(NstepArgs a) {
-#pragma clang fp contract(off)
   const int which = a.obs ? blockIdx.y : 2;         // no output frames: the scalars only (grid.y == 1)
   if (which < 2) {
     const int b = blockIdx.x;
@@ -1113,17 +1114,8 @@ __global__ void nstep_gather_kernel(NstepArgs a) {
   if (b >= a.B) return;
   const long p = a.pos[b];
   for (int j = 0; j < a.A; ++j) a.act_out[(long)b * a.A + j] = a.action[p * a.A + j];
-  float r = 0.f, d = 1.f;
-  for (int i = 0; i < a.nstep; ++i) {
-    // one rounding per operation: the product is pinned in a register before the add (the packed-math
-    // vectoriser otherwise emits v_pk_fma_f32 here, contract(off) notwithstanding)
-    float t = d * a.reward[p + i];
-    asm volatile("" : "+v"(t));
-    r = r + t;
-    float gd = a.discount[p + i] * a.gamma;
-    asm volatile("" : "+v"(gd));
-    d = d * gd;
-  }
+  float r, d;
+  nstep_sum(a.reward, a.discount, a.gamma, a.nstep, [p](int i) { return p + i; }, r, d);
   a.rew_out[b] = r;
   a.disc_out[b] = d;
 }

@@ -18,16 +18,18 @@
 //              every other leaf -- padding above R N, guard rows, head rows, reset rows -- is exactly 0
 //   advance    an add() moves hi and lo by at most one row: the leaves of the row that entered become
 //              first ? 0 : tree[0], those of the row that left 0, the ancestors of both ranges are recomputed
-//   draw       per.hip's stratified descent to a slot p; e = p % N, ring row r = p / N, absolute row
-//              t = T-1 - ((T-1-r) mod R); from there vec_sample_kernel's scalar block: window, indices, action,
-//              n-step reward / discount in the same float32 order with the same pinned products.  Weights
+//   draw       the stratified descent to a slot p; e = p % N, ring row r = p / N, absolute row
+//              t = T-1 - ((T-1-r) mod R); from there the uniform draw's window and batch row.  Weights
 //              (n leaf / tree[1])^-beta / max_batch with the nominal n = (hi-lo+1) N, which cancels against the maximum
 //   update     leaf(p) = (clamp(td_abs) + eps)^alpha only where p is still drawable (checked here from T, lo, hi and
 //              first: the host never reads a flag); the highest row of a repeated position wins
 // The host never learns whether the tree is empty (every drawable row a reset row): such a draw comes out as the
 // uniform path's "no drawable transition" rows, all indices on slot(lo, 0), steps 0, reward 0, discount 0, weight 1.
+//
+// What the two draws share (ring geometry, window, batch row, n-step sum) and what the tree entries share with per.hip
+// (descent, weight normalisation, priority update, ranged rebuild) is one copy each, in replay_device.h.
 #include "common.h"
-#include "per_tree.h"
+#include "replay_device.h"
 #include "../../include/drqv2_hip.h"
 
 namespace {
@@ -66,71 +68,54 @@ __global__ __launch_bounds__(256) void vec_add_kernel(VecAddArgs a) {
 }
 
 struct VecSampleArgs {
-  const uint8_t* first;
-  const float* action;
-  const float* reward;
-  const float* discount;
+  RingBatch r;      // r.g.T is not known to this entry (0)
   const double* u;
   const uint8_t* frames;
-  long* idx_out;
-  float* act_out;
-  float* rew_out;
-  float* disc_out;
-  int* steps_out;
   uint8_t* obs_out;
   uint8_t* next_obs_out;
-  long R, N, lo, hi, frame_bytes;
-  int A, B, K, nstep;
-  float gamma;
+  long frame_bytes;
+  int K;
 };
-
-__device__ __forceinline__ long vec_slot(const VecSampleArgs& a, long t, long e) { return (t % a.R) * a.N + e; }
 
 // The transition of batch row b: absolute row t and environment e; returns the window length k (1 .. nstep), or 0 when
 // the environment of candidate 0 holds no drawable transition (then t, e are candidate 0's).
 __device__ __forceinline__ int vec_choose(const VecSampleArgs& a, int b, long& t, long& e) {
-  const long rows = a.hi - a.lo + 1;
-  const long M = rows * a.N;
-  long t0 = a.lo, e0 = 0;
+  const VecRing& g = a.r.g;
+  const long rows = g.hi - g.lo + 1;
+  const long M = rows * g.N;
+  long t0 = g.lo, e0 = 0;
   bool found = false;
   for (int j = 0; j < a.K && !found; ++j) {
     long c = (long)(a.u[(long)b * a.K + j] * (double)M);
     c = c < 0 ? 0 : (c > M - 1 ? M - 1 : c);     // u is in [0, 1): the lower clamp only keeps a bad table in range
-    t = a.lo + c / a.N;
-    e = c % a.N;
+    t = g.lo + c / g.N;
+    e = c % g.N;
     if (j == 0) { t0 = t; e0 = e; }
-    found = a.first[vec_slot(a, t, e)] == 0;
+    found = g.first[ring_slot(g, t, e)] == 0;
   }
   if (!found) {
     // every candidate is a reset row: walk candidate 0's environment t0+1 .. hi, lo .. t0-1
     e = e0;
     for (long i = 1; i < rows && !found; ++i) {
-      t = a.lo + (t0 - a.lo + i) % rows;
-      found = a.first[vec_slot(a, t, e)] == 0;
+      t = g.lo + (t0 - g.lo + i) % rows;
+      found = g.first[ring_slot(g, t, e)] == 0;
     }
     if (!found) {
       t = t0;
       return 0;
     }
   }
-  int k = a.nstep;
-  for (int i = 1; i < a.nstep; ++i)
-    if (a.first[vec_slot(a, t + i, e)]) {
-      k = i;
-      break;
-    }
-  return k;
+  return ring_window(g, t, e, a.r.nstep);
 }
 
 __global__ __launch_bounds__(256) void vec_sample_kernel(VecSampleArgs a) {
-#pragma clang fp contract(off)
   const int which = a.obs_out ? blockIdx.y : 2;     // no output frames: the scalars only (grid.y == 1)
   if (which < 2) {
     const int b = blockIdx.x;
-    if (b >= a.B) return;
+    if (b >= a.r.B) return;
     long t, e;
     const int k = vec_choose(a, b, t, e);
-    const long p = k == 0 ? vec_slot(a, t, e) : vec_slot(a, which == 0 ? t - 1 : t + k - 1, e);
+    const long p = ring_slot(a.r.g, k == 0 ? t : (which == 0 ? t - 1 : t + k - 1), e);
     const uint4* src = reinterpret_cast<const uint4*>(a.frames + p * a.frame_bytes);
     uint4* dst = reinterpret_cast<uint4*>((which == 0 ? a.obs_out : a.next_obs_out) + (long)b * a.frame_bytes);
     const long n16 = a.frame_bytes >> 4;
@@ -138,53 +123,13 @@ __global__ __launch_bounds__(256) void vec_sample_kernel(VecSampleArgs a) {
     return;
   }
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.B) return;
+  if (b >= a.r.B) return;
   long t, e;
   const int k = vec_choose(a, b, t, e);
-  const long p = vec_slot(a, t, e);
-  a.idx_out[b] = k == 0 ? p : vec_slot(a, t - 1, e);
-  a.idx_out[(long)a.B + b] = k == 0 ? p : vec_slot(a, t + k - 1, e);
-  a.idx_out[2L * a.B + b] = p;
-  a.steps_out[b] = k;
-  for (int j = 0; j < a.A; ++j) a.act_out[(long)b * a.A + j] = a.action[p * a.A + j];
-  // nstep_gather_kernel's accumulation over k rows of the ring: one rounding per operation, the products pinned in
-  // registers before the add / multiply that consumes them (see there)
-  float r = 0.f, d = 1.f;
-  for (int i = 0; i < k; ++i) {
-    const long q = vec_slot(a, t + i, e);
-    float x = d * a.reward[q];
-    asm volatile("" : "+v"(x));
-    r = r + x;
-    float gd = a.discount[q] * a.gamma;
-    asm volatile("" : "+v"(gd));
-    d = d * gd;
-  }
-  a.rew_out[b] = r;
-  a.disc_out[b] = k == 0 ? 0.f : d;
+  ring_emit_row(a.r, b, t, e, k);
 }
 
 // ---- prioritized sampling: the sum tree over the ring's slots -----------------------------------------------------
-struct VecRing {
-  const uint8_t* first;
-  long R, N, T, lo, hi;
-};
-
-__device__ __forceinline__ long ring_slot(const VecRing& g, long t, long e) { return (t % g.R) * g.N + e; }
-
-// the absolute row ring row r holds with T rows added: the newest t <= T-1 with t mod R == r (negative: never written)
-__device__ __forceinline__ long ring_row_of(const VecRing& g, long r) {
-  long d = (g.T - 1 - r) % g.R;
-  if (d < 0) d += g.R;
-  return g.T - 1 - d;
-}
-
-// slot p holds a drawable transition: inside the ring, its row t among lo .. hi, no reset row
-__device__ __forceinline__ bool ring_drawable(const VecRing& g, long p, long& t) {
-  if (p < 0 || p >= g.R * g.N) return false;
-  t = ring_row_of(g, p / g.N);
-  return t >= g.lo && t <= g.hi && g.first[p] == 0;
-}
-
 __global__ __launch_bounds__(kPerThreads) void vec_per_advance_kernel(double* tree, long L, const uint8_t* first, long N,
                                                                       long enter_row, long leave_row) {
   const double v = tree[0];
@@ -201,143 +146,53 @@ __global__ __launch_bounds__(kPerThreads) void vec_per_advance_kernel(double* tr
     a[1] = L + s0;
     b[1] = L + s0 + N - 1;
   }
-  // the ancestors of both ranges, level by level.  Where the ranges meet further up, two threads store the same sum of
-  // the same children (as the rows of per_update_kernel that share a node do)
-  for (long w = L; w > 1; w >>= 1) {
-    __syncthreads();
-    for (int q = 0; q < 2; ++q) {
-      if (a[q] < 0) continue;
-      a[q] >>= 1;
-      b[q] >>= 1;
-      for (long k = a[q] + threadIdx.x; k <= b[q]; k += kPerThreads) tree[k] = tree[2 * k] + tree[2 * k + 1];
-    }
-  }
+  per_rebuild_ranges(tree, L, a, b);
 }
 
 struct VecPerSampleArgs {
+  RingBatch r;
   const double* tree;
-  const float* action;
-  const float* reward;
-  const float* discount;
   const double* u;
-  long* idx_out;
-  float* act_out;
-  float* rew_out;
-  float* disc_out;
-  int* steps_out;
   float* weight_out;
-  VecRing g;
   long L;
-  int A, B, nstep;
-  float gamma;
   double beta;
 };
 
 __global__ __launch_bounds__(kPerThreads) void vec_per_sample_kernel(VecPerSampleArgs a) {
-#pragma clang fp contract(off)
-  __shared__ double sm[kPerThreads];
-  const VecRing& g = a.g;
+  const VecRing& g = a.r.g;
   const double total = a.tree[1];
   const double n = (double)((g.hi - g.lo + 1) * g.N);     // nominal count, reset rows included: cancels in w / wmax
   double wmax = 0.0;
-  for (int b = threadIdx.x; b < a.B; b += kPerThreads) {
-    // per_sample_kernel's descent: row b draws from its own stratum of the total mass
-    double m = ((double)b + a.u[b]) / (double)a.B * total;
-    long k = 1;
-    while (k < a.L) {
-      const double left = a.tree[2 * k], right = a.tree[2 * k + 1];
-      if ((m < left && left > 0.0) || right == 0.0) {
-        k = 2 * k;
-      } else {
-        m -= left;
-        k = 2 * k + 1;
-      }
-    }
-    long p = k - a.L, t = g.lo, e = 0;
+  for (int b = threadIdx.x; b < a.r.B; b += kPerThreads) {
+    // row b draws from its own stratum of the total mass
+    const long k = per_descend(a.tree, a.L, ((double)b + a.u[b]) / (double)a.r.B * total);
+    long t = g.lo, e = 0;
     int steps = 0;
     // an empty tree (total == 0) draws nothing; with the invariant kept a positive root never ends on a slot that is
     // not drawable, and should one arrive all the same the row is the empty one too: nothing is read out of range
-    if (total > 0.0 && ring_drawable(g, p, t)) {
-      e = p % g.N;
-      steps = a.nstep;
-      for (int i = 1; i < a.nstep; ++i)
-        if (g.first[ring_slot(g, t + i, e)]) {
-          steps = i;
-          break;
-        }
+    if (total > 0.0 && ring_drawable(g, k - a.L, t)) {
+      e = (k - a.L) % g.N;
+      steps = ring_window(g, t, e, a.r.nstep);
     } else {
       t = g.lo;
-      p = ring_slot(g, t, 0);
     }
-    // from here vec_sample_kernel's scalar block
-    a.idx_out[b] = steps == 0 ? p : ring_slot(g, t - 1, e);
-    a.idx_out[(long)a.B + b] = steps == 0 ? p : ring_slot(g, t + steps - 1, e);
-    a.idx_out[2L * a.B + b] = p;
-    a.steps_out[b] = steps;
-    for (int j = 0; j < a.A; ++j) a.act_out[(long)b * a.A + j] = a.action[p * a.A + j];
-    float r = 0.f, d = 1.f;
-    for (int i = 0; i < steps; ++i) {
-      const long q = ring_slot(g, t + i, e);
-      float x = d * a.reward[q];
-      asm volatile("" : "+v"(x));
-      r = r + x;
-      float gd = a.discount[q] * a.gamma;
-      asm volatile("" : "+v"(gd));
-      d = d * gd;
-    }
-    a.rew_out[b] = r;
-    a.disc_out[b] = steps == 0 ? 0.f : d;
+    ring_emit_row(a.r, b, t, e, steps);
     wmax = fmax(wmax, steps > 0 ? per_weight(a.tree[k], total, n, a.beta) : 1.0);
   }
-  wmax = per_block_max(wmax, sm);
-  // second pass: the same expression on the same operands gives the same bits, so the largest weight is exactly 1
-  for (int b = threadIdx.x; b < a.B; b += kPerThreads) {
-    const long pos = a.idx_out[2L * a.B + b];   // this thread's own stores
-    const double w = a.steps_out[b] > 0 ? per_weight(a.tree[a.L + pos], total, n, a.beta) : 1.0;
-    a.weight_out[b] = (float)(w / wmax);
-  }
+  per_normalise(wmax, a.r.B, [&](int b) {
+    const long pos = a.r.idx_out[2L * a.r.B + b];   // this thread's own stores
+    return a.r.steps_out[b] > 0 ? per_weight(a.tree[a.L + pos], total, n, a.beta) : 1.0;
+  }, a.weight_out);
 }
 
 __global__ __launch_bounds__(kPerThreads) void vec_per_update_kernel(double* tree, long L, VecRing g, const long* pos,
                                                                      const float* td_abs, int B, double alpha,
                                                                      double eps) {
-  __shared__ double sm[kPerThreads];
-  __shared__ long sp[kPerThreads];
-  double vmax = 0.0;
-  // leaves, as per_update_kernel writes them (the highest row of a repeated position wins, whatever the schedule), but
   // only where the position is still drawable: its slot may have left the drawable rows since the batch was drawn
-  for (int i0 = 0; i0 < B; i0 += kPerThreads) {
-    const int i = i0 + threadIdx.x;
-    const long my = i < B ? pos[i] : -1;
-    long t = 0;
-    bool win = i < B && ring_drawable(g, my, t);
-    for (int j0 = i0; j0 < B; j0 += kPerThreads) {
-      __syncthreads();
-      sp[threadIdx.x] = j0 + (int)threadIdx.x < B ? pos[j0 + threadIdx.x] : -1;
-      __syncthreads();
-      const int n = min(kPerThreads, B - j0);
-      for (int jj = 0; jj < n; ++jj)
-        if (j0 + jj > i && sp[jj] == my) win = false;
-    }
-    if (win) {
-      const double v = per_priority(td_abs[i], alpha, eps);
-      tree[L + my] = v;
-      vmax = fmax(vmax, v);
-    }
-  }
-  // ancestors: every row whose position lies in the tree recomputes the node above its leaf at each level, a skipped
-  // one too (its nodes get the sums they held); rows that share a node store the same sum
-  for (int d = 1; (L >> d) >= 1; ++d) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < B; i += kPerThreads) {
-      const long my = pos[i];
-      if (my < 0 || my >= L) continue;
-      const long k = (L + my) >> d;
-      tree[k] = tree[2 * k] + tree[2 * k + 1];
-    }
-  }
-  vmax = per_block_max(vmax, sm);
-  if (threadIdx.x == 0) tree[0] = fmax(tree[0], vmax);
+  per_update(tree, L, pos, td_abs, B, alpha, eps, [&g](long p) {
+    long t;
+    return ring_drawable(g, p, t);
+  });
 }
 
 // the arguments every tree entry shares: the tree covers the ring's slots
@@ -385,8 +240,9 @@ DRQ_API int drq_vec_sample(const uint8_t* first, const float* action, const floa
   const int given = (frames != nullptr) + (obs_out != nullptr) + (next_obs_out != nullptr);
   if (given != 0 && given != 3) return DRQ_EARG;
   if (((uintptr_t)frames | (uintptr_t)obs_out | (uintptr_t)next_obs_out) & 15) return DRQ_EARG;
-  VecSampleArgs a{first, action, reward, discount, u, frames, idx_out, act_out, rew_out, disc_out, steps_out, obs_out,
-                  next_obs_out, R, N, lo, hi, frame_bytes, A, B, K, nstep, gamma};
+  VecSampleArgs a{RingBatch{VecRing{first, R, N, 0, lo, hi}, action, reward, discount, idx_out, act_out, rew_out, disc_out,
+                            steps_out, A, B, nstep, gamma},
+                  u, frames, obs_out, next_obs_out, frame_bytes, K};
   if (obs_out) hipLaunchKernelGGL(vec_sample_kernel, dim3(B, 3), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(vec_sample_kernel, dim3((B + 255) / 256, 1), dim3(256), 0, st, a);
   DRQ_LAUNCH_CHECK();
@@ -418,8 +274,9 @@ DRQ_API int drq_vec_per_sample(const double* tree, long L, const uint8_t* first,
     return DRQ_EARG;
   if (!ring_tree_ok(tree, L, first, R, N) || A <= 0 || B <= 0 || nstep <= 0 || !(beta >= 0.0)) return DRQ_EARG;
   if (!ring_bounds_ok(R, T, lo, hi, nstep)) return DRQ_EARG;
-  VecPerSampleArgs a{tree, action, reward, discount, u, idx_out, act_out, rew_out, disc_out, steps_out, weight_out,
-                     VecRing{first, R, N, T, lo, hi}, L, A, B, nstep, gamma, beta};
+  VecPerSampleArgs a{RingBatch{VecRing{first, R, N, T, lo, hi}, action, reward, discount, idx_out, act_out, rew_out,
+                               disc_out, steps_out, A, B, nstep, gamma},
+                     tree, u, weight_out, L, beta};
   hipLaunchKernelGGL(vec_per_sample_kernel, dim3(1), dim3(kPerThreads), 0, st, a);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;

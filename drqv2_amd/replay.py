@@ -56,13 +56,16 @@ class PrioritizedBatch:
     per-sample TD errors the loss launch leaves come back through update_priorities, all in stream order."""
 
     def _per(self, store, pos, weights):
-        self.weights, self._store, self._pos, self._stamp = weights, store, pos, store._placements
+        self.weights, self._store, self._pos, self._stamp = weights, store, pos, store._stamp_now()
         return self
 
     def update_priorities(self, td_abs):
-        """td_abs: float32 [B] on the device, the |TD error| of every row -> leaf = (td_abs + eps)^alpha.  Nothing is
-        written if the store has placed an episode since this batch was drawn: a position of this batch may then lie
-        in a newer episode, whose fresh priority must not be overwritten with an error of the evicted one."""
+        """td_abs: float32 [B] on the device, the |TD error| of every row -> leaf = (td_abs + eps)^alpha.
+        DeviceReplay: nothing is written if the store has placed an episode since this batch was drawn: a position of
+        this batch may then lie in a newer episode, whose fresh priority must not be overwritten with an error of the
+        evicted one.  VecDeviceReplay: only rows whose position is still drawable are written (one launch checks that on
+        the device), and nothing if `guard_rows` or more rows were added since the draw: the batch's slots may then hold
+        other transitions."""
         self._store._update_priorities(self, td_abs)
 
 
@@ -74,18 +77,61 @@ class _PrioritizedIndexed(PrioritizedBatch, IndexedBatch):
     pass
 
 
-class _PrioritizedRing(_PrioritizedIndexed):
-    """What a prioritized VecDeviceReplay yields.  The stamp is the number of rows the ring held at the draw."""
+def _rotating(cache, B, make):
+    """The next of the four buffer sets a store keeps for batches of B rows in `cache` (a dict: one batch size at a
+    time); make() builds one set.  Four sets, used in turn: the device tensors are written in stream order (no hazard),
+    but the pinned host staging of a set is overwritten by the HOST when batch k+4 is drawn, and its upload must have run
+    by then: StepEngine.update keeps at most two updates queued behind the running one (_throttle), so three batches
+    can be pending at most.  A consumer of its own must bound its run-ahead likewise (or use DeviceReplay.gather())."""
+    bufs = cache.get(B)
+    if bufs is None:
+        bufs = [make(), make(), make(), make(), 0]
+        cache.clear()
+        cache[B] = bufs
+    cur = bufs[bufs[4]]
+    bufs[4] = (bufs[4] + 1) & 3
+    return cur
 
-    def _per(self, store, pos, weights):
-        self.weights, self._store, self._pos, self._stamp = weights, store, pos, store.T
-        return self
 
-    def update_priorities(self, td_abs):
-        """td_abs: float32 [B] on the device -> leaf = (td_abs + eps)^alpha for every row whose position is still
-        drawable (one launch checks that on the device).  Nothing is written if `guard_rows` or more rows were added
-        since the draw: the batch's slots may then hold other transitions."""
-        self._store._update_priorities(self, td_abs)
+def _td_rows(pos, td_abs):
+    """B, with td_abs checked to be the |TD error| rows of the batch drawn at the device positions pos [B]"""
+    B = pos.numel()
+    if (not torch.is_tensor(td_abs) or td_abs.dtype != torch.float32 or td_abs.device != pos.device
+            or td_abs.numel() != B or not td_abs.is_contiguous()):
+        raise _lib.DrqError(f"update_priorities(): contiguous float32 [{B}] on {pos.device} required")
+    return B
+
+
+def _on_gpu(store, what):
+    if store.device.type != "cuda":
+        raise _lib.DrqError(f"{what} on the GPU: the HIP path has no CPU fallback")
+
+
+def _priority_args(store, priority_alpha, priority_beta, priority_eps):
+    """The priority arguments of a store's constructor, checked: sets the attributes of a uniform store (no tree) and
+    returns alpha as a float, or None for uniform sampling."""
+    store.priority_alpha = None
+    store.priority_beta, store.priority_eps = float(priority_beta), float(priority_eps)
+    store.tree = None
+    if priority_alpha is None:
+        return None
+    a = float(priority_alpha)
+    if isinstance(priority_alpha, bool) or not (0.0 < a <= 1.0):
+        raise ValueError(f"priority_alpha {priority_alpha!r}: None or a float in (0, 1]")
+    if not (store.priority_beta >= 0.0) or not (0.0 < store.priority_eps < float("inf")):
+        raise ValueError("priority_beta must be >= 0 and priority_eps > 0")
+    return a
+
+
+def _priority_tree(store, slots, alpha):
+    """makes `store` a prioritized one: the sum tree over `slots` slots, tree[0] (the running maximum leaf: what a
+    position that becomes drawable starts at) = 1"""
+    _on_gpu(store, "prioritized replay keeps its sum tree")
+    store.priority_alpha = alpha
+    store.tree_leaves = 1 << max(0, slots - 1).bit_length()        # smallest power of two >= slots
+    store.tree = torch.zeros(2 * store.tree_leaves, dtype=torch.float64, device=store.device)
+    store.tree[0] = 1.0
+    store._pbufs = {}
 
 
 class BatchIterator:
@@ -144,24 +190,11 @@ class DeviceReplay:
         # reference's loader yields
         self.indexed = bool(indexed)
         self._ibufs = {}
-        self.priority_alpha = None
-        self.priority_beta, self.priority_eps = float(priority_beta), float(priority_eps)
         self._placements = 0        # episodes placed so far: what a PrioritizedBatch compares before it writes priorities
         self.n_valid = 0            # drawable positions (prioritized store)
-        self.tree = None
-        if priority_alpha is not None:
-            a = float(priority_alpha)
-            if isinstance(priority_alpha, bool) or not (0.0 < a <= 1.0):
-                raise ValueError(f"priority_alpha {priority_alpha!r}: None or a float in (0, 1]")
-            if not (self.priority_beta >= 0.0) or not (0.0 < self.priority_eps < float("inf")):
-                raise ValueError("priority_beta must be >= 0 and priority_eps > 0")
-            if self.device.type != "cuda":
-                raise _lib.DrqError("prioritized replay keeps its sum tree on the GPU: the HIP path has no CPU fallback")
-            self.priority_alpha = a
-            self.tree_leaves = 1 << max(0, self.capacity - 1).bit_length()      # smallest power of two >= capacity
-            self.tree = torch.zeros(2 * self.tree_leaves, dtype=torch.float64, device=dev)
-            self.tree[0] = 1.0      # running maximum leaf: what a new episode's positions start at
-            self._pbufs = {}
+        alpha = _priority_args(self, priority_alpha, priority_beta, priority_eps)
+        if alpha is not None:
+            _priority_tree(self, self.capacity, alpha)
 
     # ---- storage -------------------------------------------------------------------------
     def __len__(self):
@@ -236,8 +269,7 @@ class DeviceReplay:
     def gather(self, pos):
         """pos: int64 store indices [B] (host array or device tensor) -> (obs, action, reward, discount, next_obs) on
         the device, shaped like the reference's batch ([B,*obs], [B,A], [B,1], [B,1], [B,*obs])."""
-        if self.device.type != "cuda":
-            raise _lib.DrqError("replay batch assembly runs on the GPU: the HIP path has no CPU fallback")
+        _on_gpu(self, "replay batch assembly runs")
         lib = _lib.load()
         if not torch.is_tensor(pos):
             pos = torch.from_numpy(np.ascontiguousarray(pos, np.int64))
@@ -262,25 +294,15 @@ class DeviceReplay:
     def gather_indexed(self, pos):
         """pos: host int64 store indices [B] -> IndexedBatch: action rows and n-step reward / discount assembled by the
         same kernel (its frame copies skipped), obs = frame pos-1, next_obs = frame pos+nstep-1 as indices."""
-        if self.device.type != "cuda":
-            raise _lib.DrqError("replay batch assembly runs on the GPU: the HIP path has no CPU fallback")
+        _on_gpu(self, "replay batch assembly runs")
         lib = _lib.load()
         pos = np.ascontiguousarray(pos, np.int64)
         B = pos.size
-        bufs = self._ibufs.get(B)
-        if bufs is None:
-            dev = self.device
-            # four sets, used in turn.  The device tensors are written in stream order (no hazard), but the pinned host
-            # staging of set s is overwritten by the HOST when batch k+4 is drawn, and its upload must have run by then:
-            # StepEngine.update keeps at most two updates queued behind the running one (_throttle), so three batches
-            # can be pending at most.  A consumer of its own must bound its run-ahead likewise (or use gather()).
-            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), torch.empty((B, self.A), dtype=torch.float32, device=dev),
-                          torch.empty((B, 1), dtype=torch.float32, device=dev), torch.empty((B, 1), dtype=torch.float32, device=dev),
-                          torch.empty((3, B), dtype=torch.int64).pin_memory())
-            bufs = [mk(), mk(), mk(), mk(), 0]
-            self._ibufs = {B: bufs}
-        idx, act, rew, disc, host = bufs[bufs[4]]
-        bufs[4] = (bufs[4] + 1) & 3
+        dev = self.device
+        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        idx, act, rew, disc, host = _rotating(self._ibufs, B, lambda: (
+            torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
+            torch.empty((3, B), dtype=torch.int64).pin_memory()))
         h = host.numpy()
         h[0], h[1], h[2] = pos - 1, pos + self.nstep - 1, pos
         idx.copy_(host, non_blocking=True)
@@ -296,20 +318,14 @@ class DeviceReplay:
             raise _lib.DrqError("replay: no stored episode is at least nstep long")
         lib = _lib.load()
         B = int(batch_size)
-        bufs = self._pbufs.get(B)
-        if bufs is None:
-            dev = self.device
-            # four sets used in turn, like gather_indexed's (and for its reason: the pinned u row of a set is
-            # overwritten by the host when batch k+4 is drawn); a set also holds the weights of its batch and, for
-            # indexed batches, their action / reward / discount rows (materialised ones use gather()'s buffers)
-            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
-                          f(B), torch.empty((B,), dtype=torch.float64).pin_memory(),
-                          (f(B, self.A), f(B, 1), f(B, 1)) if self.indexed else None)
-            bufs = [mk(), mk(), mk(), mk(), 0]
-            self._pbufs = {B: bufs}
-        idx, u, w, host, rows = bufs[bufs[4]]
-        bufs[4] = (bufs[4] + 1) & 3
+        dev = self.device
+        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        # a set also holds the weights of its batch and, for indexed batches, their action / reward / discount rows
+        # (materialised ones use gather()'s buffers)
+        idx, u, w, host, rows = _rotating(self._pbufs, B, lambda: (
+            torch.empty((3, B), dtype=torch.int64, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
+            f(B), torch.empty((B,), dtype=torch.float64).pin_memory(),
+            (f(B, self.A), f(B, 1), f(B, 1)) if self.indexed else None))
         host.numpy()[:] = self.rng.random_sample(B)
         u.copy_(host, non_blocking=True)
         with torch.cuda.device(self.device):
@@ -326,14 +342,14 @@ class DeviceReplay:
             batch = _PrioritizedTuple(self.gather(idx[2]))
         return batch._per(self, idx[2], w)
 
+    def _stamp_now(self):
+        return self._placements
+
     def _update_priorities(self, batch, td_abs):
         if batch._stamp != self._placements:
             return                      # an episode was placed since the draw: see PrioritizedBatch.update_priorities
         pos = batch._pos
-        B = pos.numel()
-        if (not torch.is_tensor(td_abs) or td_abs.dtype != torch.float32 or td_abs.device != pos.device
-                or td_abs.numel() != B or not td_abs.is_contiguous()):
-            raise _lib.DrqError(f"update_priorities(): contiguous float32 [{B}] on {pos.device} required")
+        B = _td_rows(pos, td_abs)
         with torch.cuda.device(self.device):
             check(_lib.load().drq_per_update(ptr(self.tree), self.tree_leaves, ptr(pos), ptr(td_abs), B, self.priority_alpha,
                                              self.priority_eps, self._stream()), "drq_per_update")
@@ -407,24 +423,11 @@ class VecDeviceReplay:
         self._stage = None          # pinned + device staging of one row, for host inputs
         self._bufs = {}
         self._frames_out = {}
-        self.priority_alpha = None
-        self.priority_beta, self.priority_eps = float(priority_beta), float(priority_eps)
-        self.tree = None
-        if priority_alpha is not None:
-            a = float(priority_alpha)
-            if isinstance(priority_alpha, bool) or not (0.0 < a <= 1.0):
-                raise ValueError(f"priority_alpha {priority_alpha!r}: None or a float in (0, 1]")
-            if not (self.priority_beta >= 0.0) or not (0.0 < self.priority_eps < float("inf")):
-                raise ValueError("priority_beta must be >= 0 and priority_eps > 0")
+        alpha = _priority_args(self, priority_alpha, priority_beta, priority_eps)
+        if alpha is not None:
             if not self.indexed:
                 raise ValueError("prioritized sampling on the ring yields indexed batches: indexed=True required")
-            if self.device.type != "cuda":
-                raise _lib.DrqError("prioritized replay keeps its sum tree on the GPU: the HIP path has no CPU fallback")
-            self.priority_alpha = a
-            self.tree_leaves = 1 << max(0, S - 1).bit_length()      # smallest power of two >= rows * num_envs
-            self.tree = torch.zeros(2 * self.tree_leaves, dtype=torch.float64, device=dev)
-            self.tree[0] = 1.0      # running maximum leaf: what a row that becomes drawable starts at
-            self._pbufs = {}
+            _priority_tree(self, S, alpha)
 
     # ---- storage -------------------------------------------------------------------------
     def bounds(self):
@@ -485,8 +488,7 @@ class VecDeviceReplay:
                 self._row(reward, "reward", [(N,), (N, 1)], f32),
                 self._row(discount, "discount", [(N,), (N, 1)], f32),
                 None if first is None else self._row(first, "first", [(N,)], (torch.uint8, torch.bool))]
-        if self.device.type != "cuda":
-            raise _lib.DrqError("the step-major replay lives on the GPU: the HIP path has no CPU fallback")
+        _on_gpu(self, "the step-major replay lives")
         with torch.cuda.device(self.device):
             src = [t if t is None or t.is_cuda else self._staged(k, t) for k, t in enumerate(args)]
             check(_lib.load().drq_vec_add(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
@@ -509,27 +511,18 @@ class VecDeviceReplay:
     def sample(self, batch_size):
         """IndexedBatch (indexed=True: the frames stay in the ring) or the materialised 5-tuple of the reference's loader,
         shaped like DeviceReplay's.  One random_sample((B, K)) call on the store's RandomState per batch."""
-        if self.device.type != "cuda":
-            raise _lib.DrqError("the step-major replay lives on the GPU: the HIP path has no CPU fallback")
+        _on_gpu(self, "the step-major replay lives")
         lo, hi = self.bounds()
         if hi < lo:
             raise _lib.DrqError(f"replay: {self.T} rows added, no drawable row yet (nstep {self.nstep})")
         if self.tree is not None:
             return self._sample_prioritized(int(batch_size), lo, hi)
         B, K, dev = int(batch_size), self.K, self.device
-        bufs = self._bufs.get(B)
-        if bufs is None:
-            # four sets used in turn, like DeviceReplay.gather_indexed's and for its reason: the pinned u table of a set
-            # is overwritten by the host when batch k+4 is drawn, and its upload must have run by then
-            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
-                          torch.empty((B,), dtype=torch.int32, device=dev),
-                          torch.empty((B, K), dtype=torch.float64, device=dev),
-                          torch.empty((B, K), dtype=torch.float64).pin_memory())
-            bufs = [mk(), mk(), mk(), mk(), 0]
-            self._bufs = {B: bufs}
-        idx, act, rew, disc, steps, u, host = bufs[bufs[4]]
-        bufs[4] = (bufs[4] + 1) & 3
+        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        idx, act, rew, disc, steps, u, host = _rotating(self._bufs, B, lambda: (
+            torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
+            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B, K), dtype=torch.float64, device=dev),
+            torch.empty((B, K), dtype=torch.float64).pin_memory()))
         host.numpy()[:] = self.rng.random_sample((B, K))
         u.copy_(host, non_blocking=True)
         obs = nxt = None
@@ -555,18 +548,11 @@ class VecDeviceReplay:
         """One stratified draw on the device: u ~ U[0,1)^B from the store's RandomState (one random_sample call per
         batch) -> drq_vec_per_sample.  Returns a PrioritizedBatch that is an IndexedBatch."""
         dev = self.device
-        bufs = self._pbufs.get(B)
-        if bufs is None:
-            # four sets used in turn, like sample()'s and for its reason
-            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-            mk = lambda: (torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
-                          torch.empty((B,), dtype=torch.int32, device=dev), f(B),
-                          torch.empty((B,), dtype=torch.float64, device=dev),
-                          torch.empty((B,), dtype=torch.float64).pin_memory())
-            bufs = [mk(), mk(), mk(), mk(), 0]
-            self._pbufs = {B: bufs}
-        idx, act, rew, disc, steps, w, u, host = bufs[bufs[4]]
-        bufs[4] = (bufs[4] + 1) & 3
+        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        idx, act, rew, disc, steps, w, u, host = _rotating(self._pbufs, B, lambda: (
+            torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
+            torch.empty((B,), dtype=torch.int32, device=dev), f(B), torch.empty((B,), dtype=torch.float64, device=dev),
+            torch.empty((B,), dtype=torch.float64).pin_memory()))
         host.numpy()[:] = self.rng.random_sample(B)
         u.copy_(host, non_blocking=True)
         with torch.cuda.device(dev):
@@ -576,16 +562,16 @@ class VecDeviceReplay:
                                                  ptr(act), ptr(rew), ptr(disc), ptr(steps), ptr(w), self._stream()),
                   "drq_vec_per_sample")
         self.last_steps, self.last_index = steps, idx
-        return _PrioritizedRing(self.frames, idx[0], act, rew, disc, idx[1])._per(self, idx[2], w)
+        return _PrioritizedIndexed(self.frames, idx[0], act, rew, disc, idx[1])._per(self, idx[2], w)
+
+    def _stamp_now(self):
+        return self.T               # the number of rows the ring held at the draw
 
     def _update_priorities(self, batch, td_abs):
         if self.T - batch._stamp >= self.guard_rows:
-            return                      # the batch's slots may hold other transitions: see _PrioritizedRing
+            return                      # the batch's slots may hold other transitions: see PrioritizedBatch.update_priorities
         pos = batch._pos
-        B = pos.numel()
-        if (not torch.is_tensor(td_abs) or td_abs.dtype != torch.float32 or td_abs.device != pos.device
-                or td_abs.numel() != B or not td_abs.is_contiguous()):
-            raise _lib.DrqError(f"update_priorities(): contiguous float32 [{B}] on {pos.device} required")
+        B = _td_rows(pos, td_abs)
         lo, hi = self.bounds()
         with torch.cuda.device(self.device):
             check(_lib.load().drq_vec_per_update(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N, self.T,

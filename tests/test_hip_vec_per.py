@@ -231,6 +231,90 @@ def test_update(lib, B):
         assert np.array_equal(d[n].cpu().numpy(), ring[n]), n
 
 
+# ------------------------------------------------------------------------------------------------ ring == episode store
+@pytest.fixture(scope="module")
+def small_ring(lib):
+    """A ring of R = 8 rows, N = 3, nstep 3, guard 0 after T = 2R + 5 adds with no reset flag but the one row 0 always
+    carries (long overwritten): every drawable slot holds a transition, which is what the episode store's entries assume
+    of a positive leaf.  The tree is the device's own: drq_vec_per_advance after every add, then one priority update of
+    all drawable slots with random errors.  Host copies; the tests upload them and leave them as they are."""
+    Rs, N, nstep, T = 8, 3, 3, 2 * 8 + 5
+    vp = VP.VecPEROracle(Rs, N, A, FB, nstep, 0.99, guard_rows=0)
+    L = vp.L
+    shapes = {"frames": (Rs * N, FB), "action": (Rs * N, A), "reward": (Rs * N,), "discount": (Rs * N,), "first": (Rs * N,)}
+    store = {n: torch.zeros(shapes[n], dtype=dt, device="cuda") for n, dt in ARRAYS}
+    tree = f64(vp.tree).cuda()
+    r = rs_(8)
+    for t in range(T):
+        row = random_row(r, N, p_reset=0.0)
+        vp.add(*row)
+        d = [torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint8 if i in (0, 4) else np.float32)).cuda() for i, x in enumerate(row)]
+        assert lib.drq_vec_add(*(p(store[n]) for n, _ in ARRAYS), Rs, N, A, FB, t, *(p(x) for x in d), None) == 0
+        enter, leave = VP.entering_leaving(t + 1, Rs, nstep, 0)
+        assert lib.drq_vec_per_advance(p(tree), L, p(store["first"]), Rs, N, t + 1, enter, leave, None) == 0
+    lo, hi = vp.bounds()
+    assert (lo, hi) == (T - Rs + 1, T - nstep) and not store["first"].any()
+    valid = np.nonzero(vp.expected_leaf_mask())[0]
+    assert valid.size == (hi - lo + 1) * N and same_tree(tree.cpu().numpy(), vp.tree)
+    td = (10.0 ** r.uniform(-3, 3, valid.size)).astype(np.float32)
+    assert lib.drq_vec_per_update(p(tree), L, p(store["first"]), Rs, N, T, lo, hi, p(i64(valid).cuda()), p(f32(td).cuda()),
+                                  valid.size, 0.6, 1e-6, None) == 0
+    torch.cuda.synchronize()
+    got = tree.cpu().numpy()
+    assert inner_ok(got) and np.array_equal(got[L:] > 0, vp.expected_leaf_mask()) and np.unique(got[L + valid]).size > 10
+    return dict(R=Rs, N=N, nstep=nstep, T=T, L=L, lo=lo, hi=hi, valid=valid, tree=got,
+                ring={n: store[n].cpu() for n, _ in ARRAYS})
+
+
+@pytest.mark.parametrize("B", [1, 37, 1100])
+def test_ring_draw_equals_the_episode_stores(lib, small_ring, B):
+    """The descent and the weights are one piece of device code for both stores: on a ring without reset rows
+    drq_per_sample with n_valid = (hi - lo + 1) N and the same u names the same positions and gives the same weights as
+    drq_vec_per_sample, bit for bit.  B = 1100 strides past the 1,024 threads"""
+    s = small_ring
+    Rs, N, L, lo, hi, beta = s["R"], s["N"], s["L"], s["lo"], s["hi"], 0.4
+    u = rs_(B).random_sample(B)
+    u[0], u[-1] = (0.0, np.nextafter(1.0, 0.0)) if B > 1 else (u[0], u[0])
+    d = {n: dev(s["ring"][n], n) for n, _ in ARRAYS}
+    tree, ud = dev(f64(s["tree"]), "tree"), dev(f64(u), "u")
+    o = dict(idx=out(3, B, dtype=torch.int64, name="idx"), act=out(B, A, name="act"), rew=out(B, name="rew"),
+             disc=out(B, name="disc"), steps=out(B, dtype=torch.int32, name="steps"), w=out(B, name="weights"))
+    assert lib.drq_vec_per_sample(p(tree), L, p(d["first"]), p(d["action"]), p(d["reward"]), p(d["discount"]), Rs, N, A,
+                                  s["T"], lo, hi, p(ud), B, s["nstep"], 0.99, beta, p(o["idx"]), p(o["act"]), p(o["rew"]),
+                                  p(o["disc"]), p(o["steps"]), p(o["w"]), None) == 0
+    idx, w = out(3, B, dtype=torch.int64, name="flat idx"), out(B, name="flat weights")
+    assert lib.drq_per_sample(p(tree), L, p(ud), B, s["nstep"], (hi - lo + 1) * N, beta, p(idx), p(w), None) == 0
+    torch.cuda.synchronize()
+    pos = o["idx"][2].cpu().numpy()
+    assert np.isin(pos, s["valid"]).all() and (B == 1 or np.unique(pos).size > 1)
+    assert np.array_equal(idx[2].cpu().numpy(), pos)
+    assert np.array_equal(raw(w), raw(o["w"])) and float(o["w"].max()) == 1.0
+    assert same_tree(tree.cpu().numpy(), s["tree"])
+
+
+@pytest.mark.parametrize("B", [8, 1100])
+def test_ring_update_equals_the_episode_stores(lib, small_ring, B):
+    """The priority update is one piece of device code for both stores: for positions among the drawable slots, repeats
+    included, drq_per_update and drq_vec_per_update leave identical trees, all 2L doubles, bit for bit"""
+    s = small_ring
+    Rs, N, L = s["R"], s["N"], s["L"]
+    r = rs_(B)
+    pos = r.choice(s["valid"], B).astype(np.int64)
+    pos[-1] = pos[0]
+    td = (10.0 ** r.uniform(-3, 3, B)).astype(np.float32)
+    assert np.unique(pos).size < B and td[0] != td[-1]
+    first = dev(s["ring"]["first"], "first")
+    pd, tdd = dev(i64(pos), "pos"), dev(f32(td), "td")
+    flat, ring = dev(f64(s["tree"]), "flat tree"), dev(f64(s["tree"]), "ring tree")
+    assert lib.drq_per_update(p(flat), L, p(pd), p(tdd), B, 0.6, 1e-6, None) == 0
+    assert lib.drq_vec_per_update(p(ring), L, p(first), Rs, N, s["T"], s["lo"], s["hi"], p(pd), p(tdd), B, 0.6, 1e-6,
+                                  None) == 0
+    torch.cuda.synchronize()
+    got = ring.cpu().numpy()
+    assert same_tree(flat.cpu().numpy(), got)
+    assert inner_ok(got) and not same_tree(got, s["tree"]) and got[0] == max(s["tree"][0], got[L:].max())
+
+
 # ------------------------------------------------------------------------------------------------ refusals
 def test_refusals(lib):
     """every DRQ_EARG case of the three entries: the outputs stay poison, the tree stays what it was"""
