@@ -272,6 +272,10 @@ class DrQV2Agent:
         # float32 [B] on the device, the critic loss becomes mean_i w_i (Q - y)_i^2 per head (StepEngine.update)
         weights = getattr(batch, "weights", None)
         wkw = {} if weights is None else {"loss_weights": weights}
+        # drqv2_amd.replay.FrameBatch: `frames` is a ring of single frames, the indices name the newest frame of each
+        # stack and the ring's flags tell the fused aug+conv1 launch where the other two are (StepEngine.update)
+        if getattr(batch, "ring", None) is not None:
+            wkw["ring"] = batch.ring
         obs, action, reward, discount, next_obs = utils.to_torch(batch, self.device)
         eng = self._engine
         A = eng.A

@@ -48,6 +48,8 @@ PROTOTYPES = {
     "drq_conv1_aug_fwd_bf16": (I, [P, P, P, P, P, P, P, P, P, I, I, P]),
     "drq_conv1_aug_fwd_bf16_nhwc": (I, [P, P, P, P, P, P, P, P, P, I, I, P]),
     "drq_conv1_aug_fwd_indexed": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, P]),
+    "drq_conv1_aug_fwd_frames": (I, [P, P, L, L, P, P, P, P, P, P, P, P, P, I, I, P]),
+    "drq_conv1_aug_fwd_frames_bf16": (I, [P, P, L, L, P, P, P, P, P, P, P, P, P, I, I, P]),
     "drq_conv3x3_fwd": (I, [P, P, P, P, I, I, I, I, I, L, L, L, L, P]),
     "drq_conv3x3_dgrad": (I, [P, P, P, P, I, I, L, L, L, L, P]),
     "drq_conv3x3_fwd_wino": (I, [P, P, P, P, I, I, I, L, L, L, L, P]),
@@ -103,6 +105,7 @@ PROTOTYPES = {
     "drq_vec_per_advance": (I, [P, L, P, L, L, L, L, L, P]),
     "drq_vec_per_sample": (I, [P, L, P, P, P, P, L, L, I, L, L, L, P, I, I, F, D, P, P, P, P, P, P, P]),
     "drq_vec_per_update": (I, [P, L, P, L, L, L, L, L, P, P, I, D, D, P]),
+    "drq_vec_stack_gather": (I, [P, P, L, L, L, P, L, I, P, P]),
     "drq_relu_mask_pad": (I, [P, P, P, L, I, I, P]),
     "drq_conv1_dgrad": (I, [P, P, P, I, P]),
     "drq_aug_bwd_f32": (I, [P, P, P, P, I, I, I, I, P]),
@@ -113,6 +116,7 @@ PROTOTYPES = {
     "drq_update_phase": (I, [C.POINTER(DrqStep), I]),
     "drq_update_phase_bc": (I, [C.POINTER(DrqStep), I, F]),
     "drq_update_phase_per": (I, [C.POINTER(DrqStep), I, P, P]),
+    "drq_update_phase_frames": (I, [C.POINTER(DrqStep), I, P, L, L, P, P]),
     "drq_act_forward": (I, [C.POINTER(DrqStep), P, I, P]),
     "drq_act_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_act_batch": (I, [P, I, I, I, I, P, I, P, F, P, P, P, SZ, P]),

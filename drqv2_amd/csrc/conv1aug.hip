@@ -19,6 +19,7 @@
 // unfused path (tests/test_hip_ops.py).
 #include "common.h"
 #include "internal.h"
+#include "replay_device.h"
 #include "wino_u.h"
 
 namespace {
@@ -41,12 +42,18 @@ constexpr int NTHR = 256;                                 // 4 waves (512 with w
                                                           // of 50 us, but the stage times add up either way: 90 vs 86 us)
 constexpr int NWAVE = NTHR / 64;
 constexpr int MAXU = 64;                                  // units per workgroup (shift table); the grid grows beyond it
-constexpr int LDS_BYTES = (XS_FLOATS + U8_ALLOC + H + 3 * MAXU) * 4;   // + base grid, shift table, frame table
+constexpr int FG = 3, GC = C / FG;       // frame groups of a stack, channels per group (frame_stack 3 of RGB frames)
+constexpr int LDS_BYTES = (XS_FLOATS + U8_ALLOC + H + (2 + FG) * MAXU) * 4;   // + base grid, shift table, frame table
+static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups share a CU's LDS");
 
 struct Conv1AugArgs {
   const uint8_t* obs[2];     // view 0 = obs, view 1 = next_obs: [n][9][84][84] -- or, with fidx, a store of frames
   const long* fidx[2];       // optional: row b of the view is frame fidx[view][b] of obs[view] (device replay: the batch is
                              // never materialised, the kernel gathers its source rows straight from the store)
+  // optional, with fidx: obs[view] is a ring of SINGLE frames u8 [R N][3][84][84], fidx names the slot of the newest
+  // frame of row b's stack and the other two follow from the `first` flags (ring_stack_slots, replay_device.h)
+  const uint8_t* ring_first;
+  long ring_R, ring_N;
   const float* shift[2];     // [n][2] (x, y)
   const float* base;         // [84]
   const float* w;            // [32][9][3][3]
@@ -99,7 +106,9 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
   const uint8_t* u8b = reinterpret_cast<const uint8_t*>(u8w);
   float* bg = smem + XS_FLOATS + U8_ALLOC;                         // [84] base grid
   float* shs = bg + H;                                             // [MAXU][2] shifts (x, y) of this workgroup's units
-  int* fof = reinterpret_cast<int*>(shs + 2 * MAXU);               // [MAXU] frame number of the unit's source in obs[view]
+  // [MAXU][FG] where the unit's source lies in obs[view], per group of GC channels, in units of GC*HW bytes: 3f, 3f+1,
+  // 3f+2 for stack f of a batch or a store of stacks, three slots for a ring of single frames
+  int* fof = reinterpret_cast<int*>(shs + 2 * MAXU);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
@@ -120,7 +129,17 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
       const int view = f >= a.n ? 1 : 0, fb = f - view * a.n;
       shs[2 * k + 0] = a.shift[view][2 * fb + 0];
       shs[2 * k + 1] = a.shift[view][2 * fb + 1];
-      fof[k] = a.fidx[view] ? (int)a.fidx[view][fb] : fb;
+      const long f0 = a.fidx[view] ? a.fidx[view][fb] : fb;
+      if (a.ring_first) {
+        const long S = a.ring_R * a.ring_N;
+        long sl[FG];
+        ring_stack_slots(a.ring_first, a.ring_R, a.ring_N, f0 < 0 ? 0 : (f0 < S ? f0 : S - 1), sl);
+#pragma unroll
+        for (int g = 0; g < FG; ++g) fof[FG * k + g] = (int)sl[g];
+      } else {
+#pragma unroll
+        for (int g = 0; g < FG; ++g) fof[FG * k + g] = (int)(FG * f0 + g);
+      }
     }
   }
   // A operand: this lane's weights, step s = c*9 + t -> w[cout = col][cin = 2c + half][t]; cin 9 does not exist
@@ -166,7 +185,7 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
   // unit = (frame of the stacked [2n] batch, band of output rows); everything here is wave-uniform and comes from
   // LDS tables: no vector-memory load (and so no vmcnt wait) between the DMA issue and the tiles
   struct Unit {
-    int f, r0, R, i0, nr, sy_lo, nsrc, fo;
+    int f, r0, R, i0, nr, sy_lo, nsrc, fo[FG];
     float shx, shy;
   };
   auto make_unit = [&](int k) {
@@ -182,7 +201,8 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
     q.nr = 2 * q.R + 1 + (band == NBAND - 1 ? 1 : 0);
     q.shx = shs[2 * k + 0] * sc;
     q.shy = shs[2 * k + 1] * sc;
-    q.fo = fof[k];
+#pragma unroll
+    for (int g = 0; g < FG; ++g) q.fo[g] = fof[FG * k + g];
     float fa, fbb;
     coordv(q.i0, q.shy, fa);
     coordv(q.i0 + q.nr - 1, q.shy, fbb);
@@ -193,17 +213,22 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
   // stage 1: the source rows of a unit -> LDS by LDS-DMA (no register destination: nothing downstream waits for
   // them until the explicit vmcnt(0) at the top of the unit's iteration).  One wave-instruction fills 64 consecutive
   // dwords of the [channel][row][dword] tile; the per-lane SOURCE address does the row gather.  Rows past the
-  // band's last source row re-load that row (harmless).
+  // band's last source row re-load that row (harmless).  The three channel groups of a stack have a source of their
+  // own each (wave-uniform; a lane picks its group's).
   auto dma_src = [&](const Unit& q) {
     const int view = q.f >= a.n ? 1 : 0;
-    const uint8_t* src = a.obs[view] + (long)q.fo * C * HW;
+    const uint8_t* src3[FG];
+#pragma unroll
+    for (int g = 0; g < FG; ++g) src3[g] = a.obs[view] + (long)q.fo[g] * GC * HW;
     for (int k = wid; k < NDMA; k += NWAVE) {
       int e = k * 64 + lane;
       e = e < U8_DWORDS ? e : U8_DWORDS - 1;
       const int rowid = e / HQ, qd = e - rowid * HQ;
       const int ch = rowid / SROWS, r = rowid - ch * SROWS;
       const int rr = r < q.nsrc ? r : q.nsrc - 1;
-      const unsigned* g = reinterpret_cast<const unsigned*>(src + (long)ch * HW + (long)(q.sy_lo + rr) * H) + qd;
+      const int grp = ch / GC;
+      const uint8_t* src = grp == 0 ? src3[0] : (grp == 1 ? src3[1] : src3[2]);
+      const unsigned* g = reinterpret_cast<const unsigned*>(src + (ch - grp * GC) * HW + (q.sy_lo + rr) * H) + qd;
       __builtin_amdgcn_global_load_lds((glb_ptr_t)g, (lds_ptr_t)(u8w + k * 64), 4, 0, 0);
     }
   };
@@ -415,16 +440,20 @@ __global__ __launch_bounds__(NTHR, 2 * NTHR / 256) void conv1_aug_kernel(Conv1Au
 int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                           const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
                           int n_store, hipStream_t st, const float* const* wino_w, float* wino_u, const long* fidx0,
-                          const long* fidx1) {
+                          const long* fidx1, const uint8_t* ring_first, long ring_R, long ring_N) {
   if (!obs || !shift || !obs1 || !shift1 || !base_grid || !w || !bias || !y || n <= 0 || n_store < 0 || n_store > 2 * n)
     return DRQ_EARG;
   if (n_store > 0 && !xaug) return DRQ_EARG;
   if (((uintptr_t)obs & 3) || ((uintptr_t)obs1 & 3)) return DRQ_EARG;     // rows are read as dwords
+  // a ring of single frames: one store for both views, the newest-frame slots of both, slot numbers that fit the table
+  if (ring_first && (!fidx0 || !fidx1 || obs != obs1 || ring_R <= 0 || ring_N <= 0 || ring_R > INT32_MAX / ring_N))
+    return DRQ_EARG;
   const size_t yb = (size_t)2 * n * 32 * PO * (bf_mma == 2 ? 2 : 4);      // 2: bf16 [2n][41][41][32]
   if (yb >= (1ull << 31) || (bf_mma == 2 && ((uintptr_t)y & 15))) return DRQ_EARG;
   Conv1AugArgs a{};
   a.obs[0] = obs; a.obs[1] = obs1;
   a.fidx[0] = fidx0; a.fidx[1] = fidx1;
+  a.ring_first = ring_first; a.ring_R = ring_R; a.ring_N = ring_N;
   a.shift[0] = shift; a.shift[1] = shift1;
   a.base = base_grid; a.w = w; a.bias = bias; a.xaug = xaug; a.y = y;
   a.n = n; a.n_store = n_store; a.y_bytes = (unsigned)yb; a.stagger = 1;
@@ -463,7 +492,7 @@ DRQ_API int drq_conv1_aug_fwd(const uint8_t* obs, const float* shift, const uint
                               const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
                               int n_store, hipStream_t st) {
   return drq_conv1_aug_fwd_any(0, obs, shift, obs1, shift1, base_grid, w, bias, xaug, y, n, n_store, st, nullptr, nullptr,
-                               nullptr, nullptr);
+                               nullptr, nullptr, nullptr, 0, 0);
 }
 
 DRQ_API int drq_conv1_aug_fwd_indexed(const uint8_t* frames, const long* idx, const float* shift, const uint8_t* frames1,
@@ -471,19 +500,37 @@ DRQ_API int drq_conv1_aug_fwd_indexed(const uint8_t* frames, const long* idx, co
                                       const float* bias, float* xaug, float* y, int n, int n_store, hipStream_t st) {
   if (!idx || !idx1) return DRQ_EARG;
   return drq_conv1_aug_fwd_any(0, frames, shift, frames1, shift1, base_grid, w, bias, xaug, y, n, n_store, st, nullptr,
-                               nullptr, idx, idx1);
+                               nullptr, idx, idx1, nullptr, 0, 0);
+}
+
+DRQ_API int drq_conv1_aug_fwd_frames(const uint8_t* frames, const uint8_t* first, long R, long N, const long* idx,
+                                     const float* shift, const long* idx1, const float* shift1, const float* base_grid,
+                                     const float* w, const float* bias, float* xaug, float* y, int n, int n_store,
+                                     hipStream_t st) {
+  if (!first || !idx || !idx1) return DRQ_EARG;
+  return drq_conv1_aug_fwd_any(0, frames, shift, frames, shift1, base_grid, w, bias, xaug, y, n, n_store, st, nullptr,
+                               nullptr, idx, idx1, first, R, N);
+}
+
+DRQ_API int drq_conv1_aug_fwd_frames_bf16(const uint8_t* frames, const uint8_t* first, long R, long N, const long* idx,
+                                          const float* shift, const long* idx1, const float* shift1,
+                                          const float* base_grid, const float* w, const float* bias, float* xaug,
+                                          float* y, int n, int n_store, hipStream_t st) {
+  if (!first || !idx || !idx1) return DRQ_EARG;
+  return drq_conv1_aug_fwd_any(1, frames, shift, frames, shift1, base_grid, w, bias, xaug, y, n, n_store, st, nullptr,
+                               nullptr, idx, idx1, first, R, N);
 }
 
 DRQ_API int drq_conv1_aug_fwd_bf16(const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                                    const float* base_grid, const float* w, const float* bias, float* xaug, float* y,
                                    int n, int n_store, hipStream_t st) {
   return drq_conv1_aug_fwd_any(1, obs, shift, obs1, shift1, base_grid, w, bias, xaug, y, n, n_store, st, nullptr, nullptr,
-                               nullptr, nullptr);
+                               nullptr, nullptr, nullptr, 0, 0);
 }
 
 DRQ_API int drq_conv1_aug_fwd_bf16_nhwc(const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                                         const float* base_grid, const float* w, const float* bias, float* xaug,
                                         void* y_nhwc, int n, int n_store, hipStream_t st) {
   return drq_conv1_aug_fwd_any(2, obs, shift, obs1, shift1, base_grid, w, bias, xaug, (float*)y_nhwc, n, n_store, st,
-                               nullptr, nullptr, nullptr, nullptr);
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0);
 }

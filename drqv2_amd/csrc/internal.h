@@ -104,11 +104,12 @@ int drq_polout_l1_fwd(const float* p2, const float* w3, const float* b3, float* 
                       long lda_hi, const float* noise_lo, float* mu_lo, float* ha_lo, long lda_lo, int nheads,
                       const float* const* w, const float* const* b, float* const* y, hipStream_t st);
 
-// ---- conv1aug.hip: bf_mma selects the bf16-MFMA form of the layer's products
+// ---- conv1aug.hip: bf_mma selects the bf16-MFMA form of the layer's products; ring_first != NULL: obs == obs1 is a
+// ring of single frames (R rows x N environments), fidx0 / fidx1 the newest-frame slots of the stacks
 int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                           const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
                           int n_store, hipStream_t st, const float* const* wino_w, float* wino_u, const long* fidx0,
-                          const long* fidx1);
+                          const long* fidx1, const uint8_t* ring_first, long ring_R, long ring_N);
 
 // ---- conv_wino.hip: the Winograd kernels with the layer's U image prepared by conv1_aug_kernel's rider
 int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,

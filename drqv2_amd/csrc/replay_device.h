@@ -1,8 +1,9 @@
 // The device code the replay stores share: the n-step sum (elementwise.hip's flat store, vecreplay.hip's ring), the
-// priority sum tree (per.hip's episode store, vecreplay.hip's ring) and the ring's geometry and batch rows (the
-// uniform and the prioritized draw of vecreplay.hip).  Layout and rules are the contract of include/drqv2_hip.h; the
-// memory-ordering argument of the tree is per.hip's header comment: ONE workgroup of kPerThreads threads walks the
-// levels with __syncthreads() between them, nothing crosses workgroups.
+// priority sum tree (per.hip's episode store, vecreplay.hip's ring), the ring's geometry and batch rows (the uniform
+// and the prioritized draw of vecreplay.hip) and the frame stack of a single-frame ring (vecframes.hip's gather,
+// conv1aug.hip's ring mode).  Layout and rules are the contract of include/drqv2_hip.h; the memory-ordering argument of
+// the tree is per.hip's header comment: ONE workgroup of kPerThreads threads walks the levels with __syncthreads()
+// between them, nothing crosses workgroups.
 #pragma once
 #include "common.h"
 
@@ -195,6 +196,27 @@ __device__ __forceinline__ void ring_emit_row(const RingBatch& a, int b, long t,
   nstep_sum(a.reward, a.discount, a.gamma, steps, [&](int i) { return ring_slot(g, t + i, e); }, r, d);
   a.rew_out[b] = r;
   a.disc_out[b] = steps == 0 ? 0.f : d;
+}
+
+// ---- single-frame rings: the frame stack is put together when it is read -------------------------------------------
+// (contract: include/drqv2_hip.h, "single-frame step-major replay"; vecframes.hip's gather, conv1aug.hip's ring mode)
+// The slots of the three frames of the stack whose newest frame lives in slot p0 (0 <= p0 < R N), oldest first: the
+// rows one and two back of the same environment, ring rows modulo R, refilled from the reset row on (dmc.py:98-109).
+// Every slot that is read or returned lies in [0, R N) whatever the flags hold; the second flag is read only where
+// the first does not decide.
+__device__ __forceinline__ void ring_stack_slots(const uint8_t* first, long R, long N, long p0, long (&s)[3]) {
+  const long wrap = (R - 1) * N;
+  const long p1 = p0 >= N ? p0 - N : p0 + wrap;
+  const long p2 = p1 >= N ? p1 - N : p1 + wrap;
+  s[2] = p0;
+  if (first[p0]) {
+    s[0] = s[1] = p0;
+  } else if (first[p1]) {
+    s[0] = s[1] = p1;
+  } else {
+    s[0] = p2;
+    s[1] = p1;
+  }
 }
 
 }  // namespace

@@ -188,6 +188,10 @@ struct Ctx {
   const float* is_weight = nullptr;
   float* td_abs = nullptr;
   bool per() const { return is_weight != nullptr; }
+  // single-frame ring (drq_update_phase_frames): s->obs is a ring of R x N single frames, the indices name the newest
+  // frame of each stack and the fused aug+conv1 launch gathers the other two by these flags.  Null = stacks as stored.
+  const uint8_t* ring_first = nullptr;
+  long ring_R = 0, ring_N = 0;
   // B rows fit the LDS of the Q-output backward kernels that compute a loss as well (drq_qout_bwd_td / _actor)
   bool qout_loss_fits_lds() const { return ((size_t)s->B + 5 * 1024 + 16) * 4 <= 60 * 1024; }
   bool actor_loss_fused() const { return fuse_actor_loss && qout_loss_fits_lds(); }
@@ -388,7 +392,7 @@ int phase_encode(const Ctx& c) {
   CK(drq_conv1_aug_fwd_any(c.acts16() ? 2 : c.bf16(), s->obs, s->shift_obs, s->next_obs, s->shift_next, s->base_grid,
                            c.p(c.P.enc_w[0]), c.p(c.P.enc_b[0]), aug, c.ws(W_ACT1), B, s->store_aug_next ? 2 * B : B, st,
                            c.bf16() ? nullptr : wino_w, c.bf16() ? nullptr : c.ws(W_WINO_U), s->obs_index,
-                           s->next_obs_index));
+                           s->next_obs_index, c.ring_first, c.ring_R, c.ring_N));
   // layers 2..4 on both views in one pass (:244-246)
   CK(encoder_forward(c, nullptr, 2 * B, c.ws(W_ACT1), c.ws(W_ACT2), c.ws(W_ACT3), c.ws(W_FEAT), true));
   return 0;
@@ -847,7 +851,8 @@ DRQ_API long drq_step_ws_offset(int B, int C, int A, int F, int H, int id) {
 }
 
 namespace {
-int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_weight = nullptr, float* td_abs = nullptr) {
+int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_weight = nullptr, float* td_abs = nullptr,
+                 const uint8_t* ring_first = nullptr, long ring_R = 0, long ring_N = 0) {
   CK(check_step(s));
   if (!s->obs || !s->next_obs || !s->action || !s->reward || !s->discount || !s->shift_obs || !s->shift_next ||
       !s->noise_critic || !s->noise_actor || !s->base_grid || !s->grads || !s->adam_m || !s->adam_v || !s->sums)
@@ -858,6 +863,9 @@ int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_we
   c.bc_alpha = bc_alpha;
   c.is_weight = is_weight;
   c.td_abs = td_abs;
+  c.ring_first = ring_first;
+  c.ring_R = ring_R;
+  c.ring_N = ring_N;
   if (runs(phase, DRQ_PHASE_ENCODE)) CK(phase_encode(c));
   if (runs(phase, DRQ_PHASE_CRITIC_HEADS)) {
     CK(c.stamp(6));
@@ -901,6 +909,14 @@ DRQ_API int drq_update_phase_per(const DrqStep* s, int phase, const float* is_we
   // single GPU only: the weights of a data-parallel batch would need a normalisation over all ranks' rows
   if (!is_weight || !td_abs || (s && s->global_B != s->B)) return DRQ_EARG;
   return update_phase(s, phase, 0.f, is_weight, td_abs);
+}
+
+DRQ_API int drq_update_phase_frames(const DrqStep* s, int phase, const uint8_t* first, long R, long N,
+                                    const float* is_weight, float* td_abs) {
+  // the indexed update on a ring of single frames; single GPU only, as the ring's prioritized form
+  if (!first || R <= 0 || N <= 0 || (is_weight != nullptr) != (td_abs != nullptr)) return DRQ_EARG;
+  if (s && (!s->obs_index || !s->next_obs_index || s->obs != s->next_obs || s->global_B != s->B)) return DRQ_EARG;
+  return update_phase(s, phase, 0.f, is_weight, td_abs, first, R, N);
 }
 
 DRQ_API int drq_publish_sums(const float* sums, float* sums_host, unsigned seq, drq_stream_t stream) {

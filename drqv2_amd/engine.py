@@ -450,6 +450,25 @@ class StepEngine:
     _PER_BC = ("per-sample loss weights and behaviour cloning cannot be combined: the two forms of the update are "
                "separate entries of the library (drq_update_phase_per / drq_update_phase_bc)")
 
+    # ---- single-frame rings: the stacks are gathered by the fused aug+conv1 launch ----------------
+    _RING_DP = ("batches from a single-frame ring and data parallelism cannot be combined: the ring's update is a "
+                "single-GPU entry of the library (drq_update_phase_frames)")
+    _RING_BC = ("batches from a single-frame ring and behaviour cloning cannot be combined: the two forms of the update "
+                "are separate entries of the library (drq_update_phase_frames / drq_update_phase_bc)")
+
+    def _ring(self, ring):
+        """validates update()'s ring = (first, R, N) of a FrameBatch"""
+        if self.pg is not None:
+            raise _lib.DrqError(self._RING_DP)
+        if self.bc_alpha is not None:
+            raise _lib.DrqError(self._RING_BC)
+        first, R, N = ring
+        if (not torch.is_tensor(first) or first.dtype != torch.uint8 or first.device != self.device
+                or not first.is_contiguous() or R <= 0 or N <= 0 or first.numel() != R * N):
+            raise _lib.DrqError(f"update(): the ring's flags must be a contiguous uint8 tensor of R N = {R} x {N} "
+                                f"elements on {self.device}")
+        return first, int(R), int(N)
+
     def _loss_weights(self, w, B):
         """validates update()'s loss_weights and returns (weights, the td_abs buffer of this update)"""
         if self.pg is not None:
@@ -592,11 +611,15 @@ class StepEngine:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _phase(self, desc, k, per=None):
+    def _phase(self, desc, k, per=None, ring=None):
         # the library launches on the CURRENT HIP device: make that the agent's (an agent on cuda:1 in a process
         # whose current device is 0 would otherwise launch device-1 pointers on device 0)
         with torch.cuda.device(self.device):
-            if per is not None:         # (loss weights, td_abs): the weighted critic loss (_loss_weights)
+            if ring is not None:        # (first, R, N): the frames are a single-frame ring (_ring), weighted or not
+                w, td = per if per is not None else (None, None)
+                check(_lib.load().drq_update_phase_frames(ctypes.byref(desc), k, ptr(ring[0]), ring[1], ring[2], ptr(w),
+                                                          ptr(td)), f"drq_update_phase_frames({k})")
+            elif per is not None:       # (loss weights, td_abs): the weighted critic loss (_loss_weights)
                 check(_lib.load().drq_update_phase_per(ctypes.byref(desc), k, ptr(per[0]), ptr(per[1])),
                       f"drq_update_phase_per({k})")
             elif self.bc_alpha is not None:
@@ -686,17 +709,26 @@ class StepEngine:
         return d
 
     def update(self, obs, action, reward, discount, next_obs, shift_obs, shift_next, noise_critic, noise_actor, std,
-               clip, tau, B_global=None, obs_index=None, next_obs_index=None, loss_weights=None):
+               clip, tau, B_global=None, obs_index=None, next_obs_index=None, loss_weights=None, ring=None):
         """All tensors are this rank's shard, on the GPU.  Returns the 8-float sums tensor (device).
         loss_weights (float32 [B], device): the critic loss weighted per sample (prioritized replay,
         drq_update_phase_per); the per-sample |TD error| is left in self.last_td_abs.  Single GPU, fp32, no BC.
         obs_index / next_obs_index (int64 [B], device): the batch is not materialised -- obs / next_obs are frame stores
-        ([slots, C*84*84] or [slots, C, 84, 84] uint8) and row b is frame index[b] (DrqStep.obs_index)."""
+        ([slots, C*84*84] or [slots, C, 84, 84] uint8) and row b is frame index[b] (DrqStep.obs_index).
+        ring (with the indices; drqv2_amd.replay.FrameBatch.ring = (first, R, N)): obs and next_obs are ONE ring of single
+        frames [R N, 3*84*84], the indices name the newest frame of each stack and the fused aug+conv1 launch gathers the
+        rest by the flags (drq_update_phase_frames).  Single GPU, no BC; with loss_weights fp32 only."""
         indexed = obs_index is not None
+        if ring is not None:
+            ring = self._ring(ring)
+            if not indexed or obs is not next_obs or obs.numel() != ring[1] * ring[2] * 3 * 84 * 84:
+                raise _lib.DrqError("update(): a single-frame ring is one uint8 store of R N frames of 3 x 84 x 84 for both "
+                                    "views, read through obs_index / next_obs_index")
         if indexed:
             B = obs_index.numel()
             for nm, t, ix in (("obs", obs, obs_index), ("next_obs", next_obs, next_obs_index)):
-                if (t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() % (self.C * 84 * 84) or
+                if (t.dtype != torch.uint8 or not t.is_contiguous() or
+                        t.numel() % ((3 if ring is not None else self.C) * 84 * 84) or
                         ix is None or ix.dtype != torch.int64 or ix.numel() != B or not ix.is_contiguous()):
                     raise _lib.DrqError(f"update(): indexed {nm}: a contiguous uint8 frame store and {B} int64 indices")
                 if not (ix.is_cuda or ix.is_pinned()):       # a pageable host pointer would fault on the GPU
@@ -717,7 +749,7 @@ class StepEngine:
         steps = (self.critic_opt.begin_step(), self.encoder_opt.begin_step(), self.actor_opt.begin_step())
         d = self.make_desc(B, B_global, std, clip, tau, steps)
         keep = (obs, action, reward, discount, next_obs, shift_obs, shift_next, noise_critic, noise_actor, obs_index,
-                next_obs_index, per)
+                next_obs_index, per, ring)
         d.obs, d.next_obs = ptr(obs), ptr(next_obs)
         d.obs_index, d.next_obs_index = ptr(obs_index), ptr(next_obs_index)
         d.action, d.reward, d.discount = ptr(action), ptr(reward), ptr(discount)
@@ -725,7 +757,7 @@ class StepEngine:
         d.noise_critic, d.noise_actor = ptr(noise_critic), ptr(noise_actor)
         if self.pg is None:
             self._throttle(steps[2] & 0xFFFFFFFF)
-            self._phase(d, _lib.PHASE_ALL, per)
+            self._phase(d, _lib.PHASE_ALL, per, ring)
             self.last_td_abs = per[1] if per is not None else None
             self._last_seq = steps[2] & 0xFFFFFFFF
         else:

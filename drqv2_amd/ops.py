@@ -99,6 +99,36 @@ def conv1_aug_fwd_indexed(frames, idx, shift, frames1, idx1, shift1, w, b, n_sto
     return y, xaug
 
 
+def conv1_aug_fwd_frames(frames, first, R, N, idx, shift, idx1, shift1, w, b, n_store=None, base=None, bf16=False):
+    """drq_conv1_aug_fwd_frames(_bf16): both views are stacks of a single-frame ring (frames [R N, 3*84*84] uint8, first
+    [R N] uint8), idx / idx1 (int64) the slots of their newest frames."""
+    lib = _lib.load()
+    n = idx.numel()
+    _need(frames, torch.uint8, "frames"), _need(first, torch.uint8, "first")
+    shift, shift1 = _need(shift.reshape(n, 2), name="shift"), _need(shift1.reshape(n, 2), name="shift1")
+    base = aug_base_grid(84, 4, frames.device) if base is None else _need(base, name="base")
+    n_store = n if n_store is None else n_store
+    y = _alloc((2 * n, 32, 41, 41), torch.float32, frames.device)
+    xaug = _alloc((2 * n, 9, 84, 84), torch.float32, frames.device, "zero")
+    fn = lib.drq_conv1_aug_fwd_frames_bf16 if bf16 else lib.drq_conv1_aug_fwd_frames
+    check(fn(ptr(frames), ptr(first), R, N, ptr(idx), ptr(shift), ptr(idx1), ptr(shift1), ptr(base),
+             ptr(_need(w, name="w")), ptr(_need(b, name="b")), ptr(xaug), ptr(y), n, n_store, _stream()),
+          "drq_conv1_aug_fwd_frames")
+    return y, xaug
+
+
+def vec_stack_gather(frames, first, R, N, slots=None, t=0):
+    """drq_vec_stack_gather: the frame stacks [n, 3 * frame bytes] whose newest frames are `slots` (int64), or, without
+    slots, those of the N environments of absolute row t, out of a single-frame ring (frames [R N, frame bytes])."""
+    lib = _lib.load()
+    _need(frames, torch.uint8, "frames"), _need(first, torch.uint8, "first")
+    n, fb = (N if slots is None else slots.numel()), frames.shape[1]
+    out = _alloc((n, 3 * fb), torch.uint8, frames.device)
+    check(lib.drq_vec_stack_gather(ptr(frames), ptr(first), R, N, fb, ptr(slots), t, n, ptr(out), _stream()),
+          "drq_vec_stack_gather")
+    return out
+
+
 def u8_normalize(x):
     lib = _lib.load()
     _need(x, torch.uint8, "obs")

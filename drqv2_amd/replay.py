@@ -23,6 +23,11 @@ Vectorised collection (new: VecDeviceReplay, csrc/vecreplay.hip).  N environment
 step into a ring, straight from device tensors; episode boundaries are flags on the device, an n-step window ends at
 one, and the batches are the IndexedBatch above.  The episode store and everything it does are unchanged.  With
 `priority_alpha` the ring carries the same sum tree over its slots, kept and drawn from entirely on the device.
+
+Single frames (new: VecFrameReplay, csrc/vecframes.hip).  The same ring with ONE 3 x 84 x 84 frame per slot instead of the
+three-frame stack: a third of the memory and of add()'s traffic.  The stack is put together where it is read -- by the
+fused aug+conv1 launch of update() (a FrameBatch carries the ring's flags), by observation() for act_batch(), by
+materialize() -- following the reset rule of the reference's FrameStackWrapper (dmc.py:87-109).
 """
 import numpy as np
 import torch
@@ -47,6 +52,37 @@ class IndexedBatch(tuple):
         obs_idx, action, reward, discount, next_idx = self
         shp = (obs_idx.numel(),) + tuple(obs_shape)
         return (self.frames[obs_idx].view(shp), action, reward, discount, self.frames[next_idx].view(shp))
+
+
+class FrameBatch(IndexedBatch):
+    """An IndexedBatch drawn from a ring of SINGLE frames (VecFrameReplay): obs / next_obs are the slots of the newest
+    frame of each stack, and the batch also carries the ring -- `ring` = (first, R, N): the reset flags uint8 [R N] on
+    the device and the ring's shape.  DrQV2Agent.update() hands all of it to the fused aug+conv1 launch, which gathers
+    every 9-channel stack from three slots (drq_update_phase_frames); the stacks are never materialised."""
+
+    def __new__(cls, frames, obs_idx, action, reward, discount, next_idx, first, R, N):
+        self = super().__new__(cls, frames, obs_idx, action, reward, discount, next_idx)
+        self.ring = (first, int(R), int(N))
+        return self
+
+    def stacks(self, slots, out=None):
+        """uint8 [n, 3 * frame bytes]: the stacks whose newest frames are `slots` (int64 [n] on the device), one launch
+        (drq_vec_stack_gather) on the current stream; out: a buffer to write into"""
+        first, R, N = self.ring
+        n, fb = slots.numel(), self.frames.shape[1]
+        if out is None:
+            out = torch.empty((n, 3 * fb), dtype=torch.uint8, device=self.frames.device)
+        with torch.cuda.device(self.frames.device):
+            check(_lib.load().drq_vec_stack_gather(ptr(self.frames), ptr(first), R, N, fb, ptr(slots.contiguous()), 0, n,
+                                                   ptr(out), torch.cuda.current_stream().cuda_stream),
+                  "drq_vec_stack_gather")
+        return out
+
+    def materialize(self, obs_shape=(9, 84, 84), out=(None, None)):
+        """The batch as the reference's loader would hand it over, the stacks gathered from the ring."""
+        obs_idx, action, reward, discount, next_idx = self
+        shp = (obs_idx.numel(),) + tuple(obs_shape)
+        return (self.stacks(obs_idx, out[0]).view(shp), action, reward, discount, self.stacks(next_idx, out[1]).view(shp))
 
 
 class PrioritizedBatch:
@@ -74,6 +110,10 @@ class _PrioritizedTuple(PrioritizedBatch, tuple):
 
 
 class _PrioritizedIndexed(PrioritizedBatch, IndexedBatch):
+    pass
+
+
+class _PrioritizedFrames(PrioritizedBatch, FrameBatch):
     pass
 
 
@@ -393,6 +433,7 @@ class VecDeviceReplay:
     cannot know: the batch then consists of steps-0 rows on slot(lo, 0) with weight 1."""
 
     K = 4       # candidates per batch row (the columns of the u table)
+    _draw_copies = True     # a materialised batch's frames are copied by the draw itself (drq_vec_sample)
 
     def __init__(self, rows, num_envs, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=True,
                  guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
@@ -400,7 +441,8 @@ class VecDeviceReplay:
         allocated and every draw and launch is what it was.  priority_beta is a plain attribute, read at every draw."""
         self.device = torch.device(device)
         self.obs_shape = tuple(int(s) for s in obs_shape)
-        self.frame_bytes = int(np.prod(self.obs_shape))
+        self.slot_shape = self.obs_shape           # what add() stores per environment; here the whole observation
+        self.frame_bytes = self.stack_bytes = int(np.prod(self.obs_shape))     # bytes per slot, per observation
         self.R, self.N, self.A = int(rows), int(num_envs), int(action_dim)
         self.nstep, self.gamma, self.guard_rows = int(nstep), float(discount), int(guard_rows)
         if self.frame_bytes <= 0 or self.frame_bytes % 16:
@@ -433,6 +475,10 @@ class VecDeviceReplay:
     def bounds(self):
         """(lo, hi): the drawable rows; hi < lo while there are none"""
         return max(1, self.T - self.R + 1 + self.guard_rows), self.T - self.nstep
+
+    def _batch(self, prioritized, idx, act, rew, disc):
+        """the indexed batch of a draw whose slots are idx [3][B]"""
+        return (_PrioritizedIndexed if prioritized else IndexedBatch)(self.frames, idx[0], act, rew, disc, idx[1])
 
     def __len__(self):
         """drawable transitions, reset rows included: rows x environments"""
@@ -483,7 +529,7 @@ class VecDeviceReplay:
         handed to the launch as they are and nothing waits; numpy arrays and host tensors are staged with a blocking
         copy."""
         N, f32 = self.N, (torch.float32, torch.float64)
-        args = [self._row(obs, "obs", [(N,) + self.obs_shape, (N, self.frame_bytes)], (torch.uint8,)),
+        args = [self._row(obs, "obs", [(N,) + self.slot_shape, (N, self.frame_bytes)], (torch.uint8,)),
                 self._row(action, "action", [(N, self.A)], f32),
                 self._row(reward, "reward", [(N,), (N, 1)], f32),
                 self._row(discount, "discount", [(N,), (N, 1)], f32),
@@ -529,18 +575,22 @@ class VecDeviceReplay:
         if not self.indexed:
             out = self._frames_out.get(B)
             if out is None:         # one batch size at a time, reused every call (DeviceReplay.gather's buffers)
-                out = tuple(torch.empty((B, self.frame_bytes), dtype=torch.uint8, device=dev) for _ in range(2))
+                out = tuple(torch.empty((B, self.stack_bytes), dtype=torch.uint8, device=dev) for _ in range(2))
                 self._frames_out = {B: out}
             obs, nxt = out
+        copies = not self.indexed and self._draw_copies
         with torch.cuda.device(dev):
             check(_lib.load().drq_vec_sample(ptr(self.first), ptr(self.action), ptr(self.reward), ptr(self.discount), self.R,
                                              self.N, self.A, self.frame_bytes, lo, hi, ptr(u), B, K, self.nstep, self.gamma,
                                              ptr(idx), ptr(act), ptr(rew), ptr(disc), ptr(steps),
-                                             None if self.indexed else ptr(self.frames), ptr(obs), ptr(nxt), self._stream()),
-                  "drq_vec_sample")
+                                             ptr(self.frames) if copies else None, ptr(obs) if copies else None,
+                                             ptr(nxt) if copies else None, self._stream()), "drq_vec_sample")
         self.last_steps, self.last_index = steps, idx
+        batch = self._batch(False, idx, act, rew, disc)
         if self.indexed:
-            return IndexedBatch(self.frames, idx[0], act, rew, disc, idx[1])
+            return batch
+        if not copies:              # the ring holds no whole observation to copy: the batch gathers them
+            return batch.materialize(self.obs_shape, (obs, nxt))
         shp = (B,) + self.obs_shape
         return obs.view(shp), act, rew, disc, nxt.view(shp)
 
@@ -562,7 +612,7 @@ class VecDeviceReplay:
                                                  ptr(act), ptr(rew), ptr(disc), ptr(steps), ptr(w), self._stream()),
                   "drq_vec_per_sample")
         self.last_steps, self.last_index = steps, idx
-        return _PrioritizedIndexed(self.frames, idx[0], act, rew, disc, idx[1])._per(self, idx[2], w)
+        return self._batch(True, idx, act, rew, disc)._per(self, idx[2], w)
 
     def _stamp_now(self):
         return self.T               # the number of rows the ring held at the draw
@@ -582,3 +632,68 @@ class VecDeviceReplay:
         return BatchIterator(lambda: self.sample(self.batch_size))
 
     batch_size = 256
+
+
+class VecFrameReplay(VecDeviceReplay):
+    """VecDeviceReplay with ONE frame per slot (new; the contract is in include/drqv2_hip.h, "single-frame step-major
+    replay"): add() takes the newest uint8 [N, 3, 84, 84] frame of every environment, as a renderer hands it out, and a
+    slot is 21,168 bytes instead of the 63,504 of a three-frame stack whose two older frames its neighbours hold anyway.
+    The 9-channel observation is put together when it is read, by the rule of the reference's FrameStackWrapper
+    (dmc.py:87-109): the frames of rows t-2, t-1, t of the environment, refilled with the episode's first frame where a
+    reset row lies among them.  Nobody stacks on the host:
+      observation()   the stacks of the newest row, for agent.act_batch()
+      sample()        a FrameBatch (indexed=True): the frames stay in the ring, update()'s fused aug+conv1 launch
+                      gathers the stacks itself; indexed=False: the materialised 5-tuple, gathered by one kernel
+    Everything else -- rows, flags, windows, draws, `priority_alpha`, guard_rows -- is VecDeviceReplay's, launch for
+    launch.  The drawable rows start two rows later, lo = max(1, T - rows + 1 + guard_rows + 2): the oldest frame of an
+    obs stack lies three rows before its transition and must stay in the ring while guard_rows rows are added; hence
+    rows >= nstep + guard_rows + 4.  A VecDeviceReplay(guard_rows + 2) fed the stacks draws the same batches.
+    Restrictions of update() on these batches: single GPU, no behaviour cloning, and prioritized batches in fp32 only.
+    Only three-frame stacks of 3 x 84 x 84 frames: the kernels that gather are built for them."""
+
+    _draw_copies = False
+
+    def __init__(self, rows, num_envs, action_dim, nstep, discount, device, frame_shape=(3, 84, 84), seed=None,
+                 indexed=True, guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
+        if tuple(int(s) for s in frame_shape) != (3, 84, 84):
+            raise ValueError(f"frame_shape {tuple(frame_shape)}: the single-frame ring stacks three (3, 84, 84) frames")
+        if int(rows) < int(nstep) + int(guard_rows) + 4:
+            raise ValueError(f"rows {rows}: at least nstep + guard_rows + 4 = {int(nstep) + int(guard_rows) + 4}")
+        super().__init__(rows, num_envs, frame_shape, action_dim, nstep, discount, device, seed=seed, indexed=indexed,
+                         guard_rows=guard_rows, priority_alpha=priority_alpha, priority_beta=priority_beta,
+                         priority_eps=priority_eps)
+        self.frame_shape = self.slot_shape
+        self.obs_shape = (9, 84, 84)               # what observation() and a materialised batch hold
+        self.stack_bytes = 3 * self.frame_bytes
+        self._obs_out = None
+
+    def bounds(self):
+        """(lo, hi): the drawable rows; hi < lo while there are none"""
+        return max(1, self.T - self.R + 1 + self.guard_rows + 2), self.T - self.nstep
+
+    def _batch(self, prioritized, idx, act, rew, disc):
+        return (_PrioritizedFrames if prioritized else FrameBatch)(self.frames, idx[0], act, rew, disc, idx[1], self.first,
+                                                                   self.R, self.N)
+
+    def add(self, frame, action, reward, discount, first=None):
+        """As VecDeviceReplay.add(), with frame uint8 [N, 3, 84, 84]: the newest frame of every environment after the
+        step (on a reset row: the first frame of the new episode)."""
+        super().add(frame, action, reward, discount, first)
+
+    def observation(self):
+        """uint8 [N, 9, 84, 84] on the device: the frame stacks of the newest row, what a FrameStackWrapper per
+        environment would return after the last add() -- ready for agent.act_batch().  One launch
+        (drq_vec_stack_gather), nothing waits.  Two output buffers are used in turn: a returned tensor is overwritten
+        by the second observation() call after it, so a caller that keeps one longer clones it."""
+        _on_gpu(self, "the step-major replay lives")
+        if self.T == 0:
+            raise _lib.DrqError("observation(): no row has been added yet")
+        if self._obs_out is None:
+            self._obs_out = [torch.empty((self.N,) + self.obs_shape, dtype=torch.uint8, device=self.device)
+                             for _ in range(2)] + [0]
+        out = self._obs_out[self._obs_out[2]]
+        self._obs_out[2] ^= 1
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_stack_gather(ptr(self.frames), ptr(self.first), self.R, self.N, self.frame_bytes, None,
+                                                   self.T - 1, self.N, ptr(out), self._stream()), "drq_vec_stack_gather")
+        return out

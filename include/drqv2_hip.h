@@ -56,6 +56,19 @@ int drq_conv1_aug_fwd(const uint8_t* obs, const float* shift, const uint8_t* obs
 int drq_conv1_aug_fwd_indexed(const uint8_t* frames, const int64_t* idx, const float* shift, const uint8_t* frames1,
                               const int64_t* idx1, const float* shift1, const float* base_grid, const float* w,
                               const float* bias, float* xaug, float* y, int n, int n_store, drq_stream_t stream);
+/* the same with both views taken from ONE ring of single frames ("single-frame step-major replay" below): frames u8
+ * [R N][3][84][84], first u8 [R N]; idx[b] / idx1[b] in [0, R N) are the slots of the NEWEST frame of row b's two stacks,
+ * the launch finds the other two frames by the flags.  Bit-identical to drq_conv1_aug_fwd on the stacks
+ * drq_vec_stack_gather produces for idx and idx1; _bf16: likewise to drq_conv1_aug_fwd_bf16.  DRQ_EARG also for null
+ * first / idx / idx1, R, N <= 0 or R N > INT32_MAX. */
+int drq_conv1_aug_fwd_frames(const uint8_t* frames, const uint8_t* first, long R, long N, const int64_t* idx,
+                             const float* shift, const int64_t* idx1, const float* shift1, const float* base_grid,
+                             const float* w, const float* bias, float* xaug, float* y, int n, int n_store,
+                             drq_stream_t stream);
+int drq_conv1_aug_fwd_frames_bf16(const uint8_t* frames, const uint8_t* first, long R, long N, const int64_t* idx,
+                                  const float* shift, const int64_t* idx1, const float* shift1, const float* base_grid,
+                                  const float* w, const float* bias, float* xaug, float* y, int n, int n_store,
+                                  drq_stream_t stream);
 int drq_conv1_aug_fwd_bf16(const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                            const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
                            int n_store, drq_stream_t stream);
@@ -427,6 +440,35 @@ int drq_vec_per_sample(const double* tree, long L, const uint8_t* first, const f
 int drq_vec_per_update(double* tree, long L, const uint8_t* first, long R, long N, long T, long lo, long hi,
                        const long* pos, const float* td_abs, int B, double alpha, double eps, drq_stream_t stream);
 
+/* ---- single-frame step-major replay: the ring stores ONE frame per slot and a frame stack is put together where it is
+ * read.  New functionality (the reference stacks in the environment wrapper, dmc.py:87-109, and stores every stack
+ * whole: two thirds of each slot repeat its neighbours); these definitions are the contract.
+ * Storage: the ring of "step-major replay", R rows x N environments, with frames u8 [R N][fb], fb = 3*84*84 = 21168: one
+ *   CHW frame per slot, the newest frame of the observation after step t.  action, reward, discount and first are
+ *   unchanged, and so are drq_vec_add (frame_bytes = fb), drq_vec_sample (without frame outputs) and the
+ *   drq_vec_per_* entries.
+ * The stack at (t, e) is what FrameStackWrapper holds after step t (dmc.py:87-88, 98-109): three frames concatenated
+ *   along the channel axis, oldest first, refilled with the first frame on reset.  With p0 = slot(t, e),
+ *   p1 = slot(t-1, e), p2 = slot(t-2, e), rows modulo R:
+ *     first[p0] != 0       -> (p0, p0, p0)
+ *     else first[p1] != 0  -> (p1, p1, p0)
+ *     else                 -> (p2, p1, p0)
+ *   Row 0 is always a reset row, so no row below 0 is ever addressed; whatever the flags hold, every slot read lies in
+ *   the ring, and first[p1] is read only where first[p0] does not decide.
+ * Transitions are as before: at (t, e), obs is the stack at (t-1, e), next_obs the stack at (t+k-1, e); idx_out[0] and
+ *   idx_out[1] of the draws are the slots of the NEWEST frame of each stack.
+ * Drawable rows: hi = T - nstep, lo = max(1, T - R + 1 + guard_rows + 2).  The two extra rows keep the oldest frame of an
+ *   obs stack (row t-3) inside the ring while guard_rows rows are added; R >= nstep + guard_rows + 4.
+ *
+ * drq_vec_stack_gather: one launch writes out u8 [n][3 frame_bytes], row b = the stack whose newest frame is slot
+ *   slots[b] (int64 [n] on the device, each in [0, R N); a slot outside leaves its row unwritten and reads nothing).
+ *   slots == NULL: the n = N stacks of absolute row t >= 0, environment b in row b -- the observations after step t.
+ *   16-byte loads and stores; any frame_bytes % 16 == 0.
+ *   DRQ_EARG, nothing written: null frames / first / out, R, N, n, frame_bytes <= 0, frame_bytes % 16 != 0, frames or out
+ *   not 16-byte aligned, slots not 8-byte aligned; without slots: t < 0 or n != N. */
+int drq_vec_stack_gather(const uint8_t* frames, const uint8_t* first, long R, long N, long frame_bytes,
+                         const int64_t* slots, long t, int n, uint8_t* out, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,
@@ -592,6 +634,16 @@ int drq_update_phase_bc(const DrqStep* s, int phase, float bc_alpha);
  * other sums and the actor step are the plain update's; weights of 1.0f give the plain update bit for bit.
  * DRQ_EARG: null is_weight / td_abs, or global_B != B (single GPU only).  The descriptor is unchanged. */
 int drq_update_phase_per(const DrqStep* s, int phase, const float* is_weight, float* td_abs);
+
+/* The indexed update on a single-frame ring ("single-frame step-major replay"): s->obs == s->next_obs = the ring's
+ * frames u8 [R N][3][84][84], s->obs_index / s->next_obs_index = the newest-frame slots of the two stacks of every row,
+ * first u8 [R N] the ring's flags.  is_weight and td_abs: both NULL = the plain loss, both given =
+ * drq_update_phase_per's weighted loss.  The launches are the indexed update's one for one (the fused aug+conv1 launch
+ * gathers the stacks); the result is, bit for bit, the update on the stacks drq_vec_stack_gather produces.
+ * DRQ_EARG: null first, R, N <= 0, missing indices, s->obs != s->next_obs, global_B != B (single GPU only), one of
+ * is_weight / td_abs without the other.  The descriptor is unchanged. */
+int drq_update_phase_frames(const DrqStep* s, int phase, const uint8_t* first, long R, long N, const float* is_weight,
+                            float* td_abs);
 
 /* sums[0..7] -> sums_host[0..7], then seq -> slot 8 with system-scope release (see DrqStep.sums_host); for hosts
  * that reduce the sums themselves before publishing them. */

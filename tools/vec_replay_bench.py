@@ -26,6 +26,13 @@ drq_vec_per_update more).  Same steps, updates, repeats and the same two figures
 ever reset here, so every drawable slot carries a priority.
 
   python tools/vec_replay_bench.py --priority-alpha 0.6 [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--updates 200]
+
+--single-frames measures the single-frame ring (VecFrameReplay: one 3x84x84 frame per slot, the stacks gathered by the
+consumer) against the stacked ring of the same shape, alternated in the same way: add() + sample(256) per environment
+step -- the single-frame add() moves a third of the bytes --, update() with one add() in front of it (the fused
+aug+conv1 launch gathers the stacks from three slots), and observation(), the gather that feeds act_batch().
+
+  python tools/vec_replay_bench.py --single-frames [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--updates 200]
 """
 import argparse
 import os
@@ -38,7 +45,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
 from drqv2_amd import synth  # noqa: E402
-from drqv2_amd.replay import DeviceReplay, VecDeviceReplay  # noqa: E402
+from drqv2_amd.replay import DeviceReplay, VecDeviceReplay, VecFrameReplay  # noqa: E402
 
 OBS = (9, 84, 84)
 A, NSTEP, B = 6, 3, 256
@@ -132,36 +139,57 @@ def make_agent():
 def prioritized(N, args, ag):
     """uniform ring against prioritized ring at N environments: collection steps, then updates, alternated per repeat"""
     rows = pool_rows(N)
-    first = torch.zeros(N, dtype=torch.bool, device="cuda")
     mk = lambda alpha: VecDeviceReplay(max(32, SLOTS // N), N, OBS, A, NSTEP, 0.99, "cuda", seed=1, priority_alpha=alpha)
-    rings = {"uniform": mk(None), "prioritized": mk(args.priority_alpha)}
+    two_rings(N, args, ag, {"uniform": (mk(None), rows), "prioritized": (mk(args.priority_alpha), rows)})
+
+
+def single_frames(N, args, ag):
+    """stacked ring against single-frame ring at N environments, same rows and slots; then observation()"""
+    rows = pool_rows(N)
+    newest = [(r[0][:, 6:9].contiguous(),) + r[1:] for r in rows]      # the frame a renderer hands out
+    R = max(32, SLOTS // N)
+    single = VecFrameReplay(R, N, A, NSTEP, 0.99, "cuda", seed=1)
+    stacked = VecDeviceReplay(R, N, OBS, A, NSTEP, 0.99, "cuda", seed=1)
+    print(f"N={N:5d}  bytes per slot: stacked {stacked.frame_bytes}, single {single.frame_bytes}; per add(): "
+          f"{N * stacked.frame_bytes / 1e6:.1f} MB against {N * single.frame_bytes / 1e6:.1f} MB", flush=True)
+    two_rings(N, args, ag, {"stacked": (stacked, rows), "single": (single, newest)})
+    v = [timed(lambda i: single.observation(), args.steps) for _ in range(args.repeats)]
+    print(f"N={N:5d}  single      ring  observation(): device-event {spread([x[0] for x in v])}   host wall "
+          f"{spread([x[1] for x in v])}   ({args.steps} x {args.repeats})", flush=True)
+
+
+def two_rings(N, args, ag, rings):
+    """rings: name -> (store, its pool of rows); collection steps, then updates, alternated per repeat"""
+    first = torch.zeros(N, dtype=torch.bool, device="cuda")
+    rows = {k: r for k, (_, r) in rings.items()}
+    rings = {k: ring for k, (ring, _) in rings.items()}
     its = {}
     for k, ring in rings.items():
         ring.batch_size = B
         for i in range(NSTEP + 1 + 20):
-            ring.add(*rows[i & 3], first)
+            ring.add(*rows[k][i & 3], first)
         its[k] = iter(ring)
 
-    def step(ring):
+    def step(k):
         def fn(i):
-            ring.add(*rows[i & 3], first)
-            ring.sample(B)
+            rings[k].add(*rows[k][i & 3], first)
+            rings[k].sample(B)
         return fn
 
     def update(k):
         def fn(i):
-            rings[k].add(*rows[i & 3], first)
+            rings[k].add(*rows[k][i & 3], first)
             ag.update(its[k], i)
         return fn
 
     for k in rings:
         for i in range(20):
-            step(rings[k])(i)
+            step(k)(i)
             update(k)(i)
     res = {(what, k): [] for what in ("step", "update") for k in rings}
     for _ in range(args.repeats):
         for k in rings:
-            res["step", k].append(timed(step(rings[k]), args.steps))
+            res["step", k].append(timed(step(k), args.steps))
         for k in rings:
             res["update", k].append(timed(update(k), args.updates))
     for (what, k), v in res.items():
@@ -215,13 +243,15 @@ def main():
     ap.add_argument("--envs", default="16,256,1024")
     ap.add_argument("--priority-alpha", type=float, default=None,
                     help="measure the uniform ring against the prioritized one instead of against the episode store")
+    ap.add_argument("--single-frames", action="store_true",
+                    help="measure the stacked ring against the single-frame ring (VecFrameReplay) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
-    if args.priority_alpha is not None:
+    if args.priority_alpha is not None or args.single_frames:
         ag = make_agent()
         for N in (int(x) for x in args.envs.split(",")):
-            prioritized(N, args, ag)
+            (single_frames if args.single_frames else prioritized)(N, args, ag)
             torch.cuda.empty_cache()
         return
     for N in (int(x) for x in args.envs.split(",")):
