@@ -6,6 +6,14 @@
 // 16-byte pieces.  Which slot that is follows from the newest frame's slot and at most two `first` bytes
 // (ring_stack_slots, replay_device.h: shared with the fused aug+conv1 launch, which gathers the same stacks on its own);
 // every lane reads the same bytes, so the loads are broadcast.  Plain vector loads and stores, no atomics.
+//
+// drq_nstep_gather_frames is drq_nstep_gather (elementwise.hip) for an episode store of single frames: a flat ring of R
+// slots, N = 1, every episode contiguous with first = 1 on its first slot.  One launch of B x (6 P + 1) workgroups:
+// workgroup (b, 6 P) with b < ceil(B / 256) does the scalars of 256 batch rows, one thread per row, with nstep_sum --
+// drq_nstep_gather's arithmetic on the same operands; workgroup (b, g P + j) copies piece j of frame g of row b (g = 0 .. 2:
+// the obs stack, 3 .. 5: the next_obs stack, oldest frame first), kFramePiece 16-byte chunks per thread, all of a
+// thread's loads issued before its first store.  Consecutive lanes move consecutive 16-byte chunks: every wave
+// instruction is 1 KiB, contiguous and aligned to 16 bytes.  No LDS, nothing crosses workgroups.
 #include "common.h"
 #include "replay_device.h"
 #include "../../include/drqv2_hip.h"
@@ -34,7 +42,84 @@ __global__ __launch_bounds__(256) void vec_stack_gather_kernel(StackGatherArgs a
   for (long i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
 }
 
+constexpr int kFramePiece = 2;      // 16-byte chunks per thread: 21,168-byte frames are 1,323 chunks = 3 pieces of 512
+
+struct NstepFramesArgs {
+  const uint8_t* frames;
+  const uint8_t* first;
+  const float* action;
+  const float* reward;
+  const float* discount;
+  const long* pos;
+  uint8_t* obs;           // null (with next_obs): the scalars only
+  uint8_t* next_obs;
+  float* act_out;
+  float* rew_out;
+  float* disc_out;
+  long R, frame_bytes;
+  int B, A, nstep, pieces;
+  float gamma;
+};
+
+__global__ __launch_bounds__(256) void nstep_gather_frames_kernel(NstepFramesArgs a) {
+  const int y = a.obs ? blockIdx.y : 6 * a.pieces;  // no output frames: the scalars only (grid.y == 1)
+  if (y == 6 * a.pieces) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const long p = a.pos[b];
+    if (p < 1 || p > a.R - a.nstep) return;         // slot p-1 or the window p .. p+nstep-1 is no part of the store
+    for (int j = 0; j < a.A; ++j) a.act_out[(long)b * a.A + j] = a.action[p * a.A + j];
+    float r, d;
+    nstep_sum(a.reward, a.discount, a.gamma, a.nstep, [p](int i) { return p + i; }, r, d);
+    a.rew_out[b] = r;
+    a.disc_out[b] = d;
+    return;
+  }
+  const int b = blockIdx.x;
+  const long p = a.pos[b];
+  if (p < 1 || p > a.R - a.nstep) return;           // the row is left as it was, nothing is read
+  const int g = y / a.pieces, piece = y - g * a.pieces;
+  const bool next = g >= 3;
+  long s[3];
+  ring_stack_slots(a.first, a.R, 1, next ? p + a.nstep - 1 : p - 1, s);
+  const int f = next ? g - 3 : g;
+  const uint4* src = reinterpret_cast<const uint4*>(a.frames + s[f] * a.frame_bytes);
+  uint4* dst = reinterpret_cast<uint4*>((next ? a.next_obs : a.obs) + ((long)b * 3 + f) * a.frame_bytes);
+  const long n16 = a.frame_bytes >> 4;
+  const long i0 = (long)piece * (kFramePiece * 256) + threadIdx.x;
+  uint4 v[kFramePiece];
+#pragma unroll
+  for (int u = 0; u < kFramePiece; ++u)
+    if (i0 + u * 256 < n16) v[u] = src[i0 + u * 256];
+#pragma unroll
+  for (int u = 0; u < kFramePiece; ++u)
+    if (i0 + u * 256 < n16) dst[i0 + u * 256] = v[u];
+}
+
 }  // namespace
+
+DRQ_API int drq_nstep_gather_frames(const uint8_t* frames, const uint8_t* first, long R, const float* action,
+                                    const float* reward, const float* discount, const long* pos, int B, int A,
+                                    long frame_bytes, int nstep, float gamma, uint8_t* obs, float* act_out, float* rew_out,
+                                    float* disc_out, uint8_t* next_obs, drq_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!frames || !first || !action || !reward || !discount || !pos || !act_out || !rew_out || !disc_out) return DRQ_EARG;
+  if ((obs != nullptr) != (next_obs != nullptr)) return DRQ_EARG;
+  if (R <= 0 || B <= 0 || A <= 0 || nstep <= 0 || frame_bytes <= 0 || frame_bytes % 16) return DRQ_EARG;
+  if (((uintptr_t)frames | (uintptr_t)obs | (uintptr_t)next_obs) & 15) return DRQ_EARG;
+  if (((uintptr_t)action | (uintptr_t)reward | (uintptr_t)discount | (uintptr_t)act_out | (uintptr_t)rew_out |
+       (uintptr_t)disc_out) & 3)
+    return DRQ_EARG;
+  if ((uintptr_t)pos & 7) return DRQ_EARG;
+  const long pieces = ((frame_bytes >> 4) + kFramePiece * 256 - 1) / (kFramePiece * 256);
+  if (6 * pieces + 1 > 65535) return DRQ_EARG;          // grid.y: frames beyond 85 MB
+  NstepFramesArgs a{frames, first, action, reward, discount, pos, obs, next_obs, act_out, rew_out, disc_out, R,
+                    frame_bytes, B, A, nstep, (int)pieces, gamma};
+  if (obs) hipLaunchKernelGGL(nstep_gather_frames_kernel, dim3(B, 6 * (unsigned)pieces + 1), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(nstep_gather_frames_kernel, dim3((B + 255) / 256, 1), dim3(256), 0, st, a);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
 
 DRQ_API int drq_vec_stack_gather(const uint8_t* frames, const uint8_t* first, long R, long N, long frame_bytes,
                                  const long* slots, long t, int n, uint8_t* out, drq_stream_t stream) {

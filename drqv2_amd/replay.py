@@ -28,6 +28,10 @@ Single frames (new: VecFrameReplay, csrc/vecframes.hip).  The same ring with ONE
 three-frame stack: a third of the memory and of add()'s traffic.  The stack is put together where it is read -- by the
 fused aug+conv1 launch of update() (a FrameBatch carries the ring's flags), by observation() for act_batch(), by
 materialize() -- following the reset rule of the reference's FrameStackWrapper (dmc.py:87-109).
+
+Single frames in the episode store (new: DeviceReplay(single_frames=True)).  The episode store is that ring with N = 1:
+episodes are contiguous, a `first` byte marks the slot each one starts on.  add_episode() keeps the newest frame of every
+step, indexed batches are FrameBatch objects, materialised ones come from one launch (drq_nstep_gather_frames).
 """
 import numpy as np
 import torch
@@ -55,10 +59,11 @@ class IndexedBatch(tuple):
 
 
 class FrameBatch(IndexedBatch):
-    """An IndexedBatch drawn from a ring of SINGLE frames (VecFrameReplay): obs / next_obs are the slots of the newest
-    frame of each stack, and the batch also carries the ring -- `ring` = (first, R, N): the reset flags uint8 [R N] on
-    the device and the ring's shape.  DrQV2Agent.update() hands all of it to the fused aug+conv1 launch, which gathers
-    every 9-channel stack from three slots (drq_update_phase_frames); the stacks are never materialised."""
+    """An IndexedBatch drawn from a ring of SINGLE frames (VecFrameReplay, or DeviceReplay(single_frames=True): R = its
+    capacity, N = 1): obs / next_obs are the slots of the newest frame of each stack, and the batch also carries the
+    ring -- `ring` = (first, R, N): the reset flags uint8 [R N] on the device and the ring's shape.  DrQV2Agent.update()
+    hands all of it to the fused aug+conv1 launch, which gathers every 9-channel stack from three slots
+    (drq_update_phase_frames); the stacks are never materialised."""
 
     def __new__(cls, frames, obs_idx, action, reward, discount, next_idx, first, R, N):
         self = super().__new__(cls, frames, obs_idx, action, reward, discount, next_idx)
@@ -142,6 +147,24 @@ def _td_rows(pos, td_abs):
     return B
 
 
+def newest_frames(obs, check=True):
+    """The single frames of an episode's `observation`, uint8 [T+1, 3, 84, 84] contiguous: a [T+1, 3, 84, 84] array as it
+    is, of a [T+1, 9, 84, 84] array of frame stacks channels 6:9 of every step.  check: a stacked episode must be what
+    the reference's FrameStackWrapper (dmc.py:87-109) builds -- the three frames of obs[0] equal, and
+    obs[t][0:6] == obs[t-1][3:9] for t >= 1 -- or the frames dropped here could not be put together again: ValueError."""
+    obs = np.asarray(obs)
+    if obs.dtype != np.uint8 or obs.ndim != 4 or obs.shape[0] < 1 or obs.shape[1:] not in ((3, 84, 84), (9, 84, 84)):
+        raise ValueError("observation must be uint8 [T+1, 9, 84, 84] frame stacks or [T+1, 3, 84, 84] single frames")
+    if obs.shape[1] == 9 and check:
+        if not (np.array_equal(obs[0, 0:3], obs[0, 3:6]) and np.array_equal(obs[0, 3:6], obs[0, 6:9])):
+            raise ValueError("observation[0] is no reset stack: its three frames differ (dmc.py:98-103)")
+        if not np.array_equal(obs[1:, 0:6], obs[:-1, 3:9]):
+            t = 1 + int(np.argmax((obs[1:, 0:6] != obs[:-1, 3:9]).reshape(obs.shape[0] - 1, -1).any(axis=1)))
+            raise ValueError(f"observation[{t}] is no frame stack: its two older frames are not the two newer ones of "
+                             f"observation[{t - 1}] (dmc.py:105-109); check_stacks=False stores it all the same")
+    return np.ascontiguousarray(obs[:, -3:])
+
+
 def _on_gpu(store, what):
     if store.device.type != "cuda":
         raise _lib.DrqError(f"{what} on the GPU: the HIP path has no CPU fallback")
@@ -198,8 +221,21 @@ class BatchIterator:
 
 class DeviceReplay:
     def __init__(self, capacity_steps, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=False,
-                 priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
-        """priority_alpha: None = uniform sampling (no tree is allocated, the draws from the RandomState are what they
+                 priority_alpha=None, priority_beta=0.4, priority_eps=1e-6, single_frames=False, check_stacks=True):
+        """single_frames: False = every slot holds the whole observation, as the reference stores it.  True = a slot holds
+        the ONE new 3 x 84 x 84 frame of its step (21,168 bytes instead of 63,504) and `first` (uint8 [capacity] on the
+        device) marks the slot every episode starts on; obs_shape must be (9, 84, 84).  The store is then the single-frame
+        ring of include/drqv2_hip.h with N = 1 and R = capacity, and whoever reads puts the stacks together: update()'s
+        fused aug+conv1 launch (indexed=True yields FrameBatch objects), drq_nstep_gather_frames for the materialised
+        5-tuple (indexed=False, one launch), FrameBatch.materialize().  Slots, eviction, draws and the priority tree are
+        the stacked store's: same seed, same episodes, same positions.  Stale flags are harmless: those of evicted
+        episodes stay where they are, but a flag is only read for slots of a live episode, at or before the slot drawn
+        (positions start at the episode's slot 1); the frame two slots back is read only where the flags of the slot and
+        of the one before it are both 0, two slots or more past the episode's start; an episode at slot 0 has
+        first[0] = 1.  So no read leaves the episode and the ring's modulo wrap is never taken.  update() on a FrameBatch:
+        single GPU, no behaviour cloning, prioritized batches in fp32 only.
+        check_stacks: add_episode() verifies a stacked episode (newest_frames); False for a caller who knows the source.
+        priority_alpha: None = uniform sampling (no tree is allocated, the draws from the RandomState are what they
         were); a float in (0, 1] = proportional prioritized replay, sample() yields PrioritizedBatch objects.
         priority_beta is a plain attribute, read at every draw: the training loop may anneal it towards 1.
         priority_eps (> 0) keeps a transition with zero error drawable.  The order that keeps every priority update
@@ -210,7 +246,11 @@ class DeviceReplay:
         episode the iterator has not taken over yet."""
         self.device = torch.device(device)
         self.obs_shape = tuple(int(s) for s in obs_shape)
-        self.frame_bytes = int(np.prod(self.obs_shape))
+        self.single_frames, self.check_stacks = bool(single_frames), bool(check_stacks)
+        if self.single_frames and self.obs_shape != (9, 84, 84):
+            raise ValueError(f"obs_shape {self.obs_shape}: a single-frame store stacks three (3, 84, 84) frames")
+        self.stack_bytes = int(np.prod(self.obs_shape))            # bytes per observation
+        self.frame_bytes = self.stack_bytes // 3 if self.single_frames else self.stack_bytes      # bytes per slot
         if self.frame_bytes % 16:
             raise ValueError("frame size must be a multiple of 16 bytes")
         self.A = int(action_dim)
@@ -222,6 +262,8 @@ class DeviceReplay:
         self.action = torch.zeros((self.capacity, self.A), dtype=torch.float32, device=dev)
         self.reward = torch.zeros((self.capacity,), dtype=torch.float32, device=dev)
         self.discount = torch.ones((self.capacity,), dtype=torch.float32, device=dev)
+        # single frames: 1 on the slot an episode starts on (the flags of the ring, include/drqv2_hip.h)
+        self.first = torch.zeros((self.capacity,), dtype=torch.uint8, device=dev) if self.single_frames else None
         self.episodes = []          # [start_slot, steps (= T+1)], oldest first; each contiguous in the store
         self._head = 0              # next free slot
         self.rng = np.random.RandomState(seed)
@@ -275,15 +317,24 @@ class DeviceReplay:
 
     def add_episode(self, episode):
         """episode: dict of numpy arrays like the reference's npz (observation [T+1,...] uint8, action [T+1,A],
-        reward [T+1,1] or [T+1], discount likewise); index 0 is the dummy reset transition."""
-        obs = np.ascontiguousarray(episode["observation"])
+        reward [T+1,1] or [T+1], discount likewise); index 0 is the dummy reset transition.
+        A single-frame store takes observation [T+1, 9, 84, 84] (it keeps and uploads channels 6:9, after checking that
+        the episode is a frame stack: a ValueError leaves the store as it was) or [T+1, 3, 84, 84] (stored as they are)."""
+        if self.single_frames:
+            obs = newest_frames(episode["observation"], self.check_stacks)
+        else:
+            obs = np.ascontiguousarray(episode["observation"])
+            if obs.dtype != np.uint8 or int(np.prod(obs.shape[1:])) != self.frame_bytes:
+                raise ValueError("observation must be uint8 frames of the configured shape")
         n = obs.shape[0]
-        if obs.dtype != np.uint8 or int(np.prod(obs.shape[1:])) != self.frame_bytes:
-            raise ValueError("observation must be uint8 frames of the configured shape")
         start, evicted = self._place(n)
         sl = slice(start, start + n)
         dev = self.device
         self.frames[sl].copy_(torch.from_numpy(obs.reshape(n, self.frame_bytes)), non_blocking=False)
+        if self.single_frames:
+            flags = np.zeros(n, np.uint8)
+            flags[0] = 1
+            self.first[sl].copy_(torch.from_numpy(flags))
         self.action[sl].copy_(torch.from_numpy(np.asarray(episode["action"], np.float32).reshape(n, self.A)))
         self.reward[sl].copy_(torch.from_numpy(np.asarray(episode["reward"], np.float32).reshape(n)))
         self.discount[sl].copy_(torch.from_numpy(np.asarray(episode["discount"], np.float32).reshape(n)))
@@ -318,22 +369,29 @@ class DeviceReplay:
         out = self._out.get(B)
         if out is None:
             dev = self.device
-            out = (torch.empty((B, self.frame_bytes), dtype=torch.uint8, device=dev),
+            out = (torch.empty((B, self.stack_bytes), dtype=torch.uint8, device=dev),
                    torch.empty((B, self.A), dtype=torch.float32, device=dev),
                    torch.empty((B, 1), dtype=torch.float32, device=dev),
                    torch.empty((B, 1), dtype=torch.float32, device=dev),
-                   torch.empty((B, self.frame_bytes), dtype=torch.uint8, device=dev))
+                   torch.empty((B, self.stack_bytes), dtype=torch.uint8, device=dev))
             self._out = {B: out}            # one batch size at a time; the buffers are reused every call
         obs, act, rew, disc, nxt = out
+        shp = (B,) + self.obs_shape
+        if self.single_frames:              # the same batch, the stacks put together from three slots each
+            check(lib.drq_nstep_gather_frames(ptr(self.frames), ptr(self.first), self.capacity, ptr(self.action),
+                                              ptr(self.reward), ptr(self.discount), ptr(pos), B, self.A, self.frame_bytes,
+                                              self.nstep, self.gamma, ptr(obs), ptr(act), ptr(rew), ptr(disc), ptr(nxt),
+                                              torch.cuda.current_stream().cuda_stream), "drq_nstep_gather_frames")
+            return obs.view(shp), act, rew, disc, nxt.view(shp)
         check(lib.drq_nstep_gather(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(pos), B,
                                    self.A, self.frame_bytes, self.nstep, self.gamma, ptr(obs), ptr(act), ptr(rew),
                                    ptr(disc), ptr(nxt), torch.cuda.current_stream().cuda_stream), "drq_nstep_gather")
-        shp = (B,) + self.obs_shape
         return obs.view(shp), act, rew, disc, nxt.view(shp)
 
     def gather_indexed(self, pos):
         """pos: host int64 store indices [B] -> IndexedBatch: action rows and n-step reward / discount assembled by the
-        same kernel (its frame copies skipped), obs = frame pos-1, next_obs = frame pos+nstep-1 as indices."""
+        same kernel (its frame copies skipped), obs = frame pos-1, next_obs = frame pos+nstep-1 as indices.  A
+        single-frame store yields a FrameBatch: the indices name the newest frame of each stack."""
         _on_gpu(self, "replay batch assembly runs")
         lib = _lib.load()
         pos = np.ascontiguousarray(pos, np.int64)
@@ -349,7 +407,14 @@ class DeviceReplay:
         check(lib.drq_nstep_gather(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(idx[2]), B,
                                    self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act), ptr(rew), ptr(disc),
                                    None, torch.cuda.current_stream().cuda_stream), "drq_nstep_gather")
-        return IndexedBatch(self.frames, idx[0], act, rew, disc, idx[1])
+        return self._batch(False, idx, act, rew, disc)
+
+    def _batch(self, prioritized, idx, act, rew, disc):
+        """the indexed batch whose slots are idx [3][B]"""
+        if self.single_frames:
+            return (_PrioritizedFrames if prioritized else FrameBatch)(self.frames, idx[0], act, rew, disc, idx[1],
+                                                                       self.first, self.capacity, 1)
+        return (_PrioritizedIndexed if prioritized else IndexedBatch)(self.frames, idx[0], act, rew, disc, idx[1])
 
     def sample_prioritized(self, batch_size):
         """One stratified draw on the device: u ~ U[0,1)^B from the store's RandomState (one random_sample call per
@@ -377,7 +442,7 @@ class DeviceReplay:
                                            ptr(idx[2]), B, self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act),
                                            ptr(rew), ptr(disc), None, self._stream()), "drq_nstep_gather")
         if self.indexed:
-            batch = _PrioritizedIndexed(self.frames, idx[0], act, rew, disc, idx[1])
+            batch = self._batch(True, idx, act, rew, disc)
         else:
             batch = _PrioritizedTuple(self.gather(idx[2]))
         return batch._per(self, idx[2], w)

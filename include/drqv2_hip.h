@@ -469,6 +469,33 @@ int drq_vec_per_update(double* tree, long L, const uint8_t* first, long R, long 
 int drq_vec_stack_gather(const uint8_t* frames, const uint8_t* first, long R, long N, long frame_bytes,
                          const int64_t* slots, long t, int n, uint8_t* out, drq_stream_t stream);
 
+/* ---- single frames in the episode store: the flat store of "replay batch assembly on the device" with ONE frame per
+ * slot.  It is the ring above with N = 1 and R = the store's slots: frames u8 [R][frame_bytes], action f32 [R][A], reward
+ * and discount f32 [R], first u8 [R].  Every episode is contiguous, its first slot (the dummy reset transition) carries
+ * first = 1 and its other slots first = 0; the flags of slots no live episode covers hold whatever an evicted episode
+ * left.  The stack whose newest frame is slot p0 follows the rule above (p1 = p0 - 1, p2 = p0 - 2), and equals what
+ * FrameStackWrapper held at that step.  Stale flags are harmless: a flag is read only for slots of the live episode
+ * that holds the position drawn, at or before the slot drawn; p2 is read only where first[p0] == first[p1] == 0, that is
+ * two slots or more past the episode's start; an episode that starts at slot 0 has first[0] = 1.  So no read leaves
+ * the episode and the modulo wrap of the rule is never taken.  drq_conv1_aug_fwd_frames, drq_update_phase_frames and
+ * drq_vec_stack_gather serve this store unchanged (N = 1).
+ *
+ * drq_nstep_gather_frames: drq_nstep_gather on such a store, one launch.  Row b of the batch is the transition at
+ *   pos[b] (int64 [B] on the device): obs[b] = the stack whose newest frame is slot pos[b]-1, next_obs[b] = the stack at
+ *   pos[b]+nstep-1, each 3 frame_bytes bytes, oldest frame first (obs, next_obs u8 [B][3 frame_bytes]); act_out [B][A] =
+ *   action[pos], rew_out / disc_out [B] = the n-step accumulation in drq_nstep_gather's float32 operation order, bit
+ *   for bit what that entry yields.  obs == NULL && next_obs == NULL: the scalars only.  16-byte loads and stores; any
+ *   frame_bytes % 16 == 0.  A pos[b] < 1 or > R - nstep (slot pos-1 or the window pos .. pos+nstep-1 would leave
+ *   [0, R)) leaves every output of its row unwritten and reads nothing; whatever the flags hold, every slot read lies in
+ *   [0, R).
+ *   DRQ_EARG, nothing launched: a null pointer (obs and next_obs: exactly one of the two), R, B, A, nstep,
+ *   frame_bytes <= 0, frame_bytes % 16 != 0 (or beyond 85 MB), frames / obs / next_obs not 16-byte aligned, pos not
+ *   8-byte aligned, a float array not 4-byte aligned. */
+int drq_nstep_gather_frames(const uint8_t* frames, const uint8_t* first, long R, const float* action,
+                            const float* reward, const float* discount, const long* pos, int B, int A, long frame_bytes,
+                            int nstep, float gamma, uint8_t* obs, float* act_out, float* rew_out, float* disc_out,
+                            uint8_t* next_obs, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,

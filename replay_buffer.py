@@ -142,14 +142,18 @@ class _Loader:
 
 def make_replay_loader(replay_dir, max_size, batch_size, num_workers, save_snapshot, nstep, discount, device=None,
                        obs_shape=None, action_dim=None, seed=None, indexed=False, priority_alpha=None, priority_beta=0.4,
-                       priority_eps=1e-6):
+                       priority_eps=1e-6, single_frames=False, check_stacks=True):
     """Same positional signature as the reference (replay_buffer.py:173-190).  The observation / action shapes
     come from the data_specs the storage of the same replay_dir was built with (or from the keyword arguments).
     priority_alpha (None: uniform): proportional prioritized replay, see drqv2_amd.replay.DeviceReplay; episodes
     reloaded on a resume start at the running maximum priority of 1.  A prioritized store receives the episodes the
     storage finishes when the loader's iterator draws next (so that the batch drawn ahead is consumed and its priorities
     written first), not at once: until then they are not in the store, and store.sample() called directly does not
-    see them."""
+    see them.
+    single_frames (False: every draw, launch and bit as before): the device store keeps ONE 3 x 84 x 84 frame per step, a
+    third of the HBM, and the frame stacks are put together where a batch is read (drqv2_amd.replay.DeviceReplay); the
+    storage, the episode files and the batches' contents are unchanged.  check_stacks: every episode is verified to be a
+    frame stack before its older frames are dropped; False for a source known to be one."""
     ent = _entry(replay_dir)
     if ent["specs"] is not None:
         by_name = {s.name: s for s in ent["specs"]}
@@ -165,7 +169,8 @@ def make_replay_loader(replay_dir, max_size, batch_size, num_workers, save_snaps
     # indexed=True: the iterator yields drqv2_amd.replay.IndexedBatch objects (frames stay in the store, the update's first
     # kernel gathers them): what DrQV2Agent.update() consumes fastest; False: plain device tensors like the reference's
     ent["store"] = DeviceReplay(capacity, obs_shape, action_dim, nstep, discount, device, seed=seed, indexed=indexed,
-                                priority_alpha=priority_alpha, priority_beta=priority_beta, priority_eps=priority_eps)
+                                priority_alpha=priority_alpha, priority_beta=priority_beta, priority_eps=priority_eps,
+                                single_frames=single_frames, check_stacks=check_stacks)
     ent["save_snapshot"] = bool(save_snapshot)
     # resume: the newest episodes on disk that fit max_size (replay_buffer.py:120-140 walks them newest first),
     # added oldest first so that eviction order stays chronological
