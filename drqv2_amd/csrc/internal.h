@@ -154,3 +154,13 @@ int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int 
 int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const long* dy_bs,
                                     const long* dy_cs, const long* dy_rs, const long* dy_off, float* const* part,
                                     size_t part_bytes, int* nblocks, hipStream_t st);
+
+// ---- vecstats.hip: the 64-byte header of the episode statistics (include/drqv2_hip.h, "episode statistics"), as the
+// device state and the host mirror hold it
+struct VecStatsHeader {
+  long rows, episodes, length_sum;
+  double return_sum;
+  float min_return, max_return;
+  int reserved[6];
+};
+static_assert(sizeof(VecStatsHeader) == 64, "the header is 64 bytes");

@@ -32,6 +32,10 @@ materialize() -- following the reset rule of the reference's FrameStackWrapper (
 Single frames in the episode store (new: DeviceReplay(single_frames=True)).  The episode store is that ring with N = 1:
 episodes are contiguous, a `first` byte marks the slot each one starts on.  add_episode() keeps the newest frame of every
 step, indexed batches are FrameBatch objects, materialised ones come from one launch (drq_nstep_gather_frames).
+
+Episode statistics (new: VecEpisodeStats, csrc/vecstats.hip).  The reference's episode_reward / episode_step book-keeping
+(train.py:133,186,189) for N lockstep environments, kept on the device from the reward and first tensors add() takes: one
+launch per step, a pinned host mirror that nothing waits for, and a per-environment episode limit for evaluation.
 """
 import numpy as np
 import torch
@@ -762,3 +766,193 @@ class VecFrameReplay(VecDeviceReplay):
             check(_lib.load().drq_vec_stack_gather(ptr(self.frames), ptr(self.first), self.R, self.N, self.frame_bytes, None,
                                                    self.T - 1, self.N, ptr(out), self._stream()), "drq_vec_stack_gather")
         return out
+
+
+class EpisodeSnapshot:
+    """What VecEpisodeStats.poll() / read() return: a copy of one host mirror, so it stays what it is.
+      rows, episodes, length_sum, return_sum, min_return, max_return   the header (include/drqv2_hip.h, "episode statistics")
+      mean_return, mean_length   return_sum / episodes, length_sum / episodes; nan while episodes == 0
+      complete   max_episodes_per_env = k > 0: episodes == k * num_envs (every environment has finished its k); else False
+      records    numpy structured array (return f32, length i32, env i32, row i64): the newest min(episodes, log_size)
+                 counted episodes, oldest first -- the order (row, env)
+      lost       max(0, episodes - log_size): the episodes the log no longer holds
+      seq        the number of the publish() that produced it"""
+
+    RECORD = np.dtype([("return", np.float32), ("length", np.int32), ("env", np.int32), ("row", np.int64)])
+
+    def __init__(self, raw, W, N, limit, seq):
+        """raw: uint8 array, the mirror's bytes in the layout of drq_vec_stats_publish"""
+        raw = np.array(raw, copy=True)
+        i64, f32 = raw[:24].view(np.int64), raw[32:40].view(np.float32)
+        self.rows, self.episodes, self.length_sum = int(i64[0]), int(i64[1]), int(i64[2])
+        self.return_sum = float(raw[24:32].view(np.float64)[0])
+        self.min_return, self.max_return = float(f32[0]), float(f32[1])
+        self.seq, self.log_size = int(seq), int(W)
+        n = min(self.episodes, W)
+        at = np.arange(self.episodes - n, self.episodes, dtype=np.int64) % W       # oldest first
+        rec = np.empty(n, self.RECORD)
+        rec["return"] = raw[64:64 + 4 * W].view(np.float32)[at]
+        rec["length"] = raw[64 + 4 * W:64 + 8 * W].view(np.int32)[at]
+        rec["env"] = raw[64 + 8 * W:64 + 12 * W].view(np.int32)[at]
+        row0 = _stats_row_offset(W)
+        rec["row"] = raw[row0:row0 + 8 * W].view(np.int64)[at]
+        self.records = rec
+        self.lost = max(0, self.episodes - W)
+        self.complete = limit > 0 and self.episodes == limit * N
+        nan = float("nan")
+        self.mean_return = self.return_sum / self.episodes if self.episodes else nan
+        self.mean_length = self.length_sum / self.episodes if self.episodes else nan
+
+    def since(self, prev_episodes):
+        """(records, missed): the counted episodes with global number >= prev_episodes (the `episodes` of the snapshot
+        the caller logged last) that are still in the log, oldest first, and how many of them the log has lost"""
+        prev = max(0, int(prev_episodes))
+        oldest = self.episodes - len(self.records)
+        return self.records[max(0, prev - oldest):], max(0, oldest - prev)
+
+    def __repr__(self):
+        return (f"EpisodeSnapshot(rows={self.rows}, episodes={self.episodes}, mean_return={self.mean_return:.6g}, "
+                f"mean_length={self.mean_length:.6g}, min_return={self.min_return:.6g}, max_return={self.max_return:.6g}, "
+                f"lost={self.lost}, complete={self.complete})")
+
+
+def _stats_row_offset(W):
+    """byte offset of the int64 rows in a mirror of drq_vec_stats_publish: behind the three 4-byte arrays, 8-byte aligned"""
+    return (64 + 12 * W + 7) & ~7
+
+
+class VecEpisodeStats:
+    """Episode returns and lengths of N lockstep environments, kept on the device (new; the contract is in
+    include/drqv2_hip.h, "episode statistics").  It is fed the `reward` and `first` tensors the caller already hands to
+    VecDeviceReplay.add() / VecFrameReplay.add(), but knows no store, so an evaluation loop uses it as well:
+
+        stats = VecEpisodeStats(num_envs=N, device="cuda")
+        ...
+        store.add(frame, action, reward, discount, first)
+        stats.step(reward, first)           # one launch (drq_vec_stats_step), nothing waits
+        if step % 1000 == 0:
+            stats.publish()                 # one launch: the state -> a pinned host mirror; nothing waits
+            snap = stats.poll()             # the newest EpisodeSnapshot that has ARRIVED, or None; never waits
+
+    Call 0 is a reset row for every environment, like row 0 of the ring.  A `first` flag on a later call closes the
+    running episode of its environment -- unless that is empty (two resets in a row) -- as a record (return, length, env,
+    row) in a log of the newest `log_size` episodes and in the totals; the reward of a reset row is a dummy and is not
+    read; every other reward is added to the running return with one float32 add (the reference's
+    `episode_reward += time_step.reward`, train.py:186).  max_episodes_per_env = k > 0 (evaluation) counts the first k
+    episodes of EVERY environment and nothing after them -- "until K episodes have finished" would favour short ones --
+    and `snapshot.complete` says when all have theirs.
+    publish() uses FOUR pinned mirrors in turn (the idea of _rotating) and numbers them 1, 2, ...: poll() returns a
+    snapshot of the newest mirror whose sequence word equals the number it was published with.  read() publishes and
+    waits for that one.  episode_return / episode_length are the running device tensors, read-only by convention."""
+
+    _row, _device_index = VecDeviceReplay._row, VecDeviceReplay._device_index      # add()'s checks and messages
+
+    def __init__(self, num_envs, device, log_size=1024, max_episodes_per_env=0):
+        self.N, self.W, self.limit = int(num_envs), int(log_size), int(max_episodes_per_env)
+        if self.N < 1 or self.W < 1 or self.limit < 0:
+            raise ValueError("num_envs and log_size must be >= 1, max_episodes_per_env >= 0")
+        self.device = dev = torch.device(device)
+        N, W = self.N, self.W
+        self.episode_return = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.episode_length = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.episodes_done = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.header = torch.zeros(8, dtype=torch.int64, device=dev)
+        self._log = (torch.zeros(W, dtype=torch.float32, device=dev), torch.zeros(W, dtype=torch.int32, device=dev),
+                     torch.zeros(W, dtype=torch.int32, device=dev), torch.zeros(W, dtype=torch.int64, device=dev))
+        self.rows = 0               # step() calls so far: the row number of the next one
+        self.published = 0          # publish() calls so far: the sequence number of the newest
+        self._stage = None          # pinned + device staging of reward and first, for host inputs
+        self._seq_at = _stats_row_offset(W) + 8 * W
+        self._mirrors = None        # four of [pinned uint8 tensor, its numpy view, its sequence word, the number expected]
+        if dev.type == "cuda":
+            self._launch_reset()
+
+    def _state(self):
+        return [ptr(self.episode_return), ptr(self.episode_length), ptr(self.episodes_done), ptr(self.header)] + \
+            [ptr(t) for t in self._log]
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _launch_reset(self):
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_stats_reset(*self._state(), self.N, self.W, self._stream()), "drq_vec_stats_reset")
+
+    def _staged(self, k, t):
+        if self._stage is None:
+            mk = lambda dt: (torch.empty(self.N, dtype=dt).pin_memory(), torch.empty(self.N, dtype=dt, device=self.device))
+            self._stage = [mk(torch.float32), mk(torch.uint8)]
+        pin, dv = self._stage[k]
+        pin.copy_(t.reshape(pin.shape))
+        dv.copy_(pin, non_blocking=False)
+        return dv
+
+    def step(self, reward, first=None):
+        """reward float32 [N] or [N, 1] (float64 is cast), first bool / uint8 [N] or None = no environment was reset:
+        the tensors of the store's add(), checked by the same rules.  Tensors on the device go to the launch as they are
+        and nothing waits; numpy arrays and host tensors are staged with a blocking copy."""
+        N = self.N
+        args = [self._row(reward, "reward", [(N,), (N, 1)], (torch.float32, torch.float64)),
+                None if first is None else self._row(first, "first", [(N,)], (torch.uint8, torch.bool))]
+        _on_gpu(self, "the episode statistics live")
+        with torch.cuda.device(self.device):
+            src = [t if t is None or t.is_cuda else self._staged(k, t) for k, t in enumerate(args)]
+            check(_lib.load().drq_vec_stats_step(*self._state(), N, self.W, self.limit, self.rows, ptr(src[0]), ptr(src[1]),
+                                                 self._stream()), "drq_vec_stats_step")
+            for t in src:           # a caller's tensor may be freed right after step(): the launch still reads it
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream())
+            self.rows += 1
+
+    def reset(self):
+        """One launch puts everything back to the initial state (one object serves many evaluations): the next step()
+        is a reset row again.  Snapshots published before stay readable; the sequence numbers go on."""
+        _on_gpu(self, "the episode statistics live")
+        self._launch_reset()
+        self.rows = 0
+
+    def publish(self):
+        """One launch (drq_vec_stats_publish) copies the state, as it is after every step() enqueued so far, into the next
+        of the four pinned mirrors; nothing waits.  Returns the sequence number of this publish."""
+        _on_gpu(self, "the episode statistics live")
+        if self._mirrors is None:
+            self._mirrors = []
+            for _ in range(4):
+                pin = torch.zeros(self._seq_at + 8, dtype=torch.uint8).pin_memory()
+                view = pin.numpy()
+                self._mirrors.append([pin, view, view[self._seq_at:self._seq_at + 4].view(np.uint32), None])
+        self.published += 1
+        m = self._mirrors[(self.published - 1) & 3]
+        m[3] = self.published & 0xFFFFFFFF
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_stats_publish(ptr(self.header), *(ptr(t) for t in self._log), self.W, ptr(m[0]), m[3],
+                                                    self._stream()), "drq_vec_stats_publish")
+        return self.published
+
+    def _snapshot(self, m):
+        return EpisodeSnapshot(m[1], self.W, self.N, self.limit, m[3])
+
+    def poll(self):
+        """The EpisodeSnapshot of the newest publish() that has arrived on the host, or None if none has.  Never waits
+        and never synchronises: it compares four sequence words."""
+        for back in range(min(4, self.published)):
+            m = self._mirrors[(self.published - 1 - back) & 3]
+            if int(m[2][0]) == m[3]:
+                return self._snapshot(m)
+        return None
+
+    def read(self, timeout=30.0):
+        """publish(), then wait for it: short sleeps until its sequence word shows; DrqError after `timeout` seconds
+        (and one synchronise of this object's device)."""
+        import time
+        self.publish()
+        m = self._mirrors[(self.published - 1) & 3]
+        t0 = time.perf_counter()
+        while int(m[2][0]) != m[3]:
+            if time.perf_counter() - t0 > timeout:
+                torch.cuda.synchronize(self.device)
+                if int(m[2][0]) != m[3]:
+                    raise _lib.DrqError(f"VecEpisodeStats.read(): publish {self.published} has not arrived after {timeout} s")
+                break
+            time.sleep(20e-6)
+        return self._snapshot(m)

@@ -496,6 +496,52 @@ int drq_nstep_gather_frames(const uint8_t* frames, const uint8_t* first, long R,
                             int nstep, float gamma, uint8_t* obs, float* act_out, float* rew_out, float* disc_out,
                             uint8_t* next_obs, drq_stream_t stream);
 
+/* ---- episode statistics for vectorised collection.  New functionality: the reference adds up episode_reward and
+ * episode_step of its one environment on the host (train.py:133,186,189) and logs them per finished episode
+ * (:147-155); for N lockstep environments the sums live on the device, fed by the reward and first tensors of
+ * "step-major replay", and the host never reads a flag.  These definitions are the contract.  No store is involved.
+ * State, all on the device:
+ *   per environment e: ret f32 [N] the running return, len i32 [N] the running length, done i32 [N] the episodes of e
+ *     closed so far (counted or not; it stops at INT32_MAX);
+ *   header, 64 bytes, 8-byte aligned: rows i64 @0 (the number of step calls), episodes i64 @8, length_sum i64 @16,
+ *     return_sum f64 @24, min_return f32 @32 (+inf at the start), max_return f32 @36 (-inf), 24 reserved bytes (0);
+ *   a log of W records kept as four arrays: log_return f32 [W], log_length i32 [W], log_env i32 [W], log_row i64 [W].
+ * The step at call number t = row (the caller counts the calls; the entry stores rows = row + 1), for every e:
+ *   f = (t == 0) || (first != NULL && first[e] != 0): call 0 is a reset row for every environment, as row 0 of the ring.
+ *   If f and len[e] >= 1 the running episode of e is finished (a reset with len[e] == 0 -- the first row, two resets in a
+ *     row -- closes nothing): if limit == 0 || done[e] < limit it is COUNTED, a record (ret[e], len[e], e, t) and the
+ *     header totals; done[e] += 1 in either case.
+ *   If f: ret[e] = 0, len[e] = 0, and reward[e], a dummy, is not read.  Otherwise ret[e] = ret[e] + reward[e], ONE float32
+ *     add per step in step order (train.py:186 on float32 rewards), and len[e] += 1.
+ * Records.  The episodes counted by one call get the consecutive global numbers j = episodes_before + rank, rank = the
+ *   number of counted environments with a smaller index; record j lives at index j mod W.  The log so holds the newest
+ *   min(episodes, W) episodes in the order (row, env), deterministically.
+ * Totals.  episodes, length_sum, min_return and max_return are exact; return_sum adds the counted float32 returns in
+ *   float64, within a call in the kernel's own order.
+ * limit = k > 0 (evaluation): only the first k episodes of every environment are counted, later ones still reset ret and
+ *   len; the statistics are complete when episodes == k N.
+ * Each entry is one launch of one workgroup of 1,024 threads, plain loads and stores, no atomics; the caller orders them
+ * on one stream.  Any N up to INT32_MAX, any W.
+ *
+ * drq_vec_stats_step: the step above.  reward f32 [N] (may be NULL on row 0), first u8 [N] or NULL = no flags.
+ *   DRQ_EARG, nothing launched: a null state pointer, N < 1 or > INT32_MAX, W < 1, limit < 0, row < 0, a null reward with
+ *   row > 0, header or log_row not 8-byte aligned.
+ * drq_vec_stats_publish: copies header and log into host_mirror (pinned host memory, 8-byte aligned), laid out as
+ *   [header 64 bytes | log_return f32 [W] | log_length i32 [W] | log_env i32 [W] | 4 bytes of padding if W is odd |
+ *    log_row i64 [W] | seq u32]: 64 + 20 W + 4 (W odd ? 2 : 1) bytes.  Then __threadfence_system(), a workgroup barrier,
+ *   and a system-scope release store of seq by one lane (the protocol of drq_publish_sums): a host that reads seq reads
+ *   the state of every step enqueued before.
+ *   DRQ_EARG, nothing launched: a null pointer, W < 1, header / log_row / host_mirror not 8-byte aligned.
+ * drq_vec_stats_reset: one launch puts ret, len, done, the header and the log back to the initial state (zeros; min +inf,
+ *   max -inf); the caller's next step is row 0 again.  DRQ_EARG as for the step. */
+int drq_vec_stats_step(float* ret, int* len, int* done, void* header, float* log_return, int* log_length, int* log_env,
+                       long* log_row, long N, long W, int limit, long row, const float* reward, const uint8_t* first,
+                       drq_stream_t stream);
+int drq_vec_stats_publish(const void* header, const float* log_return, const int* log_length, const int* log_env,
+                          const long* log_row, long W, void* host_mirror, unsigned seq, drq_stream_t stream);
+int drq_vec_stats_reset(float* ret, int* len, int* done, void* header, float* log_return, int* log_length, int* log_env,
+                        long* log_row, long N, long W, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,

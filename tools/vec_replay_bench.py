@@ -33,6 +33,15 @@ step -- the single-frame add() moves a third of the bytes --, update() with one 
 aug+conv1 launch gathers the stacks from three slots), and observation(), the gather that feeds act_batch().
 
   python tools/vec_replay_bench.py --single-frames [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--updates 200]
+
+--episode-stats measures the episode statistics (VecEpisodeStats: drq_vec_stats_step, one launch per environment step) next
+to the ring: add() + sample(256) per environment step alone, with stats.step(reward, first) behind the add(), and with the
+same book-keeping written in torch ops (TorchStats below: running return and length, episode count, length and return
+sums, min and max -- without the record log, which has no short torch form), the three alternated inside every repeat of
+one process; then stats.step(), the torch form and publish() + poll() on their own.  One environment in 64 is reset in
+every row, so episodes do end.  Same steps, repeats and the same two figures per line as above.
+
+  python tools/vec_replay_bench.py --episode-stats [--steps 2000] [--repeats 3] [--envs 16,256,1024]
 """
 import argparse
 import os
@@ -45,7 +54,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
 from drqv2_amd import synth  # noqa: E402
-from drqv2_amd.replay import DeviceReplay, VecDeviceReplay, VecFrameReplay  # noqa: E402
+from drqv2_amd.replay import DeviceReplay, VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 OBS = (9, 84, 84)
 A, NSTEP, B = 6, 3, 256
@@ -158,6 +167,76 @@ def single_frames(N, args, ag):
           f"{spread([x[1] for x in v])}   ({args.steps} x {args.repeats})", flush=True)
 
 
+class TorchStats:
+    """the totals of VecEpisodeStats.step() in torch ops, for the comparison only: no record log, no per-environment limit"""
+
+    def __init__(self, N):
+        z = lambda dt: torch.zeros((), dtype=dt, device="cuda")
+        self.ret, self.len = torch.zeros(N, device="cuda"), torch.zeros(N, dtype=torch.int32, device="cuda")
+        self.episodes, self.length_sum, self.return_sum = z(torch.int64), z(torch.int64), z(torch.float64)
+        self.min_return, self.max_return = z(torch.float32) + float("inf"), z(torch.float32) - float("inf")
+        self.inf = z(torch.float32) + float("inf")
+
+    def step(self, reward, first):
+        closed = first & (self.len > 0)
+        self.episodes += closed.sum()
+        self.length_sum += (self.len * closed).sum()
+        self.return_sum += (self.ret * closed).sum(dtype=torch.float64)
+        self.min_return = torch.minimum(self.min_return, torch.where(closed, self.ret, self.inf).min())
+        self.max_return = torch.maximum(self.max_return, torch.where(closed, self.ret, -self.inf).max())
+        self.ret = torch.where(first, 0.0, self.ret + reward)
+        self.len = torch.where(first, 0, self.len + 1)
+
+
+def episode_stats(N, args):
+    """the ring alone, with stats.step() and with the torch book-keeping, alternated per repeat; then each on its own"""
+    rows = pool_rows(N)
+    e = torch.arange(N, device="cuda")
+    firsts = [(e + 16 * k) % 64 == 0 for k in range(4)]                   # one environment in 64 is reset in each row
+    ring = VecDeviceReplay(max(32, SLOTS // N), N, OBS, A, NSTEP, 0.99, "cuda", seed=1)
+    stats, tstats = VecEpisodeStats(N, "cuda"), TorchStats(N)
+
+    def ring_step(i):
+        ring.add(*rows[i & 3], firsts[i & 3])
+        ring.sample(B)
+
+    def stats_step(i):
+        ring.add(*rows[i & 3], firsts[i & 3])
+        stats.step(rows[i & 3][2], firsts[i & 3])
+        ring.sample(B)
+
+    def torch_step(i):
+        ring.add(*rows[i & 3], firsts[i & 3])
+        tstats.step(rows[i & 3][2], firsts[i & 3])
+        ring.sample(B)
+
+    def publish(i):
+        stats.publish()
+        stats.poll()
+
+    paths = {f"ring: add()+sample({B})": ring_step, "ring + stats.step()": stats_step, "ring + torch book-keeping": torch_step,
+             "stats.step() alone": lambda i: stats.step(rows[i & 3][2], firsts[i & 3]),
+             "torch book-keeping alone": lambda i: tstats.step(rows[i & 3][2], firsts[i & 3]),
+             "stats.publish() + poll()": publish}
+    for i in range(NSTEP + 1):
+        ring.add(*rows[i & 3], firsts[i & 3])
+    stats.step(rows[0][2])                                                # call 0: a reset row for every environment
+    tstats.step(rows[0][2], torch.ones(N, dtype=torch.bool, device="cuda"))
+    for fn in paths.values():
+        for i in range(20):
+            fn(i)
+    res = {k: [] for k in paths}
+    for _ in range(args.repeats):
+        for k, fn in paths.items():
+            res[k].append(timed(fn, args.steps))
+    for k, v in res.items():
+        print(f"N={N:5d}  {k:28s} per environment step: device-event {spread([x[0] for x in v])}   host wall "
+              f"{spread([x[1] for x in v])}   ({args.steps} x {args.repeats}, alternated)", flush=True)
+    snap = stats.read()
+    print(f"N={N:5d}  statistics after {snap.rows} steps: {snap.episodes} episodes, mean length {snap.mean_length:.1f}; the "
+          f"torch form counted {int(tstats.episodes)}", flush=True)
+
+
 def two_rings(N, args, ag, rings):
     """rings: name -> (store, its pool of rows); collection steps, then updates, alternated per repeat"""
     first = torch.zeros(N, dtype=torch.bool, device="cuda")
@@ -245,9 +324,16 @@ def main():
                     help="measure the uniform ring against the prioritized one instead of against the episode store")
     ap.add_argument("--single-frames", action="store_true",
                     help="measure the stacked ring against the single-frame ring (VecFrameReplay) instead")
+    ap.add_argument("--episode-stats", action="store_true",
+                    help="measure the ring with and without VecEpisodeStats.step(), and the same book-keeping in torch ops")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    if args.episode_stats:
+        for N in (int(x) for x in args.envs.split(",")):
+            episode_stats(N, args)
+            torch.cuda.empty_cache()
+        return
     if args.priority_alpha is not None or args.single_frames:
         ag = make_agent()
         for N in (int(x) for x in args.envs.split(",")):
