@@ -491,18 +491,21 @@ def qout_bwd(dqs, hs, ws_, want_wgrad=True):
     return dhs, dws, dbs
 
 
-def mlp_fwd(xs, ws_, bs, relu=True, qws=None):
+def mlp_fwd(xs, ws_, bs, relu=True, qws=None, ys=None, ldy=None):
     """hidden-layer forward on the LDS-DMA ring kernel; qws: weight rows of a following Linear(N,1) -> partial dots.
-    Returns (list of y, list of qpart [M][nq] or None)."""
+    Returns (list of y, list of qpart [M][nq] or None).  xs / ws_ may be row-strided views (their stride(0) is the
+    leading dimension); ys / ldy: caller-provided [M][ldy] output buffers (tests: rows longer than N)."""
     import ctypes
     lib = _lib.load()
     M, K = xs[0].shape
     N = ws_[0].shape[0]
     dev = xs[0].device
-    ys = [_alloc((M, N), torch.float32, dev) for _ in xs]
+    ldy = N if ldy is None else ldy
+    if ys is None:
+        ys = [_alloc((M, ldy), torch.float32, dev) for _ in xs]
     qps = [_alloc((M, N // 32), torch.float32, dev, "zero") for _ in xs] if qws else None
     nq = ctypes.c_int(0)
-    check(lib.drq_mlp_fwd(len(xs), _ptr_array(xs), xs[0].stride(0), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(ys), N,
+    check(lib.drq_mlp_fwd(len(xs), _ptr_array(xs), xs[0].stride(0), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(ys), ldy,
                           M, N, K, _ptr_array(bs) if bs else None, int(relu), _ptr_array(qws) if qws else None,
                           _ptr_array(qps) if qps else None, ctypes.byref(nq), _stream()), "drq_mlp_fwd")
     if qps:
@@ -510,29 +513,36 @@ def mlp_fwd(xs, ws_, bs, relu=True, qws=None):
     return ys, qps
 
 
-def mlp_dgrad(dys, ws_, masks=None):
+def mlp_dgrad(dys, ws_, masks=None, dxs=None, lddx=None):
+    """dxs / lddx: caller-provided [M][lddx] output buffers; dys / ws_ / masks may be row-strided views."""
     lib = _lib.load()
     M, K = dys[0].shape
     N = ws_[0].shape[1]
-    dxs = [_alloc((M, N), torch.float32, dys[0].device) for _ in dys]
+    lddx = N if lddx is None else lddx
+    if dxs is None:
+        dxs = [_alloc((M, lddx), torch.float32, dys[0].device) for _ in dys]
     check(lib.drq_mlp_dgrad(len(dys), _ptr_array(dys), dys[0].stride(0), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(dxs),
-                            N, M, N, K, _ptr_array(masks) if masks else None, (masks[0].stride(0) if masks else 0),
+                            lddx, M, N, K, _ptr_array(masks) if masks else None, (masks[0].stride(0) if masks else 0),
                             _stream()), "drq_mlp_dgrad")
     return dxs
 
 
-def mlp_wgrad_dgrad(dys, xs, ws_, masks=None):
-    """both gradients of one hidden layer in one launch: returns (dws, dbs, dxs)."""
+def mlp_wgrad_dgrad(dys, xs, ws_, masks=None, dws=None, dxs=None, lddx=None):
+    """both gradients of one hidden layer in one launch: returns (dws, dbs, dxs).  dws (dense [Nout][Kin]) and dxs
+    ([Brows][lddx]) may be caller-provided buffers; dys / xs / ws_ / masks may be row-strided views."""
     lib = _lib.load()
     Brows, Nout = dys[0].shape
     Kin = xs[0].shape[1]
     dev = dys[0].device
-    dws = [_alloc((Nout, Kin), torch.float32, dev) for _ in dys]
+    lddx = Kin if lddx is None else lddx
+    if dws is None:
+        dws = [_alloc((Nout, Kin), torch.float32, dev) for _ in dys]
     dbs = [_alloc((Nout,), torch.float32, dev) for _ in dys]
-    dxs = [_alloc((Brows, Kin), torch.float32, dev) for _ in dys]
+    if dxs is None:
+        dxs = [_alloc((Brows, lddx), torch.float32, dev) for _ in dys]
     check(lib.drq_mlp_wgrad_dgrad(len(dys), _ptr_array(dys), dys[0].stride(0), _ptr_array(xs), xs[0].stride(0),
                                   _ptr_array(dws), _ptr_array(dbs), _ptr_array(ws_), ws_[0].stride(0), _ptr_array(dxs),
-                                  Kin, _ptr_array(masks) if masks else None, (masks[0].stride(0) if masks else 0),
+                                  lddx, _ptr_array(masks) if masks else None, (masks[0].stride(0) if masks else 0),
                                   Brows, Nout, Kin, _stream()), "drq_mlp_wgrad_dgrad")
     return dws, dbs, dxs
 

@@ -137,7 +137,11 @@ int drq_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dy, float* dw, f
  *   C[b][m][n] = epi( sum_k A_b(m,k) * B_b(k,n) ),  epi(v) = relu?(v + bias[n]) * (aux[m][n] > 0)?
  *   a_kc: A(m,k)=A[m*lda+k] else A[k*lda+m];  b_kc: B(k,n)=B[n*ldb+k] else B[k*ldb+n].
  *   scatter_hw>0: C index = zero-padded (pad 2) NCHW gradient layout of a [M][32*hw*hw] feature map.
- *   tile: 0 auto, 1 = 32x32, 2 = 64x64 block tile; splitk: 0 auto (needs ws). */
+ *   tile: block tile (rows x columns) of the LDS-staged kernel: 0 auto, 1 = 32x32, 2 = 64x64, 3 = 64x32, 4 = 32x64
+ *   (k-tile 32), 5 = 32x32 and 6 = 64x64 with a k-tile of 64 (one barrier per 64 k).  Any tile != 0 or splitk != 0
+ *   keeps the call on that kernel (0 / 0 lets the shape-specific kernels take eligible shapes).  Every tile takes every
+ *   shape and alignment; splitk: 0 auto, else the number of K slices asked for (rounded to slices of whole multiples
+ *   of 64; needs ws when more than one remains). */
 int drq_gemm_f32(const float* A, long lda, int a_kc, const float* B, long ldb, int b_kc, float* C, long ldc,
                  int M, int N, int K, int nbatch, long a_bs, long b_bs, long c_bs, const float* bias, long bias_bs,
                  int relu, const float* aux, int ldaux, long aux_bs, int scatter_hw, int tile, int splitk,

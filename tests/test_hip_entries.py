@@ -574,7 +574,7 @@ def test_gemm_f32_batched_strides(ops, nbatch, layout, M, N, K, shared):
     ws = poison.alloc((4 * 1024 * 1024,), torch.float32, "cuda", name="split-K workspace", kind="ws")
     ldc = N + 3
     c_bs = M * ldc + 7
-    for tile in (0, 1, 2):
+    for tile in (0, 1, 2, 3, 4, 5, 6):
         for splitk in (0, 1, 3):
             C = poison.partial(out(nbatch * c_bs, name=f"C tile={tile} splitk={splitk}"))
             ops.gemm(Ac, a_kc, Bc, b_kc, M, N, K, bias=bc, relu=layout == "fwd", aux=mc, nbatch=nbatch,
