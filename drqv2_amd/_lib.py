@@ -106,6 +106,7 @@ PROTOTYPES = {
     "drq_vec_per_sample": (I, [P, L, P, P, P, P, L, L, I, L, L, L, P, I, I, F, D, P, P, P, P, P, P, P]),
     "drq_vec_per_update": (I, [P, L, P, L, L, L, L, L, P, P, I, D, D, P]),
     "drq_vec_stack_gather": (I, [P, P, L, L, L, P, L, I, P, P]),
+    "drq_vec_add_render": (I, [P, P, P, P, P, L, L, I, L, P, I, I, P, P, P, P, P]),
     "drq_vec_stats_step": (I, [P, P, P, P, P, P, P, P, L, L, I, L, P, P, P]),
     "drq_vec_stats_publish": (I, [P, P, P, P, P, L, P, C.c_uint, P]),
     "drq_vec_stats_reset": (I, [P, P, P, P, P, P, P, P, L, L, P]),

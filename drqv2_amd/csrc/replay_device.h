@@ -1,7 +1,7 @@
 // The device code the replay stores share: the n-step sum (elementwise.hip's flat store, vecreplay.hip's ring), the
 // priority sum tree (per.hip's episode store, vecreplay.hip's ring), the ring's geometry and batch rows (the uniform
-// and the prioritized draw of vecreplay.hip) and the frame stack of a single-frame ring (vecframes.hip's gather,
-// conv1aug.hip's ring mode).  Layout and rules are the contract of include/drqv2_hip.h; the memory-ordering argument of
+// and the prioritized draw of vecreplay.hip), the scalars of an added row (vecreplay.hip's add, vecrender.hip's) and the
+// frame stack of a single-frame ring (vecframes.hip's gather, conv1aug.hip's ring mode).  Layout and rules are the contract of include/drqv2_hip.h; the memory-ordering argument of
 // the tree is per.hip's header comment: ONE workgroup of kPerThreads threads walks the levels with __syncthreads()
 // between them, nothing crosses workgroups.
 #pragma once
@@ -196,6 +196,33 @@ __device__ __forceinline__ void ring_emit_row(const RingBatch& a, int b, long t,
   nstep_sum(a.reward, a.discount, a.gamma, steps, [&](int i) { return ring_slot(g, t + i, e); }, r, d);
   a.rew_out[b] = r;
   a.disc_out[b] = steps == 0 ? 0.f : d;
+}
+
+// ---- one row of an add: what is not the frame ---------------------------------------------------------------------
+// (vecreplay.hip's drq_vec_add, vecrender.hip's drq_vec_add_render)  Ring row `row` of action, reward, discount and
+// first from the sources of one step; thread tid of `step` threads, any grid.
+struct RingRowScalars {
+  float* action;
+  float* reward;
+  float* discount;
+  uint8_t* first;
+  const float* src_action;
+  const float* src_reward;
+  const float* src_discount;
+  const uint8_t* src_first;   // null = all 0
+  long row;                   // t mod R
+  int N, A, force_first;      // force_first: t == 0, every environment starts an episode
+};
+
+__device__ __forceinline__ void ring_add_scalars(const RingRowScalars& a, long tid, long step) {
+  const long base = a.row * a.N;   // first slot of the row
+  const long na = (long)a.N * a.A;
+  for (long i = tid; i < na; i += step) a.action[base * a.A + i] = a.src_action[i];
+  for (long e = tid; e < a.N; e += step) {
+    a.reward[base + e] = a.src_reward[e];
+    a.discount[base + e] = a.src_discount[e];
+    a.first[base + e] = (a.force_first || (a.src_first && a.src_first[e])) ? 1 : 0;
+  }
 }
 
 // ---- single-frame rings: the frame stack is put together when it is read -------------------------------------------

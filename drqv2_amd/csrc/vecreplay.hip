@@ -27,7 +27,8 @@
 // uniform path's "no drawable transition" rows, all indices on slot(lo, 0), steps 0, reward 0, discount 0, weight 1.
 //
 // What the two draws share (ring geometry, window, batch row, n-step sum) and what the tree entries share with per.hip
-// (descent, weight normalisation, priority update, ranged rebuild) is one copy each, in replay_device.h.
+// (descent, weight normalisation, priority update, ranged rebuild) is one copy each, in replay_device.h; so are the
+// scalars of an added row, which drq_vec_add_render (vecrender.hip) writes as drq_vec_add does.
 #include "common.h"
 #include "replay_device.h"
 #include "../../include/drqv2_hip.h"
@@ -35,36 +36,21 @@
 namespace {
 
 struct VecAddArgs {
+  RingRowScalars s;           // the row's action, reward, discount and first (replay_device.h)
   uint8_t* frames;
-  float* action;
-  float* reward;
-  float* discount;
-  uint8_t* first;
   const uint8_t* src_obs;
-  const float* src_action;
-  const float* src_reward;
-  const float* src_discount;
-  const uint8_t* src_first;   // null = all 0
-  long row;                   // t mod R
   long n16;                   // N * frame_bytes / 16
   long frame_bytes;
-  int N, A, force_first;
 };
 
 __global__ __launch_bounds__(256) void vec_add_kernel(VecAddArgs a) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long step = (long)gridDim.x * blockDim.x;
-  const long base = a.row * a.N;   // first slot of the row
+  const long base = a.s.row * a.s.N;   // first slot of the row
   const uint4* src = reinterpret_cast<const uint4*>(a.src_obs);
   uint4* dst = reinterpret_cast<uint4*>(a.frames + base * a.frame_bytes);
   for (long i = tid; i < a.n16; i += step) dst[i] = src[i];
-  const long na = (long)a.N * a.A;
-  for (long i = tid; i < na; i += step) a.action[base * a.A + i] = a.src_action[i];
-  for (long e = tid; e < a.N; e += step) {
-    a.reward[base + e] = a.src_reward[e];
-    a.discount[base + e] = a.src_discount[e];
-    a.first[base + e] = (a.force_first || (a.src_first && a.src_first[e])) ? 1 : 0;
-  }
+  ring_add_scalars(a.s, tid, step);
 }
 
 struct VecSampleArgs {
@@ -218,8 +204,9 @@ DRQ_API int drq_vec_add(uint8_t* frames, float* action, float* reward, float* di
   if (R <= 0 || N <= 0 || A <= 0 || frame_bytes <= 0 || frame_bytes % 16 || t < 0) return DRQ_EARG;
   if (N > INT32_MAX) return DRQ_EARG;
   if (((uintptr_t)frames | (uintptr_t)src_obs) & 15) return DRQ_EARG;
-  VecAddArgs a{frames, action, reward, discount, first, src_obs, src_action, src_reward, src_discount, src_first,
-               t % R, N * (frame_bytes >> 4), frame_bytes, (int)N, A, t == 0 ? 1 : 0};
+  VecAddArgs a{RingRowScalars{action, reward, discount, first, src_action, src_reward, src_discount, src_first, t % R,
+                              (int)N, A, t == 0 ? 1 : 0},
+               frames, src_obs, N * (frame_bytes >> 4), frame_bytes};
   const long want = (a.n16 + 255) / 256;
   const long cap = 8L * drq_num_cus();
   hipLaunchKernelGGL(vec_add_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, st, a);

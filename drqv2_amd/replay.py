@@ -29,6 +29,10 @@ three-frame stack: a third of the memory and of add()'s traffic.  The stack is p
 fused aug+conv1 launch of update() (a FrameBatch carries the ring's flags), by observation() for act_batch(), by
 materialize() -- following the reset rule of the reference's FrameStackWrapper (dmc.py:87-109).
 
+Renderer images (new: VecFrameReplay.add_render, csrc/vecrender.hip).  add() for the channels-last image of S x S pixels
+a GPU renderer hands out, S = 84 .. 336: one launch resizes it into the slot with an exact integer area average instead
+of a chain of torch ops in front of add().
+
 Single frames in the episode store (new: DeviceReplay(single_frames=True)).  The episode store is that ring with N = 1:
 episodes are contiguous, a `first` byte marks the slot each one starts on.  add_episode() keeps the newest frame of every
 step, indexed batches are FrameBatch objects, materialised ones come from one launch (drq_nstep_gather_frames).
@@ -597,18 +601,29 @@ class VecDeviceReplay:
         reset).  Row 0 is a reset row for every environment whatever `first` says.  Tensors on the store's device are
         handed to the launch as they are and nothing waits; numpy arrays and host tensors are staged with a blocking
         copy."""
+        N = self.N
+        args = [self._row(obs, "obs", [(N,) + self.slot_shape, (N, self.frame_bytes)], (torch.uint8,))]
+        args += self._scalar_rows(action, reward, discount, first)
+        self._write_row(args, self._staged, lambda src: check(_lib.load().drq_vec_add(
+            ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(self.first), self.R, N, self.A,
+            self.frame_bytes, self.T, *(ptr(t) for t in src), self._stream()), "drq_vec_add"))
+
+    def _scalar_rows(self, action, reward, discount, first):
+        """what every add takes besides the frames, checked like them"""
         N, f32 = self.N, (torch.float32, torch.float64)
-        args = [self._row(obs, "obs", [(N,) + self.slot_shape, (N, self.frame_bytes)], (torch.uint8,)),
-                self._row(action, "action", [(N, self.A)], f32),
+        return [self._row(action, "action", [(N, self.A)], f32),
                 self._row(reward, "reward", [(N,), (N, 1)], f32),
                 self._row(discount, "discount", [(N,), (N, 1)], f32),
                 None if first is None else self._row(first, "first", [(N,)], (torch.uint8, torch.bool))]
+
+    def _write_row(self, args, staged, launch):
+        """the tail every add shares: host arguments are staged (staged(k, t): argument k on the device), launch(src)
+        writes row T, then the row counts and the tree follows"""
+        N = self.N
         _on_gpu(self, "the step-major replay lives")
         with torch.cuda.device(self.device):
-            src = [t if t is None or t.is_cuda else self._staged(k, t) for k, t in enumerate(args)]
-            check(_lib.load().drq_vec_add(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
-                                          ptr(self.first), self.R, N, self.A, self.frame_bytes, self.T, *(ptr(t) for t in src),
-                                          self._stream()), "drq_vec_add")
+            src = [t if t is None or t.is_cuda else staged(k, t) for k, t in enumerate(args)]
+            launch(src)
             for t in src:           # a caller's tensor may be freed right after add(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())
@@ -713,6 +728,8 @@ class VecFrameReplay(VecDeviceReplay):
       observation()   the stacks of the newest row, for agent.act_batch()
       sample()        a FrameBatch (indexed=True): the frames stay in the ring, update()'s fused aug+conv1 launch
                       gathers the stacks itself; indexed=False: the materialised 5-tuple, gathered by one kernel
+    and nobody resizes or transposes in front of add(): add_render() takes the renderer's own uint8 [N, S, S, 3 or 4]
+    image, S = 84 .. 336, and writes the frames with one launch by an exact integer area average.
     Everything else -- rows, flags, windows, draws, `priority_alpha`, guard_rows -- is VecDeviceReplay's, launch for
     launch.  The drawable rows start two rows later, lo = max(1, T - rows + 1 + guard_rows + 2): the oldest frame of an
     obs stack lies three rows before its transition and must stay in the ring while guard_rows rows are added; hence
@@ -735,6 +752,7 @@ class VecFrameReplay(VecDeviceReplay):
         self.obs_shape = (9, 84, 84)               # what observation() and a materialised batch hold
         self.stack_bytes = 3 * self.frame_bytes
         self._obs_out = None
+        self._render_stage = None   # pinned + device staging of one host image of add_render()
 
     def bounds(self):
         """(lo, hi): the drawable rows; hi < lo while there are none"""
@@ -748,6 +766,56 @@ class VecFrameReplay(VecDeviceReplay):
         """As VecDeviceReplay.add(), with frame uint8 [N, 3, 84, 84]: the newest frame of every environment after the
         step (on a reset row: the first frame of the new episode)."""
         super().add(frame, action, reward, discount, first)
+
+    RENDER_SIZES = (84, 336)    # no upsampling; 4 x 84: at most 5 taps per axis, sums < 2^31, 41 KB of LDS per band
+
+    def _image(self, x):
+        """the image of add_render() as a contiguous uint8 tensor, checked; still where the caller has it"""
+        t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+        lo, hi = self.RENDER_SIZES
+        if not torch.is_tensor(t):
+            raise ValueError("add_render(): image must be a numpy array or a tensor")
+        if t.dim() != 4 or t.shape[0] != self.N:
+            raise ValueError(f"add_render(): image of shape ({self.N}, S, S, 3 or 4) required, got {tuple(t.shape)}")
+        if t.shape[1] != t.shape[2]:
+            raise ValueError(f"add_render(): image must be square, got {t.shape[1]} x {t.shape[2]}")
+        if not lo <= t.shape[1] <= hi:
+            raise ValueError(f"add_render(): image size {lo} .. {hi} required, got {t.shape[1]}")
+        if t.shape[3] not in (3, 4):
+            raise ValueError(f"add_render(): image with 3 or 4 channels last required, got {t.shape[3]}")
+        if t.dtype != torch.uint8:
+            raise ValueError(f"add_render(): image must be {torch.uint8}, got {t.dtype}")
+        if t.device.type != "cpu" and t.device != self._device_index():
+            raise ValueError(f"add_render(): image is on {t.device}, the store on {self.device}")
+        t = t.contiguous()
+        return t.clone() if t.data_ptr() % 4 else t        # a view that starts inside a dword: the kernel reads dwords
+
+    def _staged_image(self, t):
+        """a host image -> the device, through a pinned buffer of its shape: a blocking copy, like _staged()"""
+        if self._render_stage is None or self._render_stage[0].shape != t.shape:
+            self._render_stage = (torch.empty(t.shape, dtype=torch.uint8).pin_memory(),
+                                  torch.empty(t.shape, dtype=torch.uint8, device=self.device))
+        pin, dv = self._render_stage
+        pin.copy_(t)
+        dv.copy_(pin, non_blocking=False)
+        return dv
+
+    def add_render(self, image, action, reward, discount, first=None):
+        """add() for the image a renderer hands out: uint8 [N, S, S, 3 or 4], channels last, S = 84 .. 336 (a fourth
+        channel is never read).  One launch (drq_vec_add_render) resizes it to the [N, 3, 84, 84] frames of the row by
+        the exact integer area average of include/drqv2_hip.h, "renderer images" -- S = 84: the transposition, S = 84 k:
+        the mean of every k x k block rounded half up -- and writes action, reward, discount and first as add() does.
+        The effect is add(resize(image), ...), bit for bit; the other arguments, their checks and what follows the
+        launch are add()'s, and the two may alternate on one store.  An image on the store's device goes to the
+        launch as it is; a numpy array or host tensor is staged through a pinned buffer of its shape with a blocking
+        copy."""
+        args = [self._image(image)] + self._scalar_rows(action, reward, discount, first)
+        S, Cin = int(args[0].shape[1]), int(args[0].shape[3])
+        self._write_row(args, lambda k, t: self._staged_image(t) if k == 0 else self._staged(k, t),
+                        lambda src: check(_lib.load().drq_vec_add_render(
+                            ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(self.first),
+                            self.R, self.N, self.A, self.T, ptr(src[0]), S, Cin, *(ptr(t) for t in src[1:]),
+                            self._stream()), "drq_vec_add_render"))
 
     def observation(self):
         """uint8 [N, 9, 84, 84] on the device: the frame stacks of the newest row, what a FrameStackWrapper per

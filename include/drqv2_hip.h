@@ -473,6 +473,35 @@ int drq_vec_per_update(double* tree, long L, const uint8_t* first, long R, long 
 int drq_vec_stack_gather(const uint8_t* frames, const uint8_t* first, long R, long N, long frame_bytes,
                          const int64_t* slots, long t, int n, uint8_t* out, drq_stream_t stream);
 
+/* ---- renderer images: an add on the single-frame ring above that takes the image as a GPU renderer hands it out and
+ * resizes it on the way in.  New functionality (the reference renders 84 x 84 on the host, dmc.py); these definitions
+ * are the contract.
+ * src_image is u8 [N][S][S][Cin], channels last, square, S = 84 .. 336, Cin = 3 or 4; a fourth channel (alpha, padding)
+ * is never read.  The frame written is u8 [3][84][84], the exact area average in integer arithmetic, no float anywhere:
+ *   Measure an image axis in units of 1/84 input pixel: input pixel i covers [84 i, 84 (i+1)), output pixel o covers
+ *   [S o, S (o+1)), and the weight of i in o is their overlap
+ *     w(o, i) = max(0, min(S (o+1), 84 (i+1)) - max(S o, 84 i)).
+ *   Every row of w sums to S, every column to 84, and a row has at most 5 non-zero entries for S <= 336 (at most 4
+ *   for S <= 256 and for S = 336; 5 first at S = 257).
+ *     frame[e][c][y][x] = (sum_i sum_j w(y, i) w(x, j) image[e][i][j][c] + (S S) / 2) / (S S),   c = 0, 1, 2,
+ *   both divisions integer divisions (round half up).  The sum is at most 255 S^2, and with the rounding term
+ *   255.5 * 336^2 = 28,844,928 < 2^31: 32-bit integers hold it.  S ends at 336 = 4 * 84: up to there a row of w has
+ *   at most 5 entries and the input rows of 4 output rows, with their horizontal sums, take 41 KB of LDS at most.
+ *   Consequences: S = 84 is the plain HWC -> CHW transposition; S = 84 k gives the mean of each k x k block rounded half
+ *   up, (sum + k^2 / 2) / k^2; a constant image stays constant.
+ *
+ * drq_vec_add_render: drq_vec_add for a ring with frame_bytes = 21168 whose frame source is such an image: one launch
+ *   writes frames[(t mod R) N + e][21168] by the rule above for all N environments, and row t mod R of action, reward,
+ *   discount and first exactly as drq_vec_add does from the same sources (t == 0 stores first = 1 for every environment;
+ *   src_first NULL = all 0).  Nothing outside the image is read, nothing outside the row is written.
+ *   DRQ_EARG, nothing written: null pointers (but src_first), R, N, A <= 0, t < 0, S outside 84 .. 336, Cin not 3 or 4,
+ *   frames not 16-byte aligned, src_image not 4-byte aligned; N > INT32_MAX / 21 (one workgroup per environment and
+ *   band of 4 output rows). */
+int drq_vec_add_render(uint8_t* frames, float* action, float* reward, float* discount, uint8_t* first, long R, long N,
+                       int A, long t, const uint8_t* src_image, int S, int Cin, const float* src_action,
+                       const float* src_reward, const float* src_discount, const uint8_t* src_first,
+                       drq_stream_t stream);
+
 /* ---- single frames in the episode store: the flat store of "replay batch assembly on the device" with ONE frame per
  * slot.  It is the ring above with N = 1 and R = the store's slots: frames u8 [R][frame_bytes], action f32 [R][A], reward
  * and discount f32 [R], first u8 [R].  Every episode is contiguous, its first slot (the dummy reset transition) carries

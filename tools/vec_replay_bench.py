@@ -42,6 +42,16 @@ one process; then stats.step(), the torch form and publish() + poll() on their o
 every row, so episodes do end.  Same steps, repeats and the same two figures per line as above.
 
   python tools/vec_replay_bench.py --episode-stats [--steps 2000] [--repeats 3] [--envs 16,256,1024]
+
+--render measures VecFrameReplay.add_render() -- the renderer's uint8 [N, S, S, 4] image resized into the ring by one launch
+(drq_vec_add_render) -- against what a user writes in front of add() today, in torch ops (torch_chain below: permute, float,
+avg_pool2d where 84 divides S and interpolate(mode="area") elsewhere, round, uint8, contiguous; at S = 84 the permute and
+the copy alone), and add() of a ready frame as the baseline, the three alternated inside every repeat of one process on one
+ring, for S = 84, 128, 168.  The images come from a pool of four per size.  Per line the same two figures as above, and
+for add_render() the bytes it moves (image read + frames written) over its device-event time.  The torch chain rounds
+float32 means half to even, so its frames are not add_render()'s everywhere; the tool counts the bytes that differ.
+
+  python tools/vec_replay_bench.py --render [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--sizes 84,128,168]
 """
 import argparse
 import os
@@ -237,6 +247,49 @@ def episode_stats(N, args):
           f"torch form counted {int(tstats.episodes)}", flush=True)
 
 
+def torch_chain(image):
+    """what stands in front of add() without add_render(), for the comparison only: RGBA [N, S, S, 4] -> uint8 [N, 3, 84, 84]"""
+    S = image.shape[1]
+    x = image[..., :3].permute(0, 3, 1, 2)
+    if S == 84:
+        return x.contiguous()
+    x = x.float()
+    x = torch.nn.functional.avg_pool2d(x, S // 84) if S % 84 == 0 else torch.nn.functional.interpolate(x, size=(84, 84), mode="area")
+    return x.round().to(torch.uint8).contiguous()
+
+
+def render(N, S, args):
+    """add() of a ready frame, add_render() of the image and the torch chain + add(), alternated per repeat on one ring"""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N + S)
+    rows = [(torch.randint(0, 256, (N, S, S, 4), dtype=torch.uint8, device="cuda", generator=g),
+             torch.rand(N, A, device="cuda", generator=g) * 2 - 1, torch.rand(N, device="cuda", generator=g),
+             torch.ones(N, device="cuda")) for _ in range(4)]
+    frames = [torch_chain(r[0]) for r in rows]
+    first = torch.zeros(N, dtype=torch.bool, device="cuda")
+    ring = VecFrameReplay(max(32, SLOTS // N), N, A, NSTEP, 0.99, "cuda", seed=1)
+    paths = {"add() of a ready frame": lambda i: ring.add(frames[i & 3], *rows[i & 3][1:], first),
+             "add_render()": lambda i: ring.add_render(*rows[i & 3], first),
+             "torch chain + add()": lambda i: ring.add(torch_chain(rows[i & 3][0]), *rows[i & 3][1:], first)}
+    ring.add_render(*rows[0], first)
+    mine = ring.frames[:N].view(N, 3, 84, 84).clone()
+    diff = int((mine != frames[0]).sum())
+    for fn in paths.values():
+        for i in range(20):
+            fn(i)
+    res = {k: [] for k in paths}
+    for _ in range(args.repeats):
+        for k, fn in paths.items():
+            res[k].append(timed(fn, args.steps))
+    for k, v in res.items():
+        print(f"N={N:5d} S={S:3d}  {k:24s}: device-event {spread([x[0] for x in v])}   host wall "
+              f"{spread([x[1] for x in v])}   ({args.steps} x {args.repeats}, alternated)", flush=True)
+    moved = N * (S * S * 4 + ring.frame_bytes)
+    dev = sorted(x[0] for x in res["add_render()"])[args.repeats // 2]
+    print(f"N={N:5d} S={S:3d}  add_render() moves {moved / 1e6:.1f} MB: {moved / dev / 1e3:.1f} GB/s over its device-event time; "
+          f"the torch chain's frames differ in {diff} of {mine.numel()} bytes", flush=True)
+
+
 def two_rings(N, args, ag, rings):
     """rings: name -> (store, its pool of rows); collection steps, then updates, alternated per repeat"""
     first = torch.zeros(N, dtype=torch.bool, device="cuda")
@@ -326,9 +379,18 @@ def main():
                     help="measure the stacked ring against the single-frame ring (VecFrameReplay) instead")
     ap.add_argument("--episode-stats", action="store_true",
                     help="measure the ring with and without VecEpisodeStats.step(), and the same book-keeping in torch ops")
+    ap.add_argument("--render", action="store_true",
+                    help="measure add_render() against the torch resize chain in front of add(), and add() alone")
+    ap.add_argument("--sizes", default="84,128,168", help="image sizes of --render")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    if args.render:
+        for N in (int(x) for x in args.envs.split(",")):
+            for S in (int(x) for x in args.sizes.split(",")):
+                render(N, S, args)
+                torch.cuda.empty_cache()
+        return
     if args.episode_stats:
         for N in (int(x) for x in args.envs.split(",")):
             episode_stats(N, args)
