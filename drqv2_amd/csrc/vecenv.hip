@@ -1,0 +1,215 @@
+// A built-in device environment for vectorised collection (contract: include/drqv2_hip.h, "device environment").  New
+// functionality: the reference steps one dm_control environment on the host (dmc.py, train.py:160-190); the rings of
+// "step-major replay" take device tensors of N lockstep environments and nothing in the tree produced them.  "Reach" is
+// a point in a square that must reach a target; it emits exactly what VecFrameReplay.add(), add_render() and
+// VecEpisodeStats.step() take -- the 3 x 84 x 84 frame, reward, discount and first of every environment -- and is
+// deterministic to the bit (tests/vec_env_oracle.py restates it in numpy).  It is no benchmark task.
+//
+// drq_vec_reach_step is one launch of N workgroups of 256 threads, one per environment:
+//   state     every thread loads the seven state words of its environment and computes the reset or the step itself, in
+//             registers -- the same IEEE operations on the same operands in every lane, so all 256 agree
+//   barrier   __syncthreads(): every lane has read the old state before thread 0 stores the new one and the three scalars
+//   frame     1,323 pieces of 16 bytes, 5 or 6 per lane, consecutive lanes consecutive pieces.  A lane decodes (c, i, j)
+//             from its flat offset once (7,056 = 441 x 16: a piece never crosses a channel plane; 84 = 5 x 16 + 4: it may
+//             cross a row), then walks 16 pixels: background, target disc, agent disc, in integers
+// No LDS, no atomics, nothing crosses workgroups; an environment's state is read and written by its own workgroup only.
+// This file is compiled with -ffp-contract=off (build.py): the contract is single float32 operations in the written
+// order, and hipcc's default would fuse a * 0.1f + pos and (x + 1) * 41.5f + 0.5f into one rounding.
+//
+// drq_vec_reach_image writes the renderer-shaped uint8 [N][S][S][C] image of frames, S = 84 k: every pixel k x k times,
+// channels last, a fourth channel 255.  N x ceil(pieces / 1,024) workgroups of 256 threads, 16-byte stores, the source
+// bytes through the cache (a frame is 21 KB); k and C are template arguments, so the decode divides by constants.
+#include "common.h"
+#include "../../include/drqv2_hip.h"
+
+namespace {
+
+constexpr int kSide = 84;
+constexpr int kPlane = kSide * kSide;             // 7,056 bytes = 441 x 16
+constexpr int kFrame = 3 * kPlane;                // 21,168 bytes = 1,323 x 16
+constexpr int kPieces = kFrame / 16;
+constexpr int kThreads = 256;
+constexpr int kTargetR2 = 25, kAgentR2 = 16;
+
+__host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {    // the murmur3 finaliser
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// draw k of episode `episode` of environment e: uniform on the 2^24 grid of [0, 1), then into [-0.9, 0.9]
+__device__ __forceinline__ float reach_draw(unsigned seed, unsigned e, unsigned episode, unsigned k) {
+  const unsigned h = fmix32(seed ^ e * 0x9E3779B9u ^ episode * 0x85EBCA6Bu ^ k * 0xC2B2AE35u);
+  const float u = (float)(h >> 8) * 5.9604644775390625e-8f;          // 2^-24: exact
+  return (u * 2.0f - 1.0f) * 0.9f;
+}
+
+__device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
+
+__device__ __forceinline__ int pixel_centre(float x) { return (int)floorf((x + 1.0f) * 41.5f + 0.5f); }
+
+struct ReachArgs {
+  float* pos;             // [N][2]
+  float* target;          // [N][2]
+  int* t;
+  unsigned* episode;
+  uint8_t* over;
+  const float* action;    // [N][A]; null only with reset_all
+  uint8_t* frame;         // [N][3][84][84]
+  float* reward;
+  float* discount;
+  uint8_t* first;
+  unsigned seed;
+  int A, episode_length, reset_all;
+};
+
+__global__ __launch_bounds__(kThreads) void vec_reach_step_kernel(ReachArgs a) {
+  const long e = blockIdx.x;
+  float px = a.pos[2 * e], py = a.pos[2 * e + 1], tx = a.target[2 * e], ty = a.target[2 * e + 1];
+  int t = a.t[e];
+  unsigned episode = a.episode[e];
+  unsigned over = a.over[e];
+  float reward = 0.0f, discount = 1.0f;
+  unsigned first;
+  if (a.reset_all || over) {
+    episode += 1u;
+    t = 0;
+    over = 0u;
+    px = reach_draw(a.seed, (unsigned)e, episode, 0u);
+    py = reach_draw(a.seed, (unsigned)e, episode, 1u);
+    tx = reach_draw(a.seed, (unsigned)e, episode, 2u);
+    ty = reach_draw(a.seed, (unsigned)e, episode, 3u);
+    first = 1u;
+  } else {
+    float ax = a.action[e * a.A], ay = a.action[e * a.A + 1];
+    ax = ax != ax ? 0.0f : clamp1(ax);
+    ay = ay != ay ? 0.0f : clamp1(ay);
+    px = clamp1(px + ax * 0.1f);
+    py = clamp1(py + ay * 0.1f);
+    t += 1;
+    const float dx = px - tx, dy = py - ty;
+    const float d2 = dx * dx + dy * dy;
+    const float r = 1.0f - d2;
+    reward = r > 0.0f ? r : 0.0f;
+    if (d2 <= 0.01f) {
+      discount = 0.0f;
+      over = 1u;
+    } else if (t == a.episode_length) {
+      over = 1u;
+    }
+    first = 0u;
+  }
+  __syncthreads();            // every lane holds the old state: thread 0 may now replace it
+  if (threadIdx.x == 0) {
+    a.pos[2 * e] = px;
+    a.pos[2 * e + 1] = py;
+    a.target[2 * e] = tx;
+    a.target[2 * e + 1] = ty;
+    a.t[e] = t;
+    a.episode[e] = episode;
+    a.over[e] = (uint8_t)over;
+    a.reward[e] = reward;
+    a.discount[e] = discount;
+    a.first[e] = (uint8_t)first;
+  }
+
+  const int acx = pixel_centre(px), acy = pixel_centre(py), tcx = pixel_centre(tx), tcy = pixel_centre(ty);
+  uint4* dst = reinterpret_cast<uint4*>(a.frame + e * (long)kFrame);
+  for (int v = threadIdx.x; v < kPieces; v += kThreads) {
+    const int o = 16 * v;
+    const int c = o / kPlane, rem = o - c * kPlane;
+    int i = rem / kSide, j = rem - i * kSide;
+    const unsigned target_colour = c == 1 ? 255u : 64u, agent_colour = c == 0 ? 255u : 64u;
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      unsigned p = 32u + (unsigned)((i + j) >> 2);
+      const int tdx = j - tcx, tdy = i - tcy, adx = j - acx, ady = i - acy;
+      if (tdx * tdx + tdy * tdy <= kTargetR2) p = target_colour;
+      if (adx * adx + ady * ady <= kAgentR2) p = agent_colour;
+      w[b >> 2] |= p << (8 * (b & 3));
+      if (++j == kSide) {
+        j = 0;
+        ++i;
+      }
+    }
+    dst[v] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+// image[e][y][x][ch] = frame[e][ch][y / K][x / K], ch < 3; 255 for ch == 3.  A piece is 16 consecutive bytes of the image
+// of one environment (84^2 K^2 C is a multiple of 16).
+template <int K, int C>
+__global__ __launch_bounds__(kThreads) void vec_reach_image_kernel(const uint8_t* __restrict__ frame, uint8_t* image) {
+  constexpr int S = kSide * K;
+  constexpr int kBytes = S * S * C, kImagePieces = kBytes / 16;
+  static_assert(kBytes % 16 == 0, "an image is whole 16-byte pieces");
+  const long e = blockIdx.x;
+  const uint8_t* src = frame + e * (long)kFrame;
+  uint4* dst = reinterpret_cast<uint4*>(image + e * (long)kBytes);
+  for (int v = blockIdx.y * kThreads + threadIdx.x; v < kImagePieces; v += gridDim.y * kThreads) {
+    const int o = 16 * v;
+    int pix = o / C, ch = o - pix * C;
+    int y = pix / S, x = pix - y * S;
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      const unsigned p = ch == 3 ? 255u : (unsigned)src[ch * kPlane + (y / K) * kSide + x / K];
+      w[b >> 2] |= p << (8 * (b & 3));
+      if (++ch == C) {
+        ch = 0;
+        if (++x == S) {
+          x = 0;
+          ++y;
+        }
+      }
+    }
+    dst[v] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+template <int K>
+void launch_image(int C, dim3 grid, hipStream_t st, const uint8_t* frame, uint8_t* image) {
+  if (C == 4) hipLaunchKernelGGL((vec_reach_image_kernel<K, 4>), grid, dim3(kThreads), 0, st, frame, image);
+  else hipLaunchKernelGGL((vec_reach_image_kernel<K, 3>), grid, dim3(kThreads), 0, st, frame, image);
+}
+
+}  // namespace
+
+DRQ_API int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
+                               const float* action, unsigned seed, int episode_length, int reset_all, uint8_t* frame,
+                               float* reward, float* discount, uint8_t* first, drq_stream_t stream) {
+  if (!pos || !target || !t || !episode || !over || !frame || !reward || !discount || !first) return DRQ_EARG;
+  if (N < 1 || N > INT32_MAX || A < 2 || episode_length < 1) return DRQ_EARG;
+  if (reset_all != 0 && reset_all != 1) return DRQ_EARG;
+  if (!action && !reset_all) return DRQ_EARG;
+  if ((uintptr_t)frame & 15) return DRQ_EARG;
+  if (((uintptr_t)pos | (uintptr_t)target | (uintptr_t)t | (uintptr_t)episode | (uintptr_t)reward | (uintptr_t)discount |
+       (uintptr_t)action) & 3)
+    return DRQ_EARG;
+  ReachArgs a{pos, target, t, episode, over, action, frame, reward, discount, first, seed, A, episode_length, reset_all};
+  hipLaunchKernelGGL(vec_reach_step_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, a);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream) {
+  if (!frame || !image || N < 1 || N > INT32_MAX) return DRQ_EARG;
+  if (S < kSide || S > 4 * kSide || S % kSide || (C != 3 && C != 4)) return DRQ_EARG;
+  if (((uintptr_t)frame | (uintptr_t)image) & 15) return DRQ_EARG;
+  const int K = S / kSide;
+  const int pieces = S * S * C / 16;
+  const dim3 grid((unsigned)N, (unsigned)((pieces + 4 * kThreads - 1) / (4 * kThreads)));      // at most 28 in y
+  hipStream_t st = (hipStream_t)stream;
+  switch (K) {
+    case 1: launch_image<1>(C, grid, st, frame, image); break;
+    case 2: launch_image<2>(C, grid, st, frame, image); break;
+    case 3: launch_image<3>(C, grid, st, frame, image); break;
+    default: launch_image<4>(C, grid, st, frame, image); break;
+  }
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}

@@ -1,0 +1,143 @@
+"""Built-in device environments for vectorised collection (new; the reference steps one dm_control environment on the
+host, dmc.py / train.py:160-190).
+
+VecReach is the producer the device-side collection path was missing: N lockstep environments of a small pixel task
+("reach": a point in a square must reach a target) stepped by ONE launch (csrc/vecenv.hip, drq_vec_reach_step) that writes
+what VecFrameReplay.add(), add_render() and VecEpisodeStats.step() take -- uint8 [N, 3, 84, 84] frames, reward, discount
+and first -- as device tensors on the current stream.  The task is specified to the bit in include/drqv2_hip.h ("device
+environment") and restated in numpy by tests/vec_env_oracle.py.  It is not a benchmark task and says nothing about DMC.
+"""
+import torch
+
+from . import _lib
+from ._lib import check, ptr
+
+
+class VecReach:
+    """N environments of the reach task on the device.
+
+        env = VecReach(num_envs=N, device="cuda", action_dim=A, episode_length=250, seed=0)
+        frame = env.reset()                                   # uint8 [N, 3, 84, 84]
+        frame, reward, discount, first = env.step(action)     # action float32 [N, A] on the device
+
+    Per environment: pos and target in [-1, 1]^2, t (steps of this episode), episode (a counter), over (the last step
+    ended the episode).  step() moves pos by clamp(action[:, :2], -1, 1) * 0.1 (NaN counts as 0; further columns are
+    ignored), reward = max(0, 1 - |pos - target|^2); |pos - target|^2 <= 0.01 ends the episode with discount 0 (reached),
+    t == episode_length with discount 1 (the time limit).  The step() AFTER one that ended the episode is the reset row
+    of that environment: first = 1, reward 0, discount 1, the first frame of a new episode whose positions are a hash of
+    (seed, environment, episode); its action is ignored.  So resets are staggered across the environments, as the rings
+    and the statistics expect them.  Everything is deterministic to the bit for a seed and a sequence of actions.
+
+    Every return is a device tensor written by a launch on the current stream; nothing waits for the GPU.  step() and
+    reset() write into TWO output sets (frame, reward, discount, first) used in turn, as VecFrameReplay.observation()
+    does: a returned tensor is overwritten by the second step() / reset() call after it, so a caller that keeps one
+    longer clones it.  image() rotates two buffers per (size, channels) in the same way."""
+
+    FRAME_SHAPE = (3, 84, 84)
+    IMAGE_SIZES = (84, 168, 252, 336)
+
+    def __init__(self, num_envs, device, action_dim=2, episode_length=250, seed=0):
+        self.N, self.A, self.episode_length = int(num_envs), int(action_dim), int(episode_length)
+        if self.N < 1 or self.A < 2 or self.episode_length < 1:
+            raise ValueError("num_envs and episode_length must be >= 1, action_dim >= 2")
+        self.seed = int(seed) & 0xFFFFFFFF
+        self.device = dev = torch.device(device)
+        N = self.N
+        self.pos = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+        self.target = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+        self.t = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)       # uint32 on the device: state() views it so
+        self.over = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._out = None            # two of (frame, reward, discount, first), then the index of the next
+        self._frame = None          # the frames of the newest step() / reset()
+        self._images = {}           # (size, channels) -> [buffer, buffer, index of the next]
+
+    def _device_index(self):
+        d = self.device
+        if d.type == "cuda" and d.index is None:
+            return torch.device("cuda", torch.cuda.current_device())
+        return d
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _on_gpu(self):
+        if self.device.type != "cuda":
+            raise _lib.DrqError("the device environment lives on the GPU: the HIP path has no CPU fallback")
+
+    def _action(self, action):
+        N, A = self.N, self.A
+        if not torch.is_tensor(action):
+            raise ValueError("step(): action must be a tensor on the environment's device")
+        if tuple(action.shape) != (N, A):
+            raise ValueError(f"step(): action of shape {(N, A)} required, got {tuple(action.shape)}")
+        if action.dtype != torch.float32:
+            raise ValueError(f"step(): action must be {torch.float32}, got {action.dtype}")
+        if action.device != self._device_index():
+            raise ValueError(f"step(): action is on {action.device}, the environment on {self.device}")
+        return action.contiguous()
+
+    def _launch(self, action, reset_all):
+        if self._out is None:
+            dev, N = self.device, self.N
+            self._out = [(torch.empty((N,) + self.FRAME_SHAPE, dtype=torch.uint8, device=dev),
+                          torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev),
+                          torch.empty(N, dtype=torch.uint8, device=dev)) for _ in range(2)] + [0]
+        out = self._out[self._out[2]]
+        self._out[2] ^= 1
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_reach_step(ptr(self.pos), ptr(self.target), ptr(self.t), ptr(self.episode),
+                                                 ptr(self.over), self.N, self.A, ptr(action), self.seed,
+                                                 self.episode_length, int(reset_all), *(ptr(o) for o in out),
+                                                 self._stream()), "drq_vec_reach_step")
+            if action is not None:  # a caller's tensor may be freed right after step(): the launch still reads it
+                action.record_stream(torch.cuda.current_stream())
+        self._frame = out[0]
+        return out
+
+    def reset(self):
+        """Starts a new episode in every environment (one launch) and returns its first frames, uint8 [N, 3, 84, 84].  The
+        row is a reset row for every environment: what goes into the ring beside it is add(frame, zeros, zeros, ones)."""
+        self._on_gpu()
+        return self._launch(None, True)[0]
+
+    def step(self, action):
+        """action: float32 [N, action_dim] tensor on the environment's device (what agent.act_batch() returns); ValueError
+        otherwise.  One launch; returns (frame uint8 [N, 3, 84, 84], reward float32 [N], discount float32 [N], first
+        uint8 [N]) from one of the two output sets used in turn.  An environment whose previous step ended its episode is
+        reset by this call: first = 1, the frame is the new episode's first, reward = 0 and discount = 1 are dummies."""
+        action = self._action(action)
+        self._on_gpu()
+        if self._frame is None:
+            raise _lib.DrqError("step(): call reset() first")
+        return self._launch(action, False)
+
+    def image(self, size=84, channels=3):
+        """The current frames as a renderer hands images out: uint8 [N, size, size, channels], channels last, size 84,
+        168, 252 or 336 (every pixel size / 84 times in both directions), channels 3 or 4 (the fourth is 255).  One
+        launch (drq_vec_reach_image); VecFrameReplay.add_render() of it stores exactly the frame."""
+        size, channels = int(size), int(channels)
+        if size not in self.IMAGE_SIZES or channels not in (3, 4):
+            raise ValueError(f"image(): size in {self.IMAGE_SIZES} and 3 or 4 channels required, got {size}, {channels}")
+        self._on_gpu()
+        if self._frame is None:
+            raise _lib.DrqError("image(): call reset() first")
+        bufs = self._images.get((size, channels))
+        if bufs is None:
+            bufs = self._images[size, channels] = [torch.empty((self.N, size, size, channels), dtype=torch.uint8,
+                                                               device=self.device) for _ in range(2)] + [0]
+        out = bufs[bufs[2]]
+        bufs[2] ^= 1
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_reach_image(ptr(self._frame), ptr(out), self.N, size, channels, self._stream()),
+                  "drq_vec_reach_image")
+        return out
+
+    def state(self):
+        """Host copies of the state, for tests and debugging: {"pos": float32 [N, 2], "target": float32 [N, 2], "t": int32
+        [N], "episode": uint32 [N], "over": uint8 [N]}.  This SYNCHRONISES: the copies wait for every launch enqueued so
+        far.  Nothing in a collection loop should call it."""
+        import numpy as np
+        s = {k: getattr(self, k).cpu().numpy() for k in ("pos", "target", "t", "episode", "over")}
+        s["episode"] = s["episode"].view(np.uint32)
+        return s

@@ -575,6 +575,48 @@ int drq_vec_stats_publish(const void* header, const float* log_return, const int
 int drq_vec_stats_reset(float* ret, int* len, int* done, void* header, float* log_return, int* log_length, int* log_env,
                         long* log_row, long N, long W, drq_stream_t stream);
 
+/* ---- device environment.  New functionality: the reference steps one dm_control environment on the host (dmc.py,
+ * train.py:160-190); this is a small pixel task that lives on the device and steps N lockstep environments with one
+ * launch, the reference producer of what "single-frame step-major replay", "renderer images" and "episode statistics"
+ * consume.  It is no benchmark task.  These definitions are the contract; they are exact to the bit.
+ * The task ("reach"): a point in the square [-1, 1]^2 must reach a target.  State per environment e, all on the device:
+ *   pos f32 [N][2], target f32 [N][2], t i32 [N] (the steps taken in this episode), episode u32 [N] (counts the episodes
+ *   of e; 0 before the first reset), over u8 [N] (1 = the last step ended the episode).
+ * Every float operation below is ONE IEEE float32 operation, in the written order, never fused.
+ * Reset of e (when reset_all = 1, or in a step when over[e] == 1):
+ *   episode += 1 (mod 2^32), t = 0, over = 0; four draws k = 0 .. 3 give pos.x, pos.y, target.x, target.y:
+ *     h = fmix32(seed ^ e * 0x9E3779B9 ^ episode * 0x85EBCA6B ^ k * 0xC2B2AE35) in uint32 arithmetic, episode the new count,
+ *     fmix32 the murmur3 finaliser (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16);
+ *     u = float(h >> 8) * 2^-24;  v = (u * 2 - 1) * 0.9f
+ *   outputs: first = 1, reward = 0, discount = 1, the frame of the new state.  The action of e is not read.
+ * Step of e (every environment that is not being reset):
+ *   a = action[e][0 .. 1]; a NaN becomes 0, otherwise a < -1 becomes -1 and a > 1 becomes 1; columns 2 .. A-1 are not read
+ *   pos = clamp(pos + a * 0.1f, -1, 1) per component (a multiply, an add, the clamp);  t += 1
+ *   dx = pos.x - target.x, dy = pos.y - target.y;  d2 = dx * dx + dy * dy;  r = 1 - d2;  reward = r > 0 ? r : 0
+ *   d2 <= 0.01f: discount = 0, over = 1 (reached: a true terminal);  else t == episode_length: discount = 1, over = 1
+ *   (the time limit);  else discount = 1.  first = 0.
+ * Frame of a state, u8 [3][84][84], pixel (i, j) = row i, column j:
+ *   cx = (int)floorf((x + 1) * 41.5f + 0.5f) and cy likewise from y, for pos (the agent) and for target: 0 .. 83
+ *   background 32 + ((i + j) >> 2) in all three channels;  the target, a disc (j-cx)^2 + (i-cy)^2 <= 25 in (64, 255, 64);
+ *   the agent drawn over it, a disc <= 16 in (255, 64, 64).  Integers after the two centres.
+ *
+ * drq_vec_reach_step: one launch advances all N states by the rules above and writes frame u8 [N][3][84][84], reward and
+ *   discount f32 [N], first u8 [N]: every byte of the four, nothing else but the state.  reset_all = 1 resets every
+ *   environment (action may be NULL then).  N workgroups of 256 threads, one per environment: every lane reads the old
+ *   state, a workgroup barrier, one lane stores the new state and the scalars, all store the frame as 16-byte pieces.
+ *   No state of one environment is touched by another's workgroup; the caller orders the launches on one stream.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 2,
+ *   episode_length < 1, reset_all not 0 or 1, frame not 16-byte aligned, a float / int array not 4-byte aligned.
+ * drq_vec_reach_image: the renderer-shaped image of such frames, u8 [N][S][S][C], S = 84 k, k = 1 .. 4, C = 3 or 4:
+ *   image[e][y][x][c] = frame[e][c][y / k][x / k] for c < 3 and 255 for c == 3 -- every pixel k x k times, channels last.
+ *   The area average of "renderer images" returns the frame exactly ((k^2 v + k^2 / 2) / k^2 = v).
+ *   DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX, S not 84, 168, 252 or 336, C not 3 or 4, frame or
+ *   image not 16-byte aligned. */
+int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
+                       const float* action, unsigned seed, int episode_length, int reset_all, uint8_t* frame,
+                       float* reward, float* discount, uint8_t* first, drq_stream_t stream);
+int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,

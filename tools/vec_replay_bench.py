@@ -52,6 +52,12 @@ for add_render() the bytes it moves (image read + frames written) over its devic
 float32 means half to even, so its frames are not add_render()'s everywhere; the tool counts the bytes that differ.
 
   python tools/vec_replay_bench.py --render [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--sizes 84,128,168]
+
+--env reach measures the built-in environment (drqv2_amd.envs.VecReach: drq_vec_reach_step, one launch per step of all N)
+next to the single-frame ring it feeds: env.step(), ring.add() of one step's outputs, and the two together, alternated
+inside every repeat of one process.  Same steps, repeats and the same two figures per line as above.
+
+  python tools/vec_replay_bench.py --env reach [--steps 2000] [--repeats 3] [--envs 16,256,1024]
 """
 import argparse
 import os
@@ -290,6 +296,36 @@ def render(N, S, args):
           f"the torch chain's frames differ in {diff} of {mine.numel()} bytes", flush=True)
 
 
+def reach(N, args):
+    """VecReach.step(), VecFrameReplay.add() of one step's outputs, and both, alternated per repeat"""
+    from drqv2_amd.envs import VecReach
+    env = VecReach(N, "cuda", action_dim=A, episode_length=250, seed=1)
+    ring = VecFrameReplay(max(32, SLOTS // N), N, A, NSTEP, 0.99, "cuda", seed=1)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N)
+    actions = [torch.rand(N, A, device="cuda", generator=g) * 2 - 1 for _ in range(4)]
+    env.reset()
+    held = tuple(t.clone() for t in env.step(actions[0]))
+
+    def both(i):
+        frame, reward, discount, first = env.step(actions[i & 3])
+        ring.add(frame, actions[i & 3], reward, discount, first)
+
+    paths = {"env.step()": lambda i: env.step(actions[i & 3]),
+             "ring.add() of a step's outputs": lambda i: ring.add(held[0], actions[i & 3], *held[1:]),
+             "env.step() + ring.add()": both}
+    for fn in paths.values():
+        for i in range(20):
+            fn(i)
+    res = {k: [] for k in paths}
+    for _ in range(args.repeats):
+        for k, fn in paths.items():
+            res[k].append(timed(fn, args.steps))
+    for k, v in res.items():
+        print(f"N={N:5d}  {k:31s}: device-event {spread([x[0] for x in v])}   host wall {spread([x[1] for x in v])}   "
+              f"({args.steps} x {args.repeats}, alternated)", flush=True)
+
+
 def two_rings(N, args, ag, rings):
     """rings: name -> (store, its pool of rows); collection steps, then updates, alternated per repeat"""
     first = torch.zeros(N, dtype=torch.bool, device="cuda")
@@ -382,9 +418,16 @@ def main():
     ap.add_argument("--render", action="store_true",
                     help="measure add_render() against the torch resize chain in front of add(), and add() alone")
     ap.add_argument("--sizes", default="84,128,168", help="image sizes of --render")
+    ap.add_argument("--env", choices=["reach"], default=None,
+                    help="measure the built-in environment's step() next to the single-frame ring's add()")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    if args.env:
+        for N in (int(x) for x in args.envs.split(",")):
+            reach(N, args)
+            torch.cuda.empty_cache()
+        return
     if args.render:
         for N in (int(x) for x in args.envs.split(",")):
             for S in (int(x) for x in args.sizes.split(",")):

@@ -1,0 +1,116 @@
+"""The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
+
+  VecReach (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
+
+Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
+return (and length) of the episodes that finished in every interval, from VecEpisodeStats, and afterwards the mean return of
+uniform-random actions over the SAME number of episodes on a second VecReach of the same seed, measured in the same
+process: that is the baseline the training curve is read against, not a constant written down in advance.
+
+  python tools/vec_train_demo.py [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
+                                 [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
+
+This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
+updates; it is no benchmark and makes no claim about DMC.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import drqv2  # noqa: E402
+from drqv2_amd.envs import VecReach  # noqa: E402
+from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
+
+
+def random_baseline(args, episodes):
+    """mean return and length of the first `episodes` episodes under uniform-random actions, same N, length and seed"""
+    N, A = args.envs, args.action_dim
+    env = VecReach(N, "cuda", action_dim=A, episode_length=args.episode_length, seed=args.seed)
+    stats = VecEpisodeStats(N, "cuda", log_size=max(1024, episodes + 64 * N))      # 100 more steps end at most 50 N more
+    g = torch.Generator(device="cuda")
+    g.manual_seed(args.seed)
+    env.reset()
+    stats.step(torch.zeros(N, device="cuda"))
+    while True:
+        for _ in range(100):
+            _, reward, _, first = env.step(torch.rand(N, A, device="cuda", generator=g) * 2 - 1)
+            stats.step(reward, first)
+        snap = stats.read()
+        if snap.episodes >= episodes:
+            rec = snap.records[:episodes]                  # oldest first: the log is large enough to hold them all
+            return float(rec["return"].mean()), float(rec["length"].mean()), snap.rows - 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20000, help="environment steps (each of all N environments)")
+    ap.add_argument("--envs", type=int, default=16)
+    ap.add_argument("--action-dim", type=int, default=2)
+    ap.add_argument("--episode-length", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=1000, help="steps of uniform-random actions before the first update")
+    ap.add_argument("--report", type=int, default=2000, help="steps per reporting interval")
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--rows", type=int, default=4096, help="rows of the ring (x N environments)")
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--feature-dim", type=int, default=50)
+    ap.add_argument("--hidden-dim", type=int, default=256)
+    ap.add_argument("--stddev", default="linear(1.0,0.1,10000)")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("vec_train_demo.py runs on the GPU: no device found")
+    N, A = args.envs, args.action_dim
+    torch.manual_seed(args.seed)
+    torch.cuda.manual_seed_all(args.seed)
+    print(f"reach: N={N} environments, episode_length={args.episode_length}, A={A}; {args.steps} steps, warm-up {args.warmup}, "
+          f"batch {args.batch}, lr {args.lr}, feature_dim {args.feature_dim}, hidden_dim {args.hidden_dim}, stddev "
+          f"{args.stddev}, seed {args.seed}", flush=True)
+
+    agent = drqv2.DrQV2Agent((9, 84, 84), (A,), "cuda", args.lr, args.feature_dim, args.hidden_dim, 0.01, args.warmup, 1,
+                             args.stddev, 0.3, False)
+    env = VecReach(N, "cuda", action_dim=A, episode_length=args.episode_length, seed=args.seed)
+    store = VecFrameReplay(rows=args.rows, num_envs=N, action_dim=A, nstep=3, discount=0.99, device="cuda", seed=args.seed)
+    store.batch_size = args.batch
+    stats = VecEpisodeStats(N, "cuda", log_size=max(1024, 2 * N * args.report))
+    it = iter(store)
+    zeros_NA, zeros_N, ones_N = torch.zeros(N, A, device="cuda"), torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
+
+    frame = env.reset()
+    store.add(frame, zeros_NA, zeros_N, ones_N)                      # row 0: the reset row of every environment
+    stats.step(zeros_N)
+    logged, updates, t0 = 0, 0, time.perf_counter()
+    for step in range(args.steps):
+        action = agent.act_batch(store.observation(), step, False)   # [N, A], stays on the device
+        frame, reward, discount, first = env.step(action)
+        store.add(frame, action, reward, discount, first)
+        stats.step(reward, first)
+        if step >= args.warmup:
+            agent.update(it, step)
+            updates += 1
+        if (step + 1) % args.report == 0:
+            snap = stats.read()                                      # the one wait per interval
+            new, missed = snap.since(logged)
+            logged = snap.episodes
+            mean = f"{new['return'].mean():7.3f}" if len(new) else "    n/a"
+            length = f"{new['length'].mean():5.1f}" if len(new) else "  n/a"
+            print(f"step {step + 1:6d}  updates {updates:6d}  episodes {snap.episodes:6d} (+{len(new) + missed})  mean return "
+                  f"{mean}  mean length {length}  return per step "
+                  f"{(new['return'].sum() / max(1, new['length'].sum())):.3f}  [{time.perf_counter() - t0:.1f} s]", flush=True)
+    snap = stats.read()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    print(f"trained: {snap.episodes} episodes in {snap.rows - 1} steps x {N} environments, mean return over all of them "
+          f"{snap.mean_return:.3f}, mean length {snap.mean_length:.1f}; {wall:.1f} s, {1e3 * wall / args.steps:.2f} ms per step",
+          flush=True)
+    b_ret, b_len, b_steps = random_baseline(args, snap.episodes)
+    print(f"baseline: uniform-random actions, the first {snap.episodes} episodes ({b_steps} steps): mean return {b_ret:.3f}, "
+          f"mean length {b_len:.1f}, return per step {b_ret / b_len:.3f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
