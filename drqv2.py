@@ -466,7 +466,7 @@ class DrQV2Agent:
                 "encoder": cpu(self.encoder.state_dict()), "actor": cpu(self.actor.state_dict()),
                 "critic": cpu(self.critic.state_dict()), "critic_target": cpu(self.critic_target.state_dict()),
                 "opt": {n: getattr(self, n).export_state() for n in ("encoder_opt", "actor_opt", "critic_opt")},
-                "bc_alpha": self._engine.bc_alpha}
+                "bc_alpha": self._engine.bc_alpha, "compute_dtype": "bf16" if self._engine.bf16 else "fp32"}
 
     def _load_reference_state(self, st):
         """`st` is the __dict__ of an agent pickled by the REFERENCE's class (train.py:192-198 pickles the object and
@@ -512,11 +512,23 @@ class DrQV2Agent:
             kw["device"] = "cpu"
         with torch.random.fork_rng(devices=[]):      # building the nets must not move the global RNG
             self.__init__(**kw)
+        self._restore(st)
+
+    def _restore(self, st):
+        """what __setstate__ does once the agent is built: weights, target, Adam moments and step counts, the DrQ+BC and
+        compute-dtype settings, the training flag -- copied into the arenas of THIS agent.  drqv2_amd.checkpoint.load()
+        calls it on a live agent whose constructor arguments it has compared with st["init"]."""
+        self._engine.flush()        # data parallel: a deferred Adam step must land before the restored weights do
         self.encoder.load_state_dict(st["encoder"])
         self.actor.load_state_dict(st["actor"])
         self.critic.load_state_dict(st["critic"])
         self.critic_target.load_state_dict(st["critic_target"])
         for n, s in st["opt"].items():
             getattr(self, n).import_state(s)
+        dtype = st.get("compute_dtype")                    # absent in snapshots written before it was saved: as it is
+        if dtype == "fp32":
+            self.set_compute_dtype("fp32")
         self.set_behavior_cloning(st.get("bc_alpha"))      # absent in snapshots written before DrQ+BC: off
+        if dtype == "bf16":
+            self.set_compute_dtype("bf16")
         self.train(st["training"])

@@ -111,6 +111,7 @@ PROTOTYPES = {
     "drq_vec_stats_publish": (I, [P, P, P, P, P, L, P, C.c_uint, P]),
     "drq_vec_stats_reset": (I, [P, P, P, P, P, P, P, P, L, L, P]),
     "drq_vec_reach_step": (I, [P, P, P, P, P, L, I, P, C.c_uint, I, I, P, P, P, P, P]),
+    "drq_vec_reach_render": (I, [P, P, L, P, P]),
     "drq_vec_reach_image": (I, [P, P, L, I, I, P]),
     "drq_nstep_gather_frames": (I, [P, P, L, P, P, P, P, I, I, L, I, F, P, P, P, P, P, P]),
     "drq_relu_mask_pad": (I, [P, P, P, L, I, I, P]),

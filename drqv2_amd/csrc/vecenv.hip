@@ -16,6 +16,10 @@
 // This file is compiled with -ffp-contract=off (build.py): the contract is single float32 operations in the written
 // order, and hipcc's default would fuse a * 0.1f + pos and (x + 1) * 41.5f + 0.5f into one rounding.
 //
+// drq_vec_reach_render draws the frames of the states as they are and changes nothing else: the frame part above alone, N
+// workgroups of 256 threads, the same device function (reach_frame) -- what a restored environment shows before its next
+// step, since a checkpoint holds the state and not the frames derived from it.
+//
 // drq_vec_reach_image writes the renderer-shaped uint8 [N][S][S][C] image of frames, S = 84 k: every pixel k x k times,
 // channels last, a fourth channel 255.  N x ceil(pieces / 1,024) workgroups of 256 threads, 16-byte stores, the source
 // bytes through the cache (a frame is 21 KB); k and C are template arguments, so the decode divides by constants.
@@ -50,6 +54,33 @@ __device__ __forceinline__ float reach_draw(unsigned seed, unsigned e, unsigned 
 __device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
 __device__ __forceinline__ int pixel_centre(float x) { return (int)floorf((x + 1.0f) * 41.5f + 0.5f); }
+
+// The pixel rule: the frame of the state (px, py, tx, ty) into the 21,168 bytes at `frame`, by the 256 threads of a
+// workgroup -- 1,323 pieces of 16 bytes, consecutive lanes consecutive pieces.  The step and the render kernel share it.
+__device__ __forceinline__ void reach_frame(float px, float py, float tx, float ty, uint8_t* frame) {
+  const int acx = pixel_centre(px), acy = pixel_centre(py), tcx = pixel_centre(tx), tcy = pixel_centre(ty);
+  uint4* dst = reinterpret_cast<uint4*>(frame);
+  for (int v = threadIdx.x; v < kPieces; v += kThreads) {
+    const int o = 16 * v;
+    const int c = o / kPlane, rem = o - c * kPlane;
+    int i = rem / kSide, j = rem - i * kSide;
+    const unsigned target_colour = c == 1 ? 255u : 64u, agent_colour = c == 0 ? 255u : 64u;
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      unsigned p = 32u + (unsigned)((i + j) >> 2);
+      const int tdx = j - tcx, tdy = i - tcy, adx = j - acx, ady = i - acy;
+      if (tdx * tdx + tdy * tdy <= kTargetR2) p = target_colour;
+      if (adx * adx + ady * ady <= kAgentR2) p = agent_colour;
+      w[b >> 2] |= p << (8 * (b & 3));
+      if (++j == kSide) {
+        j = 0;
+        ++i;
+      }
+    }
+    dst[v] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
 
 struct ReachArgs {
   float* pos;             // [N][2]
@@ -116,28 +147,14 @@ __global__ __launch_bounds__(kThreads) void vec_reach_step_kernel(ReachArgs a) {
     a.first[e] = (uint8_t)first;
   }
 
-  const int acx = pixel_centre(px), acy = pixel_centre(py), tcx = pixel_centre(tx), tcy = pixel_centre(ty);
-  uint4* dst = reinterpret_cast<uint4*>(a.frame + e * (long)kFrame);
-  for (int v = threadIdx.x; v < kPieces; v += kThreads) {
-    const int o = 16 * v;
-    const int c = o / kPlane, rem = o - c * kPlane;
-    int i = rem / kSide, j = rem - i * kSide;
-    const unsigned target_colour = c == 1 ? 255u : 64u, agent_colour = c == 0 ? 255u : 64u;
-    unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-      unsigned p = 32u + (unsigned)((i + j) >> 2);
-      const int tdx = j - tcx, tdy = i - tcy, adx = j - acx, ady = i - acy;
-      if (tdx * tdx + tdy * tdy <= kTargetR2) p = target_colour;
-      if (adx * adx + ady * ady <= kAgentR2) p = agent_colour;
-      w[b >> 2] |= p << (8 * (b & 3));
-      if (++j == kSide) {
-        j = 0;
-        ++i;
-      }
-    }
-    dst[v] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  reach_frame(px, py, tx, ty, a.frame + e * (long)kFrame);
+}
+
+// the frames of the states as they are: the frame part of the step kernel alone, same launch shape
+__global__ __launch_bounds__(kThreads) void vec_reach_render_kernel(const float* __restrict__ pos,
+                                                                    const float* __restrict__ target, uint8_t* frame) {
+  const long e = blockIdx.x;
+  reach_frame(pos[2 * e], pos[2 * e + 1], target[2 * e], target[2 * e + 1], frame + e * (long)kFrame);
 }
 
 // image[e][y][x][ch] = frame[e][ch][y / K][x / K], ch < 3; 255 for ch == 3.  A piece is 16 consecutive bytes of the image
@@ -192,6 +209,15 @@ DRQ_API int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* epis
     return DRQ_EARG;
   ReachArgs a{pos, target, t, episode, over, action, frame, reward, discount, first, seed, A, episode_length, reset_all};
   hipLaunchKernelGGL(vec_reach_step_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, a);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_vec_reach_render(const float* pos, const float* target, long N, uint8_t* frame, drq_stream_t stream) {
+  if (!pos || !target || !frame || N < 1 || N > INT32_MAX) return DRQ_EARG;
+  if ((uintptr_t)frame & 15) return DRQ_EARG;
+  if (((uintptr_t)pos | (uintptr_t)target) & 3) return DRQ_EARG;
+  hipLaunchKernelGGL(vec_reach_render_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, pos, target, frame);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .checkpoint import check_state, host
 
 
 class VecReach:
@@ -30,8 +31,11 @@ class VecReach:
 
     Every return is a device tensor written by a launch on the current stream; nothing waits for the GPU.  step() and
     reset() write into TWO output sets (frame, reward, discount, first) used in turn, as VecFrameReplay.observation()
-    does: a returned tensor is overwritten by the second step() / reset() call after it, so a caller that keeps one
-    longer clones it.  image() rotates two buffers per (size, channels) in the same way."""
+    does: a returned tensor is overwritten by the second step() / reset() / render() call after it, so a caller that
+    keeps one longer clones it.  image() rotates two buffers per (size, channels) in the same way.
+
+    Checkpoints: state_dict() / load_state_dict() save and restore the seven state words per environment; the frames are
+    derived data and are drawn again from the restored state (render(): drq_vec_reach_render, one launch)."""
 
     FRAME_SHAPE = (3, 84, 84)
     IMAGE_SIZES = (84, 168, 252, 336)
@@ -77,7 +81,8 @@ class VecReach:
             raise ValueError(f"step(): action is on {action.device}, the environment on {self.device}")
         return action.contiguous()
 
-    def _launch(self, action, reset_all):
+    def _next_out(self):
+        """the output set (frame, reward, discount, first) the next launch writes"""
         if self._out is None:
             dev, N = self.device, self.N
             self._out = [(torch.empty((N,) + self.FRAME_SHAPE, dtype=torch.uint8, device=dev),
@@ -85,6 +90,10 @@ class VecReach:
                           torch.empty(N, dtype=torch.uint8, device=dev)) for _ in range(2)] + [0]
         out = self._out[self._out[2]]
         self._out[2] ^= 1
+        return out
+
+    def _launch(self, action, reset_all):
+        out = self._next_out()
         with torch.cuda.device(self.device):
             check(_lib.load().drq_vec_reach_step(ptr(self.pos), ptr(self.target), ptr(self.t), ptr(self.episode),
                                                  ptr(self.over), self.N, self.A, ptr(action), self.seed,
@@ -111,6 +120,24 @@ class VecReach:
         if self._frame is None:
             raise _lib.DrqError("step(): call reset() first")
         return self._launch(action, False)
+
+    def render(self):
+        """The frames of the current state, uint8 [N, 3, 84, 84]: one launch (drq_vec_reach_render) that reads pos and
+        target and changes no state.  After reset() or step() it returns exactly the frame they returned; after
+        load_state_dict() it is how the restored environment gets its frames.  It writes into the next of the two output
+        sets, like step(), and that frame becomes the one image() reads."""
+        self._on_gpu()
+        if self._frame is None:
+            raise _lib.DrqError("render(): call reset() or load_state_dict() first")
+        return self._render()
+
+    def _render(self):
+        out = self._next_out()
+        with torch.cuda.device(self.device):
+            check(_lib.load().drq_vec_reach_render(ptr(self.pos), ptr(self.target), self.N, ptr(out[0]), self._stream()),
+                  "drq_vec_reach_render")
+        self._frame = out[0]
+        return out[0]
 
     def image(self, size=84, channels=3):
         """The current frames as a renderer hands images out: uint8 [N, size, size, channels], channels last, size 84,
@@ -141,3 +168,33 @@ class VecReach:
         s = {k: getattr(self, k).cpu().numpy() for k in ("pos", "target", "t", "episode", "over")}
         s["episode"] = s["episode"].view(np.uint32)
         return s
+
+    # ---- checkpoints ---------------------------------------------------------------------
+    _STATE = ("pos", "target", "t", "episode", "over")
+
+    def state_dict(self):
+        """The environment as a plain dict of CPU tensors and Python scalars: "format": 1, "kind", the configuration (N,
+        A, episode_length, seed) and the seven state words per environment (pos, target, t, episode, over; episode as the
+        int32 tensor that holds its uint32 bits).  The newest frames are not in it: they are a function of the state.  This SYNCHRONISES the environment's device, like
+        state(): the copies wait for every launch enqueued so far."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        sd = {"format": 1, "kind": type(self).__name__, "reset": self._frame is not None,
+              "config": {"N": self.N, "A": self.A, "episode_length": self.episode_length, "seed": self.seed}}
+        for k in self._STATE:
+            sd[k] = host(getattr(self, k))
+        return sd
+
+    def load_state_dict(self, sd):
+        """Restores what state_dict() saved, into a fresh or a used environment.  ValueError, with nothing changed, for a
+        wrong "format" / "kind" or a configuration that differs from this object's (every differing field is named).  The
+        frames are drawn from the restored state with one launch (render()'s), so step() and image() work without a
+        reset() -- unless the saved environment had never been reset.  DrqError on a CPU device, after the checks."""
+        check_state(self, sd, {"N": self.N, "A": self.A, "episode_length": self.episode_length, "seed": self.seed},
+                    {k: getattr(self, k) for k in self._STATE})
+        self._on_gpu()
+        for k in self._STATE:
+            getattr(self, k).copy_(sd[k])
+        self._frame = None
+        if sd.get("reset", True):
+            self._render()

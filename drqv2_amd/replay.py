@@ -40,12 +40,17 @@ step, indexed batches are FrameBatch objects, materialised ones come from one la
 Episode statistics (new: VecEpisodeStats, csrc/vecstats.hip).  The reference's episode_reward / episode_step book-keeping
 (train.py:133,186,189) for N lockstep environments, kept on the device from the reward and first tensors add() takes: one
 launch per step, a pinned host mirror that nothing waits for, and a per-environment episode limit for evaluation.
+
+Checkpoints (new: state_dict() / load_state_dict() on VecDeviceReplay, VecFrameReplay, BatchIterator and VecEpisodeStats;
+drqv2_amd/checkpoint.py puts them into one file with the agent and the generators).  A restored loop continues bit for
+bit as the uninterrupted one would have.  The episode store keeps the reference's way: episodes are its unit.
 """
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .checkpoint import check_state, host
 
 
 class IndexedBatch(tuple):
@@ -211,9 +216,13 @@ class BatchIterator:
     GPU is busy instead of in front of the next update's first launch (the reference's DataLoader workers run further
     ahead still, replay_buffer.py:173-190).  The draws and their order are those of plain next() calls."""
 
-    def __init__(self, draw):
+    def __init__(self, draw, store=None):
+        """draw: the function that draws one batch.  store: the VecDeviceReplay / VecFrameReplay it draws from, which
+        makes the iterator saveable (state_dict); None for any other source."""
         self._draw = draw
+        self._store = store
         self._ahead = None
+        self._drawn = None          # (index [3][B], steps [B]) of the look-ahead batch: the store's last_index / last_steps
 
     def __iter__(self):
         return self
@@ -225,6 +234,69 @@ class BatchIterator:
     def prefetch(self):
         if self._ahead is None:
             self._ahead = self._draw()
+            if self._store is not None:
+                self._drawn = (self._store.last_index, self._store.last_steps)
+
+    def state_dict(self):
+        """The look-ahead as a plain dict of CPU tensors and Python scalars: "format": 1, "kind", "pending", and for a
+        pending batch its index tensor [3, B] (obs, next_obs and transition slots), action, reward, discount and steps,
+        for a prioritized one also the weights and the stamp (the store's T at the draw).  The batch was drawn right after
+        the last update() and has consumed its random numbers: drawing it again after a restore would give another, so
+        it is state.  SYNCHRONISES the store's device.  DrqError: an iterator built without a store (DeviceReplay's), a
+        pending batch of a store with indexed=False."""
+        store = self._store
+        if store is None:
+            raise _lib.DrqError("BatchIterator.state_dict(): this iterator was built without a store: only the iterators "
+                                "of VecDeviceReplay / VecFrameReplay can be saved")
+        sd = {"format": 1, "kind": "BatchIterator", "pending": self._ahead is not None}
+        if self._ahead is None:
+            return sd
+        if not store.indexed:
+            raise _lib.DrqError("BatchIterator.state_dict(): a pending materialised batch (indexed=False) cannot be saved")
+        if store.device.type == "cuda":
+            torch.cuda.synchronize(store.device)
+        b = self._ahead
+        sd.update(index=host(self._drawn[0]), steps=host(self._drawn[1]), action=host(b[1]), reward=host(b[2]),
+                  discount=host(b[3]), prioritized=isinstance(b, PrioritizedBatch))
+        if sd["prioritized"]:
+            sd.update(weights=host(b.weights), stamp=int(b._stamp))
+        return sd
+
+    def load_state_dict(self, sd):
+        """Restores what state_dict() saved, after the store has been restored: a pending batch is rebuilt through the
+        store's own batch types over the RESTORED ring -- an IndexedBatch, FrameBatch or PrioritizedBatch on the store's
+        device, whose update_priorities() obeys the guard_rows rule with the saved stamp -- and becomes the store's
+        last_index / last_steps, as it was when it was saved.  ValueError, with nothing changed: a wrong "format" /
+        "kind", a batch that does not fit the store (its action width, its slots, uniform against prioritized)."""
+        store = self._store
+        if store is None:
+            raise _lib.DrqError("BatchIterator.load_state_dict(): this iterator was built without a store")
+        check_state(self, sd, kind="BatchIterator")
+        if not sd.get("pending"):
+            self._ahead = self._drawn = None
+            return
+        index = sd.get("index")
+        if not torch.is_tensor(index) or index.dim() != 2 or index.shape[0] != 3:
+            raise ValueError("BatchIterator.load_state_dict(): a pending batch needs its index tensor [3, B]")
+        B, per = int(index.shape[1]), bool(sd.get("prioritized"))
+        want = {"index": ((3, B), torch.int64), "steps": ((B,), torch.int32), "action": ((B, store.A), torch.float32),
+                "reward": ((B, 1), torch.float32), "discount": ((B, 1), torch.float32)}
+        if per:
+            want["weights"] = ((B,), torch.float32)
+        check_state(self, sd, tensors=want, kind="BatchIterator")
+        if per != (store.tree is not None) or not store.indexed:
+            raise ValueError("BatchIterator.load_state_dict(): the saved batch is "
+                             f"{'prioritized' if per else 'uniform'} and indexed, the store is not")
+        if B and not (0 <= int(index.min()) and int(index.max()) < store.R * store.N):
+            raise ValueError(f"BatchIterator.load_state_dict(): slots outside the ring of {store.R * store.N}")
+        dev = store.device
+        idx, steps, act, rew, disc = (sd[k].to(dev) for k in ("index", "steps", "action", "reward", "discount"))
+        batch = store._batch(per, idx, act, rew, disc)
+        if per:
+            batch._per(store, idx[2], sd["weights"].to(dev))
+            batch._stamp = int(sd["stamp"])
+        self._ahead, self._drawn = batch, (idx, steps)
+        store.last_index, store.last_steps = idx, steps
 
 
 class DeviceReplay:
@@ -491,7 +563,11 @@ class VecDeviceReplay:
     lo = max(1, T - rows + 1 + guard_rows): an IndexedBatch stays valid while fewer than `guard_rows` rows are added
     between its draw and the update that consumes it (the iterator's one batch of look-ahead needs 1).
     Every environment must hold a non-reset row among the drawable ones; a batch row drawn from one that does not comes
-    out with steps 0, reward 0 and discount 0.  Not here: episode files / resume, rows for a subset of the environments.
+    out with steps 0, reward 0 and discount 0.  Not here: episode files, rows for a subset of the environments.
+
+    Checkpoints: state_dict() / load_state_dict() save and restore T, the live slots of the ring, the RandomState,
+    priority_beta and the whole priority tree; iter(store) is a BatchIterator that knows its store and saves its
+    look-ahead batch.  A restored store draws, windows and weights exactly as the saved one would have gone on to.
 
     Prioritized sampling (`priority_alpha`, indexed batches only): a sum tree over the ring's slots in HBM, laid out and
     drawn from like DeviceReplay's (csrc/per.hip), maintained without the host ever reading a flag.  A leaf is positive
@@ -713,9 +789,75 @@ class VecDeviceReplay:
                                                  self._stream()), "drq_vec_per_update")
 
     def __iter__(self):
-        return BatchIterator(lambda: self.sample(self.batch_size))
+        return BatchIterator(lambda: self.sample(self.batch_size), self)
 
     batch_size = 256
+
+    # ---- checkpoints ---------------------------------------------------------------------
+    _RING = ("frames", "action", "reward", "discount", "first")
+
+    def _config(self):
+        return {"R": self.R, "N": self.N, "A": self.A, "slot_shape": tuple(self.slot_shape), "nstep": self.nstep,
+                "gamma": self.gamma, "guard_rows": self.guard_rows, "indexed": self.indexed,
+                "priority_alpha": self.priority_alpha, "priority_eps": self.priority_eps}
+
+    def state_dict(self, frames=True):
+        """The store as a plain dict of CPU tensors and Python scalars: "format": 1, "kind" (the class), "config" (R, N, A,
+        slot_shape, nstep, gamma, guard_rows, indexed, priority_alpha, priority_eps), T, priority_beta, the RandomState
+        ("rng": get_state() with the key as an int64 tensor), the LIVE slots of frames, action, reward, discount and first
+        -- slot (t mod R) N + e holds row t, so the first min(T, R) N -- and, prioritized, the whole tree (double
+        [2 leaves]; tree[0] is the running maximum).  frames=False leaves the five ring arrays out (the caller keeps the
+        ring some other way).  The ring goes through host memory whole: frame_bytes per live slot.  This SYNCHRONISES
+        the store's device.  The rotating staging sets are not state."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        live = min(self.T, self.R) * self.N
+        name, key, pos, has_gauss, cached = self.rng.get_state()
+        sd = {"format": 1, "kind": type(self).__name__, "config": self._config(), "T": self.T,
+              "priority_beta": self.priority_beta, "live_slots": live, "ring": bool(frames),
+              "rng": (name, torch.from_numpy(key.astype(np.int64)), int(pos), int(has_gauss), float(cached))}
+        if frames:
+            for n in self._RING:
+                sd[n] = host(getattr(self, n)[:live])
+        if self.tree is not None:
+            sd["tree"] = host(self.tree)
+        return sd
+
+    def load_state_dict(self, sd, frames=True):
+        """Restores what state_dict() saved, into a fresh or a used store; ValueError, with NOTHING changed, for a wrong
+        "format" / "kind" (the class counts), a configuration that differs from this store's (every differing field is
+        named), arrays of another shape, or a dict saved with frames=False -- unless frames=False here says the caller
+        means it: T, the generator and the tree are restored, the ring arrays stay as they are.  After a load the slots
+        above the live ones hold what the constructor puts there, last_steps and last_index are None, and the staging
+        sets are kept.  Works on a CPU store as well (no launch is involved)."""
+        check_state(self, sd, self._config())
+        T, live = sd.get("T"), sd.get("live_slots")
+        if not isinstance(T, int) or T < 0 or live != min(T, self.R) * self.N:
+            raise ValueError(f"{type(self).__name__}.load_state_dict(): T {T!r} and live_slots {live!r} do not fit a ring "
+                             f"of {self.R} rows x {self.N}")
+        if frames and not sd.get("ring"):
+            raise ValueError(f"{type(self).__name__}.load_state_dict(): the state was saved with frames=False and holds no "
+                             "ring; load_state_dict(sd, frames=False) restores the rest")
+        want = {n: ((live,) + tuple(getattr(self, n).shape[1:]), getattr(self, n).dtype) for n in self._RING} if frames else {}
+        if self.tree is not None:
+            want["tree"] = self.tree
+        check_state(self, sd, tensors=want)
+        rng = sd.get("rng")
+        if (not isinstance(rng, (tuple, list)) or len(rng) != 5 or not torch.is_tensor(rng[1]) or rng[1].numel() != 624
+                or not 0 <= int(rng[2]) <= 624):
+            raise ValueError(f"{type(self).__name__}.load_state_dict(): no RandomState in the saved state")
+        if frames:
+            for n in self._RING:
+                getattr(self, n)[:live].copy_(sd[n])
+            self.action[live:].zero_()
+            self.reward[live:].zero_()
+            self.discount[live:].fill_(1.0)
+            self.first[live:].fill_(1)
+        if self.tree is not None:
+            self.tree.copy_(sd["tree"])
+        self.T, self.priority_beta = T, float(sd["priority_beta"])
+        self.rng.set_state((rng[0], rng[1].numpy().astype(np.uint32), int(rng[2]), int(rng[3]), float(rng[4])))
+        self.last_steps = self.last_index = None
 
 
 class VecFrameReplay(VecDeviceReplay):
@@ -999,6 +1141,36 @@ class VecEpisodeStats:
 
     def _snapshot(self, m):
         return EpisodeSnapshot(m[1], self.W, self.N, self.limit, m[3])
+
+    # ---- checkpoints ---------------------------------------------------------------------
+    _LOG = ("log_return", "log_length", "log_env", "log_row")
+
+    def _tensors(self):
+        t = {k: getattr(self, k) for k in ("episode_return", "episode_length", "episodes_done", "header")}
+        t.update(zip(self._LOG, self._log))
+        return t
+
+    def state_dict(self):
+        """The statistics as a plain dict of CPU tensors and Python scalars: "format": 1, "kind", "config" (N, W, limit),
+        episode_return, episode_length, episodes_done, header, the four log arrays and rows.  The publish sequence number
+        and the pinned mirrors belong to the live object.  This SYNCHRONISES the object's device."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        sd = {"format": 1, "kind": type(self).__name__, "config": {"N": self.N, "W": self.W, "limit": self.limit},
+              "rows": self.rows}
+        sd.update((k, host(t)) for k, t in self._tensors().items())
+        return sd
+
+    def load_state_dict(self, sd):
+        """Restores what state_dict() saved, into a fresh or a used object; ValueError, with nothing changed, for a wrong
+        "format" / "kind" or a configuration that differs (every differing field is named).  The sequence numbers of
+        publish() simply go on; a read() after the load returns the header and records of a read() before the save."""
+        check_state(self, sd, {"N": self.N, "W": self.W, "limit": self.limit}, self._tensors())
+        if not isinstance(sd.get("rows"), int) or sd["rows"] < 0:
+            raise ValueError(f"VecEpisodeStats.load_state_dict(): rows {sd.get('rows')!r}")
+        for k, t in self._tensors().items():
+            t.copy_(sd[k])
+        self.rows = sd["rows"]
 
     def poll(self):
         """The EpisodeSnapshot of the newest publish() that has arrived on the host, or None if none has.  Never waits

@@ -607,6 +607,12 @@ int drq_vec_stats_reset(float* ret, int* len, int* done, void* header, float* lo
  *   No state of one environment is touched by another's workgroup; the caller orders the launches on one stream.
  *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 2,
  *   episode_length < 1, reset_all not 0 or 1, frame not 16-byte aligned, a float / int array not 4-byte aligned.
+ * drq_vec_reach_render: the frames of the states as they are, u8 [N][3][84][84], by the frame rule above: every byte of
+ *   frame, nothing else -- pos and target are only read, t / episode / over are not involved.  After a step or a reset it
+ *   writes exactly the frame that call wrote (the same device function); it is what a restored environment shows before
+ *   its next step.  N workgroups of 256 threads, 16-byte pieces, like the frame part of drq_vec_reach_step.
+ *   DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX, frame not 16-byte aligned, pos or target not
+ *   4-byte aligned.
  * drq_vec_reach_image: the renderer-shaped image of such frames, u8 [N][S][S][C], S = 84 k, k = 1 .. 4, C = 3 or 4:
  *   image[e][y][x][c] = frame[e][c][y / k][x / k] for c < 3 and 255 for c == 3 -- every pixel k x k times, channels last.
  *   The area average of "renderer images" returns the frame exactly ((k^2 v + k^2 / 2) / k^2 = v).
@@ -615,6 +621,7 @@ int drq_vec_stats_reset(float* ret, int* len, int* done, void* header, float* lo
 int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
                        const float* action, unsigned seed, int episode_length, int reset_all, uint8_t* frame,
                        float* reward, float* discount, uint8_t* first, drq_stream_t stream);
+int drq_vec_reach_render(const float* pos, const float* target, long N, uint8_t* frame, drq_stream_t stream);
 int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream);
 
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls

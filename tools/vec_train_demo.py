@@ -10,6 +10,12 @@ process: that is the baseline the training curve is read against, not a constant
 
   python tools/vec_train_demo.py [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
+                                 [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
+
+--checkpoint PATH saves the whole loop (drqv2_amd.checkpoint: agent, ring, look-ahead batch, environment, statistics, the
+generators) at the end of every --checkpoint-every'th iteration; --resume loads PATH into freshly built objects and goes
+on at the saved step, so the report lines that follow are those of the uninterrupted run, digit for digit (the wall
+times aside).  The other arguments must be the ones the saved run was given; --steps may grow.
 
 This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
 updates; it is no benchmark and makes no claim about DMC.
@@ -23,6 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
+from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.envs import VecReach  # noqa: E402
 from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
 
@@ -61,7 +68,12 @@ def main():
     ap.add_argument("--hidden-dim", type=int, default=256)
     ap.add_argument("--stddev", default="linear(1.0,0.1,10000)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--checkpoint", default=None, metavar="PATH", help="the checkpoint file")
+    ap.add_argument("--checkpoint-every", type=int, default=0, metavar="STEPS", help="save every STEPS steps (0: never)")
+    ap.add_argument("--resume", action="store_true", help="continue from the checkpoint file")
     args = ap.parse_args()
+    if (args.checkpoint_every or args.resume) and not args.checkpoint:
+        raise SystemExit("--checkpoint-every and --resume need --checkpoint PATH")
     if not torch.cuda.is_available():
         raise SystemExit("vec_train_demo.py runs on the GPU: no device found")
     N, A = args.envs, args.action_dim
@@ -80,11 +92,17 @@ def main():
     it = iter(store)
     zeros_NA, zeros_N, ones_N = torch.zeros(N, A, device="cuda"), torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
 
-    frame = env.reset()
-    store.add(frame, zeros_NA, zeros_N, ones_N)                      # row 0: the reset row of every environment
-    stats.step(zeros_N)
-    logged, updates, t0 = 0, 0, time.perf_counter()
-    for step in range(args.steps):
+    start, logged, updates = 0, 0, 0
+    if args.resume:
+        extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats)
+        start, logged, updates = extra["step"], extra["logged"], extra["updates"]
+        print(f"resumed {args.checkpoint} at step {start}", flush=True)
+    else:
+        frame = env.reset()
+        store.add(frame, zeros_NA, zeros_N, ones_N)                  # row 0: the reset row of every environment
+        stats.step(zeros_N)
+    t0 = time.perf_counter()
+    for step in range(start, args.steps):
         action = agent.act_batch(store.observation(), step, False)   # [N, A], stays on the device
         frame, reward, discount, first = env.step(action)
         store.add(frame, action, reward, discount, first)
@@ -101,11 +119,14 @@ def main():
             print(f"step {step + 1:6d}  updates {updates:6d}  episodes {snap.episodes:6d} (+{len(new) + missed})  mean return "
                   f"{mean}  mean length {length}  return per step "
                   f"{(new['return'].sum() / max(1, new['length'].sum())):.3f}  [{time.perf_counter() - t0:.1f} s]", flush=True)
+        if args.checkpoint_every and (step + 1) % args.checkpoint_every == 0:    # the end of an iteration: this WAITS
+            checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats,
+                            extra={"step": step + 1, "logged": logged, "updates": updates})
     snap = stats.read()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     print(f"trained: {snap.episodes} episodes in {snap.rows - 1} steps x {N} environments, mean return over all of them "
-          f"{snap.mean_return:.3f}, mean length {snap.mean_length:.1f}; {wall:.1f} s, {1e3 * wall / args.steps:.2f} ms per step",
+          f"{snap.mean_return:.3f}, mean length {snap.mean_length:.1f}; {wall:.1f} s, {1e3 * wall / max(1, args.steps - start):.2f} ms per step",
           flush=True)
     b_ret, b_len, b_steps = random_baseline(args, snap.episodes)
     print(f"baseline: uniform-random actions, the first {snap.episodes} episodes ({b_steps} steps): mean return {b_ret:.3f}, "
