@@ -9,7 +9,8 @@ Reference: /root/reference/drqv2.py.  Parity contract (tests/):
     utils.py:119 twice) and runs aug -> encoder -> critic step -> actor step -> target update in
     hand-written HIP kernels; there is no PyTorch/CPU fallback for that path;
   * metrics: the same 8 keys as python floats when use_tb, {} on gated-off steps;
-  * set_behavior_cloning(alpha) (new, not in the reference): DrQ+BC, the TD3+BC actor loss fused into update().
+  * set_behavior_cloning(alpha) (new, not in the reference): DrQ+BC, the TD3+BC actor loss fused into update();
+  * dormant_ratio(obs) / perturb(alpha) (new): DrM's two primitives beside the unchanged update().
 """
 import math
 
@@ -139,6 +140,8 @@ class DrQV2Agent:
         # True: it returns 0-d DEVICE tensors and never waits for the GPU; Logger.log() calls .item() on tensors
         # itself (logger.py:143-144), so train.py works unchanged and the wait moves to the logging cadence.
         self.metrics_on_device = False
+        self.last_dormant = None           # dormant_ratio(): {layer: (dormant, units, layer mean)} of the last call
+        self.last_dormant_scores = None    # ... and {layer: scores}
 
         self.train()
         self.critic_target.train()
@@ -234,6 +237,89 @@ class DrQV2Agent:
             if step < self.num_expl_steps:
                 action.uniform_(-1.0, 1.0)
         return action if on_device else action.cpu().numpy()
+
+    # ---- DrM building blocks (new, not in the reference): dormant ratio and weight perturbation ----
+    @staticmethod
+    def _net_names(nets, allowed, what):
+        if isinstance(nets, str):
+            nets = (nets,)
+        try:
+            nets = tuple(nets)
+        except TypeError:
+            nets = (nets,)
+        if not nets or len(set(nets)) != len(nets) or any(not isinstance(n, str) or n not in allowed for n in nets):
+            raise ValueError(f"{what}: nets {nets!r} must be distinct names out of {allowed}")
+        return tuple(n for n in allowed if n in nets)              # the order of `allowed`, whatever order was given
+
+    @staticmethod
+    def _unit_float(v, lo, hi, what):
+        """a real number in [lo, hi] that is one as an fp32 too (the kernels take it as such); no bools, no NaN"""
+        try:
+            ok = not isinstance(v, bool) and lo <= float(v) <= hi and lo <= float(np.float32(v)) <= hi
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(what)
+        return float(v)
+
+    def dormant_ratio(self, obs, action=None, tau=0.025, nets=("actor",)):
+        """The dormant ratio (Sokar et al. 2023; the quantity DrM, Xu et al. 2024, steers exploration and perturbation by)
+        of the named networks on a batch, as a 0-d float32 DEVICE tensor in [0, 1]; nothing waits for the GPU.
+        The contract:
+          * obs: uint8 [n >= 1, 9, 84, 84] on the agent's device; action (needed by "critic"): float32 [n, A] there.
+          * scored layers, each by its POST-ACTIVATION output: "actor" -- the trunk output (F units, after LayerNorm and
+            tanh) and the two hidden ReLU layers of the policy (H units each); "critic" -- its trunk output and the two
+            hidden layers of both Q heads (F + 4H units).  (DrM's public code hooks the nn.Linear outputs instead, so its
+            numbers are not these.)
+          * score_j = mean over the batch of |output_j|; unit j of a layer is dormant when score_j <= tau * (mean of the
+            layer's scores), and every unit of a layer whose mean is 0 is.  The ratio is dormant units over units, summed
+            over the scored layers.
+        The forward is the modules' fp32 forward (also when the compute dtype of update() is bf16) without augmentation,
+        in buffers of its own: n is not tied to the update's batch and the step workspace is not touched.  No gradient,
+        no optimiser state and no random numbers are involved (the generators do not move); a deferred optimiser step is
+        completed first, as in act().  `last_dormant` then holds {layer: (dormant, units, layer mean)} and
+        `last_dormant_scores` {layer: scores}, device tensors; layers are named "actor.trunk", "actor.policy.0",
+        "actor.policy.2", "critic.trunk", "critic.Q1.0", ... (the index of the nn.Linear whose activation is scored)."""
+        tau = self._unit_float(tau, 0.0, 3.0e38, f"dormant_ratio(): tau {tau!r} must be a finite float >= 0")
+        nets = self._net_names(nets, ("actor", "critic"), "dormant_ratio()")
+        if "critic" in nets and action is None:
+            raise ValueError("dormant_ratio(): the critic's layers need an action batch")
+        if str(self.device).startswith("cpu"):
+            raise _lib.DrqError("DrQV2Agent.update/act need the GPU: the HIP path has no CPU fallback")
+        ratio, self.last_dormant, self.last_dormant_scores = self._engine.dormant_ratio(obs, action, tau, nets)
+        return ratio
+
+    def perturb(self, alpha, nets=("encoder", "actor", "critic"), generator=None):
+        """DrM's perturbation: p <- alpha p + (1 - alpha) p0 for every parameter of the named networks, p0 a fresh
+        initialisation -- throw-away modules of the same constructors (the reference's weight_init), built on the CPU in
+        the order encoder, actor, critic from `generator` (a CPU torch.Generator, which is advanced) or else from the
+        global torch generator -- copied to the device once and applied by one launch per parameter segment.
+        "critic" pulls critic_target toward the SAME p0, so the target keeps its relation to the critic.  The Adam
+        moments and step counts are left as they are.  alpha is a float in [0, 1]: 1 changes nothing, launches nothing
+        and draws nothing; 0 is a re-initialisation.  A deferred optimiser step is completed first.  Single GPU only.
+        Stateless: a checkpoint has nothing to save for it."""
+        alpha = self._unit_float(alpha, 0.0, 1.0, f"perturb(): alpha {alpha!r} must be a float in [0, 1]")
+        nets = self._net_names(nets, ("encoder", "actor", "critic"), "perturb()")
+        if generator is not None and (not isinstance(generator, torch.Generator) or generator.device.type != "cpu"):
+            raise ValueError("perturb(): generator must be a CPU torch.Generator")
+        if str(self.device).startswith("cpu"):
+            raise _lib.DrqError("DrQV2Agent.update/act need the GPU: the HIP path has no CPU fallback")
+        if self._engine.pg is not None:
+            raise _lib.DrqError(self._engine._PERTURB_DP)
+        if alpha == 1.0:
+            return self
+        kw = self._init_kwargs
+        dims = (self.encoder.repr_dim, kw["action_shape"], kw["feature_dim"], kw["hidden_dim"])
+        make = {"encoder": lambda: Encoder(kw["obs_shape"]), "actor": lambda: Actor(*dims), "critic": lambda: Critic(*dims)}
+        if generator is None:
+            fresh = {n: make[n]() for n in nets}
+        else:
+            with torch.random.fork_rng(devices=[]):          # the constructors draw from the global generator
+                torch.random.set_rng_state(generator.get_state())
+                fresh = {n: make[n]() for n in nets}
+                generator.set_state(torch.random.get_rng_state())
+        self._engine.perturb(alpha, {"enc" if n == "encoder" else n: m for n, m in fresh.items()})
+        return self
 
     # ---- data parallel (new: one process per GPU, RCCL all-reduce of the flat gradient arenas) ---
     def enable_data_parallel(self, process_group=None, batch_is_global=True, global_metrics=False,

@@ -118,6 +118,9 @@ PROTOTYPES = {
     "drq_conv1_dgrad": (I, [P, P, P, I, P]),
     "drq_aug_bwd_f32": (I, [P, P, P, P, I, I, I, I, P]),
     "drq_tanh_bwd": (I, [P, P, P, L, P]),
+    "drq_dormant_scores": (I, [P, L, I, I, P, P]),
+    "drq_dormant_count": (I, [P, I, F, P, P, P]),
+    "drq_lerp_flat": (I, [P, P, L, F, P]),
     "drq_param_layout": (I, [I, I, I, I, C.POINTER(L), I]),
     "drq_step_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_step_ws_offset": (L, [I, I, I, I, I, I]),

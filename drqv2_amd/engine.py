@@ -1015,3 +1015,99 @@ class StepEngine:
             return mu
         lim = 1.0 - 1e-6
         return (mu + noise * float(std)).clamp_(-lim, lim)
+
+    # ---- DrM building blocks: dormant ratio and perturbation (include/drqv2_hip.h) ----------------
+    _PERTURB_DP = ("perturb() and data parallelism cannot be combined: every rank would need the same fresh weights, and "
+                   "the sharded optimiser (ZeRO-1) a gather of the stepped parameters first; neither is built")
+
+    def dormant_forward(self, obs_u8, action=None, nets=("actor",)):
+        """The layers dormant_ratio() scores, as [(name, post-activation output [n, units])]: per net the trunk output
+        (after LayerNorm and tanh) and the two hidden ReLU layers of every head.  The fp32 forward of the modules
+        (Encoder.forward / Actor.forward / Critic.forward launch for launch, whatever the compute dtype of update()), in
+        buffers of its own: the step workspace is not touched.  No augmentation, no gradient, no random numbers."""
+        if self.device.type != "cuda":
+            raise _lib.DrqError("DrQV2Agent.update/act need the GPU: the HIP path has no CPU fallback")
+        if (not torch.is_tensor(obs_u8) or obs_u8.dtype != torch.uint8 or not obs_u8.is_cuda
+                or obs_u8.device != self.device):
+            what = f"{obs_u8.dtype} on {obs_u8.device}" if torch.is_tensor(obs_u8) else type(obs_u8).__name__
+            raise _lib.DrqError(f"dormant_ratio(): uint8 frames on {self.device} required, got {what}")
+        if obs_u8.dim() != 4 or tuple(obs_u8.shape[1:]) != (self.C, 84, 84) or obs_u8.shape[0] < 1:
+            raise _lib.DrqError(f"dormant_ratio(): frames of shape (n >= 1, {self.C}, 84, 84) required, got "
+                                f"{tuple(obs_u8.shape)}")
+        if not obs_u8.is_contiguous():
+            raise _lib.DrqError("dormant_ratio(): contiguous frames required")
+        n = obs_u8.shape[0]
+        if "critic" in nets and (not torch.is_tensor(action) or action.dtype != torch.float32
+                                 or action.device != self.device or tuple(action.shape) != (n, self.A)
+                                 or not action.is_contiguous()):
+            raise _lib.DrqError(f"dormant_ratio(): action must be contiguous float32 {(n, self.A)} on {self.device}")
+        self.flush()
+        from . import autograd, ops
+        layers = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            ws = autograd._workspace(self.device)
+            x = ops.u8_normalize(obs_u8)
+            conv = self.modules["enc"].convnet
+            for li, i in enumerate((0, 2, 4, 6)):
+                x = ops.conv3x3_fwd(x, conv[i].weight.detach(), conv[i].bias.detach(), 2 if li == 0 else 1, relu=True)
+            feat = x.view(n, -1)
+            for net in nets:
+                mod = self.modules[net]
+                lin, ln = mod.trunk[0], mod.trunk[1]
+                z = ops.linear_fwd(feat, lin.weight.detach(), lin.bias.detach(), ws=ws)
+                h = ops.ln_tanh_fwd(z, ln.weight.detach(), ln.bias.detach(), save=False)[0]
+                layers.append((f"{net}.trunk", h))
+                if net == "actor":
+                    heads = (("policy", mod.policy, h),)
+                else:
+                    ha = torch.cat([h, action], dim=-1).contiguous()
+                    heads = (("Q1", mod.Q1, ha), ("Q2", mod.Q2, ha))
+                for hname, seq, hin in heads:
+                    h1 = ops.linear_fwd(hin, seq[0].weight.detach(), seq[0].bias.detach(), relu=True, ws=ws)
+                    h2 = ops.linear_fwd(h1, seq[2].weight.detach(), seq[2].bias.detach(), relu=True, ws=ws)
+                    layers += [(f"{net}.{hname}.0", h1), (f"{net}.{hname}.2", h2)]
+        return layers
+
+    def dormant_ratio(self, obs_u8, action, tau, nets):
+        """-> (ratio, {layer: (dormant, units, mean)}, {layer: scores}), all device tensors; nothing waits for the GPU.
+        One drq_dormant_scores and one drq_dormant_count launch per layer."""
+        from . import ops
+        layers = self.dormant_forward(obs_u8, action, nets)
+        with torch.cuda.device(self.device), torch.no_grad():
+            count = torch.zeros((len(layers), 2), device=self.device, dtype=torch.int32)
+            means = torch.empty((len(layers),), device=self.device, dtype=torch.float32)
+            per, scores = {}, {}
+            for k, (name, act) in enumerate(layers):
+                scores[name] = ops.dormant_scores(act)
+                ops.dormant_count(scores[name], tau, count[k], means[k:k + 1])
+                per[name] = (count[k, 0], count[k, 1], means[k])
+            total = count.sum(0)
+            ratio = total[0].to(torch.float32) / total[1].to(torch.float32)
+        return ratio, per, scores
+
+    def perturb(self, alpha, fresh):
+        """p <- alpha p + (1 - alpha) p0 over the segments of the networks in `fresh` = {"enc" | "actor" | "critic": a
+        freshly initialised module of the same constructor, on the CPU}; "critic" pulls the target segment toward the
+        SAME p0.  One drq_lerp_flat launch per segment; the Adam moments and step counts stay as they are."""
+        if self.device.type != "cuda":
+            raise _lib.DrqError("DrQV2Agent.update/act need the GPU: the HIP path has no CPU fallback")
+        if self.pg is not None:
+            raise _lib.DrqError(self._PERTURB_DP)
+        from . import ops
+        seg = self.layout["seg"]
+        jobs = []
+        for net, mod in fresh.items():
+            b, e = seg[net]
+            p0 = torch.zeros(e - b, dtype=torch.float32)            # the alignment gaps of the arena are zero too
+            plist = list(mod.parameters())
+            assert len(plist) == len(self.layout[net]), (net, len(plist))
+            with torch.no_grad():
+                for p, off in zip(plist, self.layout[net]):
+                    p0[off - b:off - b + p.numel()].copy_(p.detach().reshape(-1))
+            jobs.append((net, p0.to(self.device)))
+        self.flush()
+        with torch.cuda.device(self.device), torch.no_grad():
+            for net, p0 in jobs:
+                for name in ((net, "target") if net == "critic" else (net,)):
+                    b, e = seg[name]
+                    ops.lerp_flat(self.params[b:e], p0, alpha)

@@ -365,6 +365,45 @@ def ema_flat(p, t, tau):
     check(lib.drq_ema_flat(ptr(p), ptr(t), p.numel(), float(tau), _stream()), "drq_ema_flat")
 
 
+def dormant_scores(act, units=None):
+    """drq_dormant_scores: act [rows, ld] (the first `units` columns are the layer, default all) -> the mean absolute
+    activation of every unit over the rows, float32 [units]."""
+    lib = _lib.load()
+    _need(act, name="act")
+    rows, ld = act.shape
+    units = ld if units is None else int(units)
+    score = _alloc((units,), torch.float32, act.device)
+    check(lib.drq_dormant_scores(ptr(act), ld, rows, units, ptr(score), _stream()), "drq_dormant_scores")
+    return score
+
+
+def dormant_count(score, tau, count, layer_mean=None):
+    """drq_dormant_count: ADDS the number of units with score <= tau * mean(score) to count[0] and the number of units
+    to count[1] (count: int32 [2], zeroed by the caller before the first layer); the layer's mean goes to layer_mean
+    (float32 [1], allocated when None), which is returned."""
+    lib = _lib.load()
+    _need(score, name="score"), _need(count, torch.int32, "count")
+    if count.numel() != 2:
+        raise _lib.DrqError("dormant_count: count must hold two int32")
+    if layer_mean is None:
+        layer_mean = _alloc((1,), torch.float32, score.device)
+    else:
+        _need(layer_mean, name="layer_mean")
+    check(lib.drq_dormant_count(ptr(score), score.numel(), float(tau), ptr(count), ptr(layer_mean), _stream()),
+          "drq_dormant_count")
+    return layer_mean
+
+
+def lerp_flat(p, p0, a):
+    """drq_lerp_flat: p <- a p + (1 - a) p0 in place over two flat float32 tensors of one length."""
+    lib = _lib.load()
+    _need(p, name="p"), _need(p0, name="p0")
+    if p.numel() != p0.numel():
+        raise _lib.DrqError(f"lerp_flat: {p.numel()} and {p0.numel()} elements")
+    check(lib.drq_lerp_flat(ptr(p), ptr(p0), p.numel(), float(a), _stream()), "drq_lerp_flat")
+    return p
+
+
 def tanh(x):
     lib = _lib.load()
     y = _alloc(x.shape, x.dtype, x.device)

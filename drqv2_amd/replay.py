@@ -237,6 +237,12 @@ class BatchIterator:
             if self._store is not None:
                 self._drawn = (self._store.last_index, self._store.last_steps)
 
+    def peek(self):
+        """The look-ahead batch without consuming it (drawn now if there is none): the batch the next update() trains on,
+        e.g. for DrQV2Agent.dormant_ratio()."""
+        self.prefetch()
+        return self._ahead
+
     def state_dict(self):
         """The look-ahead as a plain dict of CPU tensors and Python scalars: "format": 1, "kind", "pending", and for a
         pending batch its index tensor [3, B] (obs, next_obs and transition slots), action, reward, discount and steps,

@@ -650,6 +650,28 @@ int drq_aug_bwd_f32(const float* dy, const float* shift_xy, const float* base_gr
                     int pad, drq_stream_t stream);
 int drq_tanh_bwd(const float* y, const float* dy, float* dx, long n, drq_stream_t stream);
 
+/* ---- dormant ratio and perturbation: the two primitives DrM (Xu et al. 2024, "Mastering Visual RL through Dormant
+ * Ratio Minimization") adds to the DrQ-v2 update.  New functionality, the reference has neither.  Deterministic: fixed
+ * summation orders, no float atomics, the same bits on every run.
+ * drq_dormant_scores: score[j] = (sum_b |act[b*ld + j]|) / rows for j < units: the mean absolute activation of a layer's
+ *   units over a batch (Sokar et al. 2023).  rows, units >= 1, ld >= units (else DRQ_EARG).  Per column the rows are
+ *   added in the two-stage order of drq_colsum (64 columns x 16 row groups below 1,024 rows, 16 x 64 from there on), then
+ *   divided by rows.  A NaN activation makes its column's score NaN and no other.
+ * drq_dormant_count: one workgroup.  m = (sum_j score[j]) / units with the sum in this order: chain t (t < 256) adds
+ *   score[t], score[t + 256], ... in that order starting from 0, then chain t takes chain t + o for o = 128, 64, ..., 1.
+ *   Unit j is dormant when score[j] <= tau * m (one fp32 product), and every unit is when m == 0.  ADDS the number of
+ *   dormant units to count[0] and units to count[1] (int32; the caller zeroes the pair once, several layers then
+ *   accumulate into it with no host read) and writes m to layer_mean[0] (may be NULL).  tau >= 0 and finite, units >= 1,
+ *   else DRQ_EARG.  A NaN score makes m NaN and no unit of the layer dormant.
+ * drq_lerp_flat: p[i] = fmaf(a, p[i], (1 - a) * p0[i]) for i < n -- 1 - a and its product with p0[i] each rounded to
+ *   fp32, then ONE fused multiply-add; the pull of a parameter arena toward a fresh initialisation p0.  a in [0, 1] and
+ *   n >= 0, else DRQ_EARG (a NaN too); pointers 4-byte aligned.  n == 0 and a == 1 launch nothing (a == 1: p keeps its
+ *   bits); a == 0 stores p0[i] itself, whatever p[i] held.  16-byte loads where p and p0 are misaligned by the same
+ *   amount, with a scalar head and tail. */
+int drq_dormant_scores(const float* act, long ld, int rows, int units, float* score, drq_stream_t stream);
+int drq_dormant_count(const float* score, int units, float tau, int* count, float* layer_mean, drq_stream_t stream);
+int drq_lerp_flat(float* p, const float* p0, long n, float a, drq_stream_t stream);
+
 /* ---- whole-step entry: DrQV2Agent.update (drqv2.py:230-262) ------------------------------------ */
 typedef struct {
   int B, global_B, C, A, F, H;

@@ -11,6 +11,11 @@ process: that is the baseline the training curve is read against, not a constant
   python tools/vec_train_demo.py [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
+                                 [--dormant-every K] [--perturb-every K [--perturb-k 2.0]]
+
+--dormant-every K prints the actor's dormant ratio (DrQV2Agent.dormant_ratio) on the look-ahead batch every K updates;
+--perturb-every K pulls the weights toward a fresh initialisation every K updates (DrQV2Agent.perturb) with
+alpha = clip(1 - perturb_k * ratio, 0.2, 0.9).  Both are off by default, and the output is then unchanged.
 
 --checkpoint PATH saves the whole loop (drqv2_amd.checkpoint: agent, ring, look-ahead batch, environment, statistics, the
 generators) at the end of every --checkpoint-every'th iteration; --resume loads PATH into freshly built objects and goes
@@ -29,6 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
+import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.envs import VecReach  # noqa: E402
 from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
@@ -71,6 +77,11 @@ def main():
     ap.add_argument("--checkpoint", default=None, metavar="PATH", help="the checkpoint file")
     ap.add_argument("--checkpoint-every", type=int, default=0, metavar="STEPS", help="save every STEPS steps (0: never)")
     ap.add_argument("--resume", action="store_true", help="continue from the checkpoint file")
+    ap.add_argument("--dormant-every", type=int, default=0, metavar="K",
+                    help="print the actor's dormant ratio on the look-ahead batch every K updates (0: never)")
+    ap.add_argument("--perturb-every", type=int, default=0, metavar="K",
+                    help="every K updates pull the weights toward a fresh initialisation, by the dormant ratio (0: never)")
+    ap.add_argument("--perturb-k", type=float, default=2.0, help="alpha = clip(1 - k * ratio, 0.2, 0.9)")
     args = ap.parse_args()
     if (args.checkpoint_every or args.resume) and not args.checkpoint:
         raise SystemExit("--checkpoint-every and --resume need --checkpoint PATH")
@@ -110,6 +121,18 @@ def main():
         if step >= args.warmup:
             agent.update(it, step)
             updates += 1
+            show = args.dormant_every and updates % args.dormant_every == 0
+            pull = args.perturb_every and updates % args.perturb_every == 0
+            if show or pull:                                         # DrM's two primitives; these lines WAIT
+                batch = it.peek()                                    # the batch the next update trains on
+                ratio = float(agent.dormant_ratio(batch.stacks(batch[0]).view(-1, 9, 84, 84)))
+                if show:
+                    print(f"step {step + 1:6d}  updates {updates:6d}  dormant ratio (actor) {ratio:.4f}", flush=True)
+                if pull:
+                    alpha = utils.perturb_factor(ratio, args.perturb_k, 0.2, 0.9)
+                    agent.perturb(alpha)
+                    print(f"step {step + 1:6d}  updates {updates:6d}  perturbed with alpha {alpha:.3f} (dormant ratio "
+                          f"{ratio:.4f})", flush=True)
         if (step + 1) % args.report == 0:
             snap = stats.read()                                      # the one wait per interval
             new, missed = snap.since(logged)

@@ -81,6 +81,22 @@ def weight_init(m):
         m.bias.data.fill_(0.0)
 
 
+def perturb_factor(ratio, k, lo, hi):
+    """DrM's perturbation strength from a dormant ratio: alpha = clip(1 - k * ratio, lo, hi), the argument of
+    DrQV2Agent.perturb (new: not in the reference; pure host arithmetic)."""
+    return float(min(max(1.0 - float(k) * float(ratio), float(lo)), float(hi)))
+
+
+def dormant_stddev(ratio, step, schdl, target=0.2, temperature=0.1):
+    """DrM's dormant-ratio-based exploration noise as its paper states it: the larger of the schedule's value and
+    1 / (1 + exp(-(ratio - target) / temperature)).  `step` is what schedule() takes; DrM's training script counts it
+    from the step the ratio first fell below `target` ("awakening"), a book-keeping that is the caller's (new: not in
+    the reference; pure host arithmetic)."""
+    z = (float(ratio) - float(target)) / float(temperature)
+    with np.errstate(over="ignore"):
+        return max(float(schedule(schdl, step)), float(1.0 / (1.0 + np.exp(-z))))
+
+
 class Until:
     """True while step < until // action_repeat; always True without a limit (utils.py:64-73)."""
 
