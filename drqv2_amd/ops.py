@@ -129,6 +129,43 @@ def vec_stack_gather(frames, first, R, N, slots=None, t=0):
     return out
 
 
+def vec_export_rows(frames, action, reward, discount, R, N, table, stack=1):
+    """drq_vec_export_rows: the M steps (t, e, t0) of `table` (int32 [M, 3]) out of a step-major ring -> (obs uint8
+    [M, stack * frame bytes], action [M, A], reward [M], discount [M]); stack = 3 puts the observation together from the
+    frames of a single-frame ring, and a step with t == t0 gets the dummies 0, 0, 1."""
+    lib = _lib.load()
+    _need(frames, torch.uint8, "frames"), _need(table, torch.int32, "table")
+    for t, name in ((action, "action"), (reward, "reward"), (discount, "discount")):
+        _need(t, torch.float32, name)
+    if table.dim() != 2 or table.shape[1] != 3:
+        raise _lib.DrqError(f"table: int32 [M, 3] required, got {tuple(table.shape)}")
+    M, A, fb, dev = table.shape[0], action.shape[1], frames.shape[1], frames.device
+    obs = _alloc((M, stack * fb), torch.uint8, dev)
+    act, rew, disc = _alloc((M, A), torch.float32, dev), _alloc((M,), torch.float32, dev), _alloc((M,), torch.float32, dev)
+    check(lib.drq_vec_export_rows(ptr(frames), ptr(action), ptr(reward), ptr(discount), R, N, A, fb, stack, ptr(table), M,
+                                  ptr(obs), ptr(act), ptr(rew), ptr(disc), _stream()), "drq_vec_export_rows")
+    return obs, act, rew, disc
+
+
+def vec_fill(frames, action, reward, discount, first, R, N, T, src_frames, src_action, src_reward, src_discount, src_first):
+    """drq_vec_fill: rows T .. T + n - 1 of a step-major ring, in place, from step-major sources (src_frames uint8
+    [n, N, frame bytes], src_action [n, N, A], src_reward, src_discount [n, N], src_first uint8 [n, N]): what n
+    drq_vec_add calls would write, in one launch."""
+    lib = _lib.load()
+    for t, name in ((frames, "frames"), (first, "first"), (src_frames, "src_frames"), (src_first, "src_first")):
+        _need(t, torch.uint8, name)
+    for t, name in ((action, "action"), (reward, "reward"), (discount, "discount"), (src_action, "src_action"),
+                    (src_reward, "src_reward"), (src_discount, "src_discount")):
+        _need(t, torch.float32, name)
+    n, A, fb = src_first.shape[0], action.shape[1], frames.shape[1]
+    if (src_frames.numel() != n * N * fb or src_action.numel() != n * N * A or src_reward.numel() != n * N
+            or src_discount.numel() != n * N or src_first.numel() != n * N):
+        raise _lib.DrqError(f"vec_fill: sources of {n} rows x {N} environments required")
+    check(lib.drq_vec_fill(ptr(frames), ptr(action), ptr(reward), ptr(discount), ptr(first), R, N, A, fb, T, n,
+                           ptr(src_frames), ptr(src_action), ptr(src_reward), ptr(src_discount), ptr(src_first), _stream()),
+          "drq_vec_fill")
+
+
 def u8_normalize(x):
     lib = _lib.load()
     _need(x, torch.uint8, "obs")

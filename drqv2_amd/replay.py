@@ -44,13 +44,32 @@ launch per step, a pinned host mirror that nothing waits for, and a per-environm
 Checkpoints (new: state_dict() / load_state_dict() on VecDeviceReplay, VecFrameReplay, BatchIterator and VecEpisodeStats;
 drqv2_amd/checkpoint.py puts them into one file with the agent and the generators).  A restored loop continues bit for
 bit as the uninterrupted one would have.  The episode store keeps the reference's way: episodes are its unit.
+
+Episode files for the ring (new: export_episodes() / add_episodes() on VecDeviceReplay and VecFrameReplay,
+csrc/vecepisodes.hip, host planning in drqv2_amd/episodes.py).  What N environments collected leaves the ring as the
+reference's `<timestamp>_<idx>_<len>.npz` files, which make_replay_loader() and the reference's own tooling read; and a
+ring of any shape starts from such files or from episode dicts, laid out as lockstep rows and written with one launch per
+staging chunk instead of one add() per row.
 """
+import collections
+import datetime
+import pathlib
+
 import numpy as np
 import torch
 
 from . import _lib
+from . import episodes as _episodes
 from ._lib import check, ptr
 from .checkpoint import check_state, host
+
+ExportReport = collections.namedtuple("ExportReport", "files episodes transitions next_row zero_length headless open short")
+ExportReport.__doc__ = """What export_episodes() did: files (the paths written, in order), episodes and transitions (how many
+of each they hold), next_row (pass it as start_row next time), and how many runs were left out as zero_length, headless,
+open and short (drqv2_amd.episodes.plan_export says what each means)."""
+FillReport = collections.namedtuple("FillReport", "episodes transitions rows pad_rows")
+FillReport.__doc__ = """What add_episodes() did: episodes and transitions placed, rows added to the ring (T grew by that), and
+pad_rows, the reset rows that fill the shorter lanes (counted over all environments)."""
 
 
 class IndexedBatch(tuple):
@@ -569,7 +588,10 @@ class VecDeviceReplay:
     lo = max(1, T - rows + 1 + guard_rows): an IndexedBatch stays valid while fewer than `guard_rows` rows are added
     between its draw and the update that consumes it (the iterator's one batch of look-ahead needs 1).
     Every environment must hold a non-reset row among the drawable ones; a batch row drawn from one that does not comes
-    out with steps 0, reward 0 and discount 0.  Not here: episode files, rows for a subset of the environments.
+    out with steps 0, reward 0 and discount 0.  Not here: rows for a subset of the environments.
+
+    Episode files: export_episodes() writes the episodes the ring holds whole as the reference's npz files, and
+    add_episodes() fills the ring from such files or from episode dicts, one launch per staging chunk either way.
 
     Checkpoints: state_dict() / load_state_dict() save and restore T, the live slots of the ring, the RandomState,
     priority_beta and the whole priority tree; iter(store) is a BatchIterator that knows its store and saves its
@@ -709,15 +731,19 @@ class VecDeviceReplay:
             for t in src:           # a caller's tensor may be freed right after add(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())
-            self.T += 1
-            if self.tree is not None:
-                # hi and lo move by at most one row per add: the new hi enters (its flags were written nstep - 1 adds
-                # ago, on this stream), the old lo leaves
-                lo, hi = self.bounds()
-                enter, leave = (hi if hi >= lo else -1), (lo - 1 if lo >= 2 else -1)
-                if enter >= 0 or leave >= 0:
-                    check(_lib.load().drq_vec_per_advance(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, N,
-                                                          self.T, enter, leave, self._stream()), "drq_vec_per_advance")
+            self._row_added()
+
+    def _row_added(self):
+        """counts one written row and lets the tree follow (inside torch.cuda.device(self.device))"""
+        self.T += 1
+        if self.tree is not None:
+            # hi and lo move by at most one row per add: the new hi enters (its flags were written nstep - 1 adds
+            # ago, on this stream), the old lo leaves
+            lo, hi = self.bounds()
+            enter, leave = (hi if hi >= lo else -1), (lo - 1 if lo >= 2 else -1)
+            if enter >= 0 or leave >= 0:
+                check(_lib.load().drq_vec_per_advance(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N,
+                                                      self.T, enter, leave, self._stream()), "drq_vec_per_advance")
 
     # ---- sampling ------------------------------------------------------------------------
     def sample(self, batch_size):
@@ -865,6 +891,200 @@ class VecDeviceReplay:
         self.rng.set_state((rng[0], rng[1].numpy().astype(np.uint32), int(rng[2]), int(rng[3]), float(rng[4])))
         self.last_steps = self.last_index = None
 
+    # ---- episode files -------------------------------------------------------------------
+    _stack = 1      # frames per observation that drq_vec_export_rows puts together (a slot holds the whole observation)
+
+    def export_episodes(self, directory, start_row=None, include_open=False, min_length=1, chunk_bytes=256 << 20):
+        """Writes the episodes the ring holds whole into `directory` as the reference's files, one
+        `<timestamp>_<idx>_<len>.npz` each through replay_buffer.save_episode: observation uint8 [len + 1, *obs_shape],
+        action float32 [len + 1, A], reward and discount float32 [len + 1, 1]; index 0 is the reset transition with the
+        reference's dummies (action 0, reward 0, discount 1), whatever add() was handed on that row.  idx continues
+        after the files already there.  What make_replay_loader() and add_episodes() read.
+
+        This WAITS for the GPU: it synchronises the store's device, reads the `first` flags back once and plans on the
+        host (drqv2_amd.episodes.plan_export: an episode is listed when its reset row is still in the ring and the
+        next reset row of its environment has been added).  The steps are gathered chunk by chunk, at most chunk_bytes
+        each, one launch per chunk (drq_vec_export_rows) into two pinned buffers used in turn, so the host compresses
+        one chunk while the next is gathered and copied.  Compression (np.savez_compressed) dominates the run time.
+
+        start_row: only episodes that ended on row start_row - 1 or later.  The report carries next_row = T: a loop that
+        passes the previous report's next_row exports every closed episode exactly once, as long as it calls before an
+        episode's reset row leaves the ring (such an episode is counted as `headless`, not written).  include_open also
+        writes the episodes still running, cut where they are (a later call writes them again, longer); min_length
+        skips shorter ones.  Returns an ExportReport.  The ring, its RandomState, its tree and T are untouched:
+        state_dict() before and after is equal."""
+        import replay_buffer as RB          # at call time: replay_buffer imports this module
+        _on_gpu(self, "the step-major replay lives")
+        torch.cuda.synchronize(self.device)
+        plan = _episodes.plan_export(self.first.cpu().numpy(), self.T, self.R, self.N, start_row, include_open, min_length)
+        table = _episodes.export_table(plan.episodes)
+        M, A, sb, dev = int(table.shape[0]), self.A, self.stack_bytes, self.device
+        directory = pathlib.Path(directory)
+        directory.mkdir(parents=True, exist_ok=True)
+        idx = max((i for _, i, _ in RB._episode_files(directory)), default=-1) + 1
+        files = []
+        if M:
+            rows = int(max(1, min(M, int(chunk_bytes) // (sb + 4 * A + 20))))
+            mk = lambda pin: [torch.empty(s, dtype=d, device=None if pin else dev, pin_memory=pin) for s, d in (
+                ((rows, sb), torch.uint8), ((rows, A), torch.float32), ((rows,), torch.float32), ((rows,), torch.float32),
+                ((rows, 3), torch.int32))]
+            dv, pins, done = mk(False), [mk(True), mk(True)], [None, None]
+            state = {"cur": 0, "arrays": None, "idx": idx}
+            offsets = np.concatenate([[0], np.cumsum([n + 1 for _, _, n in plan.episodes])])
+
+            def drain(k, m0, m):
+                """chunk [m0, m0 + m) has arrived in pinned set k: its steps go to their episodes, full ones to disk"""
+                done[k].synchronize()
+                obs, act, rew, disc = (t.numpy() for t in pins[k][:4])
+                pos = m0
+                while pos < m0 + m:
+                    j = state["cur"]
+                    n = plan.episodes[j][2]
+                    if state["arrays"] is None:
+                        state["arrays"] = {"observation": np.empty((n + 1,) + self.obs_shape, np.uint8),
+                                           "action": np.empty((n + 1, A), np.float32),
+                                           "reward": np.empty((n + 1, 1), np.float32),
+                                           "discount": np.empty((n + 1, 1), np.float32)}
+                    a = pos - int(offsets[j])
+                    b = min(int(offsets[j + 1]), m0 + m) - int(offsets[j])
+                    s = slice(pos - m0, pos - m0 + b - a)
+                    ep = state["arrays"]
+                    ep["observation"][a:b] = obs[s].reshape((b - a,) + self.obs_shape)
+                    ep["action"][a:b] = act[s]
+                    ep["reward"][a:b, 0] = rew[s]
+                    ep["discount"][a:b, 0] = disc[s]
+                    pos += b - a
+                    if b == n + 1:
+                        ts = datetime.datetime.now().strftime("%Y%m%dT%H%M%S")
+                        fn = directory / f"{ts}_{state['idx']}_{n}.npz"
+                        RB.save_episode(ep, fn)
+                        files.append(fn)
+                        state["cur"], state["arrays"], state["idx"] = j + 1, None, state["idx"] + 1
+
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream()
+                prev = None
+                for c, m0 in enumerate(range(0, M, rows)):
+                    k, m = c & 1, min(rows, M - m0)
+                    pin = pins[k]                   # free: the chunk it held was drained before the previous launch
+                    pin[4].numpy()[:m] = table[m0:m0 + m]
+                    dv[4][:m].copy_(pin[4][:m], non_blocking=True)
+                    check(_lib.load().drq_vec_export_rows(ptr(self.frames), ptr(self.action), ptr(self.reward),
+                                                          ptr(self.discount), self.R, self.N, A, self.frame_bytes,
+                                                          self._stack, ptr(dv[4]), m, ptr(dv[0]), ptr(dv[1]), ptr(dv[2]),
+                                                          ptr(dv[3]), stream.cuda_stream), "drq_vec_export_rows")
+                    for q in range(4):
+                        pin[q][:m].copy_(dv[q][:m], non_blocking=True)
+                    done[k] = torch.cuda.Event()
+                    done[k].record(stream)
+                    if prev is not None:
+                        drain(*prev)
+                    prev = (k, m0, m)
+                drain(*prev)
+        return ExportReport(files, len(plan.episodes), sum(n for _, _, n in plan.episodes), plan.next_row,
+                            plan.zero_length, plan.headless, plan.open, plan.short)
+
+    def _episode_frames(self, obs, check):
+        """what the slots of an episode hold: its `observation`, checked against the store (ValueError).  `check` is
+        add_episodes()' argument: a slot holds the whole observation here, so there is no stack to verify and it is
+        not read; VecFrameReplay's version does"""
+        obs = np.asarray(obs)
+        if obs.dtype != np.uint8 or obs.ndim < 1 or tuple(obs.shape[1:]) != self.slot_shape:
+            raise ValueError(f"uint8 [len + 1, {', '.join(map(str, self.slot_shape))}] required, got {obs.dtype} "
+                             f"{list(obs.shape)}")
+        return np.ascontiguousarray(obs)
+
+    def _checked_episode(self, ep, name, check):
+        """an episode dict as planned_rows takes it, every field checked against the store: ValueError naming both"""
+        def bad(field, why):
+            return ValueError(f"add_episodes(): {name}: {field}: {why}")
+        for field in ("observation", "action", "reward", "discount"):
+            if field not in ep:
+                raise bad(field, "the episode has no such field")
+        try:
+            frame = self._episode_frames(ep["observation"], check)
+        except ValueError as e:
+            raise bad("observation", str(e)) from None
+        n = frame.shape[0]
+        if n < 2:
+            raise bad("observation", f"{n} step(s): an episode needs its reset step and at least one transition")
+        out = {"frame": frame}
+        for field, shapes in (("action", [(n, self.A)]), ("reward", [(n,), (n, 1)]), ("discount", [(n,), (n, 1)])):
+            x = np.asarray(ep[field])
+            if x.dtype != np.float32:
+                raise bad(field, f"float32 required, got {x.dtype}")
+            if tuple(x.shape) not in shapes:
+                raise bad(field, f"shape {list(shapes[0])} required (len + 1 = {n}, the store's action_dim = {self.A}), "
+                                 f"got {list(x.shape)}")
+            out[field] = np.ascontiguousarray(x)
+        return out
+
+    def add_episodes(self, source, check=True, chunk_bytes=256 << 20):
+        """Fills the ring from episodes that already exist.  source: a directory of the reference's episode files (read
+        with replay_buffer's own listing and load_episode, oldest first), or a list of episode dicts with `observation`
+        uint8 [len + 1, *obs_shape], `action` float32 [len + 1, A], `reward` and `discount` float32 [len + 1] or
+        [len + 1, 1].  All of them are held in host memory while the call runs.
+
+        Every episode is checked against the store before anything is written: ValueError names the episode and the
+        field.  drqv2_amd.episodes.plan_fill then lays them out as lockstep rows -- each episode, in order, into the
+        environment with the fewest rows so far, the shorter environments padded at their end with reset rows -- and if
+        that takes L > R rows per environment it is a ValueError too: split the data or enlarge the ring.  The rows are
+        staged step-major through two pinned buffers used in turn, at most chunk_bytes each, and written with one launch
+        per chunk (drq_vec_fill); a prioritized store's tree then follows row by row (drq_vec_per_advance), as after
+        add().  The store ends in the state L add() calls with the planned rows (drqv2_amd.episodes.planned_rows) would
+        have left, bit for bit: frames, action, reward, discount, first, T and the tree.  Checkpoints need nothing new.
+
+        A look-ahead batch drawn before the call is stale, as after any `guard_rows` adds: make a new iterator.  Every
+        environment ends on a finished episode (or a pad row), so the next live add() must be a reset row for every
+        environment.  Returns a FillReport.  DrqError for a store on the CPU, after the checks."""
+        import replay_buffer as RB          # at call time: replay_buffer imports this module
+        from ._lib import check as rc_check  # the module's `check` is hidden by this method's argument of that name
+        if isinstance(source, (str, pathlib.Path)):
+            files = [fn for fn, _, _ in RB._episode_files(source)]
+            named = [(fn.name, RB.load_episode(fn)) for fn in files]
+        else:
+            named = [(f"episode {i}", ep) for i, ep in enumerate(source)]
+        eps = [self._checked_episode(ep, name, check) for name, ep in named]
+        lengths = [ep["frame"].shape[0] - 1 for ep in eps]
+        plan = _episodes.plan_fill(lengths, self.N)
+        L, N, A, R = plan.L, self.N, self.A, self.R
+        if L > R:
+            raise ValueError(f"add_episodes(): {len(eps)} episodes need L = {L} rows per environment, the ring has R = {R}: "
+                             "split the data or enlarge the ring")
+        _on_gpu(self, "the step-major replay lives")
+        report = FillReport(len(eps), sum(lengths), L, plan.pad_rows)
+        if L == 0:
+            return report
+        # a prioritized store: no row of a chunk may overwrite flags the tree still has to read for an earlier row of
+        # it (the row that enters is nstep - 1 rows behind the one just written)
+        cap = R - self.nstep if self.tree is not None else R
+        rows = int(max(1, min(L, cap, int(chunk_bytes) // (N * (self.frame_bytes + 4 * A + 9)))))
+        dev = self.device
+        mk = lambda pin: [torch.empty(s, dtype=d, device=None if pin else dev, pin_memory=pin) for s, d in (
+            ((rows, N) + self.slot_shape, torch.uint8), ((rows, N, A), torch.float32), ((rows, N), torch.float32),
+            ((rows, N), torch.float32), ((rows, N), torch.uint8))]
+        dv, pins, done = mk(False), [mk(True), mk(True)], [None, None]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream()
+            for c, r0 in enumerate(range(0, L, rows)):
+                k, n = c & 1, min(rows, L - r0)
+                if done[k] is not None:
+                    done[k].synchronize()       # the upload of the chunk this pinned set held has run
+                _episodes.planned_rows(plan, eps, r0, r0 + n, out=[t.numpy() for t in pins[k]])
+                for d, p in zip(dv, pins[k]):
+                    d[:n].copy_(p[:n], non_blocking=True)
+                done[k] = torch.cuda.Event()
+                done[k].record(stream)
+                rc_check(_lib.load().drq_vec_fill(ptr(self.frames), ptr(self.action), ptr(self.reward),
+                                                  ptr(self.discount), ptr(self.first), R, N, A, self.frame_bytes, self.T,
+                                                  n, *(ptr(d) for d in dv), stream.cuda_stream), "drq_vec_fill")
+                for _ in range(n):
+                    self._row_added()
+            for ev in done:
+                if ev is not None:
+                    ev.synchronize()
+        return report
+
 
 class VecFrameReplay(VecDeviceReplay):
     """VecDeviceReplay with ONE frame per slot (new; the contract is in include/drqv2_hip.h, "single-frame step-major
@@ -886,6 +1106,13 @@ class VecFrameReplay(VecDeviceReplay):
     Only three-frame stacks of 3 x 84 x 84 frames: the kernels that gather are built for them."""
 
     _draw_copies = False
+    _stack = 3              # export_episodes() writes the 9-channel stacks, put together by the launch that gathers them
+
+    def _episode_frames(self, obs, check):
+        """add_episodes() takes uint8 [len + 1, 9, 84, 84] frame stacks and keeps the newest frame of each -- check: after
+        verifying that they are what a FrameStackWrapper builds (newest_frames) -- or [len + 1, 3, 84, 84] single frames
+        as they are"""
+        return newest_frames(obs, check)
 
     def __init__(self, rows, num_envs, action_dim, nstep, discount, device, frame_shape=(3, 84, 84), seed=None,
                  indexed=True, guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):

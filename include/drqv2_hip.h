@@ -624,6 +624,39 @@ int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uin
 int drq_vec_reach_render(const float* pos, const float* target, long N, uint8_t* frame, drq_stream_t stream);
 int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream);
 
+/* ---- episode files for the step-major ring.  New functionality: the bulk movements between the ring of "step-major
+ * replay" / "single-frame step-major replay" and episode-major staging (an episode file of the reference,
+ * replay_buffer.py:22-34, is arrays [len + 1][...] whose index 0 is the dummy reset transition).  The host plans
+ * (drqv2_amd/episodes.py), these launches copy; these definitions are the contract.
+ *
+ * drq_vec_export_rows: one launch gathers M steps.  table is int32 [M][3] on the device, entry m = (t, e, t0): absolute row
+ *   t of environment e in the episode whose reset row is t0 <= t.  stack = 1: a slot holds the whole observation, obs u8
+ *   [M][frame_bytes] receives slot (t, e).  stack = 3: a slot holds one frame, obs u8 [M][3 frame_bytes] receives the
+ *   frames of rows max(t-2, t0), max(t-1, t0), t of environment e, oldest first -- the reference's FrameStackWrapper
+ *   (dmc.py:87-109) inside that episode, and what drq_vec_stack_gather gives for slot (t, e) when the flags of rows
+ *   t0 .. t say the same (first only on t0).  No flag is read.  act_out f32 [M][A], rew_out f32 [M], disc_out f32 [M]
+ *   receive the ring's action, reward and discount of (t, e), and for t == t0 the canonical dummies 0, 0, 1 whatever the
+ *   ring holds.  An entry with e outside [0, N), t0 < 0 or t < t0 leaves its output rows as they were; no other entry
+ *   can address anything outside the ring (rows are taken modulo R).  That the rows are still live is the caller's.
+ *   DRQ_EARG, nothing launched: a null pointer, R, N, A, M <= 0, frame_bytes <= 0 or % 16 != 0, stack not 1 or 3, frames
+ *   or obs not 16-byte aligned, another pointer not 4-byte aligned.
+ * drq_vec_fill: one launch writes the n consecutive rows T .. T+n-1 for all N environments from step-major sources:
+ *   src_frames u8 [n][N][frame_bytes] (16-byte aligned), src_action f32 [n][N][A], src_reward, src_discount f32 [n][N],
+ *   src_first u8 [n][N].  The effect is exactly that of drq_vec_add(t = T + i, the sources of row i) for i = 0 .. n-1:
+ *   row 0 stores first = 1 for every environment whatever src_first says, and rows past the ring's end continue at ring
+ *   row 0 within the one launch.  n <= R, so no two rows share a ring row.  That is the entry's only limit on n: a
+ *   caller that keeps a priority tree and lets it follow row by row afterwards (drq_vec_per_advance reads the flags of
+ *   the row nstep - 1 behind the one it counts) chooses n <= R - nstep itself, so that no row of the launch has
+ *   overwritten those flags.
+ *   DRQ_EARG, nothing launched: a null pointer (src_first too), R, N, A, n <= 0, n > R, T < 0, frame_bytes <= 0 or
+ *   % 16 != 0, frames / src_frames not 16-byte aligned, a float pointer not 4-byte aligned. */
+int drq_vec_export_rows(const uint8_t* frames, const float* action, const float* reward, const float* discount, long R,
+                        long N, int A, long frame_bytes, int stack, const int* table, int M, uint8_t* obs, float* act_out,
+                        float* rew_out, float* disc_out, drq_stream_t stream);
+int drq_vec_fill(uint8_t* frames, float* action, float* reward, float* discount, uint8_t* first, long R, long N, int A,
+                 long frame_bytes, long T, int n, const uint8_t* src_frames, const float* src_action,
+                 const float* src_reward, const float* src_discount, const uint8_t* src_first, drq_stream_t stream);
+
 /* ---- the four random draws of one update in one launch, bit-identical to the ATen launches of the reference's calls
  * (torch.randint(0, range, (B,1,1,2), dtype=float32) x2 from drqv2.py:34,241-242; torch.empty((B,A)).normal_() x2 from
  * utils.py:135 via drqv2.py:183,211): Philox4x32-10, key = seed, subsequence = element index, offsets offset + 0, 4, 8,

@@ -12,6 +12,7 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
                                  [--dormant-every K] [--perturb-every K [--perturb-k 2.0]]
+                                 [--export-dir DIR] [--prefill-dir DIR]
 
 --dormant-every K prints the actor's dormant ratio (DrQV2Agent.dormant_ratio) on the look-ahead batch every K updates;
 --perturb-every K pulls the weights toward a fresh initialisation every K updates (DrQV2Agent.perturb) with
@@ -21,6 +22,13 @@ alpha = clip(1 - perturb_k * ratio, 0.2, 0.9).  Both are off by default, and the
 generators) at the end of every --checkpoint-every'th iteration; --resume loads PATH into freshly built objects and goes
 on at the saved step, so the report lines that follow are those of the uninterrupted run, digit for digit (the wall
 times aside).  The other arguments must be the ones the saved run was given; --steps may grow.
+
+--export-dir DIR writes the episodes that finished since the last report as the reference's episode files at every
+reporting interval (VecFrameReplay.export_episodes from the previous report's next_row: each closed episode once; the call
+WAITS, like the read-out beside it; --report x --envs steps must fit the ring, or episodes leave it unwritten and are
+counted as headless).  --prefill-dir DIR loads such a directory into the ring before the first reset row
+(VecFrameReplay.add_episodes), e.g. what an earlier run exported; a resumed run has its ring from the checkpoint and skips
+it.  Both are off by default, and the output is then unchanged.
 
 This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
 updates; it is no benchmark and makes no claim about DMC.
@@ -82,6 +90,10 @@ def main():
     ap.add_argument("--perturb-every", type=int, default=0, metavar="K",
                     help="every K updates pull the weights toward a fresh initialisation, by the dormant ratio (0: never)")
     ap.add_argument("--perturb-k", type=float, default=2.0, help="alpha = clip(1 - k * ratio, 0.2, 0.9)")
+    ap.add_argument("--export-dir", default=None, metavar="DIR",
+                    help="write the episodes finished since the last report as episode files at every reporting interval")
+    ap.add_argument("--prefill-dir", default=None, metavar="DIR",
+                    help="load a directory of episode files into the ring before the first reset row")
     args = ap.parse_args()
     if (args.checkpoint_every or args.resume) and not args.checkpoint:
         raise SystemExit("--checkpoint-every and --resume need --checkpoint PATH")
@@ -103,14 +115,23 @@ def main():
     it = iter(store)
     zeros_NA, zeros_N, ones_N = torch.zeros(N, A, device="cuda"), torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
 
-    start, logged, updates = 0, 0, 0
+    start, logged, updates, export_from = 0, 0, 0, None
     if args.resume:
         extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats)
-        start, logged, updates = extra["step"], extra["logged"], extra["updates"]
+        start, logged, updates, export_from = extra["step"], extra["logged"], extra["updates"], extra.get("export_from")
         print(f"resumed {args.checkpoint} at step {start}", flush=True)
     else:
+        if args.prefill_dir:
+            fill = store.add_episodes(args.prefill_dir)
+            print(f"prefilled from {args.prefill_dir}: {fill.episodes} episodes, {fill.transitions} transitions in "
+                  f"{fill.rows} rows ({fill.pad_rows} pad rows)", flush=True)
+            # the prefilled episodes are on disk already: exports start behind the reset row below, which closes the
+            # last of them (row T; an episode is listed when the row after its end is start_row or later)
+            export_from = store.T + 1
         frame = env.reset()
-        store.add(frame, zeros_NA, zeros_N, ones_N)                  # row 0: the reset row of every environment
+        # the reset row of every environment, flagged as one: only row 0 of an empty ring is a reset row by itself, and
+        # after a prefill this row must not continue the prefilled episodes
+        store.add(frame, zeros_NA, zeros_N, ones_N, torch.ones(N, dtype=torch.uint8, device="cuda"))
         stats.step(zeros_N)
     t0 = time.perf_counter()
     for step in range(start, args.steps):
@@ -142,9 +163,15 @@ def main():
             print(f"step {step + 1:6d}  updates {updates:6d}  episodes {snap.episodes:6d} (+{len(new) + missed})  mean return "
                   f"{mean}  mean length {length}  return per step "
                   f"{(new['return'].sum() / max(1, new['length'].sum())):.3f}  [{time.perf_counter() - t0:.1f} s]", flush=True)
+            if args.export_dir:                                      # this WAITS as well
+                rep = store.export_episodes(args.export_dir, start_row=export_from)
+                export_from = rep.next_row
+                print(f"step {step + 1:6d}  exported {rep.episodes} episodes ({rep.transitions} transitions) to "
+                      f"{args.export_dir}; left out: {rep.open} open, {rep.headless} headless, {rep.zero_length} zero-length",
+                      flush=True)
         if args.checkpoint_every and (step + 1) % args.checkpoint_every == 0:    # the end of an iteration: this WAITS
             checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats,
-                            extra={"step": step + 1, "logged": logged, "updates": updates})
+                            extra={"step": step + 1, "logged": logged, "updates": updates, "export_from": export_from})
     snap = stats.read()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
