@@ -166,6 +166,41 @@ def vec_fill(frames, action, reward, discount, first, R, N, T, src_frames, src_a
           "drq_vec_fill")
 
 
+def vec_stack_push(prev, frame, first=None, reset_all=False):
+    """drq_vec_stack_push: the frame stacks uint8 [N, 9, 84, 84] after `frame` (uint8 [N, 3, 84, 84]) has been pushed onto
+    `prev` (None with reset_all) -- a reset environment (first[e], or all) holds its frame three times."""
+    lib = _lib.load()
+    _need(frame, torch.uint8, "frame")
+    if frame.dim() != 4 or tuple(frame.shape[1:]) != (3, 84, 84):
+        raise _lib.DrqError(f"frame: uint8 [N, 3, 84, 84] required, got {tuple(frame.shape)}")
+    N = frame.shape[0]
+    if prev is not None and (_need(prev, torch.uint8, "prev").numel() != N * 9 * 84 * 84):
+        raise _lib.DrqError(f"prev: uint8 [{N}, 9, 84, 84] required, got {tuple(prev.shape)}")
+    if first is not None and _need(first, torch.uint8, "first").numel() != N:
+        raise _lib.DrqError(f"first: uint8 [{N}] required, got {tuple(first.shape)}")
+    out = _alloc((N, 9, 84, 84), torch.uint8, frame.device)
+    check(lib.drq_vec_stack_push(ptr(prev), ptr(out), ptr(frame), ptr(first), N, int(bool(reset_all)), _stream()),
+          "drq_vec_stack_push")
+    return out
+
+
+def vec_video_record(frame, envs, grid, scale, done=None, limit=0):
+    """drq_vec_video_record: the mosaic uint8 [GH 84 k, GW 84 k, 3] of the environments `envs` (int32 [M]) out of `frame`
+    (uint8 [N, 3, 84, 84]), grid = (GH, GW), scale = k; with done (int32 [N]) and limit > 0 the tiles of environments
+    with done >= limit are dimmed."""
+    lib = _lib.load()
+    _need(frame, torch.uint8, "frame"), _need(envs, torch.int32, "envs")
+    if frame.dim() != 4 or tuple(frame.shape[1:]) != (3, 84, 84):
+        raise _lib.DrqError(f"frame: uint8 [N, 3, 84, 84] required, got {tuple(frame.shape)}")
+    N, (GH, GW), k = frame.shape[0], grid, int(scale)
+    if done is not None and _need(done, torch.int32, "done").numel() != N:
+        raise _lib.DrqError(f"done: int32 [{N}] required, got {tuple(done.shape)}")
+    out = _alloc((GH * 84 * k, GW * 84 * k, 3), torch.uint8, frame.device)
+    check(lib.drq_vec_video_record(ptr(frame), ptr(envs), envs.numel(), ptr(done), int(limit), ptr(out), GH, GW, k, N,
+                                   _stream()), "drq_vec_video_record")
+    return out
+
+
 def u8_normalize(x):
     lib = _lib.load()
     _need(x, torch.uint8, "obs")

@@ -624,6 +624,41 @@ int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uin
 int drq_vec_reach_render(const float* pos, const float* target, long N, uint8_t* frame, drq_stream_t stream);
 int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream);
 
+/* ---- evaluation.  New functionality: the reference evaluates its one environment on the host -- the 9-channel
+ * observation comes out of a FrameStackWrapper (dmc.py:87-109), the episodes are recorded by video.py (train.py:98-122).
+ * For N lockstep environments whose frames are device tensors ("device environment") both are one launch each, and
+ * neither needs a ring of "single-frame step-major replay".  These definitions are the contract; everything is integer
+ * arithmetic and exact to the bit.  A frame is u8 [3][84][84] = 21,168 bytes = 1,323 pieces of 16 bytes; a stack is three
+ * frames along the channel axis, u8 [9][84][84] = 63,504 bytes = 3,969 pieces, oldest frame first.
+ *
+ * drq_vec_stack_push: the FrameStackWrapper rule for N environments.  prev, next u8 [N][9][84][84], frame u8
+ *   [N][3][84][84], first u8 [N] or NULL = no flags.  For every environment e:
+ *     reset_all or first[e] != 0:  next[e] = (frame[e], frame[e], frame[e])           (dmc.py:98-103)
+ *     otherwise:                   next[e][0:6] = prev[e][3:9], next[e][6:9] = frame[e]   (:105-109)
+ *   prev[e] is not read for a reset environment; with reset_all = 1 prev may be NULL.  Every byte of next is written,
+ *   nothing else.  N x 4 workgroups of 256 threads, 16-byte pieces: a piece never crosses a frame, so every source and
+ *   destination piece is whole and 16-byte aligned.  No LDS, no atomics; the caller orders the launches on one stream.
+ *   DRQ_EARG, nothing launched: a null next or frame, a null prev without reset_all, N < 1 or > INT32_MAX, reset_all not
+ *   0 or 1, prev / next / frame not 16-byte aligned, prev or frame overlapping next.
+ * drq_vec_video_record: one mosaic image of the newest frames.  out u8 [GH S][GW S][3], S = 84 k, k = 1 .. 4, channels
+ *   last.  Tile m < GH GW sits at tile row gy = m / GW, tile column gx = m % GW.  A tile with m < M shows environment
+ *   e = envs[m] (envs: i32 [M] on the device, every entry in [0, N): the caller checks that once; the entry reads nothing
+ *   for an e outside and leaves that tile zero): the byte at tile-local (y, x, c) is frame[e][c][y / k][x / k] -- every
+ *   pixel k x k times, fused with the transposition.  Dimming: if done != NULL (i32 [N], the `done` of "episode
+ *   statistics") and limit > 0 and done[e] >= limit, the tile shows an episode that no longer counts and the byte is that
+ *   value >> 2.  Tiles m >= M are zero.  Every byte of out is written by every call, nothing else.
+ *   The image is walked as one flat array of GH GW 21,168 k^2 bytes, a multiple of 16 for every k, in pieces of 16 bytes
+ *   when out is 16-byte aligned, of 4 when it is 4-byte aligned, else of 1: a tile row is 252 k bytes, a multiple of 16
+ *   only for k = 4, so a piece may run from one tile into the next or into the next image row, and the store width
+ *   follows from the address of out alone.  ceil(pieces / 1,024) workgroups of 256 threads (at most 65,536, then they
+ *   stride), no LDS, no atomics.
+ *   DRQ_EARG, nothing launched: a null frame, envs or out, k outside 1 .. 4, M < 1, M > GH GW, GH or GW < 1, GH GW > 2^20,
+ *   N < 1 or > INT32_MAX, limit < 0, envs or done not 4-byte aligned. */
+int drq_vec_stack_push(const uint8_t* prev, uint8_t* next, const uint8_t* frame, const uint8_t* first, long N,
+                       int reset_all, drq_stream_t stream);
+int drq_vec_video_record(const uint8_t* frame, const int* envs, int M, const int* done, int limit, uint8_t* out, int GH,
+                         int GW, int k, long N, drq_stream_t stream);
+
 /* ---- episode files for the step-major ring.  New functionality: the bulk movements between the ring of "step-major
  * replay" / "single-frame step-major replay" and episode-major staging (an episode file of the reference,
  * replay_buffer.py:22-34, is arrays [len + 1][...] whose index 0 is the dummy reset transition).  The host plans

@@ -58,6 +58,14 @@ next to the single-frame ring it feeds: env.step(), ring.add() of one step's out
 inside every repeat of one process.  Same steps, repeats and the same two figures per line as above.
 
   python tools/vec_replay_bench.py --env reach [--steps 2000] [--repeats 3] [--envs 16,256,1024]
+
+--eval-stack measures the evaluation pieces (drqv2_amd.evaluate): VecFrameStack.push() -- drq_vec_stack_push, one launch --
+beside what an evaluation loop used before it, VecFrameReplay.add() + observation() (two launches), and add() alone, the
+three alternated inside every repeat of one process; then VecVideo.record() at its defaults (16 environments, 4 x 4 tiles,
+scale 2) and the host wall of VecVideo.save() for a 102-image clip of a VecReach rollout, as .png and as .npy.  Same
+steps, repeats and the same two figures per line as above.
+
+  python tools/vec_replay_bench.py --eval-stack [--steps 2000] [--repeats 3] [--envs 16,256,1024]
 """
 import argparse
 import os
@@ -326,6 +334,82 @@ def reach(N, args):
               f"({args.steps} x {args.repeats}, alternated)", flush=True)
 
 
+def eval_stack(N, args):
+    """VecFrameStack.push() beside what stood in for it, VecFrameReplay.add() + observation(), alternated per repeat"""
+    from drqv2_amd.evaluate import VecFrameStack
+    rows = pool_rows(N)
+    newest = [(r[0][:, 6:9].contiguous(),) + r[1:] for r in rows]      # the frame a renderer hands out
+    first = torch.zeros(N, dtype=torch.bool, device="cuda")
+    ring = VecFrameReplay(max(32, SLOTS // N), N, A, NSTEP, 0.99, "cuda", seed=1)
+    stack = VecFrameStack(N, "cuda")
+
+    def ring_pair(i):
+        ring.add(*newest[i & 3], first)
+        ring.observation()
+
+    paths = {"stack.push()": lambda i: stack.push(newest[i & 3][0], first),
+             "ring.add() + observation()": ring_pair,
+             "ring.add() alone": lambda i: ring.add(*newest[i & 3], first)}
+    for fn in paths.values():
+        for i in range(20):
+            fn(i)
+    res = {k: [] for k in paths}
+    for _ in range(args.repeats):
+        for k, fn in paths.items():
+            res[k].append(timed(fn, args.steps))
+    for k, v in res.items():
+        print(f"N={N:5d}  {k:27s}: device-event {spread([x[0] for x in v])}   host wall {spread([x[1] for x in v])}   "
+              f"({args.steps} x {args.repeats}, alternated)", flush=True)
+
+
+def eval_video(args):
+    """VecVideo.record() at its defaults (the first 16 environments, 4 x 4 tiles, scale 2), then save() of a clip as the
+    demo records it: 102 images of a VecReach rollout under uniform-random actions"""
+    import tempfile
+    from drqv2_amd.envs import VecReach
+    from drqv2_amd.evaluate import VecVideo
+    N = 16
+    env = VecReach(N, "cuda", action_dim=A, episode_length=50, seed=1)
+    video = VecVideo(N, "cuda")
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N)
+    actions = [torch.rand(N, A, device="cuda", generator=g) * 2 - 1 for _ in range(4)]
+    frame = env.reset().clone()
+    done = torch.zeros(N, dtype=torch.int32, device="cuda")
+    done[::3] = 1                                                         # a third of the tiles dimmed
+
+    def record(i):
+        if len(video) == video.max_frames:
+            video.clear()
+        video.record(frame, done, 1)
+
+    for i in range(20):
+        record(i)
+    v = [timed(record, args.steps) for _ in range(args.repeats)]
+    nbytes = video.buffer[0].numel()
+    print(f"N={N:5d}  video.record() ({video.grid[0]} x {video.grid[1]} tiles, scale {video.scale}, {nbytes / 1e6:.2f} MB per "
+          f"image): device-event {spread([x[0] for x in v])}   host wall {spread([x[1] for x in v])}   "
+          f"({args.steps} x {args.repeats})", flush=True)
+    video.clear()
+    video.record(frame)
+    for i in range(101):
+        video.record(env.step(actions[i & 3])[0])
+    with tempfile.TemporaryDirectory() as d:
+        for ext in (".png", ".npy"):
+            path, t = os.path.join(d, "clip" + ext), []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                size = video.save(path)
+                t.append(time.perf_counter() - t0)
+            print(f"N={N:5d}  video.save({ext}) of {len(video)} images ({len(video) * nbytes / 1e6:.1f} MB raw -> "
+                  f"{size / 1e6:.2f} MB): host wall {sorted(t)[len(t) // 2]:.3f} s [{min(t):.3f} .. {max(t):.3f}]", flush=True)
+        t0 = time.perf_counter()
+        host = video.clip().cpu().numpy()
+        t1 = time.perf_counter()
+        print(f"N={N:5d}  of which the copy of the clip to the host: {t1 - t0:.3f} s ({host.nbytes / 1e6:.1f} MB); the rest is "
+              f"zlib and the file", flush=True)
+
+
 def two_rings(N, args, ag, rings):
     """rings: name -> (store, its pool of rows); collection steps, then updates, alternated per repeat"""
     first = torch.zeros(N, dtype=torch.bool, device="cuda")
@@ -420,9 +504,17 @@ def main():
     ap.add_argument("--sizes", default="84,128,168", help="image sizes of --render")
     ap.add_argument("--env", choices=["reach"], default=None,
                     help="measure the built-in environment's step() next to the single-frame ring's add()")
+    ap.add_argument("--eval-stack", action="store_true",
+                    help="measure VecFrameStack.push() beside VecFrameReplay.add() + observation(), and VecVideo.record() / save()")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    if args.eval_stack:
+        for N in (int(x) for x in args.envs.split(",")):
+            eval_stack(N, args)
+            torch.cuda.empty_cache()
+        eval_video(args)
+        return
     if args.env:
         for N in (int(x) for x in args.envs.split(",")):
             reach(N, args)

@@ -13,6 +13,13 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
                                  [--dormant-every K] [--perturb-every K [--perturb-k 2.0]]
                                  [--export-dir DIR] [--prefill-dir DIR]
+                                 [--eval-every STEPS [--eval-episodes K] [--video DIR]]
+
+--eval-every STEPS evaluates the policy every STEPS steps (drqv2_amd.evaluate.evaluate: the first --eval-episodes episodes of
+every environment under act_batch(..., eval_mode=True), on a second VecReach of its own seed, --seed + 1) and prints the
+mean, smallest and largest return; --video DIR records those episodes (VecVideo: a mosaic of the first 16 environments,
+one launch per step) and writes DIR/eval_<step>.png, an animated PNG.  An evaluation draws from no generator and touches
+neither ring nor optimiser, so the training lines of a run are the same with and without it.  Off by default.
 
 --dormant-every K prints the actor's dormant ratio (DrQV2Agent.dormant_ratio) on the look-ahead batch every K updates;
 --perturb-every K pulls the weights toward a fresh initialisation every K updates (DrQV2Agent.perturb) with
@@ -45,6 +52,7 @@ import drqv2  # noqa: E402
 import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.envs import VecReach  # noqa: E402
+from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
@@ -94,7 +102,12 @@ def main():
                     help="write the episodes finished since the last report as episode files at every reporting interval")
     ap.add_argument("--prefill-dir", default=None, metavar="DIR",
                     help="load a directory of episode files into the ring before the first reset row")
+    ap.add_argument("--eval-every", type=int, default=0, metavar="STEPS", help="evaluate every STEPS steps (0: never)")
+    ap.add_argument("--eval-episodes", type=int, default=1, metavar="K", help="episodes per environment of an evaluation")
+    ap.add_argument("--video", default=None, metavar="DIR", help="write every evaluation as DIR/eval_<step>.png")
     args = ap.parse_args()
+    if args.video and not args.eval_every:
+        raise SystemExit("--video needs --eval-every STEPS")
     if (args.checkpoint_every or args.resume) and not args.checkpoint:
         raise SystemExit("--checkpoint-every and --resume need --checkpoint PATH")
     if not torch.cuda.is_available():
@@ -114,6 +127,15 @@ def main():
     stats = VecEpisodeStats(N, "cuda", log_size=max(1024, 2 * N * args.report))
     it = iter(store)
     zeros_NA, zeros_N, ones_N = torch.zeros(N, A, device="cuda"), torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
+
+    if args.eval_every:
+        K = args.eval_episodes
+        eval_env = VecReach(N, "cuda", action_dim=A, episode_length=args.episode_length, seed=args.seed + 1)
+        eval_stats = VecEpisodeStats(N, "cuda", log_size=max(1024, K * N), max_episodes_per_env=K)
+        eval_stack, video = VecFrameStack(N, "cuda"), None
+        if args.video:
+            os.makedirs(args.video, exist_ok=True)
+            video = VecVideo(N, "cuda", max_frames=K * (args.episode_length + 1) + 51)    # evaluate()'s max_steps, and row 0
 
     start, logged, updates, export_from = 0, 0, 0, None
     if args.resume:
@@ -169,6 +191,22 @@ def main():
                 print(f"step {step + 1:6d}  exported {rep.episodes} episodes ({rep.transitions} transitions) to "
                       f"{args.export_dir}; left out: {rep.open} open, {rep.headless} headless, {rep.zero_length} zero-length",
                       flush=True)
+        if args.eval_every and (step + 1) % args.eval_every == 0:    # between two training steps: this WAITS, once per 50 steps
+            if video is not None:
+                video.clear()
+            te = time.perf_counter()
+            res = evaluate(agent, eval_env, K, step, stats=eval_stats, stack=eval_stack, video=video)
+            rec = res.snapshot.records
+            print(f"step {step + 1:6d}  eval: {res.snapshot.episodes} episodes ({K} per environment) in {res.steps} steps: mean "
+                  f"return {res.snapshot.mean_return:7.3f}  min {res.snapshot.min_return:7.3f}  max "
+                  f"{res.snapshot.max_return:7.3f}  mean length {rec['length'].mean():5.1f}  "
+                  f"[{time.perf_counter() - te:.2f} s]", flush=True)
+            if video is not None:
+                path = os.path.join(args.video, f"eval_{step + 1}.png")
+                ts = time.perf_counter()
+                size = video.save(path)
+                print(f"step {step + 1:6d}  eval: {len(video)} images of {video.image_shape[1]} x {video.image_shape[0]} -> {path} "
+                      f"({size / 1e6:.2f} MB) [save {time.perf_counter() - ts:.2f} s]", flush=True)
         if args.checkpoint_every and (step + 1) % args.checkpoint_every == 0:    # the end of an iteration: this WAITS
             checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats,
                             extra={"step": step + 1, "logged": logged, "updates": updates, "export_from": export_from})
