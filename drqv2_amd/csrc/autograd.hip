@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void conv1_dgrad_kernel(const float* __restric
   }
 }
 
-// RandomShiftsAug backward.  The forward (elementwise.hip aug_kernel) samples output (i, j) from the four taps
+// RandomShiftsAug backward.  The forward (aug.hip aug_kernel) samples output (i, j) from the four taps
 // (x0 + {0,1}, y0 + {0,1}) of the replicate-padded frame with weights wx_t * wy_u that are 0 / 1 only up to fp32
 // rounding of the grid coordinate (1e-5 off at the far end of the frame).  Its exact adjoint: source pixel (sy, sx)
 // collects dy[i][j] * wy(i) * wx(j), where wx(j) sums the x weights of the taps of column j that land on sx after the

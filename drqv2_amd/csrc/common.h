@@ -47,6 +47,14 @@ static inline int drq_num_cus() {
   return n[dev];
 }
 
+// grid of a flat grid-stride kernel over n elements: one thread per element up to eight workgroups per CU
+static inline unsigned drq_grid_for(long n, int block = 256) {
+  long g = (n + block - 1) / block;
+  const long cap = 8L * drq_num_cus();
+  if (g > cap) g = cap;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+
 // Metrics mirror (DrqStep.sums_host): eight floats and a sequence word in pinned (fine-grained, uncached) host memory,
 // written by ONE lane.  A system-scope release before the sequence word would write back every dirty line of the XCD's
 // L2 first (it is what makes OTHER threads' cached stores visible) -- measured: 3.5 us of the publishing launch at batch

@@ -82,7 +82,7 @@ __device__ __forceinline__ unsigned pack_bf16_c1(float lo, float hi) {      // R
   return __builtin_bit_cast(unsigned, v);
 }
 
-__device__ __forceinline__ float div255(float v) {   // correctly rounded v / 255 (see elementwise.hip)
+__device__ __forceinline__ float div255(float v) {   // correctly rounded v / 255 (see aug.hip)
   const float r = 1.0f / 255.0f;
   const float q = __fmul_rn(v, r);
   const float e = __fmaf_rn(-q, 255.0f, v);

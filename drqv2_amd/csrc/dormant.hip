@@ -1,7 +1,7 @@
 // DrM building blocks (contract: include/drqv2_hip.h, "dormant ratio and perturbation"; new functionality, the reference
 // has neither).  Three small HBM-bound passes, all deterministic: fixed summation orders, no float atomics.
 //
-//   drq_dormant_scores   score[j] = (sum_b |act[b][j]|) / rows -- the layout of colsum_kernel (elementwise.hip): a
+//   drq_dormant_scores   score[j] = (sum_b |act[b][j]|) / rows -- the layout of colsum_kernel (layernorm.hip): a
 //                        workgroup owns CW columns, its 1024 / CW row groups add their rows in two chains each, the
 //                        row-group sums are added in index order.  64 x 16 below 1,024 rows, 16 x 64 from there on.
 //   drq_dormant_count    ONE workgroup of 256 threads: the layer mean m in a fixed order (chain t adds scores t, t + 256,

@@ -5,13 +5,9 @@
 #pragma once
 #include "common.h"
 
-// ---- elementwise.hip
-// LayerNorm+tanh of n problems; problem i may also copy tail_n (<= 64) columns of tail[i] behind its F outputs
-int drq_ln_tanh_fwd_multi_ex(int n, const float* const* z, int ldz, const float* const* gamma,
-                             const float* const* beta, float* const* out, const int* ldo, float* const* xhat,
-                             float* const* rstd, int rows, int F, const float* const* tail, const int* tail_ld,
-                             int tail_n, hipStream_t st);
-// ... that sums the split-K partials of drq_gemm_batched_partial
+// ---- layernorm.hip
+// LayerNorm+tanh of n problems; problem i may also copy tail_n (<= 64) columns of tail[i] behind its F outputs, and
+// part != NULL sums the split-K partials of drq_gemm_batched_partial instead of reading z
 int drq_ln_tanh_fwd_multi_part(int n, const float* const* z, int ldz, const float* const* gamma,
                                const float* const* beta, float* const* out, const int* ldo, float* const* xhat,
                                float* const* rstd, int rows, int F, const float* const* tail, const int* tail_ld,
@@ -22,36 +18,38 @@ int drq_ln_tanh_bwd_part(const float* dh0, int ld0, const float* dh1, int ld1, c
                          int ldp, hipStream_t st);
 int drq_ln_param_grad(const float* dln, const float* xhat, float* dgamma, float* dbeta, int rows, int F,
                       hipStream_t st);
+
+// ---- losses.hip: the actor loss that also publishes to the host mirror (the C entries pass no mirror).
+// a_beh != NULL: the DrQ+BC loss; NULL: the plain loss, ldb and alpha unused
+int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda, const float* a_beh, long ldb,
+                      const float* mu, float std, float alpha, float* dq1, float* dq2, float* sums, int B, int A,
+                      float inv_global_B, float* sums_host, unsigned seq, hipStream_t st);
+
+// ---- qout.hip: the twin-Q output layer backward with a loss computed inside it
+// the TD loss; is_weight and td_abs [B] both given: weighted per row (prioritized replay, drq_td_mse_w's arithmetic),
+// both NULL: the plain loss
 int drq_qout_bwd_td(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
-                    const float* discount, float inv_global_B, float* sums, const float* const* h,
-                    const float* const* w, float* const* dh, float* const* dw, float* const* db, int B, int H,
-                    hipStream_t st);
-// ... with the loss weighted per row (prioritized replay, drq_td_mse_w's arithmetic); also leaves td_abs [B]
-int drq_qout_bwd_td_w(const float* tq1, const float* tq2, const float* q1, const float* q2, const float* reward,
-                      const float* discount, const float* is_weight, float inv_global_B, float* sums, float* td_abs,
-                      const float* const* h, const float* const* w, float* const* dh, float* const* dw,
-                      float* const* db, int B, int H, hipStream_t st);
-int drq_qout_bwd_actor(const float* q1, const float* q2, const float* act, long lda, const float* mu, float std, int A,
-                       float inv_global_B, float* sums, float* sums_host, unsigned seq, const float* const* h,
-                       const float* const* w, float* const* dh, int B, int H, hipStream_t st);
+                    const float* discount, const float* is_weight, float inv_global_B, float* sums, float* td_abs,
+                    const float* const* h, const float* const* w, float* const* dh, float* const* dw, float* const* db,
+                    int B, int H, hipStream_t st);
+// the actor loss, published to the host mirror when one is given; a_beh as for drq_actor_loss_ex
+int drq_qout_bwd_actor(const float* q1, const float* q2, const float* act, long lda, const float* a_beh, long ldb,
+                       const float* mu, float std, float alpha, int A, float inv_global_B, float* sums,
+                       float* sums_host, unsigned seq, const float* const* h, const float* const* w, float* const* dh,
+                       int B, int H, hipStream_t st);
+
+// ---- policy_out.hip
 int drq_policy_out_fwd(const float* h2, const float* w, const float* b, float* p3, int rows, int H, int A,
                        const float* noise, float std, float clip, int use_clip, int srow0, float* mu_out,
                        float* a_out, long lda_out, const float* noise0, float* mu_out0, float* a_out0, long lda_out0,
                        hipStream_t st);
-int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, const float* mu, const float* p2,
-                       const float* w, float* dp2, float* dw, float* db, int B, int H, int A, const float* part,
-                       int splitk, hipStream_t st);
-int drq_actor_loss_ex(const float* q1, const float* q2, const float* a, long lda, const float* mu, float std,
-                      float* dq1, float* dq2, float* sums, int B, int A, float inv_global_B, float* sums_host,
-                      unsigned seq, hipStream_t st);
-// DrQ+BC forms of the two loss launches that also publish to the host mirror (the C entries pass no mirror)
-int drq_actor_loss_bc_ex(const float* q1, const float* q2, const float* a, long lda, const float* a_beh, long ldb,
-                         const float* mu, float std, float alpha, float* dq1, float* dq2, float* sums, int B, int A,
-                         float inv_global_B, float* sums_host, unsigned seq, hipStream_t st);
-int drq_qout_bwd_actor_bc_ex(const float* q1, const float* q2, const float* act, long lda, const float* a_beh, long ldb,
-                             const float* mu, float std, float alpha, int A, float inv_global_B, float* sums,
-                             float* sums_host, unsigned seq, const float* const* h, const float* const* w,
-                             float* const* dh, int B, int H, hipStream_t st);
+// a_beh != NULL: the DrQ+BC pull in dmu (act, lda, ldb, bc_scale); NULL: the plain backward
+int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, const float* mu, const float* act,
+                       long lda, const float* a_beh, long ldb, float bc_scale, const float* p2, const float* w,
+                       float* dp2, float* dw, float* db, int B, int H, int A, const float* part, int splitk,
+                       hipStream_t st);
+
+// ---- optim.hip: Adam over two independent segments in one launch
 int drq_adam_flat2(float* p0, const float* g0, float* m0, float* v0, long n0, long step0, float* p1, const float* g1,
                    float* m1, float* v1, long n1, long step1, double lr, float gscale, hipStream_t st);
 

@@ -1,4 +1,4 @@
-// The device code the replay stores share: the n-step sum (elementwise.hip's flat store, vecreplay.hip's ring), the
+// The device code the replay stores share: the n-step sum (vecframes.hip's flat stores, vecreplay.hip's ring), the
 // priority sum tree (per.hip's episode store, vecreplay.hip's ring), the ring's geometry and batch rows (the uniform
 // and the prioritized draw of vecreplay.hip), the scalars of an added row (vecreplay.hip's add, vecrender.hip's) and the
 // frame stack of a single-frame ring (vecframes.hip's gather, conv1aug.hip's ring mode).  Layout and rules are the contract of include/drqv2_hip.h; the memory-ordering argument of

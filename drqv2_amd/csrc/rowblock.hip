@@ -150,7 +150,7 @@ struct LnL1Args {
   long slab;              // floats between consecutive split-K records of one problem
 };
 
-// The split-K sum of ln_tanh_fwd_kernel (elementwise.hip sum_partials: four interleaved chains over the records, then a
+// The split-K sum of ln_tanh_fwd_kernel (device_sums.h sum_partials: four interleaved chains over the records, then a
 // tree) for FOUR rows of one lane at once.  p[r]: the element in record 0 (a valid address also for rows / features
 // that do not exist: the caller clamps, and discards the result).  All 4 x 16 loads of a batch are in flight together.
 __device__ __forceinline__ void sum_partials4(const float* const (&p)[4], long slab, int splitk, float (&out)[4]) {

@@ -1,5 +1,5 @@
 // Whole-step orchestration of DrQV2Agent.update (drqv2.py:230-262) on one HIP stream.
-// Host code only: sequences the kernels of conv.hip / gemm.hip / elementwise.hip over a caller-owned
+// Host code only: sequences the kernels of the conv, gemm, layernorm, qout, policy_out and optim files over a caller-owned
 // workspace.  No allocation, no synchronisation, no global state.
 #include "common.h"
 #include "internal.h"
@@ -178,10 +178,11 @@ struct Ctx {
   bool fuse_actor_loss = false;
   // DrQ+BC (drq_update_phase_bc): alpha > 0 swaps the actor loss and the policy output backward for their BC forms;
   // 0 = the launches and arguments of the plain update.  a_beh is the action the critic loss consumed: phase 4 copied
-  // it into the action columns of HA_C, which nothing writes again before the next update's phase 4.
+  // it into the action columns of HA_C, which nothing writes again before the next update's phase 4.  Null when BC is
+  // off: that is how the launchers with an optional BC form tell the two apart.
   float bc_alpha = 0.f;
   bool bc() const { return bc_alpha > 0.f; }
-  const float* a_beh() const { return ws(W_HA_C) + s->F; }
+  const float* a_beh() const { return bc() ? ws(W_HA_C) + s->F : nullptr; }
   float bc_scale() const { return 2.0f / ((float)s->global_B * (float)s->A); }
   // prioritized replay (drq_update_phase_per): the critic loss weighted per row by is_weight [B]; phase 4 also leaves
   // the per-sample error in td_abs [B].  Null = the launches and arguments of the plain update.
@@ -512,12 +513,9 @@ int phase_critic_heads(const Ctx& c) {
           *gb2[2] = {c.g(cr.b[0][2]), c.g(cr.b[1][2])};
     // TD target + twin MSE (:185-189) and layer 3 (hidden -> 1) backward in one pass: dq never leaves the chip,
     // sums[0..4] come from the same launch
-    if (c.qout_loss_fits_lds() && c.per()) {
-      CK(drq_qout_bwd_td_w(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, c.is_weight,
-                           invB, s->sums, c.td_abs, c2c, w2, dc2, gw2, gb2, B, H, st));
-    } else if (c.qout_loss_fits_lds()) {
-      CK(drq_qout_bwd_td(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, invB, s->sums,
-                         c2c, w2, dc2, gw2, gb2, B, H, st));
+    if (c.qout_loss_fits_lds()) {
+      CK(drq_qout_bwd_td(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_Q), c.ws(W_Q) + B, s->reward, s->discount, c.is_weight,
+                         invB, s->sums, c.td_abs, c2c, w2, dc2, gw2, gb2, B, H, st));
     } else {
       // beyond 10,224 rows only: update() takes 4,096 at most, so neither form of this route runs from the Python side
       // (a C caller's batch can reach it); drq_td_mse_w is tested as an op
@@ -703,13 +701,10 @@ int phase_actor_forward(const Ctx& c, bool with_opt = true) {
   }
   const float invB = 1.0f / (float)s->global_B;
   // the loss kernel also publishes the eight sums to the host mirror when one is given
-  if (!c.actor_loss_fused() && c.bc())
-    CK(drq_actor_loss_bc_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.a_beh(), FA, c.ws(W_MU_O), s->std,
-                            c.bc_alpha, c.ws(W_DQ), c.ws(W_DQ) + B, s->sums, B, A, invB, s->sums_host,
-                            (unsigned)s->step_actor, st));
-  else if (!c.actor_loss_fused())
-    CK(drq_actor_loss_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.ws(W_MU_O), s->std, c.ws(W_DQ),
-                         c.ws(W_DQ) + B, s->sums, B, A, invB, s->sums_host, (unsigned)s->step_actor, st));
+  if (!c.actor_loss_fused())
+    CK(drq_actor_loss_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.a_beh(), FA, c.ws(W_MU_O), s->std,
+                         c.bc_alpha, c.ws(W_DQ), c.ws(W_DQ) + B, s->sums, B, A, invB, s->sums_host,
+                         (unsigned)s->step_actor, st));
   return 0;
 }
 
@@ -735,14 +730,10 @@ int phase_actor_backward(const Ctx& c) {
     const float *w0a[2] = {c.p(cr.w[0][0]) + F, c.p(cr.w[1][0]) + F}, *w1[2] = {c.p(cr.w[0][1]), c.p(cr.w[1][1])},
                 *w2[2] = {c.p(cr.w[0][2]), c.p(cr.w[1][2])};
     float* da[2] = {c.ws(W_DA), c.ws(W_DA) + (long)B * A};
-    if (c.actor_loss_fused() && c.bc())
-      CK(drq_qout_bwd_actor_bc_ex(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.a_beh(), FA, c.ws(W_MU_O), s->std,
-                                  c.bc_alpha, A, 1.0f / (float)s->global_B, s->sums, s->sums_host,
-                                  (unsigned)s->step_actor, t2, w2, dc2, B, H, st));
-    else if (c.actor_loss_fused())
-      CK(drq_qout_bwd_actor(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.ws(W_MU_O), s->std, A,
-                            1.0f / (float)s->global_B, s->sums, s->sums_host, (unsigned)s->step_actor, t2, w2, dc2, B, H,
-                            st));
+    if (c.actor_loss_fused())
+      CK(drq_qout_bwd_actor(c.ws(W_TQ), c.ws(W_TQ) + B, c.ws(W_HA_C2) + F, FA, c.a_beh(), FA, c.ws(W_MU_O), s->std,
+                            c.bc_alpha, A, 1.0f / (float)s->global_B, s->sums, s->sums_host, (unsigned)s->step_actor,
+                            t2, w2, dc2, B, H, st));
     else
       CK(drq_qout_bwd(2, dq, t2, w2, dc2, nullptr, nullptr, B, H, st));
     CK(c.dgrad(2, dc2c, H, w1, H, dc1, H, B, H, H, t1, H));
@@ -770,13 +761,10 @@ int phase_actor_backward(const Ctx& c) {
     const float *w0[1] = {c.p(ac.w[0][0])}, *w1[1] = {c.p(ac.w[0][1])}, *w2[1] = {c.p(ac.w[0][2])};
     float *gw0[1] = {c.g(ac.w[0][0])}, *gw1[1] = {c.g(ac.w[0][1])}, *gw2[1] = {c.g(ac.w[0][2])};
     float *gb0[1] = {c.g(ac.b[0][0])}, *gb1[1] = {c.g(ac.b[0][1])}, *gb2[1] = {c.g(ac.b[0][2])};
-    if (fused_head && c.bc()) {
-      CK(drq_policy_out_bwd_bc(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, c.a_beh(),
-                               FA, c.bc_scale(), p2[0], w2[0], dp2[0], gw2[0], gb2[0], B, H, A,
-                               sk_da > 1 ? c.gemm_ws() : nullptr, sk_da, st));
-    } else if (fused_head) {
-      CK(drq_policy_out_bwd(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), p2[0], w2[0], dp2[0], gw2[0],
-                            gb2[0], B, H, A, sk_da > 1 ? c.gemm_ws() : nullptr, sk_da, st));
+    if (fused_head) {
+      CK(drq_policy_out_bwd(c.ws(W_DA), c.ws(W_DA) + (long)B * A, A, 0, c.ws(W_MU_O), c.ws(W_HA_C2) + F, FA, c.a_beh(), FA,
+                            c.bc_scale(), p2[0], w2[0], dp2[0], gw2[0], gb2[0], B, H, A,
+                            sk_da > 1 ? c.gemm_ws() : nullptr, sk_da, st));
     } else {
       CK(c.wgrad(1, dpre, A, p2, H, gw2, gb2, B, A, H));
       CK(c.dgrad(1, dpre, A, w2, H, dp2, H, B, H, A, p2, H));

@@ -7,7 +7,8 @@
 // (ring_stack_slots, replay_device.h: shared with the fused aug+conv1 launch, which gathers the same stacks on its own);
 // every lane reads the same bytes, so the loads are broadcast.  Plain vector loads and stores, no atomics.
 //
-// drq_nstep_gather_frames is drq_nstep_gather (elementwise.hip) for an episode store of single frames: a flat ring of R
+// drq_nstep_gather (below, beside nstep_gather_kernel) assembles a batch from an episode store of whole stacks.
+// drq_nstep_gather_frames is the same for an episode store of single frames: a flat ring of R
 // slots, N = 1, every episode contiguous with first = 1 on its first slot.  One launch of B x (6 P + 1) workgroups:
 // workgroup (b, 6 P) with b < ceil(B / 256) does the scalars of 256 batch rows, one thread per row, with nstep_sum --
 // drq_nstep_gather's arithmetic on the same operands; workgroup (b, g P + j) copies piece j of frame g of row b (g = 0 .. 2:
@@ -96,7 +97,72 @@ __global__ __launch_bounds__(256) void nstep_gather_frames_kernel(NstepFramesArg
     if (i0 + u * 256 < n16) dst[i0 + u * 256] = v[u];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Replay sampling on the device (replay_buffer.py:142-160): batch row b is transition pos[b] of a flat store of
+// steps (episodes contiguous): obs = frame[pos-1], next_obs = frame[pos+nstep-1], action = action[pos], and the
+// n-step return in the reference's float32 order:  reward += discount*r[pos+i];  discount *= d[pos+i]*gamma
+// (nstep_sum, replay_device.h).
+// blockIdx.y = 0 / 1: obs / next_obs frame copy (16-byte pieces); blockIdx.y = 2: the scalars of 256 rows.
+// ------------------------------------------------------------------------------------------------
+struct NstepArgs {
+  const uint8_t* frames;
+  const float* action;
+  const float* reward;
+  const float* discount;
+  const long* pos;
+  uint8_t* obs;
+  uint8_t* next_obs;
+  float* act_out;
+  float* rew_out;
+  float* disc_out;
+  long frame_bytes;   // multiple of 16
+  int B, A, nstep;
+  float gamma;
+};
+
+__global__ void nstep_gather_kernel(NstepArgs a) {
+  const int which = a.obs ? blockIdx.y : 2;         // no output frames: the scalars only (grid.y == 1)
+  if (which < 2) {
+    const int b = blockIdx.x;
+    if (b >= a.B) return;
+    const long p = a.pos[b] + (which == 0 ? -1 : (long)a.nstep - 1);
+    const uint4* src = reinterpret_cast<const uint4*>(a.frames + p * a.frame_bytes);
+    uint4* dst = reinterpret_cast<uint4*>((which == 0 ? a.obs : a.next_obs) + (long)b * a.frame_bytes);
+    const long n16 = a.frame_bytes >> 4;
+    for (long i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    return;
+  }
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.B) return;
+  const long p = a.pos[b];
+  for (int j = 0; j < a.A; ++j) a.act_out[(long)b * a.A + j] = a.action[p * a.A + j];
+  float r, d;
+  nstep_sum(a.reward, a.discount, a.gamma, a.nstep, [p](int i) { return p + i; }, r, d);
+  a.rew_out[b] = r;
+  a.disc_out[b] = d;
+}
+
 }  // namespace
+
+// Device-side replay batch assembly (replay_buffer.py:142-160), see nstep_gather_kernel.
+DRQ_API int drq_nstep_gather(const uint8_t* frames, const float* action, const float* reward, const float* discount,
+                             const long* pos, int B, int A, long frame_bytes, int nstep, float gamma, uint8_t* obs,
+                             float* act_out, float* rew_out, float* disc_out, uint8_t* next_obs, drq_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!action || !reward || !discount || !pos || !act_out || !rew_out || !disc_out) return DRQ_EARG;
+  if ((obs != nullptr) != (next_obs != nullptr)) return DRQ_EARG;
+  if (obs && !frames) return DRQ_EARG;
+  if (B <= 0 || A <= 0 || nstep <= 0 || frame_bytes <= 0 || frame_bytes % 16) return DRQ_EARG;
+  if (((uintptr_t)frames | (uintptr_t)obs | (uintptr_t)next_obs) & 15) return DRQ_EARG;
+  NstepArgs a{frames, action, reward, discount, pos, obs, next_obs, act_out, rew_out, disc_out, frame_bytes, B, A, nstep,
+              gamma};
+  // obs == next_obs == NULL: action rows and n-step reward / discount only (the frames stay in the store and the
+  // update reads them through DrqStep.obs_index / next_obs_index)
+  if (obs) hipLaunchKernelGGL(nstep_gather_kernel, dim3(B, 3), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(nstep_gather_kernel, dim3((B + 255) / 256, 1), dim3(256), 0, st, a);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
 
 DRQ_API int drq_nstep_gather_frames(const uint8_t* frames, const uint8_t* first, long R, const float* action,
                                     const float* reward, const float* discount, const long* pos, int B, int A,

@@ -4,7 +4,7 @@
 //
 // drq_vec_add is one grid-stride copy: row t mod R of every array is contiguous (slot = row * N + env), the frames move
 // in 16-byte pieces, the few scalars per environment in 4- and 1-byte ones.  drq_vec_sample is one launch shaped like
-// nstep_gather_kernel (elementwise.hip): blockIdx.y = 2 does the scalars of 256 batch rows with one thread per row,
+// nstep_gather_kernel (vecframes.hip): blockIdx.y = 2 does the scalars of 256 batch rows with one thread per row,
 // blockIdx.y = 0 / 1 copy the obs / next_obs frame of batch row blockIdx.x.  A copy block needs the row's slots, which
 // the scalar block of the same launch computes: instead of waiting for another workgroup it evaluates the (cheap,
 // read-only) choice again -- every lane the same loads, so they are broadcast.  Plain vector stores, no atomics.

@@ -1,5 +1,5 @@
 """The augmentation kernel divides by 255 with a 3-instruction sequence instead of the IEEE division
-(drqv2_amd/csrc/elementwise.hip: div255).  tools/check_div255.py restates the sequence in exact arithmetic and checks
+(drqv2_amd/csrc/aug.hip: div255).  tools/check_div255.py restates the sequence in exact arithmetic and checks
 it against the correctly rounded quotient for every float32 mantissa; this test runs that check."""
 import os
 import runpy

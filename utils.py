@@ -1,7 +1,7 @@
 """Drop-in `utils` module for the reference training loop (train.py:20 does `import utils`).
 
 Same public names and call semantics as /root/reference/utils.py; the tensor work behind
-`soft_update_params` runs in the HIP library (drqv2_amd/csrc/elementwise.hip), everything else here is
+`soft_update_params` runs in the HIP library (drqv2_amd/csrc/optim.hip), everything else here is
 host-side control flow.  No CPU fallback for the device ops: they raise when handed CPU tensors.
 """
 import random
