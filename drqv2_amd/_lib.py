@@ -3,6 +3,8 @@ CPU or PyTorch fallback for the update path."""
 import ctypes as C
 import os
 
+import torch
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libdrqv2_hip.so")
 
@@ -148,6 +150,13 @@ PHASE_ENCODE, PHASE_CRITIC_HEADS, PHASE_CONV_BACKWARD, PHASE_ACTOR_FORWARD, PHAS
 PHASE_ENCODER_OPT, PHASE_ACTOR_OPT = 8, 9
 PHASE_CRITIC_OPT, PHASE_ACTOR_LOSS, PHASE_POLYAK, PHASE_REDRAW = 10, 11, 12, 13
 
+PARAM_LAYOUT_LEN = 59   # DRQ_PARAM_LAYOUT_LEN: the offsets drq_param_layout writes
+
+# the entries without a trailing drq_stream_t: they launch nothing, or their DrqStep carries the stream
+NO_STREAM = frozenset({"drq_abi_version", "drq_conv3x3_wgrad_ws_bytes", "drq_param_layout", "drq_step_ws_bytes",
+                       "drq_step_ws_offset", "drq_update_phase", "drq_update_phase_bc", "drq_update_phase_per",
+                       "drq_update_phase_frames", "drq_act_forward", "drq_act_ws_bytes"})
+
 _lib = None
 
 
@@ -184,6 +193,31 @@ def check(rc, what=""):
     raise DrqError(f"{what}: HIP error {rc}")
 
 
+def current_stream():
+    """the current device's current stream as the library takes it (CPU tests replace this)"""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def enqueue(name, *args, device=None):
+    """Calls the stream entry `name` with args and the current stream of `device`, made current for the call (None:
+    of the current device, as it stands); returns its status."""
+    if name not in PROTOTYPES or name in NO_STREAM:
+        raise DrqError(f"{name}: not an entry of the library that takes a stream")
+    fn = getattr(load(), name)
+    index = None if device is None else torch.device(device).index      # "cuda" without an index is the current one
+    if index is None or index == torch.cuda.current_device():
+        rc = fn(*args, current_stream())
+    else:
+        with torch.cuda.device(index):      # the library launches on the current HIP device
+            rc = fn(*args, current_stream())
+    return rc
+
+
+def launch(name, *args, device=None):
+    """enqueue() that raises DrqError, naming the entry, unless the status is DRQ_OK"""
+    check(enqueue(name, *args, device=device), name)
+
+
 def ptr(t):
     """data pointer of a torch tensor (or None)."""
     return None if t is None else t.data_ptr()
@@ -191,9 +225,9 @@ def ptr(t):
 
 def param_layout(Cc, A, Fd, H):
     lib = load()
-    buf = (L * 59)()
-    n = lib.drq_param_layout(Cc, A, Fd, H, buf, 59)
-    if n != 59:
+    buf = (L * PARAM_LAYOUT_LEN)()
+    n = lib.drq_param_layout(Cc, A, Fd, H, buf, PARAM_LAYOUT_LEN)
+    if n != PARAM_LAYOUT_LEN:
         raise DrqError("drq_param_layout failed")
     v = list(buf)
     return {"enc": v[0:8], "critic": v[8:24], "actor": v[24:34], "target": v[34:50],

@@ -12,7 +12,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
-from ._lib import check, ptr
+from ._lib import check, launch, ptr
 
 _WS = {}
 
@@ -94,9 +94,8 @@ class TrunkFn(torch.autograd.Function):
             dh = dh.contiguous()
         dz, dln = torch.empty_like(h), torch.empty_like(h)
         dg, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
-        check(_lib.load().drq_ln_tanh_bwd(ptr(dh), dh.stride(0), None, 0, ptr(h), F, ptr(xhat), ptr(rstd), ptr(gamma),
-                                          ptr(dz), ptr(dln), ptr(dg), ptr(dbeta), rows, F, ops._stream()),
-              "drq_ln_tanh_bwd")
+        launch("drq_ln_tanh_bwd", ptr(dh), dh.stride(0), None, 0, ptr(h), F, ptr(xhat), ptr(rstd), ptr(gamma), ptr(dz),
+               ptr(dln), ptr(dg), ptr(dbeta), rows, F)
         wsb = _workspace(dh.device)
         dx = dw = db = None
         if need[1] or need[2]:
@@ -117,7 +116,7 @@ def _hidden_wgrad_dgrad(dz, h, w, wsb):
         dx = torch.empty((B, Kin), device=dz.device, dtype=torch.float32)
         pa = ops._ptr_array
         rc = _lib.load().drq_mlp_wgrad_dgrad(1, pa([dz]), Nout, pa([h]), Kin, pa([dw]), pa([db]), pa([w]), Kin, pa([dx]),
-                                             Kin, pa([h]), Kin, B, Nout, Kin, ops._stream())
+                                             Kin, pa([h]), Kin, B, Nout, Kin, _lib.current_stream())
         if rc == 0:
             return dw, db, dx
         if rc != -1:                        # -1: operands not eligible for that kernel, the GEMMs below take them

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import DrqStep, check, ptr
+from ._lib import DrqStep, check, launch, ptr
 
 NETS = ("enc", "critic", "actor", "target")
 
@@ -183,9 +183,7 @@ class GradExchange:
 
     def _sum_slices(self, recv, red, ns):
         if recv.is_cuda:
-            with torch.cuda.device(self.device):
-                check(_lib.load().drq_sum_slices(ptr(recv), ns, self.world, ptr(red), ns,
-                                                 torch.cuda.current_stream(self.device).cuda_stream), "drq_sum_slices")
+            launch("drq_sum_slices", ptr(recv), ns, self.world, ptr(red), ns, device=self.device)
         else:       # gloo rehearsals on CPU tensors (tests): the same rank-order sum
             acc = recv[:ns].clone()
             for r in range(1, self.world):
@@ -204,11 +202,8 @@ class GradExchange:
         if step_fn is not None:                     # CPU tests hand in the oracle's Adam
             step_fn(ps, recv.view(self.world, ns), ms, vs)
         else:
-            with torch.cuda.device(self.device):
-                check(_lib.load().drq_adam_reduce_flat(ptr(ps), ptr(recv), ns, self.world, ptr(ms), ptr(vs), ns,
-                                                       float(lr), int(step), float(gscale),
-                                                       torch.cuda.current_stream(self.device).cuda_stream),
-                      "drq_adam_reduce_flat")
+            launch("drq_adam_reduce_flat", ptr(ps), ptr(recv), ns, self.world, ptr(ms), ptr(vs), ns, float(lr), int(step),
+                   float(gscale), device=self.device)
         red.copy_(ps)
         dist.all_gather_into_tensor(p, red, group=self.pg)
 
@@ -557,9 +552,8 @@ class StepEngine:
             self._rng_bufs = (key, (mk(n, 1, 1, 2), mk(n, 1, 1, 2), mk(n, A), mk(n, A)))
         bufs = self._rng_bufs[1]
         seed, off = gen.initial_seed(), gen.get_offset()
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_rng_draws(seed, off, 2 * n, n * A if with_noise else 0, pad_range,
-                                            *(ptr(b) for b in bufs), self._stream()), "drq_rng_draws")
+        launch("drq_rng_draws", seed, off, 2 * n, n * A if with_noise else 0, pad_range, *(ptr(b) for b in bufs),
+               device=self.device)
         gen.set_offset(off + (16 if with_noise else 8))
         if not with_noise:                              # torch's own normal_ calls, in the reference's order
             bufs[2].normal_()
@@ -805,8 +799,7 @@ class StepEngine:
                     with torch.cuda.stream(side):
                         self._allreduce_async(self.sums).wait()
                         if mirror:
-                            check(_lib.load().drq_publish_sums(ptr(self.sums), ptr(self.sums_host), seq,
-                                                               side.cuda_stream), "drq_publish_sums")
+                            launch("drq_publish_sums", ptr(self.sums), ptr(self.sums_host), seq, device=self.device)
                     self._side_busy = True
                     self._last_seq = seq if mirror else None
                 else:
@@ -1004,10 +997,8 @@ class StepEngine:
                 self._act_ws = None
                 self._act_ws = torch.zeros(need // 4, device=self.device, dtype=torch.float32)
             action = torch.empty((n, self.A), device=self.device, dtype=torch.float32)
-            with torch.cuda.device(self.device):
-                check(lib.drq_act_batch(ptr(self.params), self.C, self.A, self.F, self.H, ptr(obs_u8), n, ptr(noise),
-                                        float(std), None, ptr(action), ptr(self._act_ws), self._act_ws.numel() * 4,
-                                        self._stream()), "drq_act_batch")
+            launch("drq_act_batch", ptr(self.params), self.C, self.A, self.F, self.H, ptr(obs_u8), n, ptr(noise),
+                   float(std), None, ptr(action), ptr(self._act_ws), self._act_ws.numel() * 4, device=self.device)
             return action
         cap = 2 * self._ws_B if self._ws_B is not None else n        # drq_act_forward takes <= 2*B rows
         mu = torch.cat([self.act_forward(obs_u8[i:i + cap]) for i in range(0, n, cap)])

@@ -10,7 +10,7 @@ environment") and restated in numpy by tests/vec_env_oracle.py.  It is not a ben
 import torch
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import launch, ptr
 from .checkpoint import check_state, host
 
 
@@ -62,9 +62,6 @@ class VecReach:
             return torch.device("cuda", torch.cuda.current_device())
         return d
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _on_gpu(self):
         if self.device.type != "cuda":
             raise _lib.DrqError("the device environment lives on the GPU: the HIP path has no CPU fallback")
@@ -95,10 +92,9 @@ class VecReach:
     def _launch(self, action, reset_all):
         out = self._next_out()
         with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_reach_step(ptr(self.pos), ptr(self.target), ptr(self.t), ptr(self.episode),
-                                                 ptr(self.over), self.N, self.A, ptr(action), self.seed,
-                                                 self.episode_length, int(reset_all), *(ptr(o) for o in out),
-                                                 self._stream()), "drq_vec_reach_step")
+            launch("drq_vec_reach_step", ptr(self.pos), ptr(self.target), ptr(self.t), ptr(self.episode),
+                   ptr(self.over), self.N, self.A, ptr(action), self.seed, self.episode_length, int(reset_all),
+                   *(ptr(o) for o in out), device=self.device)
             if action is not None:  # a caller's tensor may be freed right after step(): the launch still reads it
                 action.record_stream(torch.cuda.current_stream())
         self._frame = out[0]
@@ -133,9 +129,7 @@ class VecReach:
 
     def _render(self):
         out = self._next_out()
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_reach_render(ptr(self.pos), ptr(self.target), self.N, ptr(out[0]), self._stream()),
-                  "drq_vec_reach_render")
+        launch("drq_vec_reach_render", ptr(self.pos), ptr(self.target), self.N, ptr(out[0]), device=self.device)
         self._frame = out[0]
         return out[0]
 
@@ -155,9 +149,7 @@ class VecReach:
                                                                device=self.device) for _ in range(2)] + [0]
         out = bufs[bufs[2]]
         bufs[2] ^= 1
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_reach_image(ptr(self._frame), ptr(out), self.N, size, channels, self._stream()),
-                  "drq_vec_reach_image")
+        launch("drq_vec_reach_image", ptr(self._frame), ptr(out), self.N, size, channels, device=self.device)
         return out
 
     def state(self):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import check, ptr
+from ._lib import launch, ptr
 from .replay import VecDeviceReplay, VecEpisodeStats, _on_gpu
 
 FRAME_SHAPE = (3, 84, 84)
@@ -85,8 +85,8 @@ class VecFrameStack:
         prev, out = (None if reset_all else self._bufs[self._newest]), self._bufs[self._at]
         with torch.cuda.device(self.device):
             src = [t if t is None or t.is_cuda else _pinned_stage(self._stage, k, t, self.device) for k, t in enumerate(args)]
-            check(_lib.load().drq_vec_stack_push(ptr(prev), ptr(out), ptr(src[0]), ptr(src[1]), N, int(reset_all),
-                                                 torch.cuda.current_stream(self.device).cuda_stream), "drq_vec_stack_push")
+            launch("drq_vec_stack_push", ptr(prev), ptr(out), ptr(src[0]), ptr(src[1]), N, int(reset_all),
+                   device=self.device)
             for t in src:           # a caller's tensor may be freed right after push(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())
@@ -308,10 +308,8 @@ class VecVideo:
             return
         with torch.cuda.device(self.device):
             src = [t if t is None or t.is_cuda else _pinned_stage(self._stage, k, t, self.device) for k, t in enumerate(args)]
-            check(_lib.load().drq_vec_video_record(ptr(src[0]), ptr(self._envs), len(self.envs), ptr(src[1]), limit,
-                                                   ptr(self.buffer[self._n]), self.grid[0], self.grid[1], self.scale, N,
-                                                   torch.cuda.current_stream(self.device).cuda_stream),
-                  "drq_vec_video_record")
+            launch("drq_vec_video_record", ptr(src[0]), ptr(self._envs), len(self.envs), ptr(src[1]), limit,
+                   ptr(self.buffer[self._n]), self.grid[0], self.grid[1], self.scale, N, device=self.device)
             for t in src:           # a caller's tensor may be freed right after record(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())

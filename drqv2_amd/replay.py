@@ -60,7 +60,7 @@ import torch
 
 from . import _lib
 from . import episodes as _episodes
-from ._lib import check, ptr
+from ._lib import launch, ptr
 from .checkpoint import check_state, host
 
 ExportReport = collections.namedtuple("ExportReport", "files episodes transitions next_row zero_length headless open short")
@@ -109,10 +109,8 @@ class FrameBatch(IndexedBatch):
         n, fb = slots.numel(), self.frames.shape[1]
         if out is None:
             out = torch.empty((n, 3 * fb), dtype=torch.uint8, device=self.frames.device)
-        with torch.cuda.device(self.frames.device):
-            check(_lib.load().drq_vec_stack_gather(ptr(self.frames), ptr(first), R, N, fb, ptr(slots.contiguous()), 0, n,
-                                                   ptr(out), torch.cuda.current_stream().cuda_stream),
-                  "drq_vec_stack_gather")
+        launch("drq_vec_stack_gather", ptr(self.frames), ptr(first), R, N, fb, ptr(slots.contiguous()), 0, n, ptr(out),
+               device=self.frames.device)
         return out
 
     def materialize(self, obs_shape=(9, 84, 84), out=(None, None)):
@@ -402,12 +400,8 @@ class DeviceReplay:
         self._head = end
         return start, evicted
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _fill(self, lo, hi, mode):
-        with torch.cuda.device(self.device):       # the library launches on the current HIP device
-            check(_lib.load().drq_per_fill(ptr(self.tree), self.tree_leaves, lo, hi, mode, self._stream()), "drq_per_fill")
+        launch("drq_per_fill", ptr(self.tree), self.tree_leaves, lo, hi, mode, device=self.device)
 
     def _place_priorities(self, start, n, evicted):
         """the tree after an episode of n steps went to `start`: every slot of the evicted episodes (also the part the
@@ -466,7 +460,6 @@ class DeviceReplay:
         """pos: int64 store indices [B] (host array or device tensor) -> (obs, action, reward, discount, next_obs) on
         the device, shaped like the reference's batch ([B,*obs], [B,A], [B,1], [B,1], [B,*obs])."""
         _on_gpu(self, "replay batch assembly runs")
-        lib = _lib.load()
         if not torch.is_tensor(pos):
             pos = torch.from_numpy(np.ascontiguousarray(pos, np.int64))
         pos = pos.to(self.device, non_blocking=True)
@@ -483,14 +476,13 @@ class DeviceReplay:
         obs, act, rew, disc, nxt = out
         shp = (B,) + self.obs_shape
         if self.single_frames:              # the same batch, the stacks put together from three slots each
-            check(lib.drq_nstep_gather_frames(ptr(self.frames), ptr(self.first), self.capacity, ptr(self.action),
-                                              ptr(self.reward), ptr(self.discount), ptr(pos), B, self.A, self.frame_bytes,
-                                              self.nstep, self.gamma, ptr(obs), ptr(act), ptr(rew), ptr(disc), ptr(nxt),
-                                              torch.cuda.current_stream().cuda_stream), "drq_nstep_gather_frames")
+            launch("drq_nstep_gather_frames", ptr(self.frames), ptr(self.first), self.capacity, ptr(self.action),
+                   ptr(self.reward), ptr(self.discount), ptr(pos), B, self.A, self.frame_bytes, self.nstep, self.gamma,
+                   ptr(obs), ptr(act), ptr(rew), ptr(disc), ptr(nxt), device=self.device)
             return obs.view(shp), act, rew, disc, nxt.view(shp)
-        check(lib.drq_nstep_gather(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(pos), B,
-                                   self.A, self.frame_bytes, self.nstep, self.gamma, ptr(obs), ptr(act), ptr(rew),
-                                   ptr(disc), ptr(nxt), torch.cuda.current_stream().cuda_stream), "drq_nstep_gather")
+        launch("drq_nstep_gather", ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(pos),
+               B, self.A, self.frame_bytes, self.nstep, self.gamma, ptr(obs), ptr(act), ptr(rew), ptr(disc), ptr(nxt),
+               device=self.device)
         return obs.view(shp), act, rew, disc, nxt.view(shp)
 
     def gather_indexed(self, pos):
@@ -498,7 +490,6 @@ class DeviceReplay:
         same kernel (its frame copies skipped), obs = frame pos-1, next_obs = frame pos+nstep-1 as indices.  A
         single-frame store yields a FrameBatch: the indices name the newest frame of each stack."""
         _on_gpu(self, "replay batch assembly runs")
-        lib = _lib.load()
         pos = np.ascontiguousarray(pos, np.int64)
         B = pos.size
         dev = self.device
@@ -509,9 +500,9 @@ class DeviceReplay:
         h = host.numpy()
         h[0], h[1], h[2] = pos - 1, pos + self.nstep - 1, pos
         idx.copy_(host, non_blocking=True)
-        check(lib.drq_nstep_gather(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(idx[2]), B,
-                                   self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act), ptr(rew), ptr(disc),
-                                   None, torch.cuda.current_stream().cuda_stream), "drq_nstep_gather")
+        launch("drq_nstep_gather", ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
+               ptr(idx[2]), B, self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act), ptr(rew), ptr(disc),
+               None, device=self.device)
         return self._batch(False, idx, act, rew, disc)
 
     def _batch(self, prioritized, idx, act, rew, disc):
@@ -526,7 +517,6 @@ class DeviceReplay:
         batch) -> drq_per_sample -> drq_nstep_gather on the device positions.  Returns a PrioritizedBatch."""
         if self.n_valid <= 0:
             raise _lib.DrqError("replay: no stored episode is at least nstep long")
-        lib = _lib.load()
         B = int(batch_size)
         dev = self.device
         f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
@@ -538,15 +528,13 @@ class DeviceReplay:
             (f(B, self.A), f(B, 1), f(B, 1)) if self.indexed else None))
         host.numpy()[:] = self.rng.random_sample(B)
         u.copy_(host, non_blocking=True)
-        with torch.cuda.device(self.device):
-            check(lib.drq_per_sample(ptr(self.tree), self.tree_leaves, ptr(u), B, self.nstep, self.n_valid,
-                                     float(self.priority_beta), ptr(idx), ptr(w), self._stream()), "drq_per_sample")
-            if self.indexed:
-                act, rew, disc = rows
-                check(lib.drq_nstep_gather(ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
-                                           ptr(idx[2]), B, self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act),
-                                           ptr(rew), ptr(disc), None, self._stream()), "drq_nstep_gather")
+        launch("drq_per_sample", ptr(self.tree), self.tree_leaves, ptr(u), B, self.nstep, self.n_valid,
+               float(self.priority_beta), ptr(idx), ptr(w), device=self.device)
         if self.indexed:
+            act, rew, disc = rows
+            launch("drq_nstep_gather", ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
+                   ptr(idx[2]), B, self.A, self.frame_bytes, self.nstep, self.gamma, None, ptr(act), ptr(rew), ptr(disc),
+                   None, device=self.device)
             batch = self._batch(True, idx, act, rew, disc)
         else:
             batch = _PrioritizedTuple(self.gather(idx[2]))
@@ -560,9 +548,8 @@ class DeviceReplay:
             return                      # an episode was placed since the draw: see PrioritizedBatch.update_priorities
         pos = batch._pos
         B = _td_rows(pos, td_abs)
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_per_update(ptr(self.tree), self.tree_leaves, ptr(pos), ptr(td_abs), B, self.priority_alpha,
-                                             self.priority_eps, self._stream()), "drq_per_update")
+        launch("drq_per_update", ptr(self.tree), self.tree_leaves, ptr(pos), ptr(td_abs), B, self.priority_alpha,
+               self.priority_eps, device=self.device)
 
     def sample(self, batch_size):
         if self.tree is not None:
@@ -662,9 +649,6 @@ class VecDeviceReplay:
         lo, hi = self.bounds()
         return max(0, hi - lo + 1) * self.N
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _row(self, x, name, shapes, dtypes):
         """one argument of add() as a contiguous tensor of its storage type, checked; still where the caller has it"""
         t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
@@ -708,9 +692,9 @@ class VecDeviceReplay:
         N = self.N
         args = [self._row(obs, "obs", [(N,) + self.slot_shape, (N, self.frame_bytes)], (torch.uint8,))]
         args += self._scalar_rows(action, reward, discount, first)
-        self._write_row(args, self._staged, lambda src: check(_lib.load().drq_vec_add(
-            ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(self.first), self.R, N, self.A,
-            self.frame_bytes, self.T, *(ptr(t) for t in src), self._stream()), "drq_vec_add"))
+        self._write_row(args, self._staged, lambda src: launch(
+            "drq_vec_add", ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(self.first),
+            self.R, N, self.A, self.frame_bytes, self.T, *(ptr(t) for t in src), device=self.device))
 
     def _scalar_rows(self, action, reward, discount, first):
         """what every add takes besides the frames, checked like them"""
@@ -720,14 +704,14 @@ class VecDeviceReplay:
                 self._row(discount, "discount", [(N,), (N, 1)], f32),
                 None if first is None else self._row(first, "first", [(N,)], (torch.uint8, torch.bool))]
 
-    def _write_row(self, args, staged, launch):
-        """the tail every add shares: host arguments are staged (staged(k, t): argument k on the device), launch(src)
-        writes row T, then the row counts and the tree follows"""
+    def _write_row(self, args, staged, write):
+        """the tail every add shares: host arguments are staged (staged(k, t): argument k on the device), write(src)
+        launches the entry that writes row T, then the row counts and the tree follows"""
         N = self.N
         _on_gpu(self, "the step-major replay lives")
         with torch.cuda.device(self.device):
             src = [t if t is None or t.is_cuda else staged(k, t) for k, t in enumerate(args)]
-            launch(src)
+            write(src)
             for t in src:           # a caller's tensor may be freed right after add(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())
@@ -742,8 +726,8 @@ class VecDeviceReplay:
             lo, hi = self.bounds()
             enter, leave = (hi if hi >= lo else -1), (lo - 1 if lo >= 2 else -1)
             if enter >= 0 or leave >= 0:
-                check(_lib.load().drq_vec_per_advance(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N,
-                                                      self.T, enter, leave, self._stream()), "drq_vec_per_advance")
+                launch("drq_vec_per_advance", ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N, self.T,
+                       enter, leave, device=self.device)
 
     # ---- sampling ------------------------------------------------------------------------
     def sample(self, batch_size):
@@ -771,12 +755,10 @@ class VecDeviceReplay:
                 self._frames_out = {B: out}
             obs, nxt = out
         copies = not self.indexed and self._draw_copies
-        with torch.cuda.device(dev):
-            check(_lib.load().drq_vec_sample(ptr(self.first), ptr(self.action), ptr(self.reward), ptr(self.discount), self.R,
-                                             self.N, self.A, self.frame_bytes, lo, hi, ptr(u), B, K, self.nstep, self.gamma,
-                                             ptr(idx), ptr(act), ptr(rew), ptr(disc), ptr(steps),
-                                             ptr(self.frames) if copies else None, ptr(obs) if copies else None,
-                                             ptr(nxt) if copies else None, self._stream()), "drq_vec_sample")
+        launch("drq_vec_sample", ptr(self.first), ptr(self.action), ptr(self.reward), ptr(self.discount), self.R, self.N,
+               self.A, self.frame_bytes, lo, hi, ptr(u), B, K, self.nstep, self.gamma, ptr(idx), ptr(act), ptr(rew),
+               ptr(disc), ptr(steps), ptr(self.frames) if copies else None, ptr(obs) if copies else None,
+               ptr(nxt) if copies else None, device=dev)
         self.last_steps, self.last_index = steps, idx
         batch = self._batch(False, idx, act, rew, disc)
         if self.indexed:
@@ -797,12 +779,10 @@ class VecDeviceReplay:
             torch.empty((B,), dtype=torch.float64).pin_memory()))
         host.numpy()[:] = self.rng.random_sample(B)
         u.copy_(host, non_blocking=True)
-        with torch.cuda.device(dev):
-            check(_lib.load().drq_vec_per_sample(ptr(self.tree), self.tree_leaves, ptr(self.first), ptr(self.action),
-                                                 ptr(self.reward), ptr(self.discount), self.R, self.N, self.A, self.T, lo, hi,
-                                                 ptr(u), B, self.nstep, self.gamma, float(self.priority_beta), ptr(idx),
-                                                 ptr(act), ptr(rew), ptr(disc), ptr(steps), ptr(w), self._stream()),
-                  "drq_vec_per_sample")
+        launch("drq_vec_per_sample", ptr(self.tree), self.tree_leaves, ptr(self.first), ptr(self.action),
+               ptr(self.reward), ptr(self.discount), self.R, self.N, self.A, self.T, lo, hi, ptr(u), B, self.nstep,
+               self.gamma, float(self.priority_beta), ptr(idx), ptr(act), ptr(rew), ptr(disc), ptr(steps), ptr(w),
+               device=dev)
         self.last_steps, self.last_index = steps, idx
         return self._batch(True, idx, act, rew, disc)._per(self, idx[2], w)
 
@@ -815,10 +795,8 @@ class VecDeviceReplay:
         pos = batch._pos
         B = _td_rows(pos, td_abs)
         lo, hi = self.bounds()
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_per_update(ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N, self.T,
-                                                 lo, hi, ptr(pos), ptr(td_abs), B, self.priority_alpha, self.priority_eps,
-                                                 self._stream()), "drq_vec_per_update")
+        launch("drq_vec_per_update", ptr(self.tree), self.tree_leaves, ptr(self.first), self.R, self.N, self.T, lo, hi,
+               ptr(pos), ptr(td_abs), B, self.priority_alpha, self.priority_eps, device=self.device)
 
     def __iter__(self):
         return BatchIterator(lambda: self.sample(self.batch_size), self)
@@ -969,10 +947,9 @@ class VecDeviceReplay:
                     pin = pins[k]                   # free: the chunk it held was drained before the previous launch
                     pin[4].numpy()[:m] = table[m0:m0 + m]
                     dv[4][:m].copy_(pin[4][:m], non_blocking=True)
-                    check(_lib.load().drq_vec_export_rows(ptr(self.frames), ptr(self.action), ptr(self.reward),
-                                                          ptr(self.discount), self.R, self.N, A, self.frame_bytes,
-                                                          self._stack, ptr(dv[4]), m, ptr(dv[0]), ptr(dv[1]), ptr(dv[2]),
-                                                          ptr(dv[3]), stream.cuda_stream), "drq_vec_export_rows")
+                    launch("drq_vec_export_rows", ptr(self.frames), ptr(self.action), ptr(self.reward),
+                           ptr(self.discount), self.R, self.N, A, self.frame_bytes, self._stack, ptr(dv[4]), m,
+                           ptr(dv[0]), ptr(dv[1]), ptr(dv[2]), ptr(dv[3]), device=dev)
                     for q in range(4):
                         pin[q][:m].copy_(dv[q][:m], non_blocking=True)
                     done[k] = torch.cuda.Event()
@@ -1038,7 +1015,6 @@ class VecDeviceReplay:
         environment ends on a finished episode (or a pad row), so the next live add() must be a reset row for every
         environment.  Returns a FillReport.  DrqError for a store on the CPU, after the checks."""
         import replay_buffer as RB          # at call time: replay_buffer imports this module
-        from ._lib import check as rc_check  # the module's `check` is hidden by this method's argument of that name
         if isinstance(source, (str, pathlib.Path)):
             files = [fn for fn, _, _ in RB._episode_files(source)]
             named = [(fn.name, RB.load_episode(fn)) for fn in files]
@@ -1075,9 +1051,8 @@ class VecDeviceReplay:
                     d[:n].copy_(p[:n], non_blocking=True)
                 done[k] = torch.cuda.Event()
                 done[k].record(stream)
-                rc_check(_lib.load().drq_vec_fill(ptr(self.frames), ptr(self.action), ptr(self.reward),
-                                                  ptr(self.discount), ptr(self.first), R, N, A, self.frame_bytes, self.T,
-                                                  n, *(ptr(d) for d in dv), stream.cuda_stream), "drq_vec_fill")
+                launch("drq_vec_fill", ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
+                       ptr(self.first), R, N, A, self.frame_bytes, self.T, n, *(ptr(d) for d in dv), device=dev)
                 for _ in range(n):
                     self._row_added()
             for ev in done:
@@ -1187,10 +1162,9 @@ class VecFrameReplay(VecDeviceReplay):
         args = [self._image(image)] + self._scalar_rows(action, reward, discount, first)
         S, Cin = int(args[0].shape[1]), int(args[0].shape[3])
         self._write_row(args, lambda k, t: self._staged_image(t) if k == 0 else self._staged(k, t),
-                        lambda src: check(_lib.load().drq_vec_add_render(
-                            ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount), ptr(self.first),
-                            self.R, self.N, self.A, self.T, ptr(src[0]), S, Cin, *(ptr(t) for t in src[1:]),
-                            self._stream()), "drq_vec_add_render"))
+                        lambda src: launch("drq_vec_add_render", ptr(self.frames), ptr(self.action), ptr(self.reward),
+                                           ptr(self.discount), ptr(self.first), self.R, self.N, self.A, self.T,
+                                           ptr(src[0]), S, Cin, *(ptr(t) for t in src[1:]), device=self.device))
 
     def observation(self):
         """uint8 [N, 9, 84, 84] on the device: the frame stacks of the newest row, what a FrameStackWrapper per
@@ -1205,9 +1179,8 @@ class VecFrameReplay(VecDeviceReplay):
                              for _ in range(2)] + [0]
         out = self._obs_out[self._obs_out[2]]
         self._obs_out[2] ^= 1
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_stack_gather(ptr(self.frames), ptr(self.first), self.R, self.N, self.frame_bytes, None,
-                                                   self.T - 1, self.N, ptr(out), self._stream()), "drq_vec_stack_gather")
+        launch("drq_vec_stack_gather", ptr(self.frames), ptr(self.first), self.R, self.N, self.frame_bytes, None,
+               self.T - 1, self.N, ptr(out), device=self.device)
         return out
 
 
@@ -1314,12 +1287,8 @@ class VecEpisodeStats:
         return [ptr(self.episode_return), ptr(self.episode_length), ptr(self.episodes_done), ptr(self.header)] + \
             [ptr(t) for t in self._log]
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _launch_reset(self):
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_stats_reset(*self._state(), self.N, self.W, self._stream()), "drq_vec_stats_reset")
+        launch("drq_vec_stats_reset", *self._state(), self.N, self.W, device=self.device)
 
     def _staged(self, k, t):
         if self._stage is None:
@@ -1340,8 +1309,8 @@ class VecEpisodeStats:
         _on_gpu(self, "the episode statistics live")
         with torch.cuda.device(self.device):
             src = [t if t is None or t.is_cuda else self._staged(k, t) for k, t in enumerate(args)]
-            check(_lib.load().drq_vec_stats_step(*self._state(), N, self.W, self.limit, self.rows, ptr(src[0]), ptr(src[1]),
-                                                 self._stream()), "drq_vec_stats_step")
+            launch("drq_vec_stats_step", *self._state(), N, self.W, self.limit, self.rows, ptr(src[0]), ptr(src[1]),
+                   device=self.device)
             for t in src:           # a caller's tensor may be freed right after step(): the launch still reads it
                 if t is not None:
                     t.record_stream(torch.cuda.current_stream())
@@ -1367,9 +1336,8 @@ class VecEpisodeStats:
         self.published += 1
         m = self._mirrors[(self.published - 1) & 3]
         m[3] = self.published & 0xFFFFFFFF
-        with torch.cuda.device(self.device):
-            check(_lib.load().drq_vec_stats_publish(ptr(self.header), *(ptr(t) for t in self._log), self.W, ptr(m[0]), m[3],
-                                                    self._stream()), "drq_vec_stats_publish")
+        launch("drq_vec_stats_publish", ptr(self.header), *(ptr(t) for t in self._log), self.W, ptr(m[0]), m[3],
+               device=self.device)
         return self.published
 
     def _snapshot(self, m):

@@ -3,7 +3,6 @@ iterator, the episode statistics and the device environment): everything that ne
 in host tensors and no launch is involved in saving or loading it, so the round trip is complete here; the environment's
 load ends in a launch and is refused on the CPU after its checks.  Everything is compared bit for bit."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,8 +11,8 @@ import torch
 from drqv2_amd import _lib, checkpoint
 from drqv2_amd.envs import VecReach
 from drqv2_amd.replay import BatchIterator, DeviceReplay, VecDeviceReplay, VecEpisodeStats, VecFrameReplay
+from tests import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R, N, A = 12, 3, 2
 RING = ("frames", "action", "reward", "discount", "first")
 
@@ -299,19 +298,8 @@ def test_agent_goes_in_through_its_snapshot_and_loads_in_place(tmp_path):
 
 # ------------------------------------------------------------------------------------------------ the interface
 def test_render_entry_in_header_prototypes_and_build_rule():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
     name = "drq_vec_reach_render"
-    assert name in _lib.PROTOTYPES
-    m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-    assert m, f"{name} is not declared in the header"
-    kinds = {"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D, "unsigned": _lib.C.c_uint}
-    want = []
-    for prm in m.group(1).split(","):
-        prm = " ".join(prm.split())
-        want.append(_lib.P if "*" in prm or prm.startswith("drq_stream_t") else kinds[prm.split()[0]])
-    res, args = _lib.PROTOTYPES[name]
-    assert res is _lib.I and args == want
+    abi.assert_prototype(name)
     from drqv2_amd import build
     assert "vecenv.hip" in build.SOURCES and build.FILE_FLAGS["vecenv.hip"] == ["-ffp-contract=off"]
     lib = _lib.load()

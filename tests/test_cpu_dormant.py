@@ -3,16 +3,15 @@ needs no GPU.  The numpy restatement of the contract (tests/dormant_oracle.py) o
 utils.py, the agent's validation on the CPU, and the argument errors the library reports before any launch."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from drqv2_amd import _lib
+from tests import abi
 from tests import dormant_oracle as DO
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drq_dormant_scores", "drq_dormant_count", "drq_lerp_flat")
 EARG = -1
 
@@ -25,23 +24,12 @@ def cpu_agent():
 
 
 def test_header_prototypes_and_build_list():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
-    kinds = {"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}
     for name in NEW:
-        assert name in _lib.PROTOTYPES, name
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            want.append(_lib.P if "*" in prm or prm.startswith("drq_stream_t") else kinds[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want, name
+        abi.assert_prototype(name)
         assert hasattr(_lib.load(), name)
     from drqv2_amd import build, ops
     assert "dormant.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "dormant.hip"))
-    assert "fmaf(a, p[i], (1 - a) * p0[i])" in header            # the expression the oracle restates
+    assert "fmaf(a, p[i], (1 - a) * p0[i])" in abi.text()            # the expression the oracle restates
     assert all(callable(getattr(ops, n)) for n in ("dormant_scores", "dormant_count", "lerp_flat"))
 
 

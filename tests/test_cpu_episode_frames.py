@@ -4,12 +4,12 @@ the public surface, the frame-stack check and the constructor's validation, and 
 before any launch."""
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
 
 from drqv2_amd import _lib
+from tests import abi
 from tests import episode_frames_oracle as EF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,21 +25,9 @@ def single_store(**kw):
 
 # ------------------------------------------------------------------------------------------------ the surface
 def test_header_prototype_export_and_abi_version():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
-    assert NAME in _lib.PROTOTYPES
-    m = re.search(r"\bint " + NAME + r"\((.*?)\);", header, re.S)
-    assert m, f"{NAME} is not declared in the header"
-    want = []
-    for prm in m.group(1).split(","):
-        prm = " ".join(prm.split())
-        if "*" in prm or prm.startswith("drq_stream_t"):
-            want.append(_lib.P)
-        else:
-            want.append({"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}[prm.split()[0]])
-    res, args = _lib.PROTOTYPES[NAME]
-    assert res is _lib.I and args == want and len(args) == 18
-    assert "single frames in the episode store" in header
+    abi.assert_prototype(NAME)
+    assert len(_lib.PROTOTYPES[NAME][1]) == 18
+    assert "single frames in the episode store" in abi.text()
     with open(os.path.join(ROOT, "drqv2_amd", "csrc", "step.hip")) as f:
         assert "drq_abi_version(void) { return 7; }" in f.read()        # additive: the version stays
     with open(os.path.join(ROOT, "drqv2_amd", "csrc", "vecframes.hip")) as f:

@@ -2,14 +2,13 @@
 drq_vec_export_rows, drq_vec_fill): everything that needs no GPU.  The two host plans on hand-built rings, to the entry;
 the checks add_episodes() makes before any launch; the new entries in the header, the prototype table and the build list."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 from drqv2_amd import _lib
+from tests import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drq_vec_export_rows", "drq_vec_fill")
 R, N = 12, 3
 
@@ -272,24 +271,11 @@ def test_add_episodes_reads_a_directory_oldest_first(tmp_path):
 
 # ------------------------------------------------------------------------------------------------ the ABI lists
 def test_header_prototypes_and_build_list():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
     for name in NEW:
-        assert name in _lib.PROTOTYPES, name
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            if "*" in prm or prm.startswith("drq_stream_t"):
-                want.append(_lib.P)
-            else:
-                want.append({"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want, name
+        abi.assert_prototype(name)
     from drqv2_amd import build
     assert "vecepisodes.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "vecepisodes.hip"))
-    assert "episode files for the step-major ring" in header
+    assert "episode files for the step-major ring" in abi.text()
 
 
 def test_refusals_need_no_gpu():

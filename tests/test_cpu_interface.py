@@ -226,6 +226,77 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.drq_conv3x3_fwd(None, None, None, None, 1, 9, 84, 2, 1, 1, 1, 1, 0, None) == -1
 
 
+def test_every_prototype_is_its_declaration():
+    """restype and every argtype of every entry of _lib.PROTOTYPES against include/drqv2_hip.h (tests/abi.py holds the
+    mapping); with the set equality above nothing is left uncompared"""
+    from drqv2_amd import _lib
+    from tests import abi
+    assert len(abi.declarations()) > 90
+    for name in abi.declarations():
+        abi.assert_prototype(name)
+    # launch() tells a stream entry from the rest by this list
+    assert _lib.NO_STREAM == set(abi.declarations()) - abi.stream_entries()
+
+
+def test_descriptor_enums_and_layout_length_are_the_headers():
+    from drqv2_amd import _lib
+    from tests import abi
+    fields = abi.struct_fields("DrqStep")
+    assert [f for f, _ in _lib.DrqStep._fields_] == [f for f, _ in fields]
+    for (name, ctype), (_, allowed) in zip(_lib.DrqStep._fields_, fields):
+        assert ctype in allowed, f"DrqStep.{name} is {ctype}, the header says {allowed}"
+    enums = abi.enumerators()
+    ws = {k[len("DRQ_WS_"):]: v for k, v in enums.items() if k.startswith("DRQ_WS_")}
+    assert ws.pop("NBUF_PUBLIC") == len(_lib.WS_IDS)
+    assert ws == {name: i for i, name in enumerate(_lib.WS_IDS)}
+    phases = {k[len("DRQ_"):]: v for k, v in enums.items() if k.startswith("DRQ_PHASE_")}
+    assert phases and phases == {k: v for k, v in vars(_lib).items() if k.startswith("PHASE_")}
+    assert _lib.PARAM_LAYOUT_LEN == abi.define("DRQ_PARAM_LAYOUT_LEN")
+
+
+@pytest.fixture
+def no_stream(monkeypatch):
+    """launch() without a GPU: the stream lookup gives the null stream"""
+    from drqv2_amd import _lib
+    monkeypatch.setattr(_lib, "current_stream", lambda: None)
+    return _lib
+
+
+def test_launch_checks_the_status_and_names_the_entry(no_stream):
+    _lib = no_stream
+    # the library refuses before any launch (tests/test_cpu_vec_eval.py relies on the same)
+    with pytest.raises(_lib.DrqError, match="drq_vec_stack_push.*DRQ_EARG"):
+        _lib.launch("drq_vec_stack_push", None, None, None, None, 1, 1)
+
+
+@pytest.mark.parametrize("name", ["drq_no_such_entry", "drq_param_layout"])
+def test_launch_takes_stream_entries_only(no_stream, monkeypatch, name):
+    _lib = no_stream
+    monkeypatch.setattr(_lib, "load", lambda: pytest.fail("launch() reached the library"))
+    with pytest.raises(_lib.DrqError, match=name):
+        _lib.launch(name, 9, 6, 50, 1024, None, 0)
+
+
+@pytest.mark.parametrize("kw,entry", [({}, "drq_conv1_aug_fwd"), ({"bf16": True}, "drq_conv1_aug_fwd_bf16"),
+                                      ({"bf16": True, "y_nhwc": True}, "drq_conv1_aug_fwd_bf16_nhwc")])
+def test_conv1_aug_fwd_names_the_entry_it_called(no_stream, monkeypatch, kw, entry):
+    from drqv2_amd import ops
+    _lib, called = no_stream, []
+
+    class Stub:
+        def __getattr__(self, name):
+            assert name.startswith("drq_conv1_aug_fwd"), name
+            return lambda *args: called.append(name) or -1
+
+    monkeypatch.setattr(_lib, "load", Stub)
+    monkeypatch.setattr(ops, "_need", lambda t, *a, **k: t)     # the wrapper's own rule: GPU tensors only
+    obs = torch.zeros((1, 9, 84, 84), dtype=torch.uint8)
+    w, b, shift = torch.zeros(32, 9, 3, 3), torch.zeros(32), torch.zeros(1, 2)
+    with pytest.raises(_lib.DrqError, match=entry + ":"):
+        ops.conv1_aug_fwd(obs, shift, obs, shift, w, b, **kw)
+    assert called == [entry]
+
+
 def test_config_surface_matches_reference_yaml():
     from drqv2_amd import tasks
     with open(os.path.join(G, "cfg_surface.json")) as f:

@@ -4,13 +4,13 @@ and flags, exported symbols, ABI version), the DRQ_EARG cases that are decided b
 errors and the CPU refusal of the class."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from drqv2_amd import _lib
+from tests import abi
 from tests import vec_env_oracle as E
 from tests import vec_render_oracle as VR
 
@@ -134,20 +134,11 @@ def test_replicated_image_and_its_area_average():
 
 # ------------------------------------------------------------------------------------------------ public surface
 def test_header_prototypes_build_list_symbols_and_abi_version():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
+    header = abi.text()
     assert "device environment" in header
-    ctype = {"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D, "unsigned": ctypes.c_uint}
     for name, nargs in NAMES.items():
-        assert name in _lib.PROTOTYPES, f"{name} has no prototype"
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            want.append(_lib.P if "*" in prm or prm.startswith("drq_stream_t") else ctype[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want and len(args) == nargs, name
+        abi.assert_prototype(name)
+        assert len(_lib.PROTOTYPES[name][1]) == nargs, name
     for text in ("fmix32(seed ^ e * 0x9E3779B9 ^ episode * 0x85EBCA6B ^ k * 0xC2B2AE35)", "d2 <= 0.01f",
                  "(int)floorf((x + 1) * 41.5f + 0.5f)", "32 + ((i + j) >> 2)"):
         assert text in header, text                                        # the task is part of the contract

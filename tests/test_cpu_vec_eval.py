@@ -1,9 +1,7 @@
 """Evaluation for the vectorised loop without a GPU: the prototypes of the two entries against the header, the stack
 oracle against the FrameStackWrapper and the ring's observation() oracle, the animated PNG writer and reader, and every
 argument error of drqv2_amd.evaluate.  All comparisons are exact (integers)."""
-import ctypes as C
 import os
-import re
 import struct
 import zlib
 
@@ -11,40 +9,18 @@ import numpy as np
 import pytest
 import torch
 
+from tests import abi
 from tests import vec_eval_oracle as EO
 from tests import vec_frames_oracle as FO
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("drq_vec_stack_push", "drq_vec_video_record")
-
-
-def header_argtypes(name):
-    """the ctypes argument types of a declaration of include/drqv2_hip.h"""
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        hdr = f.read()
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, f"{name} is not declared in the header"
-    out = []
-    for arg in m.group(1).split(","):
-        arg = " ".join(arg.split())
-        if "*" in arg or arg.startswith("drq_stream_t"):
-            out.append(C.c_void_p)
-        elif arg.startswith("long "):
-            out.append(C.c_long)
-        elif arg.startswith("int "):
-            out.append(C.c_int)
-        else:
-            raise AssertionError(f"{name}: argument {arg!r}")
-    return out
 
 
 def test_the_new_entries_are_declared_and_prototyped():
     from drqv2_amd import _lib, build, ops
     assert "veceval.hip" in build.SOURCES
     for name in NAMES:
-        assert name in _lib.PROTOTYPES, f"{name} is missing from _lib.PROTOTYPES"
-        res, args = _lib.PROTOTYPES[name]
-        assert res is C.c_int and args == header_argtypes(name), name
+        abi.assert_prototype(name)
     assert callable(ops.vec_stack_push) and callable(ops.vec_video_record)
     lib = _lib.load()
     # argument errors are reported before anything is launched: no GPU needed

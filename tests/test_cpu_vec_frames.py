@@ -3,38 +3,24 @@ drq_update_phase_frames): everything that needs no GPU.  The public surface, the
 against its restatement of the reference's FrameStackWrapper on random flag streams, bounds() and the constructor's
 validation, and the argument errors the library reports before any launch."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from drqv2_amd import _lib
+from tests import abi
 from tests import vec_frames_oracle as VF
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drq_vec_stack_gather", "drq_conv1_aug_fwd_frames", "drq_conv1_aug_fwd_frames_bf16", "drq_update_phase_frames")
 
 
 def test_header_prototypes_and_build_list():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
     for name in NEW:
-        assert name in _lib.PROTOTYPES, name
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            if "*" in prm or prm.startswith("drq_stream_t"):
-                want.append(_lib.C.POINTER(_lib.DrqStep) if "DrqStep" in prm else _lib.P)
-            else:
-                want.append({"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want, name
+        abi.assert_prototype(name)
     from drqv2_amd import build
     assert "vecframes.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "vecframes.hip"))
-    assert "single-frame step-major replay" in header
+    assert "single-frame step-major replay" in abi.text()
 
 
 # ------------------------------------------------------------------------------------------------ the slot rule

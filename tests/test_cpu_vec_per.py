@@ -3,12 +3,12 @@ _update): everything that needs no GPU.  The public surface (header, prototype t
 errors of the three entries and of the constructor, and the numpy restatement tests/vec_per_oracle.py on its own: the
 invariant of the tree through three wraps of the ring, the recovery of a row from its slot, the uniform limit of the draw."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 from drqv2_amd import _lib
+from tests import abi
 from tests import per_oracle as P
 from tests import vec_oracle as V
 from tests import vec_per_oracle as VP
@@ -20,21 +20,8 @@ EARG = -1
 
 # ------------------------------------------------------------------------------------------------ public surface
 def test_header_prototypes_exports_and_abi_version():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
     for name in NEW:
-        assert name in _lib.PROTOTYPES, name
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            if "*" in prm or prm.startswith("drq_stream_t"):
-                want.append(_lib.P)
-            else:
-                want.append({"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want, name
+        abi.assert_prototype(name)
     with open(os.path.join(ROOT, "drqv2_amd", "csrc", "step.hip")) as f:
         assert "drq_abi_version(void) { return 7; }" in f.read()        # additive: the version stays
     lib = _lib.load()

@@ -4,13 +4,13 @@ exported symbol, ABI version), the DRQ_EARG cases that are decided before any la
 refusal of the store."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from drqv2_amd import _lib
+from tests import abi
 from tests import vec_render_oracle as VR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,20 +99,9 @@ def test_oracle_equals_a_float64_area_average_where_that_is_exact():
 
 # ------------------------------------------------------------------------------------------------ public surface
 def test_header_prototype_build_list_symbol_and_abi_version():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
-    assert NAME in _lib.PROTOTYPES, f"{NAME} has no prototype"
-    m = re.search(r"\bint " + NAME + r"\((.*?)\);", header, re.S)
-    assert m, f"{NAME} is not declared in the header"
-    want = []
-    for prm in m.group(1).split(","):
-        prm = " ".join(prm.split())
-        if "*" in prm or prm.startswith("drq_stream_t"):
-            want.append(_lib.P)
-        else:
-            want.append({"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}[prm.split()[0]])
-    res, args = _lib.PROTOTYPES[NAME]
-    assert res is _lib.I and args == want and len(args) == 17
+    header = abi.text()
+    abi.assert_prototype(NAME)
+    assert len(_lib.PROTOTYPES[NAME][1]) == 17
     for text in ("w(o, i) = max(0, min(S (o+1), 84 (i+1)) - max(S o, 84 i))", "< 2^31", "round half up"):
         assert text in header, text                                        # the rule is part of the contract
     with open(os.path.join(ROOT, "drqv2_amd", "csrc", "step.hip")) as f:

@@ -3,7 +3,6 @@
 arithmetic, its candidate choice, and its windows against oracle.nstep_sample on columns built by hand -- and the
 argument errors and the CPU refusal of the store."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 
 from drqv2_amd import _lib
 from oracle import drq_oracle as O
+from tests import abi
 from tests import vec_oracle as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,21 +19,8 @@ NEW = ("drq_vec_add", "drq_vec_sample")
 
 # ------------------------------------------------------------------------------------------------ public surface
 def test_header_prototypes_build_list_and_abi_version():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
     for name in NEW:
-        assert name in _lib.PROTOTYPES, name
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            if "*" in prm or prm.startswith("drq_stream_t"):
-                want.append(_lib.P)
-            else:
-                want.append({"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D}[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want, name
+        abi.assert_prototype(name)
     with open(os.path.join(ROOT, "drqv2_amd", "csrc", "step.hip")) as f:
         assert "drq_abi_version(void) { return 7; }" in f.read()        # additive: the version stays
     if os.path.exists(_lib.LIB_PATH):

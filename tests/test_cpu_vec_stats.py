@@ -4,37 +4,25 @@ book-keeping loop (train.py:133,186,189), its edge cases, the class's validation
 library reports before any launch."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from drqv2_amd import _lib
+from tests import abi
 from tests.vec_stats_oracle import StatsOracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drq_vec_stats_step", "drq_vec_stats_publish", "drq_vec_stats_reset")
 EARG = -1
 
 
 def test_header_prototypes_and_build_list():
-    with open(os.path.join(ROOT, "include", "drqv2_hip.h")) as f:
-        header = f.read()
-    kinds = {"int": _lib.I, "long": _lib.L, "float": _lib.F, "double": _lib.D, "unsigned": _lib.C.c_uint}
     for name in NEW:
-        assert name in _lib.PROTOTYPES, name
-        m = re.search(r"\bint " + name + r"\((.*?)\);", header, re.S)
-        assert m, f"{name} is not declared in the header"
-        want = []
-        for prm in m.group(1).split(","):
-            prm = " ".join(prm.split())
-            want.append(_lib.P if "*" in prm or prm.startswith("drq_stream_t") else kinds[prm.split()[0]])
-        res, args = _lib.PROTOTYPES[name]
-        assert res is _lib.I and args == want, name
+        abi.assert_prototype(name)
     from drqv2_amd import build
     assert "vecstats.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "vecstats.hip"))
-    assert "episode statistics" in header
+    assert "episode statistics" in abi.text()
 
 
 # ------------------------------------------------------------------------------------------------ oracle against train.py

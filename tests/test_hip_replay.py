@@ -154,3 +154,41 @@ def test_indexed_batches_without_metrics_reads_host_running_ahead():
         outs.append((eng.params.clone(), eng.adam_m.clone(), eng.adam_v.clone()))
     for x, y in zip(*outs):
         assert torch.equal(x, y)
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.uint8).cpu()
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="a store on a device that is not the current one needs two devices")
+def test_store_on_another_device_launches_there():
+    """A DeviceReplay on cuda:1 while cuda:0 is the current device: gather(), gather_indexed(), sample_prioritized()
+    and FrameBatch.materialize() give, bit for bit, what the same calls give with cuda:1 current, and the current device
+    is left alone (every launch of the store makes the store's device current for itself: _lib.launch)."""
+    from drqv2_amd.replay import DeviceReplay, FrameBatch
+    A, nstep, B = 3, 3, 8
+    rp = DeviceReplay(40, OBS, A, nstep, 0.99, "cuda:1", seed=9, indexed=True, priority_alpha=0.6)
+    sf = DeviceReplay(40, OBS, A, nstep, 0.99, "cuda:1", seed=9, indexed=True, single_frames=True)
+
+    def calls(pos):
+        rp.rng.seed(5)
+        drawn = rp.sample_prioritized(B)
+        frames = sf.gather_indexed(pos)
+        assert isinstance(frames, FrameBatch)
+        groups = (rp.gather(pos), tuple(rp.gather_indexed(pos)), tuple(drawn) + (drawn.weights, drawn._pos),
+                  frames.materialize())
+        return [_bits(t) for g in groups for t in g]          # copies: the stores reuse their buffers
+
+    with torch.cuda.device(0):
+        for i, T in enumerate((5, 9, 7)):
+            e = episode(T, A, seed=40 + i)
+            rp.add_episode(e)
+            sf.add_episode(dict(e, observation=np.ascontiguousarray(e["observation"][:, :3])))
+        pos = rp.draw_positions(B)
+        got = calls(pos)
+        assert torch.cuda.current_device() == 0
+    with torch.cuda.device(1):
+        want = calls(pos)
+    assert len(got) == len(want) == 5 + 5 + 7 + 5
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g.numel() > 0 and torch.equal(g, w), k
