@@ -113,6 +113,7 @@ PROTOTYPES = {
     "drq_vec_stats_publish": (I, [P, P, P, P, P, L, P, C.c_uint, P]),
     "drq_vec_stats_reset": (I, [P, P, P, P, P, P, P, P, L, L, P]),
     "drq_vec_reach_step": (I, [P, P, P, P, P, L, I, P, C.c_uint, I, I, P, P, P, P, P]),
+    "drq_vec_task_step": (I, [I, P, P, P, P, P, P, L, I, P, C.c_uint, I, I, I, P, P, P, P, P, P]),
     "drq_vec_reach_render": (I, [P, P, L, P, P]),
     "drq_vec_reach_image": (I, [P, P, L, I, I, P]),
     "drq_vec_stack_push": (I, [P, P, P, P, L, I, P]),

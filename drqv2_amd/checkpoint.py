@@ -11,7 +11,8 @@ for a seed, so the state is all there is to keep:
              priority tree and priority_beta
   iterator   BatchIterator.state_dict(): the one batch of look-ahead, which was drawn BEFORE the save and has consumed its
              random numbers
-  env        VecReach.state_dict(): seven words per environment; the frames are drawn again from them
+  env        VecReach / VecPointMass.state_dict(): the task, action_repeat and the state words of every environment (seven;
+             nine with the point mass's velocity); the frames are drawn again from them
   stats      VecEpisodeStats.state_dict(): the running returns and lengths, the totals and the log
   rng        torch.get_rng_state() and torch.cuda.get_rng_state(device): update()'s draws and act_batch()'s noise
 

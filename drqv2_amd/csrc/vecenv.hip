@@ -5,9 +5,16 @@
 // VecEpisodeStats.step() take -- the 3 x 84 x 84 frame, reward, discount and first of every environment -- and is
 // deterministic to the bit (tests/vec_env_oracle.py restates it in numpy).  It is no benchmark task.
 //
-// drq_vec_reach_step is one launch of N workgroups of 256 threads, one per environment:
-//   state     every thread loads the seven state words of its environment and computes the reset or the step itself, in
-//             registers -- the same IEEE operations on the same operands in every lane, so all 256 agree
+// A second task, "pointmass", shares the square, the reset draws, the reward and the frame, and gives the point a velocity
+// that no single frame shows: the smallest task that needs the three-frame stack.  drq_vec_task_step steps either task
+// with `repeat` sub-steps per launch (the ActionRepeatWrapper of dmc.py:35-50, inside the launch: lockstep environments
+// cannot be wrapped from outside, since one that ends inside a repeat must stop there); drq_vec_reach_step is the same
+// kernel with task reach and repeat 1.
+//
+// Either step entry is one launch of N workgroups of 256 threads, one per environment:
+//   state     every thread loads the seven (point mass: nine) state words of its environment and computes the reset or
+//             the macro step itself, in registers -- the same IEEE operations on the same operands in every lane, so all
+//             256 agree, on the trip count of the sub-step loop too
 //   barrier   __syncthreads(): every lane has read the old state before thread 0 stores the new one and the three scalars
 //   frame     1,323 pieces of 16 bytes, 5 or 6 per lane, consecutive lanes consecutive pieces.  A lane decodes (c, i, j)
 //             from its flat offset once (7,056 = 441 x 16: a piece never crosses a channel plane; 84 = 5 x 16 + 4: it may
@@ -82,9 +89,10 @@ __device__ __forceinline__ void reach_frame(float px, float py, float tx, float 
   }
 }
 
-struct ReachArgs {
+struct TaskArgs {
   float* pos;             // [N][2]
   float* target;          // [N][2]
+  float* vel;             // [N][2]; the point mass only (null for reach)
   int* t;
   unsigned* episode;
   uint8_t* over;
@@ -93,18 +101,29 @@ struct ReachArgs {
   float* reward;
   float* discount;
   uint8_t* first;
+  int* substeps;          // [N]; null from drq_vec_reach_step, which has no such output
   unsigned seed;
-  int A, episode_length, reset_all;
+  int task, A, episode_length, repeat, reset_all;
 };
 
-__global__ __launch_bounds__(kThreads) void vec_reach_step_kernel(ReachArgs a) {
+// One macro step of every environment: the reset row, or up to `repeat` sub-steps of the task folded by the wrapper rule
+// (dmc.py:40-50).  task, repeat and reset_all are launch arguments and the state is the workgroup's own, so every branch
+// and the trip count of the loop are uniform across the 256 lanes.
+__global__ __launch_bounds__(kThreads) void vec_task_step_kernel(TaskArgs a) {
   const long e = blockIdx.x;
+  const bool mass = a.task == DRQ_TASK_POINTMASS;
   float px = a.pos[2 * e], py = a.pos[2 * e + 1], tx = a.target[2 * e], ty = a.target[2 * e + 1];
+  float vx = 0.0f, vy = 0.0f;
+  if (mass) {
+    vx = a.vel[2 * e];
+    vy = a.vel[2 * e + 1];
+  }
   int t = a.t[e];
   unsigned episode = a.episode[e];
   unsigned over = a.over[e];
   float reward = 0.0f, discount = 1.0f;
   unsigned first;
+  int n = 0;
   if (a.reset_all || over) {
     episode += 1u;
     t = 0;
@@ -113,24 +132,56 @@ __global__ __launch_bounds__(kThreads) void vec_reach_step_kernel(ReachArgs a) {
     py = reach_draw(a.seed, (unsigned)e, episode, 1u);
     tx = reach_draw(a.seed, (unsigned)e, episode, 2u);
     ty = reach_draw(a.seed, (unsigned)e, episode, 3u);
+    vx = vy = 0.0f;
     first = 1u;
   } else {
     float ax = a.action[e * a.A], ay = a.action[e * a.A + 1];
     ax = ax != ax ? 0.0f : clamp1(ax);
     ay = ay != ay ? 0.0f : clamp1(ay);
-    px = clamp1(px + ax * 0.1f);
-    py = clamp1(py + ay * 0.1f);
-    t += 1;
-    const float dx = px - tx, dy = py - ty;
-    const float d2 = dx * dx + dy * dy;
-    const float r = 1.0f - d2;
-    reward = r > 0.0f ? r : 0.0f;
-    if (d2 <= 0.01f) {
-      discount = 0.0f;
-      over = 1u;
-    } else if (t == a.episode_length) {
-      over = 1u;
-    }
+    do {
+      float d = 1.0f;
+      if (mass) {
+        vx = vx * 0.9f;
+        vy = vy * 0.9f;
+        vx = vx + ax * 0.02f;
+        vy = vy + ay * 0.02f;
+        const float qx = px + vx, qy = py + vy;
+        if (qx < -1.0f) {
+          px = -1.0f;
+          vx = 0.0f;
+        } else if (qx > 1.0f) {
+          px = 1.0f;
+          vx = 0.0f;
+        } else {
+          px = qx;
+        }
+        if (qy < -1.0f) {
+          py = -1.0f;
+          vy = 0.0f;
+        } else if (qy > 1.0f) {
+          py = 1.0f;
+          vy = 0.0f;
+        } else {
+          py = qy;
+        }
+      } else {
+        px = clamp1(px + ax * 0.1f);
+        py = clamp1(py + ay * 0.1f);
+      }
+      t += 1;
+      const float dx = px - tx, dy = py - ty;
+      const float d2 = dx * dx + dy * dy;
+      float r = 1.0f - d2;
+      r = r > 0.0f ? r : 0.0f;
+      if (!mass && d2 <= 0.01f) {
+        d = 0.0f;
+        over = 1u;
+      } else if (t == a.episode_length) {
+        over = 1u;
+      }
+      reward = reward + r * discount;
+      discount = discount * d;
+    } while (++n < a.repeat && !over);
     first = 0u;
   }
   __syncthreads();            // every lane holds the old state: thread 0 may now replace it
@@ -139,15 +190,33 @@ __global__ __launch_bounds__(kThreads) void vec_reach_step_kernel(ReachArgs a) {
     a.pos[2 * e + 1] = py;
     a.target[2 * e] = tx;
     a.target[2 * e + 1] = ty;
+    if (mass) {
+      a.vel[2 * e] = vx;
+      a.vel[2 * e + 1] = vy;
+    }
     a.t[e] = t;
     a.episode[e] = episode;
     a.over[e] = (uint8_t)over;
     a.reward[e] = reward;
     a.discount[e] = discount;
     a.first[e] = (uint8_t)first;
+    if (a.substeps) a.substeps[e] = n;
   }
 
   reach_frame(px, py, tx, ty, a.frame + e * (long)kFrame);
+}
+
+// the checks both step entries share; vel and substeps are checked by drq_vec_task_step itself
+int step_args_ok(const TaskArgs& a, long N) {
+  if (!a.pos || !a.target || !a.t || !a.episode || !a.over || !a.frame || !a.reward || !a.discount || !a.first) return 0;
+  if (N < 1 || N > INT32_MAX || a.A < 2 || a.episode_length < 1) return 0;
+  if (a.reset_all != 0 && a.reset_all != 1) return 0;
+  if (!a.action && !a.reset_all) return 0;
+  if ((uintptr_t)a.frame & 15) return 0;
+  if (((uintptr_t)a.pos | (uintptr_t)a.target | (uintptr_t)a.t | (uintptr_t)a.episode | (uintptr_t)a.reward |
+       (uintptr_t)a.discount | (uintptr_t)a.action) & 3)
+    return 0;
+  return 1;
 }
 
 // the frames of the states as they are: the frame part of the step kernel alone, same launch shape
@@ -199,16 +268,27 @@ void launch_image(int C, dim3 grid, hipStream_t st, const uint8_t* frame, uint8_
 DRQ_API int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
                                const float* action, unsigned seed, int episode_length, int reset_all, uint8_t* frame,
                                float* reward, float* discount, uint8_t* first, drq_stream_t stream) {
-  if (!pos || !target || !t || !episode || !over || !frame || !reward || !discount || !first) return DRQ_EARG;
-  if (N < 1 || N > INT32_MAX || A < 2 || episode_length < 1) return DRQ_EARG;
-  if (reset_all != 0 && reset_all != 1) return DRQ_EARG;
-  if (!action && !reset_all) return DRQ_EARG;
-  if ((uintptr_t)frame & 15) return DRQ_EARG;
-  if (((uintptr_t)pos | (uintptr_t)target | (uintptr_t)t | (uintptr_t)episode | (uintptr_t)reward | (uintptr_t)discount |
-       (uintptr_t)action) & 3)
-    return DRQ_EARG;
-  ReachArgs a{pos, target, t, episode, over, action, frame, reward, discount, first, seed, A, episode_length, reset_all};
-  hipLaunchKernelGGL(vec_reach_step_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, a);
+  TaskArgs a{pos,      target, nullptr, t,    episode,        over, action,         frame, reward,
+             discount, first,  nullptr, seed, DRQ_TASK_REACH, A,    episode_length, 1,     reset_all};
+  if (!step_args_ok(a, N)) return DRQ_EARG;
+  hipLaunchKernelGGL(vec_task_step_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, a);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_vec_task_step(int task, float* pos, float* target, float* vel, int* t, unsigned* episode, uint8_t* over,
+                              long N, int A, const float* action, unsigned seed, int episode_length, int repeat,
+                              int reset_all, uint8_t* frame, float* reward, float* discount, uint8_t* first, int* substeps,
+                              drq_stream_t stream) {
+  if (task != DRQ_TASK_REACH && task != DRQ_TASK_POINTMASS) return DRQ_EARG;
+  if (repeat < 1 || repeat > DRQ_TASK_MAX_REPEAT || !substeps) return DRQ_EARG;
+  if (task == DRQ_TASK_POINTMASS && !vel) return DRQ_EARG;
+  if (task == DRQ_TASK_REACH) vel = nullptr;          // reach has no velocity: the array is neither read nor written
+  if (((uintptr_t)vel | (uintptr_t)substeps) & 3) return DRQ_EARG;
+  TaskArgs a{pos,      target, vel,      t,    episode, over, action,         frame,  reward,
+             discount, first,  substeps, seed, task,    A,    episode_length, repeat, reset_all};
+  if (!step_args_ok(a, N)) return DRQ_EARG;
+  hipLaunchKernelGGL(vec_task_step_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, a);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }

@@ -2,10 +2,13 @@
 host, dmc.py / train.py:160-190).
 
 VecReach is the producer the device-side collection path was missing: N lockstep environments of a small pixel task
-("reach": a point in a square must reach a target) stepped by ONE launch (csrc/vecenv.hip, drq_vec_reach_step) that writes
+("reach": a point in a square must reach a target) stepped by ONE launch (csrc/vecenv.hip, drq_vec_task_step) that writes
 what VecFrameReplay.add(), add_render() and VecEpisodeStats.step() take -- uint8 [N, 3, 84, 84] frames, reward, discount
-and first -- as device tensors on the current stream.  The task is specified to the bit in include/drqv2_hip.h ("device
-environment") and restated in numpy by tests/vec_env_oracle.py.  It is not a benchmark task and says nothing about DMC.
+and first -- as device tensors on the current stream.  VecPointMass is the same square with momentum: the action
+accelerates the point, and its velocity is in no single frame, so it is the one task here that needs the three-frame
+stack.  Both take action_repeat (the ActionRepeatWrapper of dmc.py:35-50, inside the launch).  The tasks are specified to
+the bit in include/drqv2_hip.h ("device environment") and restated in numpy by tests/vec_env_oracle.py and
+tests/vec_tasks_oracle.py.  They are not benchmark tasks and say nothing about DMC.
 """
 import torch
 
@@ -14,33 +17,51 @@ from ._lib import launch, ptr
 from .checkpoint import check_state, host
 
 
-class VecReach:
-    """N environments of the reach task on the device.
+MAX_ACTION_REPEAT = 16        # DRQ_TASK_MAX_REPEAT
 
-        env = VecReach(num_envs=N, device="cuda", action_dim=A, episode_length=250, seed=0)
+
+class _VecTask:
+    """What the device environments share: everything but the task's name, its id in the library and its state arrays.
+
+        env = VecReach(num_envs=N, device="cuda", action_dim=A, episode_length=250, seed=0, action_repeat=1)
         frame = env.reset()                                   # uint8 [N, 3, 84, 84]
         frame, reward, discount, first = env.step(action)     # action float32 [N, A] on the device
 
+    action_repeat = K (1 .. 16) makes step() a macro step of up to K simulator steps under the one action, inside the
+    launch: reward = sum of r_i times the running product of the discounts before it, discount = their product, and an
+    environment whose episode ends inside the repeat stops there (dmc.py:40-50).  t and episode_length count simulator
+    steps, as in DMC; a row of the ring or of VecEpisodeStats is one step() call.  last_substeps is the int32 [N] device
+    tensor of the simulator steps the newest step() / reset() took per environment (0 on a reset row), from the same two
+    rotating output sets as the rest.
+
     Per environment: pos and target in [-1, 1]^2, t (steps of this episode), episode (a counter), over (the last step
-    ended the episode).  step() moves pos by clamp(action[:, :2], -1, 1) * 0.1 (NaN counts as 0; further columns are
-    ignored), reward = max(0, 1 - |pos - target|^2); |pos - target|^2 <= 0.01 ends the episode with discount 0 (reached),
-    t == episode_length with discount 1 (the time limit).  The step() AFTER one that ended the episode is the reset row
+    ended the episode).  A simulator step of reach (VecPointMass states its own) moves pos by clamp(action[:, :2], -1, 1)
+    * 0.1 (NaN counts as 0; further columns are ignored), reward = max(0, 1 - |pos - target|^2); |pos - target|^2 <= 0.01
+    ends the episode with discount 0 (reached), t == episode_length with discount 1 (the time limit).  The step() AFTER one
+    that ended the episode is the reset row
     of that environment: first = 1, reward 0, discount 1, the first frame of a new episode whose positions are a hash of
     (seed, environment, episode); its action is ignored.  So resets are staggered across the environments, as the rings
     and the statistics expect them.  Everything is deterministic to the bit for a seed and a sequence of actions.
 
     Every return is a device tensor written by a launch on the current stream; nothing waits for the GPU.  step() and
-    reset() write into TWO output sets (frame, reward, discount, first) used in turn, as VecFrameReplay.observation()
+    reset() write into TWO output sets (frame, reward, discount, first, substeps) used in turn, as VecFrameReplay.observation()
     does: a returned tensor is overwritten by the second step() / reset() / render() call after it, so a caller that
     keeps one longer clones it.  image() rotates two buffers per (size, channels) in the same way.
 
-    Checkpoints: state_dict() / load_state_dict() save and restore the seven state words per environment; the frames are
-    derived data and are drawn again from the restored state (render(): drq_vec_reach_render, one launch)."""
+    Checkpoints: state_dict() / load_state_dict() save and restore the state words of every environment (seven for
+    reach, nine with the point mass's velocity); the frames are derived data and are drawn again from the restored state
+    (render(): drq_vec_reach_render, one launch)."""
 
     FRAME_SHAPE = (3, 84, 84)
     IMAGE_SIZES = (84, 168, 252, 336)
+    TASK = TASK_ID = None       # the name in state dicts and tools; DRQ_TASK_* of include/drqv2_hip.h
+    _STATE = ("pos", "target", "t", "episode", "over")
 
-    def __init__(self, num_envs, device, action_dim=2, episode_length=250, seed=0):
+    def __init__(self, num_envs, device, action_dim=2, episode_length=250, seed=0, action_repeat=1):
+        if isinstance(action_repeat, bool) or not isinstance(action_repeat, int) \
+                or not 1 <= action_repeat <= MAX_ACTION_REPEAT:
+            raise ValueError(f"action_repeat must be an int in 1 .. {MAX_ACTION_REPEAT}, got {action_repeat!r}")
+        self.action_repeat = action_repeat
         self.N, self.A, self.episode_length = int(num_envs), int(action_dim), int(episode_length)
         if self.N < 1 or self.A < 2 or self.episode_length < 1:
             raise ValueError("num_envs and episode_length must be >= 1, action_dim >= 2")
@@ -52,7 +73,9 @@ class VecReach:
         self.t = torch.zeros(N, dtype=torch.int32, device=dev)
         self.episode = torch.zeros(N, dtype=torch.int32, device=dev)       # uint32 on the device: state() views it so
         self.over = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._out = None            # two of (frame, reward, discount, first), then the index of the next
+        self.vel = torch.zeros((N, 2), dtype=torch.float32, device=dev) if "vel" in self._STATE else None
+        self.last_substeps = None   # int32 [N] of the newest step() / reset()
+        self._out = None            # two of (frame, reward, discount, first, substeps), then the index of the next
         self._frame = None          # the frames of the newest step() / reset()
         self._images = {}           # (size, channels) -> [buffer, buffer, index of the next]
 
@@ -79,12 +102,13 @@ class VecReach:
         return action.contiguous()
 
     def _next_out(self):
-        """the output set (frame, reward, discount, first) the next launch writes"""
+        """the output set (frame, reward, discount, first, substeps) the next launch writes"""
         if self._out is None:
             dev, N = self.device, self.N
             self._out = [(torch.empty((N,) + self.FRAME_SHAPE, dtype=torch.uint8, device=dev),
                           torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev),
-                          torch.empty(N, dtype=torch.uint8, device=dev)) for _ in range(2)] + [0]
+                          torch.empty(N, dtype=torch.uint8, device=dev),
+                          torch.empty(N, dtype=torch.int32, device=dev)) for _ in range(2)] + [0]
         out = self._out[self._out[2]]
         self._out[2] ^= 1
         return out
@@ -92,13 +116,13 @@ class VecReach:
     def _launch(self, action, reset_all):
         out = self._next_out()
         with torch.cuda.device(self.device):
-            launch("drq_vec_reach_step", ptr(self.pos), ptr(self.target), ptr(self.t), ptr(self.episode),
-                   ptr(self.over), self.N, self.A, ptr(action), self.seed, self.episode_length, int(reset_all),
-                   *(ptr(o) for o in out), device=self.device)
+            launch("drq_vec_task_step", self.TASK_ID, ptr(self.pos), ptr(self.target), ptr(self.vel), ptr(self.t),
+                   ptr(self.episode), ptr(self.over), self.N, self.A, ptr(action), self.seed, self.episode_length,
+                   self.action_repeat, int(reset_all), *(ptr(o) for o in out), device=self.device)
             if action is not None:  # a caller's tensor may be freed right after step(): the launch still reads it
                 action.record_stream(torch.cuda.current_stream())
-        self._frame = out[0]
-        return out
+        self._frame, self.last_substeps = out[0], out[4]
+        return out[:4]
 
     def reset(self):
         """Starts a new episode in every environment (one launch) and returns its first frames, uint8 [N, 3, 84, 84].  The
@@ -154,39 +178,61 @@ class VecReach:
 
     def state(self):
         """Host copies of the state, for tests and debugging: {"pos": float32 [N, 2], "target": float32 [N, 2], "t": int32
-        [N], "episode": uint32 [N], "over": uint8 [N]}.  This SYNCHRONISES: the copies wait for every launch enqueued so
-        far.  Nothing in a collection loop should call it."""
+        [N], "episode": uint32 [N], "over": uint8 [N]}, and "vel": float32 [N, 2] for the point mass.  This SYNCHRONISES:
+        the copies wait for every launch enqueued so far.  Nothing in a collection loop should call it."""
         import numpy as np
-        s = {k: getattr(self, k).cpu().numpy() for k in ("pos", "target", "t", "episode", "over")}
+        s = {k: getattr(self, k).cpu().numpy() for k in self._STATE}
         s["episode"] = s["episode"].view(np.uint32)
         return s
 
     # ---- checkpoints ---------------------------------------------------------------------
-    _STATE = ("pos", "target", "t", "episode", "over")
+    def _config(self):
+        return {"N": self.N, "A": self.A, "episode_length": self.episode_length, "seed": self.seed, "task": self.TASK,
+                "action_repeat": self.action_repeat}
 
     def state_dict(self):
         """The environment as a plain dict of CPU tensors and Python scalars: "format": 1, "kind", the configuration (N,
-        A, episode_length, seed) and the seven state words per environment (pos, target, t, episode, over; episode as the
-        int32 tensor that holds its uint32 bits).  The newest frames are not in it: they are a function of the state.  This SYNCHRONISES the environment's device, like
-        state(): the copies wait for every launch enqueued so far."""
+        A, episode_length, seed, task, action_repeat) and the state words per environment (pos, target, t, episode, over,
+        and vel for the point mass; episode as the int32 tensor that holds its uint32 bits).  The newest frames are not
+        in it: they are a function of the state.  This SYNCHRONISES the environment's device, like state(): the copies
+        wait for every launch enqueued so far."""
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        sd = {"format": 1, "kind": type(self).__name__, "reset": self._frame is not None,
-              "config": {"N": self.N, "A": self.A, "episode_length": self.episode_length, "seed": self.seed}}
+        sd = {"format": 1, "kind": type(self).__name__, "reset": self._frame is not None, "config": self._config()}
         for k in self._STATE:
             sd[k] = host(getattr(self, k))
         return sd
 
     def load_state_dict(self, sd):
         """Restores what state_dict() saved, into a fresh or a used environment.  ValueError, with nothing changed, for a
-        wrong "format" / "kind" or a configuration that differs from this object's (every differing field is named).  The
-        frames are drawn from the restored state with one launch (render()'s), so step() and image() work without a
-        reset() -- unless the saved environment had never been reset.  DrqError on a CPU device, after the checks."""
-        check_state(self, sd, {"N": self.N, "A": self.A, "episode_length": self.episode_length, "seed": self.seed},
-                    {k: getattr(self, k) for k in self._STATE})
+        wrong "format" / "kind" or a configuration that differs from this object's (every differing field is named, the
+        task and action_repeat among them).  A VecReach dict written before there were tasks has neither key and is read
+        as task "reach", action_repeat 1.  The frames are drawn from the restored state with one launch (render()'s), so
+        step() and image() work without a reset() -- unless the saved environment had never been reset.  DrqError on a
+        CPU device, after the checks."""
+        if isinstance(sd, dict) and isinstance(sd.get("config"), dict) and sd.get("kind") == "VecReach":
+            sd = dict(sd, config=dict({"task": "reach", "action_repeat": 1}, **sd["config"]))
+        check_state(self, sd, self._config(), {k: getattr(self, k) for k in self._STATE})
         self._on_gpu()
         for k in self._STATE:
             getattr(self, k).copy_(sd[k])
         self._frame = None
         if sd.get("reset", True):
             self._render()
+
+
+class VecReach(_VecTask):
+    """N environments of the reach task on the device: the action moves the point, touching the target ends the episode
+    (_VecTask holds the interface and the rules)."""
+    TASK, TASK_ID = "reach", 0
+
+
+class VecPointMass(_VecTask):
+    """N environments of the point-mass task on the device: the reach square with momentum.  Per axis and simulator step
+    vel = vel * 0.9 + a * 0.02 and pos += vel; a wall stops the axis that hits it (pos = +-1, vel = 0).  The reward is
+    reach's, max(0, 1 - |pos - target|^2); touching the target does NOT end the episode: discount is 1 on every row and
+    only the time limit ends one.  Resets draw pos and target as reach does and set vel = 0.  The velocity is in no
+    frame -- two states that differ only in vel look alike -- so the policy needs the frame stack.  Same constructor and
+    methods as VecReach; state() and state_dict() carry "vel" too."""
+    TASK, TASK_ID = "pointmass", 1
+    _STATE = _VecTask._STATE + ("vel",)

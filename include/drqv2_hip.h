@@ -617,7 +617,39 @@ int drq_vec_stats_reset(float* ret, int* len, int* done, void* header, float* lo
  *   image[e][y][x][c] = frame[e][c][y / k][x / k] for c < 3 and 255 for c == 3 -- every pixel k x k times, channels last.
  *   The area average of "renderer images" returns the frame exactly ((k^2 v + k^2 / 2) / k^2 = v).
  *   DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX, S not 84, 168, 252 or 336, C not 3 or 4, frame or
- *   image not 16-byte aligned. */
+ *   image not 16-byte aligned.
+ *
+ * Tasks and action repeat.  drq_vec_task_step steps a family of tasks over the same square, each launch a MACRO step of up
+ * to `repeat` sub-steps -- the ActionRepeatWrapper of dmc.py:35-50 inside the launch, since an environment that ends in
+ * the middle of a repeat must stop there.  task: DRQ_TASK_REACH (0), the task above, or DRQ_TASK_POINTMASS (1).
+ * Macro step of e:
+ *   reset row (reset_all = 1, or over[e] == 1): the reset above, and vel = 0 for the point mass.  Outputs first = 1,
+ *     reward = 0, discount = 1, substeps = 0.  The action is not read.
+ *   otherwise: reward = 0, discount = 1, the action sanitised ONCE as above (NaN becomes 0, then the clamp to [-1, 1]).
+ *     For i = 0 .. repeat-1: one sub-step of the task gives (r_i, d_i, over);
+ *       reward = reward + r_i * discount (one multiply, then one add);  discount = discount * d_i;
+ *       stop after the sub-step that set over.
+ *     first = 0, substeps = the sub-steps executed (1 .. repeat).  t counts sub-steps, so episode_length is in simulator
+ *     steps, as in DMC.  The frame is drawn once, from the state after the last executed sub-step, by the frame rule above.
+ *   repeat = 1 is the step above bit for bit: 0 + r * 1 = r for r >= 0, and 1 * d = d.
+ * Sub-step of reach: "Step of e" above without the sanitising: the move, t += 1, reward r_i, d_i = 0 with over when
+ *   reached, else d_i = 1 and over at the time limit.
+ * Sub-step of the point mass.  State vel f32 [N][2] beside the rest.  Per axis, a the sanitised action of that axis:
+ *   v = v * 0.9f;  v = v + a * 0.02f;  p = pos + v
+ *   p < -1: pos = -1, v = 0;  p > 1: pos = 1, v = 0;  otherwise pos = p          (a wall stops the axis that hit it)
+ *   then t += 1;  d2 and r_i = max(0, 1 - d2) as in reach;  d_i = 1 always: touching the target does not end the episode;
+ *   over only when t == episode_length.  Reset draws and frame rule are those of reach: velocity is in no frame.
+ * drq_vec_task_step: writes every byte of frame, reward, discount, first and substeps (i32 [N]) and the state -- vel only
+ *   for the point mass; for reach vel is neither read nor written and may be NULL.  The launch shape is that of
+ *   drq_vec_reach_step, which is this entry with task reach, repeat 1 and no substeps output; the trip count of the
+ *   sub-step loop is uniform across a workgroup.  drq_vec_reach_render and drq_vec_reach_image serve both tasks.
+ *   DRQ_EARG, nothing launched: every condition of drq_vec_reach_step, an unknown task, repeat < 1 or
+ *   > DRQ_TASK_MAX_REPEAT, a null substeps, a null vel for the point mass, vel or substeps not 4-byte aligned. */
+enum { DRQ_TASK_REACH = 0, DRQ_TASK_POINTMASS = 1 };
+#define DRQ_TASK_MAX_REPEAT 16
+int drq_vec_task_step(int task, float* pos, float* target, float* vel, int* t, unsigned* episode, uint8_t* over, long N,
+                      int A, const float* action, unsigned seed, int episode_length, int repeat, int reset_all,
+                      uint8_t* frame, float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
 int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
                        const float* action, unsigned seed, int episode_length, int reset_all, uint8_t* frame,
                        float* reward, float* discount, uint8_t* first, drq_stream_t stream);

@@ -53,11 +53,12 @@ float32 means half to even, so its frames are not add_render()'s everywhere; the
 
   python tools/vec_replay_bench.py --render [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--sizes 84,128,168]
 
---env reach measures the built-in environment (drqv2_amd.envs.VecReach: drq_vec_reach_step, one launch per step of all N)
+--env reach | pointmass measures the built-in environment (drqv2_amd.envs.VecReach / VecPointMass: drq_vec_task_step, one
+launch per step of all N; --action-repeat K sub-steps inside it, 1 by default)
 next to the single-frame ring it feeds: env.step(), ring.add() of one step's outputs, and the two together, alternated
 inside every repeat of one process.  Same steps, repeats and the same two figures per line as above.
 
-  python tools/vec_replay_bench.py --env reach [--steps 2000] [--repeats 3] [--envs 16,256,1024]
+  python tools/vec_replay_bench.py --env reach|pointmass [--action-repeat 1] [--steps 2000] [--repeats 3] [--envs 16,256,1024]
 
 --eval-stack measures the evaluation pieces (drqv2_amd.evaluate): VecFrameStack.push() -- drq_vec_stack_push, one launch --
 beside what an evaluation loop used before it, VecFrameReplay.add() + observation() (two launches), and add() alone, the
@@ -304,10 +305,12 @@ def render(N, S, args):
           f"the torch chain's frames differ in {diff} of {mine.numel()} bytes", flush=True)
 
 
-def reach(N, args):
-    """VecReach.step(), VecFrameReplay.add() of one step's outputs, and both, alternated per repeat"""
-    from drqv2_amd.envs import VecReach
-    env = VecReach(N, "cuda", action_dim=A, episode_length=250, seed=1)
+def device_env(N, args):
+    """step() of the built-in environment (--env reach | pointmass at --action-repeat K), VecFrameReplay.add() of one
+    step's outputs, and both, alternated per repeat"""
+    from drqv2_amd.envs import VecPointMass, VecReach
+    cls = {"reach": VecReach, "pointmass": VecPointMass}[args.env]
+    env = cls(N, "cuda", action_dim=A, episode_length=250, seed=1, action_repeat=args.action_repeat)
     ring = VecFrameReplay(max(32, SLOTS // N), N, A, NSTEP, 0.99, "cuda", seed=1)
     g = torch.Generator(device="cuda")
     g.manual_seed(N)
@@ -329,8 +332,9 @@ def reach(N, args):
     for _ in range(args.repeats):
         for k, fn in paths.items():
             res[k].append(timed(fn, args.steps))
+    what = "" if (args.env, args.action_repeat) == ("reach", 1) else f"{args.env} x{args.action_repeat}  "
     for k, v in res.items():
-        print(f"N={N:5d}  {k:31s}: device-event {spread([x[0] for x in v])}   host wall {spread([x[1] for x in v])}   "
+        print(f"N={N:5d}  {what}{k:31s}: device-event {spread([x[0] for x in v])}   host wall {spread([x[1] for x in v])}   "
               f"({args.steps} x {args.repeats}, alternated)", flush=True)
 
 
@@ -502,8 +506,9 @@ def main():
     ap.add_argument("--render", action="store_true",
                     help="measure add_render() against the torch resize chain in front of add(), and add() alone")
     ap.add_argument("--sizes", default="84,128,168", help="image sizes of --render")
-    ap.add_argument("--env", choices=["reach"], default=None,
+    ap.add_argument("--env", choices=["reach", "pointmass"], default=None,
                     help="measure the built-in environment's step() next to the single-frame ring's add()")
+    ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per step() of --env, 1 .. 16")
     ap.add_argument("--eval-stack", action="store_true",
                     help="measure VecFrameStack.push() beside VecFrameReplay.add() + observation(), and VecVideo.record() / save()")
     args = ap.parse_args()
@@ -517,7 +522,7 @@ def main():
         return
     if args.env:
         for N in (int(x) for x in args.envs.split(",")):
-            reach(N, args)
+            device_env(N, args)
             torch.cuda.empty_cache()
         return
     if args.render:

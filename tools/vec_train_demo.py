@@ -1,22 +1,28 @@
 """The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
 
-  VecReach (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecReach or VecPointMass (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
   VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
 
 Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
 return (and length) of the episodes that finished in every interval, from VecEpisodeStats, and afterwards the mean return of
-uniform-random actions over the SAME number of episodes on a second VecReach of the same seed, measured in the same
+uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
+  python tools/vec_train_demo.py [--task reach|pointmass] [--action-repeat 1]
+                                 [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
                                  [--dormant-every K] [--perturb-every K [--perturb-k 2.0]]
                                  [--export-dir DIR] [--prefill-dir DIR]
                                  [--eval-every STEPS [--eval-episodes K] [--video DIR]]
 
+--task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
+--action-repeat K holds every action for up to K simulator steps inside the step launch.  Both apply to the training
+environment, the evaluation environment and the random baseline alike.  --episode-length counts simulator steps; the
+lengths that are printed count rows, i.e. agent steps.
+
 --eval-every STEPS evaluates the policy every STEPS steps (drqv2_amd.evaluate.evaluate: the first --eval-episodes episodes of
-every environment under act_batch(..., eval_mode=True), on a second VecReach of its own seed, --seed + 1) and prints the
+every environment under act_batch(..., eval_mode=True), on a second environment of its own seed, --seed + 1) and prints the
 mean, smallest and largest return; --video DIR records those episodes (VecVideo: a mosaic of the first 16 environments,
 one launch per step) and writes DIR/eval_<step>.png, an animated PNG.  An evaluation draws from no generator and touches
 neither ring nor optimiser, so the training lines of a run are the same with and without it.  Off by default.
@@ -51,15 +57,24 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
 import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
-from drqv2_amd.envs import VecReach  # noqa: E402
+from drqv2_amd.envs import VecPointMass, VecReach  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
+TASKS = {"reach": VecReach, "pointmass": VecPointMass}
+
+
+def make_env(args, seed):
+    return TASKS[args.task](args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
+                            action_repeat=args.action_repeat)
+
+
 def random_baseline(args, episodes):
-    """mean return and length of the first `episodes` episodes under uniform-random actions, same N, length and seed"""
+    """mean return and length of the first `episodes` episodes under uniform-random actions: the same task, action
+    repeat, N, length and seed"""
     N, A = args.envs, args.action_dim
-    env = VecReach(N, "cuda", action_dim=A, episode_length=args.episode_length, seed=args.seed)
+    env = make_env(args, args.seed)
     stats = VecEpisodeStats(N, "cuda", log_size=max(1024, episodes + 64 * N))      # 100 more steps end at most 50 N more
     g = torch.Generator(device="cuda")
     g.manual_seed(args.seed)
@@ -77,6 +92,8 @@ def random_baseline(args, episodes):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--task", choices=sorted(TASKS), default="reach")
+    ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per action, 1 .. 16")
     ap.add_argument("--steps", type=int, default=20000, help="environment steps (each of all N environments)")
     ap.add_argument("--envs", type=int, default=16)
     ap.add_argument("--action-dim", type=int, default=2)
@@ -115,13 +132,14 @@ def main():
     N, A = args.envs, args.action_dim
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed_all(args.seed)
-    print(f"reach: N={N} environments, episode_length={args.episode_length}, A={A}; {args.steps} steps, warm-up {args.warmup}, "
+    print(f"{args.task}: N={N} environments, episode_length={args.episode_length}, action_repeat={args.action_repeat}, A={A}; "
+          f"{args.steps} steps, warm-up {args.warmup}, "
           f"batch {args.batch}, lr {args.lr}, feature_dim {args.feature_dim}, hidden_dim {args.hidden_dim}, stddev "
           f"{args.stddev}, seed {args.seed}", flush=True)
 
     agent = drqv2.DrQV2Agent((9, 84, 84), (A,), "cuda", args.lr, args.feature_dim, args.hidden_dim, 0.01, args.warmup, 1,
                              args.stddev, 0.3, False)
-    env = VecReach(N, "cuda", action_dim=A, episode_length=args.episode_length, seed=args.seed)
+    env = make_env(args, args.seed)
     store = VecFrameReplay(rows=args.rows, num_envs=N, action_dim=A, nstep=3, discount=0.99, device="cuda", seed=args.seed)
     store.batch_size = args.batch
     stats = VecEpisodeStats(N, "cuda", log_size=max(1024, 2 * N * args.report))
@@ -130,7 +148,7 @@ def main():
 
     if args.eval_every:
         K = args.eval_episodes
-        eval_env = VecReach(N, "cuda", action_dim=A, episode_length=args.episode_length, seed=args.seed + 1)
+        eval_env = make_env(args, args.seed + 1)
         eval_stats = VecEpisodeStats(N, "cuda", log_size=max(1024, K * N), max_episodes_per_env=K)
         eval_stack, video = VecFrameStack(N, "cuda"), None
         if args.video:
