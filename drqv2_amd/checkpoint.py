@@ -14,6 +14,7 @@ for a seed, so the state is all there is to keep:
   env        VecReach / VecPointMass.state_dict(): the task, action_repeat and the state words of every environment (seven;
              nine with the point mass's velocity); the frames are drawn again from them
   stats      VecEpisodeStats.state_dict(): the running returns and lengths, the totals and the log
+  bonus      SimHashBonus.state_dict() (optional, `bonus=`): the count table of the exploration bonus in sparse form
   rng        torch.get_rng_state() and torch.cuda.get_rng_state(device): update()'s draws and act_batch()'s noise
 
         for step in range(start, steps):
@@ -83,9 +84,10 @@ def _device(*objs):
     return None
 
 
-def save(path, *, agent=None, store=None, iterator=None, env=None, stats=None, extra=None):
+def save(path, *, agent=None, store=None, iterator=None, env=None, stats=None, bonus=None, extra=None):
     """Writes one file that holds the state of every object given (module docstring) and `extra` -- plain data of the
-    caller's: numbers, strings, lists, dicts, tensors -- which load() hands back.  The generator states are torch's
+    caller's: numbers, strings, lists, dicts, tensors -- which load() hands back.  bonus= is the SimHashBonus of a loop that
+    has one (drqv2_amd/explore.py); a file saved without it is what it always was.  The generator states are torch's
     default CPU generator and the default generator of the agent's (else the store's, environment's, statistics') GPU.
     SYNCHRONISES that device.  Atomic: the file is written to path + ".tmp", flushed and fsynced, then renamed onto
     path, so a process killed during a save leaves the previous checkpoint intact."""
@@ -93,10 +95,10 @@ def save(path, *, agent=None, store=None, iterator=None, env=None, stats=None, e
     ck = {"format": FORMAT, "kind": "checkpoint", "extra": extra}
     if agent is not None:
         ck["agent"] = agent.__getstate__()
-    for name, obj in (("store", store), ("iterator", iterator), ("env", env), ("stats", stats)):
+    for name, obj in (("store", store), ("iterator", iterator), ("env", env), ("stats", stats), ("bonus", bonus)):
         if obj is not None:
             ck[name] = obj.state_dict()
-    dev = _device(agent, store, env, stats)
+    dev = _device(agent, store, env, stats, bonus)
     ck["rng"] = {"cpu": torch.get_rng_state(),
                  "cuda": torch.cuda.get_rng_state(dev) if dev is not None and torch.cuda.is_available() else None}
     tmp = path + ".tmp"
@@ -125,23 +127,23 @@ def _check_agent(agent, st):
         raise ValueError("checkpoint.load(): the saved agent does not fit this one -- " + "; ".join(bad))
 
 
-def load(path, *, agent=None, store=None, iterator=None, env=None, stats=None):
+def load(path, *, agent=None, store=None, iterator=None, env=None, stats=None, bonus=None):
     """Restores, from a file save() wrote, every object given -- freshly constructed or used -- and returns `extra`.
     The agent is loaded IN PLACE by the logic of DrQV2Agent.__setstate__ (its constructor arguments must equal the saved
     ones, the device aside); the store before its iterator, whose look-ahead batch is rebuilt over the restored ring; the
-    generator states last, so nothing the restore itself draws or launches moves them.  A part that is in the file but
+    exploration bonus's count table (bonus=) when asked for; the generator states last, so nothing the restore itself draws or launches moves them.  A part that is in the file but
     not asked for is ignored.  ValueError, before anything is changed: a part that is asked for but not in the file, a
     file that is no checkpoint of this format.  Each part then checks its configuration before it changes itself
     (ValueError naming every field that differs)."""
     ck = torch.load(os.fspath(path), map_location="cpu", weights_only=True)     # plain data only: no code is unpickled
     if not isinstance(ck, dict) or ck.get("format") != FORMAT or ck.get("kind") != "checkpoint":
         raise ValueError(f"checkpoint.load(): {path} is no checkpoint of format {FORMAT}")
-    asked = [(n, o) for n, o in (("agent", agent), ("store", store), ("iterator", iterator), ("env", env), ("stats", stats))
-             if o is not None]
+    asked = [(n, o) for n, o in (("agent", agent), ("store", store), ("iterator", iterator), ("env", env), ("stats", stats),
+                                 ("bonus", bonus)) if o is not None]
     missing = [n for n, _ in asked if n not in ck]
     if missing:
         raise ValueError(f"checkpoint.load(): {path} holds no {', '.join(missing)} (it holds "
-                         f"{', '.join(n for n in ('agent', 'store', 'iterator', 'env', 'stats') if n in ck) or 'none'})")
+                         f"{', '.join(n for n in ('agent', 'store', 'iterator', 'env', 'stats', 'bonus') if n in ck) or 'none'})")
     if agent is not None:
         _check_agent(agent, ck["agent"])
     for name, obj in asked:
@@ -152,7 +154,7 @@ def load(path, *, agent=None, store=None, iterator=None, env=None, stats=None):
     rng = ck.get("rng") or {}
     if rng.get("cpu") is not None:
         torch.set_rng_state(rng["cpu"])
-    dev = _device(agent, store, env, stats)
+    dev = _device(agent, store, env, stats, bonus)
     if rng.get("cuda") is not None and dev is not None and torch.cuda.is_available():
         torch.cuda.set_rng_state(rng["cuda"], dev)
     return ck.get("extra")

@@ -55,6 +55,17 @@ static inline unsigned drq_grid_for(long n, int block = 256) {
   return (unsigned)(g < 1 ? 1 : g);
 }
 
+// The murmur3 finaliser: the hash of the device environment's reset draws (vecenv.hip) and of the sign matrix of the
+// exploration bonus (explore.hip); the contract of either spells it out (include/drqv2_hip.h).
+__host__ __device__ __forceinline__ unsigned drq_fmix32(unsigned h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
 // Metrics mirror (DrqStep.sums_host): eight floats and a sequence word in pinned (fine-grained, uncached) host memory,
 // written by ONE lane.  A system-scope release before the sequence word would write back every dirty line of the XCD's
 // L2 first (it is what makes OTHER threads' cached stores visible) -- measured: 3.5 us of the publishing launch at batch

@@ -42,18 +42,9 @@ constexpr int kPieces = kFrame / 16;
 constexpr int kThreads = 256;
 constexpr int kTargetR2 = 25, kAgentR2 = 16;
 
-__host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {    // the murmur3 finaliser
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-
 // draw k of episode `episode` of environment e: uniform on the 2^24 grid of [0, 1), then into [-0.9, 0.9]
 __device__ __forceinline__ float reach_draw(unsigned seed, unsigned e, unsigned episode, unsigned k) {
-  const unsigned h = fmix32(seed ^ e * 0x9E3779B9u ^ episode * 0x85EBCA6Bu ^ k * 0xC2B2AE35u);
+  const unsigned h = drq_fmix32(seed ^ e * 0x9E3779B9u ^ episode * 0x85EBCA6Bu ^ k * 0xC2B2AE35u);
   const float u = (float)(h >> 8) * 5.9604644775390625e-8f;          // 2^-24: exact
   return (u * 2.0f - 1.0f) * 0.9f;
 }

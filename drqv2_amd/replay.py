@@ -616,7 +616,9 @@ class VecDeviceReplay:
         if self.R < self.nstep + self.guard_rows + 2:
             raise ValueError(f"rows {self.R}: at least nstep + guard_rows + 2 = {self.nstep + self.guard_rows + 2}")
         dev, S = self.device, self.R * self.N
-        self.frames = torch.empty((S, self.frame_bytes), dtype=torch.uint8, device=dev)
+        # zeros, not empty: slots no add() has reached are compared as part of the ring (two runs of one loop, a run
+        # against its restored copy), and what the allocator hands back depends on whatever ran in the process before
+        self.frames = torch.zeros((S, self.frame_bytes), dtype=torch.uint8, device=dev)
         self.action = torch.zeros((S, self.A), dtype=torch.float32, device=dev)
         self.reward = torch.zeros((S,), dtype=torch.float32, device=dev)
         self.discount = torch.ones((S,), dtype=torch.float32, device=dev)

@@ -656,6 +656,46 @@ int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uin
 int drq_vec_reach_render(const float* pos, const float* target, long N, uint8_t* frame, drq_stream_t stream);
 int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream);
 
+/* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
+ * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
+ * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep
+ * environments as "device environment" writes them and "single-frame step-major replay" stores them, where they are:
+ * no download, no host wait.  These definitions are the contract; everything up to the count is integer arithmetic
+ * and exact, the bonus is exact to the bit.
+ * Input: frame u8 [N][3][84][84].  Per environment n:
+ *   cells       the frame is cut into a 21 x 21 grid of 4 x 4 blocks; s[gy][gx] = the int32 sum over the 3 channels and the
+ *               16 pixels (rows 4 gy .. 4 gy + 3, columns 4 gx .. 4 gx + 3) of block (gy, gx), at most 48 x 255 = 12,240.
+ *               D = 441 cells, i = gy * 21 + gx.
+ *   centring    v_i = 441 * s_i - sum_j s_j: exact in int32 (|v_i| <= 441 * 12,240), and sum_i v_i = 0
+ *   projection  for bit j = 0 .. bits-1:  p_j = sum_i a(j, i) * v_i, accumulated in int64, with
+ *               a(j, i) = +1 if fmix32(seed ^ (j * 441 + i) * 0x9E3779B9) & 1, else -1, in uint32 arithmetic; fmix32 is the
+ *               murmur3 finaliser of "device environment".  The signs are computed, no matrix is stored.
+ *               (With k signs +1, |p_j| <= 12,240 k (882 - 2 k) <= 12,240 * 220 * 442 = 1,190,217,600: the frame that is 255
+ *               on the +1 cells and 0 elsewhere.  The sum is exact in any order; int64 leaves the bound no role.)
+ *   code        code = sum_j (p_j > 0) << j: a projection of exactly zero gives bit 0, so a uniform frame has code 0.
+ *               1 <= bits <= DRQ_SIMHASH_MAX_BITS (24).  Adding a constant to every pixel changes no v_i and no code.
+ *   table       count: i32 [2^bits], zeroed by the caller before the first step
+ *   update = 1  FIRST every environment adds 1 to count[code_n], THEN every environment reads c_n = count[code_n]: two
+ *               environments with one code in one step both see the count after both increments, and the result does
+ *               not depend on the order of the workgroups
+ *   update = 0  the step only reads: c_n may be 0
+ *   bonus       bonus_n = beta / sqrt((float)c_n) in float32, the conversion, the square root and the division each
+ *               correctly rounded (numpy: np.float32(beta) / np.sqrt(np.float32(c))); bonus_n = beta for c_n = 0
+ *   reward      with reward and reward_out (f32 [N], both or neither): reward_out_n = reward_n + bonus_n, one float32 add
+ * drq_explore_simhash_step: two launches on the stream, whose boundary is the order between incrementing and reading (no
+ *   cooperative launch, no spin).  Hash and count: N workgroups of 256 threads, one per environment; a lane owns a cell
+ *   and loads each of its 12 pixel rows as one aligned dword (a frame row is 21 dwords), so the 21,168 bytes are read
+ *   once; s and v pass through LDS; bit j is a strided sum over the 441 cells by wave j % 4, reduced inside the wave;
+ *   one lane stores code_out[n] and under update does one atomic add of 1 on count[code_n].  Bonus: one thread per
+ *   environment.  Writes every element of code_out, count_out (i32 [N]: c_n), bonus_out (f32 [N]) and, when given,
+ *   reward_out; count only by the increments; nothing else.  reward_out may be reward itself.
+ *   DRQ_EARG, nothing launched: a null frame, count, code_out, count_out or bonus_out, reward without reward_out or
+ *   reward_out without reward, N < 1 or > INT32_MAX, bits < 1 or > 24, update not 0 or 1, a pointer not 4-byte aligned. */
+#define DRQ_SIMHASH_MAX_BITS 24
+int drq_explore_simhash_step(const uint8_t* frame, long N, int bits, unsigned seed, float beta, int update, int* count,
+                             int* code_out, int* count_out, float* bonus_out, const float* reward, float* reward_out,
+                             drq_stream_t stream);
+
 /* ---- evaluation.  New functionality: the reference evaluates its one environment on the host -- the 9-channel
  * observation comes out of a FrameStackWrapper (dmc.py:87-109), the episodes are recorded by video.py (train.py:98-122).
  * For N lockstep environments whose frames are device tensors ("device environment") both are one launch each, and

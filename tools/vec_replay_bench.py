@@ -67,6 +67,14 @@ scale 2) and the host wall of VecVideo.save() for a 102-image clip of a VecReach
 steps, repeats and the same two figures per line as above.
 
   python tools/vec_replay_bench.py --eval-stack [--steps 2000] [--repeats 3] [--envs 16,256,1024]
+
+--explore measures the exploration bonus (drqv2_amd.explore.SimHashBonus: drq_explore_simhash_step, two launches per step
+of all N) on the frames of VecReach: env.step(), bonus.step(frame, reward), bonus.step(frame, update=False), and the
+collection step with the bonus in it -- env.step() + bonus.step() + ring.add() --, the four alternated inside every
+repeat of one process.  Same steps, repeats and the same two figures per line as above, and for the bonus the frame
+bytes it reads over its device-event time.
+
+  python tools/vec_replay_bench.py --explore [--explore-bits 16] [--steps 2000] [--repeats 3] [--envs 16,256]
 """
 import argparse
 import os
@@ -338,6 +346,42 @@ def device_env(N, args):
               f"({args.steps} x {args.repeats}, alternated)", flush=True)
 
 
+def explore(N, args):
+    """SimHashBonus.step(frame, reward) of VecReach's frames, env.step(), and the two with ring.add() of reward + bonus,
+    alternated per repeat; the bonus reads 21,168 bytes per environment, its rate over the device-event time is printed"""
+    from drqv2_amd.envs import VecReach
+    from drqv2_amd.explore import SimHashBonus
+    env = VecReach(N, "cuda", action_dim=A, episode_length=250, seed=1)
+    ring = VecFrameReplay(max(32, SLOTS // N), N, A, NSTEP, 0.99, "cuda", seed=1)
+    bonus = SimHashBonus(N, "cuda", bits=args.explore_bits, beta=0.1, seed=1)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N)
+    actions = [torch.rand(N, A, device="cuda", generator=g) * 2 - 1 for _ in range(4)]
+    env.reset()
+    held = tuple(t.clone() for t in env.step(actions[0]))
+
+    def loop(i):
+        frame, reward, discount, first = env.step(actions[i & 3])
+        ring.add(frame, actions[i & 3], bonus.step(frame, reward), discount, first)
+
+    paths = {"env.step()": lambda i: env.step(actions[i & 3]),
+             "bonus.step(frame, reward)": lambda i: bonus.step(held[0], held[1]),
+             "bonus.step(frame, update=False)": lambda i: bonus.step(held[0], update=False),
+             "env.step() + bonus.step() + ring.add()": loop}
+    for fn in paths.values():
+        for i in range(20):
+            fn(i)
+    res = {k: [] for k in paths}
+    for _ in range(args.repeats):
+        for k, fn in paths.items():
+            res[k].append(timed(fn, args.steps))
+    for k, v in res.items():
+        dev = sorted(x[0] for x in v)[len(v) // 2]
+        rate = f"   {N * 21168 / dev / 1e3:6.2f} GB/s of frames" if k.startswith("bonus") else ""
+        print(f"N={N:5d}  bits={args.explore_bits:2d}  {k:38s}: device-event {spread([x[0] for x in v])}   host wall "
+              f"{spread([x[1] for x in v])}   ({args.steps} x {args.repeats}, alternated){rate}", flush=True)
+
+
 def eval_stack(N, args):
     """VecFrameStack.push() beside what stood in for it, VecFrameReplay.add() + observation(), alternated per repeat"""
     from drqv2_amd.evaluate import VecFrameStack
@@ -511,9 +555,17 @@ def main():
     ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per step() of --env, 1 .. 16")
     ap.add_argument("--eval-stack", action="store_true",
                     help="measure VecFrameStack.push() beside VecFrameReplay.add() + observation(), and VecVideo.record() / save()")
+    ap.add_argument("--explore", action="store_true",
+                    help="measure SimHashBonus.step() next to the built-in environment's step() and the ring's add()")
+    ap.add_argument("--explore-bits", type=int, default=16, metavar="K", help="bits of the SimHash code of --explore, 1 .. 24")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vec_replay_bench.py measures on the GPU: no device found")
+    if args.explore:
+        for N in (int(x) for x in args.envs.split(",")):
+            explore(N, args)
+            torch.cuda.empty_cache()
+        return
     if args.eval_stack:
         for N in (int(x) for x in args.envs.split(",")):
             eval_stack(N, args)

@@ -15,6 +15,7 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--dormant-every K] [--perturb-every K [--perturb-k 2.0]]
                                  [--export-dir DIR] [--prefill-dir DIR]
                                  [--eval-every STEPS [--eval-episodes K] [--video DIR]]
+                                 [--explore-beta B [--explore-bits K]]
 
 --task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
 --action-repeat K holds every action for up to K simulator steps inside the step launch.  Both apply to the training
@@ -43,6 +44,12 @@ counted as headless).  --prefill-dir DIR loads such a directory into the ring be
 (VecFrameReplay.add_episodes), e.g. what an earlier run exported; a resumed run has its ring from the checkpoint and skips
 it.  Both are off by default, and the output is then unchanged.
 
+--explore-beta B adds a count-based exploration bonus (drqv2_amd.explore.SimHashBonus: a SimHash of the frame of
+--explore-bits K bits, 16 by default, bonus = B / sqrt(count)) to the reward that goes into the ring; the episode
+statistics, and so every return that is printed, keep the environment's own reward.  The report line then ends with the
+number of distinct codes counted so far, and the count table goes into the checkpoint.  Off by default, and the output is
+then unchanged.
+
 This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
 updates; it is no benchmark and makes no claim about DMC.
 """
@@ -59,6 +66,7 @@ import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.envs import VecPointMass, VecReach  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
+from drqv2_amd.explore import SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
@@ -122,7 +130,12 @@ def main():
     ap.add_argument("--eval-every", type=int, default=0, metavar="STEPS", help="evaluate every STEPS steps (0: never)")
     ap.add_argument("--eval-episodes", type=int, default=1, metavar="K", help="episodes per environment of an evaluation")
     ap.add_argument("--video", default=None, metavar="DIR", help="write every evaluation as DIR/eval_<step>.png")
+    ap.add_argument("--explore-beta", type=float, default=0.0, metavar="B",
+                    help="add the exploration bonus B / sqrt(count of the frame's SimHash code) to the ring's reward (0: off)")
+    ap.add_argument("--explore-bits", type=int, default=None, metavar="K", help="bits of the SimHash code, 1 .. 24 (16)")
     args = ap.parse_args()
+    if args.explore_bits is not None and not args.explore_beta:
+        raise SystemExit("--explore-bits needs --explore-beta B")
     if args.video and not args.eval_every:
         raise SystemExit("--video needs --eval-every STEPS")
     if (args.checkpoint_every or args.resume) and not args.checkpoint:
@@ -144,6 +157,10 @@ def main():
     store.batch_size = args.batch
     stats = VecEpisodeStats(N, "cuda", log_size=max(1024, 2 * N * args.report))
     it = iter(store)
+    bonus = SimHashBonus(N, "cuda", bits=args.explore_bits or 16, beta=args.explore_beta, seed=args.seed) \
+        if args.explore_beta else None
+    if bonus is not None:
+        print(f"exploration bonus: beta {bonus.beta}, {bonus.bits} bits", flush=True)
     zeros_NA, zeros_N, ones_N = torch.zeros(N, A, device="cuda"), torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
 
     if args.eval_every:
@@ -157,7 +174,7 @@ def main():
 
     start, logged, updates, export_from = 0, 0, 0, None
     if args.resume:
-        extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats)
+        extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus)
         start, logged, updates, export_from = extra["step"], extra["logged"], extra["updates"], extra.get("export_from")
         print(f"resumed {args.checkpoint} at step {start}", flush=True)
     else:
@@ -177,7 +194,8 @@ def main():
     for step in range(start, args.steps):
         action = agent.act_batch(store.observation(), step, False)   # [N, A], stays on the device
         frame, reward, discount, first = env.step(action)
-        store.add(frame, action, reward, discount, first)
+        # the ring learns from reward + bonus; the statistics keep the environment's own reward
+        store.add(frame, action, reward if bonus is None else bonus.step(frame, reward), discount, first)
         stats.step(reward, first)
         if step >= args.warmup:
             agent.update(it, step)
@@ -202,7 +220,8 @@ def main():
             length = f"{new['length'].mean():5.1f}" if len(new) else "  n/a"
             print(f"step {step + 1:6d}  updates {updates:6d}  episodes {snap.episodes:6d} (+{len(new) + missed})  mean return "
                   f"{mean}  mean length {length}  return per step "
-                  f"{(new['return'].sum() / max(1, new['length'].sum())):.3f}  [{time.perf_counter() - t0:.1f} s]", flush=True)
+                  f"{(new['return'].sum() / max(1, new['length'].sum())):.3f}  [{time.perf_counter() - t0:.1f} s]"
+                  + ("" if bonus is None else f"  distinct codes {int(bonus.distinct())}"), flush=True)
             if args.export_dir:                                      # this WAITS as well
                 rep = store.export_episodes(args.export_dir, start_row=export_from)
                 export_from = rep.next_row
@@ -226,7 +245,7 @@ def main():
                 print(f"step {step + 1:6d}  eval: {len(video)} images of {video.image_shape[1]} x {video.image_shape[0]} -> {path} "
                       f"({size / 1e6:.2f} MB) [save {time.perf_counter() - ts:.2f} s]", flush=True)
         if args.checkpoint_every and (step + 1) % args.checkpoint_every == 0:    # the end of an iteration: this WAITS
-            checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats,
+            checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus,
                             extra={"step": step + 1, "logged": logged, "updates": updates, "export_from": export_from})
     snap = stats.read()
     torch.cuda.synchronize()
