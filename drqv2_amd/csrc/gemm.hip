@@ -11,6 +11,7 @@
 // Global -> registers (prefetched one k-tile ahead) -> LDS [row][k] with pitch 34 (bank = 2*row + k:
 // conflict-free MFMA operand reads) -> MFMA.  Split-K writes dense partials; a second kernel sums them
 // in a fixed order (deterministic) and applies the epilogue.
+// Host side: the family's entries ask the planner (gemm_plan.h) and switch over launchers that test no shape.
 #include "common.h"
 #include "internal.h"
 #include "../../include/drqv2_hip.h"
@@ -548,178 +549,153 @@ __global__ void splitk_reduce_kernel(GemmArgs g) {
   epilogue_store(g, batch, m, n, (s0 + s1) + (s2 + s3));
 }
 
-// set by drq_gemm_batched_partial around one call: keep the split-K partials, the caller reduces them itself
-thread_local bool g_leave_partials = false;   // call-scoped flag of drq_gemm_batched_partial (per host thread)
-thread_local int g_last_splitk = 1;
+// after the GEMM's own launch: the split-K sum, unless there is none or the caller sums the records itself
+int reduce_records(const GemmArgs& g, const GemmCall& c) {
+  DRQ_LAUNCH_CHECK();
+  if (g.splitk == 1 || c.leave_partials) return DRQ_OK;
+  dim3 rg((unsigned)(((long)g.M * g.N + 255) / 256), g.nbatch);
+  hipLaunchKernelGGL(splitk_reduce_kernel, rg, dim3(256), 0, c.st, g);
+  return drq_launched();
+}
 
+// full: the plan's variant without range masks (instantiated for the forward form at tile 1 only)
 template <int TM, int TN, bool A_KC, bool B_KC, bool V4, int BK = BK0>
-int launch(const GemmArgs& g, hipStream_t st) {
+int launch(const GemmArgs& g, const GemmCall& c, bool full) {
   constexpr int BM = 32 * TM, BN = 32 * TN;
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.nbatch * g.splitk);
-  // the forward form of the hidden layers (all dimensions multiples of the tiles): the variant without masks
   constexpr bool HAS_FULL = TM == 1 && TN == 1 && A_KC && B_KC && V4 && BK == BK0;
-  const bool full = g.M % BM == 0 && g.N % BN == 0 && g.K % BK == 0 && g.kchunk % BK == 0;
-  if constexpr (HAS_FULL) {
-    if (full) hipLaunchKernelGGL((gemm_kernel<TM, TN, A_KC, B_KC, V4, BK, true>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((gemm_kernel<TM, TN, A_KC, B_KC, V4, BK>), grid, dim3(256), 0, st, g);
-  } else
-  hipLaunchKernelGGL((gemm_kernel<TM, TN, A_KC, B_KC, V4, BK>), grid, dim3(256), 0, st, g);
-  DRQ_LAUNCH_CHECK();
-  g_last_splitk = g.splitk;
-  if (g.splitk > 1 && !g_leave_partials) {
-    const long mn = (long)g.M * g.N;
-    dim3 rg((unsigned)((mn + 255) / 256), g.nbatch);
-    hipLaunchKernelGGL(splitk_reduce_kernel, rg, dim3(256), 0, st, g);
-    DRQ_LAUNCH_CHECK();
-  }
-  return DRQ_OK;
+  auto* kernel = gemm_kernel<TM, TN, A_KC, B_KC, V4, BK>;
+  if constexpr (HAS_FULL) kernel = full ? gemm_kernel<TM, TN, A_KC, B_KC, V4, BK, true> : kernel;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.st, g);
+  return reduce_records(g, c);
 }
 
 template <int TM, int TN, int BK = BK0>
-int dispatch(const GemmArgs& g, int a_kc, int b_kc, bool v4, hipStream_t st) {
-  if (a_kc && b_kc)
-    return v4 ? launch<TM, TN, true, true, true, BK>(g, st) : launch<TM, TN, true, true, false, BK>(g, st);
-  if (a_kc && !b_kc)
-    return v4 ? launch<TM, TN, true, false, true, BK>(g, st) : launch<TM, TN, true, false, false, BK>(g, st);
-  if (!a_kc && !b_kc) return launch<TM, TN, false, false, false, BK>(g, st);
-  return DRQ_EARG;
+int dispatch(const GemmArgs& g, const GemmCall& c, bool v4, bool full) {
+  if (c.a_kc && c.b_kc)
+    return v4 ? launch<TM, TN, true, true, true, BK>(g, c, full) : launch<TM, TN, true, true, false, BK>(g, c, full);
+  if (c.a_kc) return v4 ? launch<TM, TN, true, false, true, BK>(g, c, full) : launch<TM, TN, true, false, false, BK>(g, c, full);
+  return launch<TM, TN, false, false, false, BK>(g, c, full);
 }
 
 template <bool A_KC, bool B_KC>
-int launch_bf16(const GemmArgs& g, bool v4, hipStream_t st) {
-  // 64 < N <= 128 with a long reduction (the trunk layer at feature_dim 100): one 128-column tile reads A once
-  const bool wide = g.N > 64 && g.N <= 128 && g.K >= 4096;
+int launch_bf16(const GemmArgs& g, const GemmCall& c, bool v4, bool wide) {
   const int bn = wide ? 2 * BF_BM : BF_BM;
   dim3 grid((g.N + bn - 1) / bn, (g.M + BF_BM - 1) / BF_BM, g.nbatch * g.splitk);
-  if (wide) {
-    if (v4) hipLaunchKernelGGL((gemm_bf16_kernel<A_KC, B_KC, true, 2>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<A_KC, B_KC, false, 2>), grid, dim3(256), 0, st, g);
-  } else if (v4) hipLaunchKernelGGL((gemm_bf16_kernel<A_KC, B_KC, true>), grid, dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((gemm_bf16_kernel<A_KC, B_KC, false>), grid, dim3(256), 0, st, g);
-  DRQ_LAUNCH_CHECK();
-  g_last_splitk = g.splitk;
-  if (g.splitk > 1 && !g_leave_partials) {
-    const long mn = (long)g.M * g.N;
-    dim3 rg((unsigned)((mn + 255) / 256), g.nbatch);
-    hipLaunchKernelGGL(splitk_reduce_kernel, rg, dim3(256), 0, st, g);
-    DRQ_LAUNCH_CHECK();
+  auto* kernel = wide ? (v4 ? gemm_bf16_kernel<A_KC, B_KC, true, 2> : gemm_bf16_kernel<A_KC, B_KC, false, 2>)
+                      : (v4 ? gemm_bf16_kernel<A_KC, B_KC, true> : gemm_bf16_kernel<A_KC, B_KC, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.st, g);
+  return reduce_records(g, c);
+}
+
+// the per-problem pointers of either argument block; rowsum: false drops the fused bias gradient
+template <class Args, class Epi>
+void fill_pointers(Args& g, Epi& e, const GemmCall& c, bool rowsum = true) {
+  for (int b = 0; b < c.nbatch; ++b) {
+    g.A[b] = c.A[b]; g.B[b] = c.B[b]; g.C[b] = c.C[b];
+    e.bias[b] = c.bias_p ? c.bias_p[b] : nullptr;
+    e.aux[b] = c.aux_p ? c.aux_p[b] : nullptr;
+    e.rowsum[b] = c.rowsum_p && rowsum ? c.rowsum_p[b] : nullptr;
   }
-  return DRQ_OK;
+  g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.M = c.M; g.N = c.N; g.K = c.K;
+  e.ldaux = c.ldaux; e.relu = c.relu;
+}
+
+// gemm_kernel at the plan's block tile, or gemm_bf16_kernel after the bias gradient's own pass where the plan says so
+int launch_lds_bf16(const GemmCall& c, const GemmPlan& p) {
+  for (int b = 0; p.colsum_first && b < c.nbatch; ++b)
+    if (c.rowsum_p[b]) {
+      const int rc = drq_colsum(c.A[b], c.lda, 0, c.rowsum_p[b], 0, c.K, c.M, 1, c.st);
+      if (rc != DRQ_OK) return rc;
+    }
+  GemmArgs g{};
+  fill_pointers(g, g.ep, c, !p.colsum_first);
+  g.nbatch = c.nbatch; g.splitk = p.splitk; g.kchunk = p.kchunk; g.part = c.ws; g.ep.scatter_hw = c.scatter_hw;
+  if (p.variant == GV_BF16) {
+    if (c.a_kc && c.b_kc) return launch_bf16<true, true>(g, c, p.v4, p.full);
+    return c.a_kc ? launch_bf16<true, false>(g, c, p.v4, p.full) : launch_bf16<false, false>(g, c, p.v4, p.full);
+  }
+  switch (p.tile) {
+    case 2: return dispatch<2, 2>(g, c, p.v4, p.full);
+    case 3: return dispatch<2, 1>(g, c, p.v4, p.full);
+    case 4: return dispatch<1, 2>(g, c, p.v4, p.full);
+    case 5: return dispatch<1, 1, 64>(g, c, p.v4, p.full);
+    case 6: return dispatch<2, 2, 64>(g, c, p.v4, p.full);
+    default: return dispatch<1, 1>(g, c, p.v4, p.full);
+  }
 }
 
 }  // namespace
 
-// bf16 != 0: the bf16-MFMA kernel for every shape (fp32 storage, operands rounded when staged); see gemm_bf16_kernel
-int drq_gemm_batched_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
-                         int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
-                         const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int tile,
-                         int splitk, float* ws, size_t ws_bytes, hipStream_t st) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || nbatch <= 0 || nbatch > MAXB) return DRQ_EARG;
-  for (int b = 0; b < nbatch; ++b)
-    if (!A[b] || !B[b] || !C[b]) return DRQ_EARG;
-  if (rowsum && a_kc) return DRQ_EARG;
-  if (bf16) {
-    if (!a_kc && b_kc) return DRQ_EARG;
-    const int cus = drq_num_cus();
-    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64) * nbatch;
-    // a weight-gradient GEMM with few output tiles (the first layers: N = feature_dim (+ action_dim)) needs split-K
-    // to fill the chip, and the fused bias gradient cannot be split: it gets its own pass (column sums of dy)
-    if (rowsum && splitk == 0 && tiles < 2L * cus && K >= 512) {
-      for (int b = 0; b < nbatch; ++b)
-        if (rowsum[b]) {
-          const int rc = drq_colsum(A[b], lda, 0, rowsum[b], 0, K, M, 1, st);
-          if (rc != DRQ_OK) return rc;
-        }
-      rowsum = nullptr;
-    }
-    if (rowsum) splitk = 1;
-    if (splitk == 0) {
-      splitk = 1;
-      if (tiles < 2L * cus && K >= 512) {
-        splitk = (int)((3L * cus + tiles - 1) / tiles);
-        const int maxs = K / 256;                    // keep >= 4 k-tiles per split
-        if (splitk > maxs) splitk = maxs;
-        if (splitk < 1) splitk = 1;
-      }
-    }
-    int kchunk = ((K + splitk - 1) / splitk + 63) / 64 * 64;
-    splitk = (K + kchunk - 1) / kchunk;
-    if (splitk > 1 && (!ws || (size_t)nbatch * splitk * M * N * sizeof(float) > ws_bytes)) return DRQ_EWS;
-    GemmArgs g{};
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    bool v4 = lda % 4 == 0 && ldb % 4 == 0;
-    for (int b = 0; b < nbatch; ++b) {
-      g.A[b] = A[b]; g.B[b] = B[b]; g.C[b] = C[b];
-      g.ep.bias[b] = bias ? bias[b] : nullptr;
-      g.ep.aux[b] = aux ? aux[b] : nullptr;
-      g.ep.rowsum[b] = rowsum ? rowsum[b] : nullptr;
-      v4 = v4 && al16(A[b]) && al16(B[b]);
-    }
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.nbatch = nbatch; g.splitk = splitk; g.kchunk = kchunk; g.part = ws;
-    g.ep.ldaux = ldaux; g.ep.relu = relu; g.ep.scatter_hw = scatter_hw;
-    if (a_kc && b_kc) return launch_bf16<true, true>(g, v4, st);
-    if (a_kc && !b_kc) return launch_bf16<true, false>(g, v4, st);
-    return launch_bf16<false, false>(g, v4, st);
-  }
-  // the skinny dgrad shape of the trunk layer (K = feature_dim, N = 39200) has its own kernel; an explicit
-  // tile / splitk request keeps the generic path (tests compare the two)
-  if (nbatch == 1 && tile == 0 && splitk == 0 && N >= 4096 && N % 32 == 0 && !bias && !relu && a_kc && !b_kc &&
-      K <= 128 && !rowsum) {
-    const int rc =
-        drq_skinny_dgrad(A[0], lda, B[0], ldb, C[0], ldc, M, N, K, aux ? aux[0] : nullptr, ldaux, scatter_hw, st);
-    if (rc != DRQ_EARG) return rc;
-  }
-  // the trunk layer's weight gradient (M = feature_dim, N = 39200, K = batch) likewise
-  if (nbatch == 1 && tile == 0 && splitk == 0 && scatter_hw == 0 && !a_kc && !b_kc && M <= 128 && N >= 4096 && !bias &&
-      !relu && !aux) {
-    const int rc = drq_trunk_wgrad(A[0], lda, B[0], ldb, C[0], ldc, M, N, K, rowsum ? rowsum[0] : nullptr, st);
-    if (rc != DRQ_EARG) return rc;
-  }
-  // hidden x hidden layers at multiple-of-32 shapes: the LDS-free kernel (gemm2.hip)
-  if (tile == 0 && splitk == 0 && scatter_hw == 0) {
-    const int rc = drq_gemm2(nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, relu, aux, ldaux, rowsum, st);
-    if (rc != DRQ_EARG) return rc;
-  }
-  const int cus = drq_num_cus();
-  const long t_big = (long)((M + 63) / 64) * ((N + 63) / 64) * nbatch;
-  const long t_small = (long)((M + 31) / 32) * ((N + 31) / 32) * nbatch;
-  if (tile == 0) tile = (t_big >= 2L * cus) ? 2 : 1;
-  const long tiles = tile == 2 ? t_big : (tile >= 3 ? (t_big + t_small) / 2 : t_small);
-  if (rowsum) splitk = 1;
-  if (splitk == 0) {
-    splitk = 1;
-    if (tiles < 2L * cus && K >= 256) {
-      splitk = (int)((3L * cus + tiles - 1) / tiles);
-      const int maxs = K / 128;                      // keep >= 4 k-tiles per split
-      if (splitk > maxs) splitk = maxs;
-      if (splitk < 1) splitk = 1;
-    }
-  }
-  int kchunk = ((K + splitk - 1) / splitk + 63) / 64 * 64;
-  splitk = (K + kchunk - 1) / kchunk;
-  if (splitk > 1 && (!ws || (size_t)nbatch * splitk * M * N * sizeof(float) > ws_bytes)) return DRQ_EWS;
-  GemmArgs g{};
+bool drq_gemm_prepare(GemmCall& c) {
+  if (!c.A || !c.B || !c.C) return false;
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  bool v4 = (K % 4 == 0) && (a_kc || b_kc);
-  if (a_kc) v4 = v4 && lda % 4 == 0;
-  if (b_kc) v4 = v4 && ldb % 4 == 0;
-  for (int b = 0; b < nbatch; ++b) {
-    g.A[b] = A[b]; g.B[b] = B[b]; g.C[b] = C[b];
-    g.ep.bias[b] = bias ? bias[b] : nullptr;
-    g.ep.aux[b] = aux ? aux[b] : nullptr;
-    g.ep.rowsum[b] = rowsum ? rowsum[b] : nullptr;
-    if (a_kc) v4 = v4 && al16(A[b]);
-    if (b_kc) v4 = v4 && al16(B[b]);
+  c.a_al16 = c.b_al16 = true, c.q_unpaired = false;
+  for (int b = 0; b < c.nbatch && b < kGemmMaxBatch; ++b) {
+    if (!c.A[b] || !c.B[b] || !c.C[b]) return false;
+    c.a_al16 = c.a_al16 && al16(c.A[b]);
+    c.b_al16 = c.b_al16 && al16(c.B[b]);
+    c.q_unpaired = c.q_unpaired || (c.qw && c.qw[b]) != (c.qpart && c.qpart[b]);
   }
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-  g.nbatch = nbatch; g.splitk = splitk; g.kchunk = kchunk; g.part = ws;
-  g.ep.ldaux = ldaux; g.ep.relu = relu; g.ep.scatter_hw = scatter_hw;
-  if (tile == 3) return dispatch<2, 1>(g, a_kc, b_kc, v4, st);   // 64x32 block tile
-  if (tile == 4) return dispatch<1, 2>(g, a_kc, b_kc, v4, st);   // 32x64
-  if (tile == 5) return dispatch<1, 1, 64>(g, a_kc, b_kc, v4, st);   // 32x32, k-tile 64 (one barrier per 64 k)
-  if (tile == 6) return dispatch<2, 2, 64>(g, a_kc, b_kc, v4, st);   // 64x64, k-tile 64
-  return tile == 2 ? dispatch<2, 2>(g, a_kc, b_kc, v4, st) : dispatch<1, 1>(g, a_kc, b_kc, v4, st);
+  c.ws_al16 = c.ws && al16(c.ws);
+  if (!c.ws) c.ws_bytes = 0;
+  c.bias = c.bias_p != nullptr; c.aux = c.aux_p != nullptr; c.rowsum = c.rowsum_p != nullptr;
+  c.cus = drq_num_cus();
+  return true;
+}
+
+MlpArgs drq_gemm_fill(const GemmCall& c) {
+  MlpArgs g{};
+  fill_pointers(g, g, c);
+  for (int b = 0; b < c.nbatch; ++b) g.qw[b] = c.qw ? c.qw[b] : nullptr, g.qpart[b] = c.qpart ? c.qpart[b] : nullptr;
+  g.a_bytes = (unsigned)((size_t)(c.a_kc ? c.M : c.K) * c.lda * 4);
+  g.b_bytes = (unsigned)((size_t)(c.b_kc ? c.N : c.K) * c.ldb * 4);
+  return g;
+}
+
+int drq_gemm_launch(const GemmCall& c, const GemmPlan& p, const GemmCall* w) {
+  const bool trunk_wgrad = p.variant == GV_TRUNK_WGRAD_4 || p.variant == GV_TRUNK_WGRAD_8 || p.variant == GV_TRUNK_WGRAD_16;
+  if (c.ln.rows > 0 && !trunk_wgrad) {   // a rider without its kernel: its own launch, also ahead of a refusal below
+    const int rc = drq_ln_param_grad(c.ln.dln, c.ln.xhat, c.ln.dgamma, c.ln.dbeta, c.ln.rows, c.ln.F, c.st);
+    if (rc != DRQ_OK) return rc;
+  }
+  switch (p.variant) {
+    case GV_NONE: break;
+    case GV_EWS: return DRQ_EWS;
+    case GV_G3_FWD_64x64: case GV_G3_FWD_64x32: case GV_G3_DGRAD_64x64: case GV_G3_DGRAD_64x32: return drq_gemm3(c, p);
+    // a pair plan comes with its weight-gradient half (the refusal is for a caller inside the library that forgot it)
+    case GV_G3_PAIR_D64: case GV_G3_PAIR_D32: return w ? drq_gemm3_wgrad_dgrad(*w, c, p) : DRQ_EARG;
+    case GV_PAIR2: return w ? drq_gemm2_wgrad_dgrad(*w, c, p) : DRQ_EARG;
+    case GV_G2_KS1: case GV_G2_KS4: return drq_gemm2(c, p);
+    case GV_SKINNY_DGRAD: return drq_skinny_dgrad(c);
+    case GV_TRUNK_WGRAD_4: case GV_TRUNK_WGRAD_8: case GV_TRUNK_WGRAD_16: return drq_trunk_wgrad(c, p);
+    case GV_TRUNK_FWD_TM1: case GV_TRUNK_FWD_TM2: case GV_TRUNK_FWD_WIDE: return drq_trunk_fwd_partial(c, p);
+    case GV_LDS: case GV_BF16: return launch_lds_bf16(c, p);
+  }
+  return DRQ_EARG;
+}
+
+int drq_gemm_batched_any(GemmCall c) {
+  return drq_gemm_prepare(c) ? drq_gemm_launch(c, plan_batched(c)) : DRQ_EARG;
+}
+
+int drq_gemm_batched_partial_any(GemmCall c, int* splitk_out) {
+  c.leave_partials = true;
+  if (!drq_gemm_prepare(c)) return DRQ_EARG;
+  const GemmPlan p = plan_partial(c);
+  const int rc = drq_gemm_launch(c, p);
+  if (splitk_out) *splitk_out = rc == DRQ_OK ? p.splitk : 1;
+  return rc;
+}
+
+int drq_gemm_wgrad_dgrad(GemmCall w, GemmCall d, bool ring_pair) {
+  if (!drq_gemm_prepare(w) || !drq_gemm_prepare(d)) return DRQ_EARG;
+  GemmPlan p;
+  if (ring_pair) p = plan_ring(RING_PAIR, d, &w);
+  if (p.variant == GV_NONE && !d.bf16) p = plan_pair2(w, d);
+  if (p.variant != GV_NONE) return drq_gemm_launch(d, p, &w);
+  const int rc = drq_gemm_launch(w, plan_batched(w));
+  return rc != DRQ_OK ? rc : drq_gemm_launch(d, plan_batched(d));
 }
 
 // See include/drqv2_hip.h.  Host arrays of nbatch (<= 8) device pointers; bias/aux/rowsum arrays may be null.
@@ -727,49 +703,33 @@ DRQ_API int drq_gemm_batched_f32(int nbatch, const float* const* A, long lda, in
                          int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
                          const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int tile,
                          int splitk, float* ws, size_t ws_bytes, drq_stream_t stream) {
-  return drq_gemm_batched_any(0, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, relu, aux, ldaux, rowsum,
-                              scatter_hw, tile, splitk, ws, ws_bytes, (hipStream_t)stream);
+  GemmCall c;
+  c.nbatch = nbatch; c.A = A; c.lda = lda; c.a_kc = a_kc; c.B = B; c.ldb = ldb; c.b_kc = b_kc; c.C = C; c.ldc = ldc;
+  c.M = M; c.N = N; c.K = K; c.bias_p = bias; c.relu = relu; c.aux_p = aux; c.ldaux = ldaux; c.rowsum_p = rowsum;
+  c.scatter_hw = scatter_hw; c.tile = tile; c.splitk = splitk; c.ws = ws; c.ws_bytes = ws_bytes;
+  c.st = (hipStream_t)stream;
+  return drq_gemm_batched_any(c);
 }
 
 DRQ_API int drq_gemm_batched_bf16(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
                           int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
                           const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int splitk,
                           float* ws, size_t ws_bytes, drq_stream_t stream) {
-  return drq_gemm_batched_any(1, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, relu, aux, ldaux, rowsum,
-                              scatter_hw, 0, splitk, ws, ws_bytes, (hipStream_t)stream);
-}
-
-
-// internal (step.hip): the forward form with the split-K sum left to the caller, in either precision: a split-K
-// result stays in `ws` as partials [nbatch*splitk][M][N] (no bias, no epilogue) and *splitk_out says how many there
-// are per problem; 1 = the result went to C as usual
-int drq_gemm_batched_partial_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B,
-                                 long ldb, int b_kc, float* const* C, long ldc, int M, int N, int K,
-                                 const float* const* bias, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st) {
-  // the fp32 trunk forward (k-contiguous operands, N <= 64, long K) has its own kernel
-  if (!bf16 && a_kc && b_kc && N <= 128 && K >= 4096 && ldc == N) {
-    int sk = 1;
-    const int rc = drq_trunk_fwd_partial(nbatch, A, lda, B, ldb, M, N, K, ws, ws_bytes, &sk, st);
-    if (rc == DRQ_OK) {
-      if (splitk_out) *splitk_out = sk;
-      return DRQ_OK;
-    }
-    if (rc != DRQ_EARG) return rc;
-  }
-  g_leave_partials = true;
-  g_last_splitk = 1;
-  const int rc = drq_gemm_batched_any(bf16, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, 0, nullptr, 0,
-                                      nullptr, 0, bf16 ? 0 : 1, 0, ws, ws_bytes, st);
-  g_leave_partials = false;
-  if (splitk_out) *splitk_out = g_last_splitk;
-  return rc;
+  GemmCall c;
+  c.bf16 = true;
+  c.nbatch = nbatch; c.A = A; c.lda = lda; c.a_kc = a_kc; c.B = B; c.ldb = ldb; c.b_kc = b_kc; c.C = C; c.ldc = ldc;
+  c.M = M; c.N = N; c.K = K; c.bias_p = bias; c.relu = relu; c.aux_p = aux; c.ldaux = ldaux; c.rowsum_p = rowsum;
+  c.scatter_hw = scatter_hw; c.splitk = splitk; c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+  return drq_gemm_batched_any(c);
 }
 
 DRQ_API int drq_gemm_batched_partial(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
                              int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias,
                              float* ws, size_t ws_bytes, int* splitk_out, drq_stream_t stream) {
-  return drq_gemm_batched_partial_any(0, nbatch, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, ws, ws_bytes,
-                                      splitk_out, (hipStream_t)stream);
+  GemmCall c;
+  c.nbatch = nbatch; c.A = A; c.lda = lda; c.a_kc = a_kc; c.B = B; c.ldb = ldb; c.b_kc = b_kc; c.C = C; c.ldc = ldc;
+  c.M = M; c.N = N; c.K = K; c.bias_p = bias; c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+  return drq_gemm_batched_partial_any(c, splitk_out);
 }
 
 // strided-batch form of the same call

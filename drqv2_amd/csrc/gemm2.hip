@@ -19,29 +19,13 @@
 //     4-5 waves per SIMD cover the rest.
 // K can be split over the 4 waves of a workgroup (KS = 4, summed in wave order through LDS: deterministic) so
 // that M*N/1024 tiles x 4 waves fill the chip.  Epilogue: bias, ReLU, ReLU mask, and the bias gradient of the
-// wgrad form (row sums of A).  drq_gemm_batched_f32 (gemm.hip) routes eligible calls here.
+// wgrad form (row sums of A).  gemm_plan.h says which calls come here (plan_batched, plan_partial, plan_pair2).
 #include "common.h"
 #include "internal.h"
 
 namespace {
 
-constexpr int MAXB2 = 8;
-
-struct G2Args {
-  const float* A[MAXB2];
-  const float* B[MAXB2];
-  float* C[MAXB2];
-  const float* bias[MAXB2];
-  const float* aux[MAXB2];
-  float* rowsum[MAXB2];
-  long lda, ldb, ldc;
-  int ldaux;
-  int M, N, K;
-  int relu;
-  unsigned a_bytes, b_bytes;
-};
-
-__device__ __forceinline__ int rowmap2(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+typedef MlpArgs G2Args;   // internal.h
 
 // one k-step (32 values of k) of one operand tile -> 16 registers
 template <bool KC>
@@ -156,14 +140,14 @@ __device__ __forceinline__ void gemm2_body(const G2Args& g, int bx, int batch) {
   float mk[16];
   const float* ap = g.aux[batch];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) mk[r] = ap ? ap[(long)(m0 + rowmap2(r, half)) * g.ldaux + n] : 1.f;
+  for (int r = 0; r < 16; ++r) mk[r] = ap ? ap[(long)(m0 + mfma32_row(r, half)) * g.ldaux + n] : 1.f;
   float* c = g.C[batch];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     float v = acc[r] + bv;
     if (g.relu) v = v > 0.f ? v : 0.f;
     v = mk[r] > 0.f ? v : 0.f;
-    c[(long)(m0 + rowmap2(r, half)) * g.ldc + n] = v;
+    c[(long)(m0 + mfma32_row(r, half)) * g.ldc + n] = v;
   }
   if constexpr (!A_KC) {
     if (do_rs && half == 0) g.rowsum[batch][m0 + col] = rs;
@@ -185,25 +169,6 @@ __global__ __launch_bounds__(256) void gemm2_pair_kernel(G2Args gw, G2Args gd, i
   else gemm2_body<true, false, KSD>(gd, (int)blockIdx.x - nxw, (int)blockIdx.z);
 }
 
-inline bool gemm2_split(const G2Args& g, int nbatch) {
-  const int tiles = (g.M / 32) * (g.N / 32);
-  // split K over the waves of a workgroup when the tiles alone leave the chip under-filled
-  return (long)tiles * nbatch < 4L * drq_num_cus() * 2 && g.K % 128 == 0 && g.K >= 512;
-}
-
-template <bool A_KC, bool B_KC>
-int launch2(const G2Args& g, int nbatch, hipStream_t st) {
-  const int tiles = (g.M / 32) * (g.N / 32);
-  const bool split = gemm2_split(g, nbatch);
-  if (split) {
-    hipLaunchKernelGGL((gemm2_kernel<A_KC, B_KC, 4>), dim3(tiles, 1, nbatch), dim3(256), 0, st, g);
-  } else {
-    hipLaunchKernelGGL((gemm2_kernel<A_KC, B_KC, 1>), dim3((tiles + 3) / 4, 1, nbatch), dim3(256), 0, st, g);
-  }
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
-}
-
 // ---- trunk forward: z = feat W^T with K = repr_dim (39200), N = feature_dim (50) (drqv2.py:71-72,91-92) --------
 // Both operands are k-contiguous and N fits two 32-column tiles (four for feature_dim 100, with TM = 1), so a wave
 // takes TM row tiles x all column tiles and a slice of K: per 32-long k-step it loads 4*(TM+2) 16-byte pieces per lane for 32*TM MFMAs -- half (TM = 1)
@@ -213,8 +178,8 @@ int launch2(const G2Args& g, int nbatch, hipStream_t st) {
 // order through LDS and the workgroup writes ONE partial record [M][N] per (problem, blockIdx.x) in the split-K
 // layout of gemm.hip, which the LayerNorm kernel sums (+ bias) in a fixed order.  No VALU work in the k loop.
 struct TrunkArgs {
-  const float* A[MAXB2];
-  const float* B[MAXB2];
+  const float* A[kGemmMaxBatch];
+  const float* B[kGemmMaxBatch];
   float* part;               // [nbatch][gridDim.x][M][N]
   long lda, ldb;
   int M, N, K;
@@ -348,7 +313,7 @@ __global__ __launch_bounds__(256, 1) void trunk_fwd_kernel(TrunkArgs g) {
         float v = acc[i][j][r];
 #pragma unroll
         for (int w = 0; w < 3; ++w) v += red[((w * TM + i) * TN + j) * 1024 + r * 64 + lane];
-        if (n < g.N) out[(long)(m0 + i * 32 + rowmap2(r, half)) * g.N + n] = v;
+        if (n < g.N) out[(long)(m0 + i * 32 + mfma32_row(r, half)) * g.N + n] = v;
       }
     }
 }
@@ -487,7 +452,7 @@ __global__ __launch_bounds__(256, 1) void trunk_wgrad_kernel(TWArgs g) {
     const int n = t * 32 + col;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = mt * 32 + rowmap2(r, half);
+      const int row = mt * 32 + mfma32_row(r, half);
       if (row < g.M) c[(long)row * g.ldc + n] = acc0[r] + acc1[r];
     }
   }
@@ -504,132 +469,60 @@ __global__ __launch_bounds__(256, 1) void trunk_wgrad_kernel(TWArgs g) {
 
 }  // namespace
 
-// internal (gemm.hip): dW [M][ldc] = A^T B with A = dz [K][lda], B = feat [K][ldb], rowsum = column sums of A.
-// Returns DRQ_EARG when the problem is not eligible (the caller then uses the LDS-tiled kernel).
-// ln_*: optional rider (see TWArgs): LayerNorm parameter gradients from dln / xhat [ln_rows][ln_F]; ln_rows = 0: none.
-int drq_trunk_wgrad_ln(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                       float* rowsum, const float* ln_dln, const float* ln_xhat, float* ln_dgamma, float* ln_dbeta,
-                       int ln_rows, int ln_F, hipStream_t st) {
-  if (M < 1 || M > 128 || N < 4096 || N % 32 || (K != 128 && K != 256 && K != 512)) return DRQ_EARG;
-  if (ln_rows > 0 && (!ln_dln || !ln_xhat || !ln_dgamma || !ln_dbeta || ln_F < 1 || ln_F > 256)) return DRQ_EARG;
-  const size_t ab = (size_t)K * lda * 4, bb = (size_t)K * ldb * 4;
-  if (ab >= (1ull << 31) || bb >= (1ull << 31)) return DRQ_EARG;
-  TWArgs g{A, B, C, rowsum, lda, ldb, ldc, M, N, K, (unsigned)ab, (unsigned)bb,
-           ln_dln, ln_xhat, ln_dgamma, ln_dbeta, ln_rows > 0 ? ln_rows : 0, ln_F};
-  const int blocks = drq_num_cus() + (ln_rows > 0 ? 1 : 0);   // one wave per SIMD (128 + 64 operand registers per lane)
+// ---- launchers: the plan (gemm_plan.h) has chosen the kernel; these fill its arguments and launch.  The first:
+// dW [M][ldc] = A^T B with A = dz [K][lda], B = feat [K][ldb], rowsum = column sums of A; c.ln: optional rider (TWArgs)
+int drq_trunk_wgrad(const GemmCall& c, const GemmPlan& p) {
+  const LnRider& ln = c.ln;
+  const bool ride = ln.rows > 0;
+  TWArgs g{c.A[0], c.B[0], c.C[0], c.rowsum_p ? c.rowsum_p[0] : nullptr, c.lda, c.ldb, c.ldc, c.M, c.N, c.K,
+           (unsigned)((size_t)c.K * c.lda * 4), (unsigned)((size_t)c.K * c.ldb * 4),
+           ln.dln, ln.xhat, ln.dgamma, ln.dbeta, ride ? ln.rows : 0, ln.F};
+  const int blocks = drq_num_cus() + (ride ? 1 : 0);   // one wave per SIMD (128 + 64 operand registers per lane)
   // K = 512 (quadruped's batch): dz^T takes 256 of the wave's 512 registers; beyond that the tiled GEMM serves
-  if (K == 512) hipLaunchKernelGGL((trunk_wgrad_kernel<16>), dim3(blocks), dim3(256), 0, st, g);
-  else if (K == 256) hipLaunchKernelGGL((trunk_wgrad_kernel<8>), dim3(blocks), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((trunk_wgrad_kernel<4>), dim3(blocks), dim3(256), 0, st, g);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  if (p.variant == GV_TRUNK_WGRAD_16) hipLaunchKernelGGL((trunk_wgrad_kernel<16>), dim3(blocks), dim3(256), 0, c.st, g);
+  else if (p.variant == GV_TRUNK_WGRAD_8) hipLaunchKernelGGL((trunk_wgrad_kernel<8>), dim3(blocks), dim3(256), 0, c.st, g);
+  else hipLaunchKernelGGL((trunk_wgrad_kernel<4>), dim3(blocks), dim3(256), 0, c.st, g);
+  return drq_launched();
 }
 
-int drq_trunk_wgrad(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                    float* rowsum, hipStream_t st) {
-  return drq_trunk_wgrad_ln(A, lda, B, ldb, C, ldc, M, N, K, rowsum, nullptr, nullptr, nullptr, nullptr, 0, 0, st);
-}
-
-// internal (gemm.hip): split-K partials [nbatch * (*splitk_out)][M][N] of A[b] B[b]^T for the trunk shape.
-// Returns DRQ_EARG when the problem is not eligible (the caller then uses the LDS-tiled kernel).
-int drq_trunk_fwd_partial(int nbatch, const float* const* A, long lda, const float* const* B, long ldb, int M, int N,
-                          int K, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st) {
-  if (nbatch <= 0 || nbatch > MAXB2 || M % 32 || M < 32 || N < 1 || N > 128 || K % 32 || K < 4096) return DRQ_EARG;
-  if (lda % 4 || ldb % 4 || !ws || ((uintptr_t)ws & 15)) return DRQ_EARG;
-  const size_t ab = (size_t)M * lda * 4, bb = (size_t)N * ldb * 4;
-  if (ab >= (1ull << 31) || bb >= (1ull << 31)) return DRQ_EARG;
+// split-K records [nbatch * p.splitk][M][N] of A[b] B[b]^T for the trunk shape, into the call's workspace
+int drq_trunk_fwd_partial(const GemmCall& c, const GemmPlan& p) {
   TrunkArgs g{};
-  for (int b = 0; b < nbatch; ++b) {
-    if (((uintptr_t)A[b] & 15) || ((uintptr_t)B[b] & 15)) return DRQ_EARG;
-    g.A[b] = A[b]; g.B[b] = B[b];
-  }
-  g.part = ws; g.lda = lda; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
-  g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
-  // one workgroup per CU (one wave per SIMD): measured 51 us against 59 us with two and 66 us with four for the
-  // four trunks of the critic update -- more concurrent row streams cost more in the memory system than the
-  // extra waves hide
-  const int steps = K / 32, cus = drq_num_cus();
-  const bool wide = N > 64;               // four column tiles per wave, one row tile
-  const bool tm2 = !wide && M % 64 == 0 && (long)nbatch * (M / 32) * 4 >= 64;
-  const int rows = tm2 ? M / 64 : M / 32;
-  int blocks_k = (cus + nbatch * rows - 1) / (nbatch * rows);
-  if (blocks_k * 4 > steps) blocks_k = steps / 4;
-  // small batches (one or two row tiles): the consumer (LayerNorm) sums the split-K records row by row, and beyond
-  // ~64 records per element that sum costs more than the extra workgroups save here
-  if (blocks_k > 64) blocks_k = 64;
-  if (blocks_k < 2) return DRQ_EARG;      // a split count of 1 means "result in C" to the callers
-  if ((size_t)nbatch * blocks_k * M * N * sizeof(float) > ws_bytes) return DRQ_EWS;
-  const dim3 grid(blocks_k, rows, nbatch);
-  if (wide) hipLaunchKernelGGL((trunk_fwd_kernel<1, 4>), grid, dim3(256), 0, st, g);
-  else if (tm2) hipLaunchKernelGGL((trunk_fwd_kernel<2>), grid, dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((trunk_fwd_kernel<1>), grid, dim3(256), 0, st, g);
-  DRQ_LAUNCH_CHECK();
-  if (splitk_out) *splitk_out = blocks_k;
-  return DRQ_OK;
+  for (int b = 0; b < c.nbatch; ++b) { g.A[b] = c.A[b]; g.B[b] = c.B[b]; }
+  g.part = c.ws; g.lda = c.lda; g.ldb = c.ldb; g.M = c.M; g.N = c.N; g.K = c.K;
+  g.a_bytes = (unsigned)((size_t)c.M * c.lda * 4); g.b_bytes = (unsigned)((size_t)c.N * c.ldb * 4);
+  const dim3 grid(p.splitk, p.rows, c.nbatch);
+  if (p.variant == GV_TRUNK_FWD_WIDE) hipLaunchKernelGGL((trunk_fwd_kernel<1, 4>), grid, dim3(256), 0, c.st, g);
+  else if (p.variant == GV_TRUNK_FWD_TM2) hipLaunchKernelGGL((trunk_fwd_kernel<2>), grid, dim3(256), 0, c.st, g);
+  else hipLaunchKernelGGL((trunk_fwd_kernel<1>), grid, dim3(256), 0, c.st, g);
+  return drq_launched();
 }
 
-// Returns DRQ_EARG when the problem is not eligible (the caller then uses the LDS-tiled kernel).
-int drq_gemm2(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb, int b_kc,
-              float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
-              const float* const* aux, int ldaux, float* const* rowsum, hipStream_t st) {
-  if (nbatch <= 0 || nbatch > MAXB2 || M % 32 || N % 32 || K % 32 || K < 64 || M < 32 || N < 32) return DRQ_EARG;
-  if (!a_kc && b_kc) return DRQ_EARG;
-  if (rowsum && a_kc) return DRQ_EARG;
-  // forward form (both operands k-contiguous): every 16-byte lane load touches its own cache line, 32 lines per
-  // instruction, and the texture addresser becomes the limit (measured 37 vs 31 us on 4 x 256x1024x1024); the
-  // LDS-tiled kernel keeps that form.  With one row-contiguous operand this kernel is 1.4-1.6x faster.
-  // (re-measured with the 32-contiguous-bytes k order: 20.4 / 38.4 / 19.7 us against 16.1 / 27.5 / 15.8 us)
-  if (a_kc && b_kc) return DRQ_EARG;
-  const size_t ab = (a_kc ? (size_t)M * lda : (size_t)K * lda) * 4, bb = (b_kc ? (size_t)N * ldb : (size_t)K * ldb) * 4;
-  if (ab >= (1ull << 31) || bb >= (1ull << 31)) return DRQ_EARG;
-  if (a_kc && lda % 4) return DRQ_EARG;
-  if (b_kc && ldb % 4) return DRQ_EARG;
-  G2Args g{};
-  for (int b = 0; b < nbatch; ++b) {
-    if ((a_kc && ((uintptr_t)A[b] & 15)) || (b_kc && ((uintptr_t)B[b] & 15))) return DRQ_EARG;
-    g.A[b] = A[b]; g.B[b] = B[b]; g.C[b] = C[b];
-    g.bias[b] = bias ? bias[b] : nullptr;
-    g.aux[b] = aux ? aux[b] : nullptr;
-    g.rowsum[b] = rowsum ? rowsum[b] : nullptr;
-  }
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.M = M; g.N = N; g.K = K; g.relu = relu;
-  g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
-  if (a_kc && b_kc) return launch2<true, true>(g, nbatch, st);
-  if (a_kc && !b_kc) return launch2<true, false>(g, nbatch, st);
-  return launch2<false, false>(g, nbatch, st);
+// workgroups of a gemm2 problem: one per tile with the K split over its waves, else four tiles per workgroup
+static int gemm2_blocks(const G2Args& g, bool split) {
+  const int tiles = (g.M / 32) * (g.N / 32);
+  return split ? tiles : (tiles + 3) / 4;
 }
 
-// wgrad + dgrad of one hidden layer in one launch (see gemm2_pair_kernel).  dy [Brows][Nout] (ld lddy), x [Brows][Kin],
-// w [Nout][ldw]: dW [Nout][Kin] = dy^T x, db [Nout] = column sums of dy, dx [Brows][Kin] = (dy w) * (mask > 0).
-// Returns DRQ_EARG when a shape is not eligible (the caller then issues the two GEMMs separately).
-int drq_gemm2_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
-                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
-                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st) {
-  if (nbatch <= 0 || nbatch > MAXB2 || Brows % 32 || Nout % 32 || Kin % 32 || Brows < 64 || Nout < 64 || Kin < 32)
-    return DRQ_EARG;
-  if (lddy % 4) return DRQ_EARG;
-  G2Args gw{}, gd{};
-  for (int b = 0; b < nbatch; ++b) {
-    if (!dy[b] || !x[b] || !dw[b] || !w[b] || !dx[b] || ((uintptr_t)dy[b] & 15)) return DRQ_EARG;
-    gw.A[b] = dy[b]; gw.B[b] = x[b]; gw.C[b] = dw[b]; gw.rowsum[b] = db ? db[b] : nullptr;
-    gd.A[b] = dy[b]; gd.B[b] = w[b]; gd.C[b] = dx[b]; gd.aux[b] = mask ? mask[b] : nullptr;
-  }
-  // wgrad: A(m = n_out, k = row) = dy[k*lddy + m], B(k, n = k_in) = x[k*ldx + n]
-  gw.lda = lddy; gw.ldb = ldx; gw.ldc = Kin; gw.M = Nout; gw.N = Kin; gw.K = Brows;
-  // dgrad: A(m = row, k = n_out) = dy[m*lddy + k], B(k, n = k_in) = w[k*ldw + n]
-  gd.lda = lddy; gd.ldb = ldw; gd.ldc = lddx; gd.ldaux = ldmask; gd.M = Brows; gd.N = Kin; gd.K = Nout;
-  const size_t dyb = (size_t)Brows * lddy * 4, xb = (size_t)Brows * ldx * 4, wb = (size_t)Nout * ldw * 4;
-  if (dyb >= (1ull << 31) || xb >= (1ull << 31) || wb >= (1ull << 31)) return DRQ_EARG;
-  gw.a_bytes = (unsigned)dyb; gw.b_bytes = (unsigned)xb;
-  gd.a_bytes = (unsigned)dyb; gd.b_bytes = (unsigned)wb;
-  const bool sw = gemm2_split(gw, nbatch), sd = gemm2_split(gd, nbatch);
-  const int tw = (gw.M / 32) * (gw.N / 32), td = (gd.M / 32) * (gd.N / 32);
-  const int nxw = sw ? tw : (tw + 3) / 4, nxd = sd ? td : (td + 3) / 4;
-  const dim3 grid(nxw + nxd, 1, nbatch);
-  if (sw && sd) hipLaunchKernelGGL((gemm2_pair_kernel<4, 4>), grid, dim3(256), 0, st, gw, gd, nxw);
-  else if (sw) hipLaunchKernelGGL((gemm2_pair_kernel<4, 1>), grid, dim3(256), 0, st, gw, gd, nxw);
-  else if (sd) hipLaunchKernelGGL((gemm2_pair_kernel<1, 4>), grid, dim3(256), 0, st, gw, gd, nxw);
-  else hipLaunchKernelGGL((gemm2_pair_kernel<1, 1>), grid, dim3(256), 0, st, gw, gd, nxw);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+int drq_gemm2(const GemmCall& c, const GemmPlan& p) {
+  const G2Args g = drq_gemm_fill(c);
+  const bool split = p.variant == GV_G2_KS4;
+  const dim3 grid(gemm2_blocks(g, split), 1, c.nbatch);
+  auto* kernel = c.a_kc ? (split ? gemm2_kernel<true, false, 4> : gemm2_kernel<true, false, 1>)
+                        : (split ? gemm2_kernel<false, false, 4> : gemm2_kernel<false, false, 1>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.st, g);
+  return drq_launched();
+}
+
+// see gemm2_pair_kernel: w is dW [Nout][Kin] = dy^T x with db = column sums of dy, d is dx [Brows][Kin] = (dy W) masked
+int drq_gemm2_wgrad_dgrad(const GemmCall& w, const GemmCall& d, const GemmPlan& p) {
+  const G2Args gw = drq_gemm_fill(w), gd = drq_gemm_fill(d);
+  const bool sw = p.split_w, sd = p.split_d;
+  const int nxw = gemm2_blocks(gw, sw);
+  const dim3 grid(nxw + gemm2_blocks(gd, sd), 1, d.nbatch);
+  if (sw && sd) hipLaunchKernelGGL((gemm2_pair_kernel<4, 4>), grid, dim3(256), 0, d.st, gw, gd, nxw);
+  else if (sw) hipLaunchKernelGGL((gemm2_pair_kernel<4, 1>), grid, dim3(256), 0, d.st, gw, gd, nxw);
+  else if (sd) hipLaunchKernelGGL((gemm2_pair_kernel<1, 4>), grid, dim3(256), 0, d.st, gw, gd, nxw);
+  else hipLaunchKernelGGL((gemm2_pair_kernel<1, 1>), grid, dim3(256), 0, d.st, gw, gd, nxw);
+  return drq_launched();
 }

@@ -21,6 +21,7 @@
 // next layer's single output row: the Q head's Linear(hidden, 1) needs no launch of its own);  1 dgrad
 // dx = (dy W) masked;  2 wgrad  dW = dy^T x with the bias gradient (row sums of dy^T) fused.
 // The weight gradient and the input gradient of one layer run as block ranges of ONE launch (gemm3_pair_kernel).
+// plan_ring (gemm_plan.h) says which calls these kernels take and at which tile; the launchers below only launch.
 #include "common.h"
 #include "internal.h"
 #include "../../include/drqv2_hip.h"
@@ -28,25 +29,7 @@
 namespace {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-constexpr int MAXB3 = 8;
-
-struct G3Args {
-  const float* A[MAXB3];
-  const float* B[MAXB3];
-  float* C[MAXB3];
-  const float* bias[MAXB3];
-  const float* aux[MAXB3];      // ReLU mask source [M][ldaux] or null
-  float* rowsum[MAXB3];         // form 2: [M] row sums of A (bias gradient) or null
-  const float* qw[MAXB3];       // form 0: weight row [N] of a following Linear(N, 1) or null
-  float* qpart[MAXB3];          //         its partial dots [M][N / BN] (column tile j holds sum over the tile's columns)
-  long lda, ldb, ldc;
-  int ldaux;
-  int M, N, K;
-  int relu;
-  unsigned a_bytes, b_bytes;
-};
-
-__device__ __forceinline__ int rowmap3(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+typedef MlpArgs G3Args;   // internal.h
 
 template <int FORM, int WM, int WN, int WK, int NS>
 struct G3Cfg {
@@ -267,7 +250,7 @@ __device__ __forceinline__ void gemm3_body(const G3Args& g, int tile, int batch,
     float mk[16];
     const float* ap = g.aux[batch];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) mk[r] = ap ? ap[(long)(mrow + rowmap3(r, h)) * g.ldaux + n] : 1.f;
+    for (int r = 0; r < 16; ++r) mk[r] = ap ? ap[(long)(mrow + mfma32_row(r, h)) * g.ldaux + n] : 1.f;
     float* c = g.C[batch];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -275,7 +258,7 @@ __device__ __forceinline__ void gemm3_body(const G3Args& g, int tile, int batch,
       if (g.relu) x = x > 0.f ? x : 0.f;
       x = mk[r] > 0.f ? x : 0.f;
       v[r] = x;
-      c[(long)(mrow + rowmap3(r, h)) * g.ldc + n] = x;
+      c[(long)(mrow + mfma32_row(r, h)) * g.ldc + n] = x;
     }
     if constexpr (FORM == 2) {
       if (do_rs && h == 0) g.rowsum[batch][mrow + i] = rs;
@@ -298,7 +281,7 @@ __device__ __forceinline__ void gemm3_body(const G3Args& g, int tile, int batch,
           for (int r = 0; r < 16; ++r) p[r] += __shfl_xor(p[r], o);
         if (i == 0) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) qred[(wm * WN + wn) * 32 + rowmap3(r, h)] = p[r];
+          for (int r = 0; r < 16; ++r) qred[(wm * WN + wn) * 32 + mfma32_row(r, h)] = p[r];
         }
       }
       __syncthreads();
@@ -349,124 +332,63 @@ __global__ __launch_bounds__(256) void gemm3_pair_kernel(G3Args gw, G3Args gd, i
   }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// shape / alignment checks shared by the entries; fills the argument block
-int fill(G3Args& g, int form, int nbatch, const float* const* A, long lda, const float* const* B, long ldb,
-         float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu, const float* const* aux,
-         int ldaux, float* const* rowsum) {
-  if (nbatch <= 0 || nbatch > MAXB3 || M % 64 || N % 32 || K % 32 || M < 64 || N < 32 || K < 64) return DRQ_EARG;
-  if (lda % 4 || ldb % 4) return DRQ_EARG;
-  const bool a_kc = form < 2, b_kc = form == 0;
-  const size_t ab = (a_kc ? (size_t)M * lda : (size_t)K * lda) * 4, bb = (b_kc ? (size_t)N * ldb : (size_t)K * ldb) * 4;
-  if (ab >= (1ull << 31) || bb >= (1ull << 31)) return DRQ_EARG;
-  for (int b = 0; b < nbatch; ++b) {
-    if (!A[b] || !B[b] || !C[b] || !al16(A[b]) || !al16(B[b])) return DRQ_EARG;
-    g.A[b] = A[b]; g.B[b] = B[b]; g.C[b] = C[b];
-    g.bias[b] = bias ? bias[b] : nullptr;
-    g.aux[b] = aux ? aux[b] : nullptr;
-    g.rowsum[b] = rowsum ? rowsum[b] : nullptr;
-  }
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.M = M; g.N = N; g.K = K; g.relu = relu;
-  g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
-  return DRQ_OK;
-}
-
 }  // namespace
 
-// internal (gemm.hip, step.hip).  Returns DRQ_EARG when the problem is not eligible (the caller then uses another kernel).
-// Forward form with optional partial dots: qw[b] = weight row [N] of a following Linear(N,1), qpart[b] = [M][*nq_out]
-// partial sums (the consumer adds them in index order, plus that layer's bias).
-int drq_gemm3_fwd(int nbatch, const float* const* A, long lda, const float* const* B, long ldb, float* const* C,
-                  long ldc, int M, int N, int K, const float* const* bias, int relu, const float* const* qw,
-                  float* const* qpart, int* nq_out, hipStream_t st) {
-  G3Args g{};
-  const int rc = fill(g, 0, nbatch, A, lda, B, ldb, C, ldc, M, N, K, bias, relu, nullptr, 0, nullptr);
-  if (rc != DRQ_OK) return rc;
-  if (N % 64) return DRQ_EARG;
-  for (int b = 0; b < nbatch; ++b) {
-    g.qw[b] = qw ? qw[b] : nullptr;
-    g.qpart[b] = qpart ? qpart[b] : nullptr;
-    if ((g.qw[b] != nullptr) != (g.qpart[b] != nullptr)) return DRQ_EARG;
-  }
-  const long t64 = (long)(M / 64) * (N / 64) * nbatch;
-  // enough 64x64 tiles to give every CU one: one sub-tile per wave; else 64x32 tiles with the k-steps of a k-tile
-  // split over two wave groups (twice the workgroups, half the MFMAs per wave)
-  if (t64 >= drq_num_cus()) {
-    if (nq_out) *nq_out = N / 64;
-    hipLaunchKernelGGL((gemm3_kernel<0, 2, 2, 1, 6>), dim3((M / 64) * (N / 64), 1, nbatch), dim3(256), 0, st, g);
-  } else {
-    if (nq_out) *nq_out = N / 32;
-    hipLaunchKernelGGL((gemm3_kernel<0, 2, 1, 2, 6>), dim3((M / 64) * (N / 32), 1, nbatch), dim3(256), 0, st, g);
-  }
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+// Forward and input-gradient forms at the plan's tile (plan_ring).  Forward with optional partial dots: qpart[b] =
+// [M][p.nq] partial sums (the consumer adds them in index order, plus that layer's bias).
+int drq_gemm3(const GemmCall& c, const GemmPlan& p) {
+  const G3Args g = drq_gemm_fill(c);
+  const bool big = p.variant == GV_G3_FWD_64x64 || p.variant == GV_G3_DGRAD_64x64;
+  const dim3 grid((c.M / 64) * (c.N / (big ? 64 : 32)), 1, c.nbatch);
+  auto* kernel = c.b_kc ? (big ? gemm3_kernel<0, 2, 2, 1, 6> : gemm3_kernel<0, 2, 1, 2, 6>)
+                        : (big ? gemm3_kernel<1, 2, 2, 1, 6> : gemm3_kernel<1, 2, 1, 2, 6>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.st, g);
+  return drq_launched();
 }
 
-// dgrad: dx [M][N] = (dy [M][K] W [K][ldb]) * (mask > 0)
-int drq_gemm3_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx,
-                    long lddx, int M, int N, int K, const float* const* mask, int ldmask, hipStream_t st) {
-  G3Args g{};
-  const int rc = fill(g, 1, nbatch, dy, lddy, w, ldw, dx, lddx, M, N, K, nullptr, 0, mask, ldmask, nullptr);
-  if (rc != DRQ_OK) return rc;
-  if (N % 64) return DRQ_EARG;
-  const long t64 = (long)(M / 64) * (N / 64) * nbatch;
-  if (t64 >= drq_num_cus())
-    hipLaunchKernelGGL((gemm3_kernel<1, 2, 2, 1, 6>), dim3((M / 64) * (N / 64), 1, nbatch), dim3(256), 0, st, g);
-  else
-    hipLaunchKernelGGL((gemm3_kernel<1, 2, 1, 2, 6>), dim3((M / 64) * (N / 32), 1, nbatch), dim3(256), 0, st, g);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
-}
-
-// wgrad + dgrad of one hidden layer in one launch.  dy [Brows][Nout] (ld lddy), x [Brows][Kin] (ld ldx), w [Nout][ldw]:
-// dW [Nout][Kin] = dy^T x, db [Nout] = column sums of dy, dx [Brows][Kin] = (dy w) * (mask > 0)
-int drq_gemm3_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
-                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
-                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st) {
-  G3Args gw{}, gd{};
-  // wgrad: A(m = n_out, k = row) = dy[k*lddy + m], B(k, n = k_in) = x[k*ldx + n]
-  int rc = fill(gw, 2, nbatch, dy, lddy, x, ldx, dw, Kin, Nout, Kin, Brows, nullptr, 0, nullptr, 0, db);
-  if (rc != DRQ_OK) return rc;
-  // dgrad: A(m = row, k = n_out) = dy[m*lddy + k], B(k, n = k_in) = w[k*ldw + n]
-  rc = fill(gd, 1, nbatch, dy, lddy, w, ldw, dx, lddx, Brows, Kin, Nout, nullptr, 0, mask, ldmask, nullptr);
-  if (rc != DRQ_OK) return rc;
-  if (Kin % 64 || Nout % 64 || Brows % 64) return DRQ_EARG;
-  const int nxw = (Nout / 64) * (Kin / 64);
-  const long td64 = (long)(Brows / 64) * (Kin / 64) * nbatch;
-  if (td64 >= drq_num_cus()) {
-    const int nxd = (Brows / 64) * (Kin / 64);
-    hipLaunchKernelGGL((gemm3_pair_kernel<2, 2, 1, 4, 2, 2, 1, 6>), dim3(nxw + nxd, 1, nbatch), dim3(256), 0, st, gw, gd,
-                       nxw);
-  } else {
-    const int nxd = (Brows / 64) * (Kin / 32);
-    hipLaunchKernelGGL((gemm3_pair_kernel<2, 2, 1, 4, 2, 1, 2, 6>), dim3(nxw + nxd, 1, nbatch), dim3(256), 0, st, gw, gd,
-                       nxw);
-  }
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+// wgrad + dgrad of one hidden layer in one launch: w is dW [Nout][Kin] = dy^T x with db = column sums of dy, d is
+// dx [Brows][Kin] = (dy W) * (mask > 0); the plan chose the input-gradient half's tile
+int drq_gemm3_wgrad_dgrad(const GemmCall& w, const GemmCall& d, const GemmPlan& p) {
+  const G3Args gw = drq_gemm_fill(w), gd = drq_gemm_fill(d);
+  const bool big = p.variant == GV_G3_PAIR_D64;
+  const int nxw = (w.M / 64) * (w.N / 64);
+  const dim3 grid(nxw + (d.M / 64) * (d.N / (big ? 64 : 32)), 1, d.nbatch);
+  auto* kernel = big ? gemm3_pair_kernel<2, 2, 1, 4, 2, 2, 1, 6> : gemm3_pair_kernel<2, 2, 1, 4, 2, 1, 2, 6>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, d.st, gw, gd, nxw);
+  return drq_launched();
 }
 
 // See include/drqv2_hip.h
 DRQ_API int drq_mlp_fwd(int nbatch, const float* const* x, long ldx, const float* const* w, long ldw, float* const* y,
                         long ldy, int M, int N, int K, const float* const* bias, int relu, const float* const* qw,
                         float* const* qpart, int* nq_out, drq_stream_t stream) {
-  if (!x || !w || !y) return DRQ_EARG;
-  return drq_gemm3_fwd(nbatch, x, ldx, w, ldw, y, ldy, M, N, K, bias, relu, qw, qpart, nq_out, (hipStream_t)stream);
+  GemmCall c;
+  c.nbatch = nbatch; c.A = x; c.lda = ldx; c.B = w; c.ldb = ldw; c.C = y; c.ldc = ldy; c.M = M; c.N = N; c.K = K;
+  c.bias_p = bias; c.relu = relu; c.qw = qw; c.qpart = qpart; c.st = (hipStream_t)stream;
+  if (!drq_gemm_prepare(c)) return DRQ_EARG;
+  const GemmPlan p = plan_ring(RING_FWD, c);
+  if (nq_out && p.variant != GV_NONE) *nq_out = p.nq;
+  return drq_gemm_launch(c, p);
 }
 
 DRQ_API int drq_mlp_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* w, long ldw,
                           float* const* dx, long lddx, int M, int N, int K, const float* const* mask, int ldmask,
                           drq_stream_t stream) {
-  if (!dy || !w || !dx) return DRQ_EARG;
-  return drq_gemm3_dgrad(nbatch, dy, lddy, w, ldw, dx, lddx, M, N, K, mask, ldmask, (hipStream_t)stream);
+  GemmCall c;
+  c.nbatch = nbatch; c.A = dy; c.lda = lddy; c.B = w; c.ldb = ldw; c.b_kc = false; c.C = dx; c.ldc = lddx; c.M = M;
+  c.N = N; c.K = K; c.aux_p = mask; c.ldaux = ldmask; c.st = (hipStream_t)stream;
+  return drq_gemm_prepare(c) ? drq_gemm_launch(c, plan_ring(RING_DGRAD, c)) : DRQ_EARG;
 }
 
 DRQ_API int drq_mlp_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
                                 float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
                                 long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin,
                                 drq_stream_t stream) {
-  if (!dy || !x || !dw || !w || !dx) return DRQ_EARG;
-  return drq_gemm3_wgrad_dgrad(nbatch, dy, lddy, x, ldx, dw, db, w, ldw, dx, lddx, mask, ldmask, Brows, Nout, Kin,
-                               (hipStream_t)stream);
+  GemmCall cw, cd;   // the halves as drq_gemm3_wgrad_dgrad describes them
+  cw.nbatch = nbatch; cw.A = dy; cw.lda = lddy; cw.a_kc = false; cw.B = x; cw.ldb = ldx; cw.b_kc = false; cw.C = dw;
+  cw.ldc = Kin; cw.M = Nout; cw.N = Kin; cw.K = Brows; cw.rowsum_p = db; cw.st = (hipStream_t)stream;
+  cd.nbatch = nbatch; cd.A = dy; cd.lda = lddy; cd.B = w; cd.ldb = ldw; cd.b_kc = false; cd.C = dx; cd.ldc = lddx;
+  cd.M = Brows; cd.N = Kin; cd.K = Nout; cd.aux_p = mask; cd.ldaux = ldmask; cd.st = (hipStream_t)stream;
+  if (!drq_gemm_prepare(cw) || !drq_gemm_prepare(cd)) return DRQ_EARG;
+  return drq_gemm_launch(cd, plan_ring(RING_PAIR, cd, &cw), &cw);
 }

@@ -4,6 +4,7 @@
 // (-z defs).  Grouped by defining file.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 // ---- layernorm.hip
 // LayerNorm+tanh of n problems; problem i may also copy tail_n (<= 64) columns of tail[i] behind its F outputs, and
@@ -53,42 +54,61 @@ int drq_policy_out_bwd(const float* da1, const float* da2, long ld, int col0, co
 int drq_adam_flat2(float* p0, const float* g0, float* m0, float* v0, long n0, long step0, float* p1, const float* g1,
                    float* m1, float* v1, long n1, long step1, double lr, float gscale, hipStream_t st);
 
-// ---- gemm.hip: either precision (bf16 != 0: bf16-MFMA kernel, fp32 storage)
-int drq_gemm_batched_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb,
-                         int b_kc, float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
-                         const float* const* aux, int ldaux, float* const* rowsum, int scatter_hw, int tile,
-                         int splitk, float* ws, size_t ws_bytes, hipStream_t st);
-int drq_gemm_batched_partial_any(int bf16, int nbatch, const float* const* A, long lda, int a_kc, const float* const* B,
-                                 long ldb, int b_kc, float* const* C, long ldc, int M, int N, int K,
-                                 const float* const* bias, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st);
+// ---- the GEMM family (gemm.hip, gemm2.hip, gemm3.hip, skinny.hip).  gemm_plan.h chooses the kernel: an entry completes
+// the call's GemmShape, asks the planner and hands call and plan to drq_gemm_launch, the one switch over the launchers.
+// the LayerNorm parameter gradients that may ride in the trunk weight gradient's launch (rows = 0: none)
+struct LnRider {
+  const float *dln = nullptr, *xhat = nullptr;
+  float *dgamma = nullptr, *dbeta = nullptr;
+  int rows = 0, F = 0;
+};
+// One call: nbatch problems of one shape, C_b = epilogue(A_b B_b).  The caller sets the shape's first block and these;
+// the optional arrays may be null and so may their elements
+struct GemmCall : GemmShape {
+  const float *const *A = nullptr, *const *B = nullptr, *const *bias_p = nullptr, *const *aux_p = nullptr;
+  float *const *C = nullptr, *const *rowsum_p = nullptr;   // rowsum: bias gradient of a weight-gradient GEMM
+  const float* const* qw = nullptr;   // ring forward: weight row and partial dots of a following Linear(N, 1)
+  float* const* qpart = nullptr;
+  bool leave_partials = false;        // a split-K result stays in ws as records, the caller sums them
+  LnRider ln;                         // rides where the plan is the trunk weight gradient's kernel, else its own launch
+  float* ws = nullptr;
+  hipStream_t st = nullptr;
+};
+// argument block shared by the kernels of gemm2.hip and gemm3.hip
+struct MlpArgs {
+  const float *A[kGemmMaxBatch], *B[kGemmMaxBatch], *bias[kGemmMaxBatch];
+  const float* qw[kGemmMaxBatch];            // ring forward: weight row [N] of a following Linear(N, 1) or null
+  float* qpart[kGemmMaxBatch];               // its partial dots [M][N / BN] (column tile j: the sum over its columns)
+  const float* aux[kGemmMaxBatch];           // ReLU mask source [M][ldaux] or null
+  float *C[kGemmMaxBatch], *rowsum[kGemmMaxBatch];   // rowsum (weight-gradient form): [M] row sums of A or null
+  long lda, ldb, ldc;
+  int ldaux, M, N, K, relu;
+  unsigned a_bytes, b_bytes;
+};
+// row of element r of a lane's 32x32 MFMA accumulator (column = lane & 31, half = lane >> 5)
+__device__ __forceinline__ int mfma32_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
-// ---- skinny.hip
-int drq_skinny_dgrad(const float* dz, long lda, const float* w, long ldb, float* c, long ldc, int M, int N, int K,
-                     const float* aux, int ldaux, int scatter_hw, hipStream_t st);
-
-// ---- gemm2.hip
-int drq_trunk_wgrad(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                    float* rowsum, hipStream_t st);
-// the trunk weight gradient with the LayerNorm parameter gradients riding in the same launch
-int drq_trunk_wgrad_ln(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                       float* rowsum, const float* ln_dln, const float* ln_xhat, float* ln_dgamma, float* ln_dbeta,
-                       int ln_rows, int ln_F, hipStream_t st);
-int drq_trunk_fwd_partial(int nbatch, const float* const* A, long lda, const float* const* B, long ldb, int M, int N,
-                          int K, float* ws, size_t ws_bytes, int* splitk_out, hipStream_t st);
-int drq_gemm2(int nbatch, const float* const* A, long lda, int a_kc, const float* const* B, long ldb, int b_kc,
-              float* const* C, long ldc, int M, int N, int K, const float* const* bias, int relu,
-              const float* const* aux, int ldaux, float* const* rowsum, hipStream_t st);
-// weight gradient + input gradient of one hidden layer in one launch
-int drq_gemm2_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
-                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
-                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st);
-
-// ---- gemm3.hip: the hidden x hidden layers on the LDS-DMA ring kernel (DRQ_EARG = shape not eligible)
-int drq_gemm3_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx,
-                    long lddx, int M, int N, int K, const float* const* mask, int ldmask, hipStream_t st);
-int drq_gemm3_wgrad_dgrad(int nbatch, const float* const* dy, long lddy, const float* const* x, long ldx,
-                          float* const* dw, float* const* db, const float* const* w, long ldw, float* const* dx,
-                          long lddx, const float* const* mask, int ldmask, int Brows, int Nout, int Kin, hipStream_t st);
+// ---- gemm.hip.  drq_gemm_prepare derives the shape's second block from the pointers; false: an operand is missing
+bool drq_gemm_prepare(GemmCall& c);
+MlpArgs drq_gemm_fill(const GemmCall& c);
+// GV_NONE -> DRQ_EARG, GV_EWS -> DRQ_EWS; w: the weight-gradient half of a pair plan (c is the input-gradient half)
+int drq_gemm_launch(const GemmCall& c, const GemmPlan& p, const GemmCall* w = nullptr);
+int drq_gemm_batched_any(GemmCall c);
+// the forward form with the split-K sum left to the caller: *splitk_out records per problem in ws, 1 = result in C
+int drq_gemm_batched_partial_any(GemmCall c, int* splitk_out);
+// both gradients of one hidden layer (w: dW = dy^T x with db, d: dx = (dy W) masked): one launch where a pair kernel
+// takes the shapes (the ring kernel's if ring_pair asks for it, else the LDS-free kernel's in fp32), else two calls
+int drq_gemm_wgrad_dgrad(GemmCall w, GemmCall d, bool ring_pair);
+// ---- skinny.hip, gemm2.hip, gemm3.hip: launchers of a planned call (w, d: the halves of a pair)
+// what a launcher returns after its launch: 0 or the hipError_t
+inline int drq_launched() { DRQ_LAUNCH_CHECK(); return DRQ_OK; }
+int drq_skinny_dgrad(const GemmCall& c);
+int drq_trunk_wgrad(const GemmCall& c, const GemmPlan& p);
+int drq_trunk_fwd_partial(const GemmCall& c, const GemmPlan& p);
+int drq_gemm2(const GemmCall& c, const GemmPlan& p);
+int drq_gemm2_wgrad_dgrad(const GemmCall& w, const GemmCall& d, const GemmPlan& p);
+int drq_gemm3(const GemmCall& c, const GemmPlan& p);
+int drq_gemm3_wgrad_dgrad(const GemmCall& w, const GemmCall& d, const GemmPlan& p);
 
 // ---- rowblock.hip: LayerNorm+tanh fused with the first MLP layers; policy output layer + sample fused with the
 // target critic's first layers (DRQ_EARG = shape not eligible)

@@ -17,8 +17,6 @@ namespace {
 
 constexpr unsigned kDropOff = 0x80000000u;   // buffer offset beyond any num_records: load returns 0, store is dropped
 
-__device__ __forceinline__ int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 struct SkinnyD {
   const float* dz;    // [M][lda]
   const float* w;     // [K][ldb]
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(256, (KP <= 32 ? 5 : 2)) void skinny_dgrad_kernel(S
     const int m0 = mbase + mt * 32;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + rowmap(r, half);
+      const int m = m0 + mfma32_row(r, half);
       const unsigned off = (m < g.M && nok) ? (unsigned)(((long)m * g.ldaux + n) * 4) : kDropOff;
       mv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ars, off, 0, 0));
     }
@@ -108,7 +106,7 @@ __global__ __launch_bounds__(256, (KP <= 32 ? 5 : 2)) void skinny_dgrad_kernel(S
     for (int kp = 0; kp < KP; ++kp) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * kp * MP], wv[kp], acc, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + rowmap(r, half);
+      const int m = m0 + mfma32_row(r, half);
       float v = acc[r];
       if (use_mask) v = mv[r] > 0.f ? v : 0.f;
       const unsigned off = (m < g.M && nok) ? (unsigned)(((long)m * crow + cn) * 4) : kDropOff;
@@ -120,14 +118,14 @@ __global__ __launch_bounds__(256, (KP <= 32 ? 5 : 2)) void skinny_dgrad_kernel(S
 
 }  // namespace
 
-// ---- launchers used by drq_gemm_batched_f32 (gemm.hip); return DRQ_EARG when the shape is not theirs -------------
-int drq_skinny_dgrad(const float* dz, long lda, const float* w, long ldb, float* c, long ldc, int M, int N, int K,
-                     const float* aux, int ldaux, int scatter_hw, hipStream_t st) {
-  if (K > 128 || N % 32 != 0) return DRQ_EARG;
-  const long crow = scatter_hw > 0 ? 32L * (scatter_hw + 4) * (scatter_hw + 4) : ldc;
-  const size_t cb = (size_t)M * crow * 4, ab = aux ? (size_t)M * ldaux * 4 : 0;
-  if (cb >= (1ull << 31) || ab >= (1ull << 31)) return DRQ_EARG;
-  SkinnyD g{dz, w, aux, c, lda, ldb, ldc, ldaux, M, N, K, scatter_hw, (unsigned)cb, (unsigned)ab, 0, 0, 0};
+// ---- launcher: plan_batched (gemm_plan.h) sends the one-problem dgrad calls with N >= 4096, K <= 128 here -----------
+int drq_skinny_dgrad(const GemmCall& c) {
+  const int M = c.M, N = c.N, K = c.K;
+  const float* aux = c.aux_p ? c.aux_p[0] : nullptr;
+  const long crow = c.scatter_hw > 0 ? 32L * (c.scatter_hw + 4) * (c.scatter_hw + 4) : c.ldc;
+  const size_t cb = (size_t)M * crow * 4, ab = aux ? (size_t)M * c.ldaux * 4 : 0;
+  SkinnyD g{c.A[0], c.B[0], aux, c.C[0], c.lda, c.ldb, c.ldc, c.ldaux, M, N, K, c.scatter_hw, (unsigned)cb, (unsigned)ab,
+            0, 0, 0};
   const int mtiles = (M + 31) / 32;
   g.mt_per_block = mtiles >= 4 ? 2 : mtiles;     // 4 workgroups along M at B = 256: ~5 waves per SIMD
   if (K > 64 && g.mt_per_block > 2) g.mt_per_block = 2;   // dynamic LDS stays under 64 KB
@@ -138,10 +136,8 @@ int drq_skinny_dgrad(const float* dz, long lda, const float* w, long ldb, float*
   // the two feature dimensions of the reference's configs (50, 100) get exact register tiles
   const int kp = K == 50 ? 25 : K <= 64 ? 32 : K == 100 ? 50 : 64;
   const size_t lds = (size_t)2 * kp * (MB + 33) * 4;
-  if (kp == 25) hipLaunchKernelGGL(skinny_dgrad_kernel<25>, grid, dim3(256), lds, st, g);
-  else if (kp == 32) hipLaunchKernelGGL(skinny_dgrad_kernel<32>, grid, dim3(256), lds, st, g);
-  else if (kp == 50) hipLaunchKernelGGL(skinny_dgrad_kernel<50>, grid, dim3(256), lds, st, g);
-  else hipLaunchKernelGGL(skinny_dgrad_kernel<64>, grid, dim3(256), lds, st, g);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  auto* kernel = kp == 25 ? skinny_dgrad_kernel<25> : kp == 32 ? skinny_dgrad_kernel<32>
+                 : kp == 50 ? skinny_dgrad_kernel<50> : skinny_dgrad_kernel<64>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, c.st, g);
+  return drq_launched();
 }

@@ -231,32 +231,52 @@ struct Ctx {
   float* gemm_ws() const { return ws(W_GEMM_WS); }
   size_t gemm_ws_bytes() const { return (size_t)kGemmWsFloats * sizeof(float); }
 
+  // n problems of one shape on the update's precision, workspace and stream; the rest of a call is set by name
+  GemmCall gemm(int n, const float* const* A, long lda, int a_kc, const float* const* B, long ldb, int b_kc,
+                float* const* C, long ldc, int M, int N, int K) const {
+    GemmCall c;
+    c.bf16 = bf16(); c.nbatch = n; c.A = A; c.lda = lda; c.a_kc = a_kc; c.B = B; c.ldb = ldb; c.b_kc = b_kc; c.C = C;
+    c.ldc = ldc; c.M = M; c.N = N; c.K = K; c.ws = gemm_ws(); c.ws_bytes = gemm_ws_bytes(); c.st = st;
+    return c;
+  }
   // n problems  y_i = act(x_i W_i^T + b_i)
+  GemmCall fwd_call(int n, const float* const* x, long ldx, const float* const* w, const float* const* b,
+                    float* const* y, long ldy, int M, int N, int K, int relu = 0) const {
+    GemmCall c = gemm(n, x, ldx, 1, w, K, 1, y, ldy, M, N, K);
+    c.bias_p = b; c.relu = relu;
+    return c;
+  }
   int fwd(int n, const float* const* x, long ldx, const float* const* w, const float* const* b, float* const* y,
           long ldy, int M, int N, int K, int relu) const {
-    return drq_gemm_batched_any(bf16(), n, x, ldx, 1, w, K, 1, y, ldy, M, N, K, b, relu, nullptr, 0, nullptr, 0, 0, 0,
-                                gemm_ws(), gemm_ws_bytes(), st);
+    return drq_gemm_batched_any(fwd_call(n, x, ldx, w, b, y, ldy, M, N, K, relu));
   }
   // n problems  dx_i = (dy_i W_i) * (mask_i > 0);  W_i is [K][ldw] row-major, the first Nout columns are used
-  int dgrad(int n, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx, long lddx,
-            int M, int Nout, int K, const float* const* mask, int ldmask) const {
+  GemmCall dgrad_call(int n, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx,
+                      long lddx, int M, int Nout, int K, const float* const* mask, int ldmask) const {
+    GemmCall c = gemm(n, dy, lddy, 1, w, ldw, 0, dx, lddx, M, Nout, K);
+    c.aux_p = mask; c.ldaux = ldmask;
     // two or more hidden x hidden problems: the LDS-DMA ring kernel (measured 15.8 against 19.2 us for the two heads of
     // the actor update; one problem of 2B rows: the LDS-free kernel is as fast)
-    if (use_gemm3() && n >= 2 && K >= 256 && Nout >= 256) {
-      const int rc = drq_gemm3_dgrad(n, dy, lddy, w, ldw, dx, lddx, M, Nout, K, mask, ldmask, st);
-      if (rc != DRQ_EARG) return rc;
-    }
-    return drq_gemm_batched_any(bf16(), n, dy, lddy, 1, w, ldw, 0, dx, lddx, M, Nout, K, nullptr, 0, mask, ldmask, nullptr, 0,
-                                0, 0, gemm_ws(), gemm_ws_bytes(), st);
+    c.ring = use_gemm3() && n >= 2 && K >= 256 && Nout >= 256;
+    return c;
+  }
+  int dgrad(int n, const float* const* dy, long lddy, const float* const* w, long ldw, float* const* dx, long lddx,
+            int M, int Nout, int K, const float* const* mask, int ldmask) const {
+    return drq_gemm_batched_any(dgrad_call(n, dy, lddy, w, ldw, dx, lddx, M, Nout, K, mask, ldmask));
   }
   // n problems  dW_i = dy_i^T x_i ([N][K] row-major), db_i = column sums of dy_i (fused)
-  int wgrad(int n, const float* const* dy, long lddy, const float* const* x, long ldx, float* const* dw,
-            float* const* db, int Brows, int N, int K) const {
+  GemmCall wgrad_call(int n, const float* const* dy, long lddy, const float* const* x, long ldx, float* const* dw,
+                      float* const* db, int Brows, int N, int K) const {
+    GemmCall c = gemm(n, dy, lddy, 0, x, ldx, 0, dw, K, N, K, Brows);
+    c.rowsum_p = db;
     // the trunk's weight gradient (N = feature_dim rows, K = 39200 columns, reduction over the batch) at small
     // batches: the register-resident fp32 kernel beats the tiled bf16 GEMM (19 vs 31 us at B=256; 269 vs 153 at 2048)
-    const int prec = (bf16() && N <= 128 && K >= 4096 && Brows < 512) ? 0 : bf16();
-    return drq_gemm_batched_any(prec, n, dy, lddy, 0, x, ldx, 0, dw, K, N, K, Brows, nullptr, 0, nullptr, 0, db, 0, 0, 0,
-                                gemm_ws(), gemm_ws_bytes(), st);
+    if (N <= 128 && K >= 4096 && Brows < 512) c.bf16 = false;
+    return c;
+  }
+  int wgrad(int n, const float* const* dy, long lddy, const float* const* x, long ldx, float* const* dw,
+            float* const* db, int Brows, int N, int K) const {
+    return drq_gemm_batched_any(wgrad_call(n, dy, lddy, x, ldx, dw, db, Brows, N, K));
   }
   // The trunk's weight gradient dW = dz^T feat (+ bias gradient) with the LayerNorm parameter gradients of the same
   // trunk riding in the launch (one extra workgroup) when the dedicated kernel takes the shape; `ride` says whether
@@ -265,31 +285,20 @@ struct Ctx {
   int trunk_wgrad(const float* dz, const float* feat, float* gw, float* gb, bool ride, const float* dln,
                   const float* xhat, float* dgamma, float* dbeta) const {
     const int B = s->B, F = s->F;
-    if (ride) {
-      const int rc = drq_trunk_wgrad_ln(dz, F, feat, R, gw, R, F, (int)R, B, gb, dln, xhat, dgamma, dbeta, B, F, st);
-      if (rc != DRQ_EARG) return rc;
-      const int rc2 = drq_ln_param_grad(dln, xhat, dgamma, dbeta, B, F, st);
-      if (rc2 != 0) return rc2;
-    }
     const float *dzp[1] = {dz}, *xp[1] = {feat};
     float *gwp[1] = {gw}, *gbp[1] = {gb};
-    return wgrad(1, dzp, F, xp, R, gwp, gbp, B, F, (int)R);
+    GemmCall c = wgrad_call(1, dzp, F, xp, R, gwp, gbp, B, F, (int)R);
+    if (ride) c.ln = LnRider{dln, xhat, dgamma, dbeta, B, F};
+    return drq_gemm_batched_any(c);
   }
-  // both gradients of one layer (they read the same dy and are independent): one launch when the shape allows
+  // both gradients of one layer (they read the same dy and are independent): one launch when the shape allows -- both
+  // heads of the critic on the LDS-DMA ring kernel (25.5 against 32.6 us), else the LDS-free kernel's pair in fp32
   int wgrad_dgrad(int n, const float* const* dy, long lddy, const float* const* x, long ldx, float* const* dw,
                   float* const* db, const float* const* w, long ldw, float* const* dx, long lddx,
                   const float* const* mask, int ldmask, int Brows, int N, int K) const {
-    if (use_gemm3() && n >= 2) {   // both heads of the critic: the LDS-DMA ring kernel (25.5 against 32.6 us)
-      const int rc = drq_gemm3_wgrad_dgrad(n, dy, lddy, x, ldx, dw, db, w, ldw, dx, lddx, mask, ldmask, Brows, N, K, st);
-      if (rc != DRQ_EARG) return rc;
-    }
-    if (!bf16()) {
-      const int rc = drq_gemm2_wgrad_dgrad(n, dy, lddy, x, ldx, dw, db, w, ldw, dx, lddx, mask, ldmask, Brows, N, K, st);
-      if (rc != DRQ_EARG) return rc;
-    }
-    const int rc = wgrad(n, dy, lddy, x, ldx, dw, db, Brows, N, K);
-    if (rc != 0) return rc;
-    return dgrad(n, dy, lddy, w, ldw, dx, lddx, Brows, K, N, mask, ldmask);
+    return drq_gemm_wgrad_dgrad(wgrad_call(n, dy, lddy, x, ldx, dw, db, Brows, N, K),
+                                dgrad_call(n, dy, lddy, w, ldw, dx, lddx, Brows, K, N, mask, ldmask),
+                                use_gemm3() && n >= 2);
   }
 };
 
@@ -424,7 +433,7 @@ int phase_critic_heads(const Ctx& c) {
     float* y[4] = {z4, z4 + (long)B * F, z4 + 2L * B * F, z4 + 3L * B * F};
     // the GEMM leaves its split-K partials in the workspace: the LayerNorm kernel sums them (+ bias) itself
     int sk = 1;
-    CK(drq_gemm_batched_partial_any(c.bf16(), 4, x, R, 1, w, R, 1, y, F, B, F, (int)R, b, c.gemm_ws(), c.gemm_ws_bytes(), &sk, st));
+    CK(drq_gemm_batched_partial_any(c.fwd_call(4, x, R, w, b, y, F, B, F, (int)R), &sk));
     const float* zz[4] = {y[0], y[1], y[2], y[3]};
     const float* gm[4] = {c.p(cr.ln_g), c.p(ac.ln_g), c.p(ac.ln_g), c.p(tg.ln_g)};
     const float* bt[4] = {c.p(cr.ln_b), c.p(ac.ln_b), c.p(ac.ln_b), c.p(tg.ln_b)};
@@ -532,8 +541,7 @@ int phase_critic_heads(const Ctx& c) {
     // layer 1 (input = [h, action], shared by both heads)
     CK(c.wgrad(2, dc1c, H, hac, FA, gw0, gb0, B, H, FA));
     // the split-K partials of this dgrad stay in the workspace: the LayerNorm backward sums them (both heads)
-    CK(drq_gemm_batched_partial_any(c.bf16(), 2, dc1c, H, 1, w0, FA, 0, dha, FA, B, FA, H, nullptr, c.gemm_ws(), c.gemm_ws_bytes(),
-                                &sk_dha, st));
+    CK(drq_gemm_batched_partial_any(c.gemm(2, dc1c, H, 1, w0, FA, 0, dha, FA, B, FA, H), &sk_dha));
   }
   // trunk: LayerNorm+tanh backward, then Linear(R -> F)
   const bool ride = c.ln_rides();
@@ -548,8 +556,9 @@ int phase_critic_heads(const Ctx& c) {
     // d feat = dz W_t, masked by relu(conv4) and scattered into the padded conv-gradient layout
     // (fp32 in both precisions: this product is bound by its 8 bytes per output element, not by arithmetic, and the
     // dedicated kernel moves them faster than the tiled bf16 GEMM: 29 vs 49 us at B=256, 317 vs 371 us at B=2048)
-    CK(drq_gemm_batched_any(0, 1, dz, F, 1, w, R, 0, dy4, 0, B, (int)R, F, nullptr, 0, mk, (int)R, nullptr, 35, 0, 0,
-                            c.gemm_ws(), c.gemm_ws_bytes(), st));
+    GemmCall dfeat = c.gemm(1, dz, F, 1, w, R, 0, dy4, 0, B, (int)R, F);
+    dfeat.bf16 = false; dfeat.aux_p = mk; dfeat.ldaux = (int)R; dfeat.scatter_hw = 35;
+    CK(drq_gemm_batched_any(dfeat));
   }
 
   return 0;
@@ -671,7 +680,7 @@ int phase_actor_forward(const Ctx& c, bool with_opt = true) {
     const float *x[1] = {feat_obs}, *w[1] = {c.p(cr.trunk_w)}, *b[1] = {c.p(cr.trunk_b)};
     float* y[1] = {c.ws(W_Z_C2)};
     int sk = 1;
-    CK(drq_gemm_batched_partial_any(c.bf16(), 1, x, R, 1, w, R, 1, y, F, B, F, (int)R, b, c.gemm_ws(), c.gemm_ws_bytes(), &sk, st));
+    CK(drq_gemm_batched_partial_any(c.fwd_call(1, x, R, w, b, y, F, B, F, (int)R), &sk));
     const float *zz[1] = {y[0]}, *gm[1] = {c.p(cr.ln_g)}, *bt[1] = {c.p(cr.ln_b)};
     float* out[1] = {c.ws(W_HA_C2)};
     const int ldo[1] = {FA};
@@ -740,8 +749,7 @@ int phase_actor_backward(const Ctx& c) {
     // action columns of layer 1 only; with the fused output-layer backward the split-K partials stay in the
     // workspace and that kernel sums them
     if (fused_head)
-      CK(drq_gemm_batched_partial_any(c.bf16(), 2, dc1c, H, 1, w0a, FA, 0, da, A, B, A, H, nullptr, c.gemm_ws(), c.gemm_ws_bytes(),
-                                  &sk_da, st));
+      CK(drq_gemm_batched_partial_any(c.gemm(2, dc1c, H, 1, w0a, FA, 0, da, A, B, A, H), &sk_da));
     else
       CK(c.dgrad(2, dc1c, H, w0a, FA, da, A, B, A, H, nullptr, 0));
   }
@@ -771,8 +779,7 @@ int phase_actor_backward(const Ctx& c) {
     }
     CK(c.wgrad_dgrad(1, dp2c, H, p1, H, gw1, gb1, w1, H, dp1, H, p1, H, B, H, H));
     CK(c.wgrad(1, dp1c, H, h, F, gw0, gb0, B, H, F));
-    CK(drq_gemm_batched_partial_any(c.bf16(), 1, dp1c, H, 1, w0, F, 0, dh, F, B, F, H, nullptr, c.gemm_ws(), c.gemm_ws_bytes(), &sk_dh,
-                                st));
+    CK(drq_gemm_batched_partial_any(c.gemm(1, dp1c, H, 1, w0, F, 0, dh, F, B, F, H), &sk_dh));
   }
   const bool ride = c.ln_rides();
   CK(drq_ln_tanh_bwd_part(c.ws(W_DH_A), F, nullptr, 0, c.ws(W_HROWS), F, c.ws(W_XHAT_A), c.ws(W_RSTD_A), c.p(ac.ln_g),

@@ -1,18 +1,14 @@
 """The host-side dispatch of the fp32 GEMM family, restated in plain Python, and the table of op-test cases built on it
 (a helper module: not collected, needs no GPU).
 
-One public call can land on many kernels depending on shape, alignment and the CU count.  The functions below mirror,
-rule for rule, the selection code of
-
-  csrc/gemm3.hip   fill(), drq_gemm3_fwd(), drq_gemm3_dgrad(), drq_gemm3_wgrad_dgrad(), xcd_decode()
-  csrc/gemm2.hip   drq_gemm2(), gemm2_split(), launch2(), drq_trunk_wgrad_ln(), drq_trunk_fwd_partial()
-  csrc/skinny.hip  drq_skinny_dgrad()
-  csrc/gemm.hip    drq_gemm_batched_any() (the fp32 half), launch(), dispatch(), drq_gemm_batched_partial_any()
-
-(the 2 GiB operand-size refusals are left out: no test shape comes near them).  A change to one of those functions has
-to be repeated here; tests/test_cpu_gemm_variants.py then says which variant lost its test row or which threshold is
-no longer tested on both sides, and tests/test_hip_gemm_variants.py asserts the two decisions the ABI shows
-(*nq_out of drq_mlp_fwd, *splitk_out of drq_gemm_batched_partial).
+One public call can land on many kernels depending on shape, alignment and the CU count.  The library decides that in
+one place, the planners of drqv2_amd/csrc/gemm_plan.h (plan_ring, plan_batched, plan_partial); the functions below
+restate their fp32 rules (the 2 GiB operand-size refusals are left out: no test shape comes near them) and also record
+each threshold decision on the way, which the planner does not.  tests/test_cpu_gemm_variants.py compiles the planner
+for the host and holds this restatement to it, variant, split count and nq, over the table and a sweep across every
+threshold; it also says which variant lost its test row or which threshold is no longer tested on both sides.
+tests/test_hip_gemm_variants.py asserts the two decisions the ABI shows (*nq_out of drq_mlp_fwd, *splitk_out of
+drq_gemm_batched_partial).
 
 Every function returns a Sel: the variant name (EARG = the entry refuses), the split count where there is one, the
 number of partial-dot columns of the forward, and the threshold decisions it took on the way (name -> bool).
@@ -45,7 +41,7 @@ def _sel(name, d, split=None, nq=None):
     return Sel(name, split, nq, dict(d))
 
 
-# ---------------------------------------------------------------------------------------------- csrc/gemm3.hip
+# ---------------------------------------------------------------------------------------------- plan_ring
 def _g3_fill(n, M, N, K, lda, ldb, aligned):
     if n <= 0 or n > 8 or M % 64 or N % 32 or K % 32 or M < 64 or N < 32 or K < 64:
         return False
@@ -98,7 +94,7 @@ def ring_pair(n, Brows, Nout, Kin, lddy=None, ldx=None, ldw=None, aligned=True, 
     return _sel("g3_pair_d64" if big else "g3_pair_d32", d)
 
 
-# ------------------------------------------------------------------- csrc/gemm.hip, gemm2.hip, skinny.hip (fp32)
+# ------------------------------------------------------------------- plan_batched, plan_partial (fp32)
 def batched(layout, n, M, N, K, lda=None, ldb=None, a_al=True, b_al=True, tile=0, splitk=0, bias=False, relu=False,
             aux=False, rowsum=False, scatter_hw=0, cus=CUS, _d=None):
     """drq_gemm_batched_f32 / drq_gemm_f32 -> drq_gemm_batched_any(bf16 = 0)"""
@@ -109,16 +105,16 @@ def batched(layout, n, M, N, K, lda=None, ldb=None, a_al=True, b_al=True, tile=0
     if M <= 0 or N <= 0 or K <= 0 or n <= 0 or n > 8 or (rowsum and a_kc):
         return _sel(EARG, d)
     plain = n == 1 and tile == 0 and splitk == 0 and not bias and not relu
-    # drq_skinny_dgrad (refuses K > 128 itself)
+    # the skinny dgrad kernel
     if plain and layout == "dgrad" and not rowsum and N % 32 == 0:
         if d("skinny.N>=4096", N >= 4096) and d("skinny.K<=128", K <= 128):
             return _sel("skinny_dgrad", d)
-    # drq_trunk_wgrad
+    # the trunk weight gradient
     if plain and scatter_hw == 0 and layout == "wgrad" and not aux:
         if d("trunk_wgrad.M<=128", M <= 128) and d("trunk_wgrad.N>=4096", N >= 4096) and N % 32 == 0:
             if d("trunk_wgrad.K in {128,256,512}", K in (128, 256, 512)):
                 return _sel("trunk_wgrad_%d" % (K // 32), d)
-    # drq_gemm2 (refuses the forward layout)
+    # the LDS-free kernel (not the forward layout)
     if tile == 0 and splitk == 0 and scatter_hw == 0:
         ok = M % 32 == 0 and N % 32 == 0 and K % 32 == 0 and K >= 64 and M >= 32 and N >= 32 and not b_kc
         if a_kc:
@@ -148,7 +144,7 @@ def batched(layout, n, M, N, K, lda=None, ldb=None, a_al=True, b_al=True, tile=0
     if b_kc:
         v4 = v4 and ldb % 4 == 0 and b_al
     if layout == "wgrad":
-        v4 = False                                   # dispatch(): both operands row-contiguous -> the scalar loaders
+        v4 = False                                   # both operands row-contiguous -> the scalar loaders
     else:
         d("lds.v4", v4)
     if tile not in (2, 3, 4, 5, 6):
@@ -178,7 +174,7 @@ def partial(n, M, N, K, lda=None, ldb=None, ldc=None, aligned=True, cus=CUS):
                 bk = 64
             if bk >= 2:
                 return _sel("trunk_fwd_wide" if wide else "trunk_fwd_tm2" if tm2 else "trunk_fwd_tm1", d, split=bk)
-    return batched("fwd", n, M, N, K, lda, ldb, aligned, aligned, tile=1, _d=d)
+    return batched("fwd", n, M, N, K, lda, ldb, aligned, aligned, tile=1, cus=cus, _d=d)
 
 
 VARIANTS = (
