@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // The library is built with -fvisibility=hidden: only the entry points declared in include/drqv2_hip.h carry
 // DRQ_API, which exports them with C linkage; everything else (kernels' host stubs, the cross-file launchers of
@@ -23,9 +24,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 
-// Encoder geometry (drqv2.py:55-59): 84 -(k3,s2)-> 41 -> 39 -> 37 -> 35, 32 channels.
-static constexpr int kEncH[5] = {84, 41, 39, 37, 35};
-static constexpr int kCout = 32;
+static constexpr int kCout = 32;   // output channels of every encoder layer (geometry: kEncH, conv_plan.h)
 
 // Per-device host-side caches (the CU count, "kernel attribute already set" flags) are indexed by the current HIP
 // device: an agent on cuda:1 must not reuse what was established for cuda:0.
@@ -45,6 +44,25 @@ static inline int drq_num_cus() {
     n[dev] = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
   }
   return n[dev];
+}
+
+// raises Kernel's dynamic LDS limit to `bytes`, once per device (every instantiation has its own flags): 0 or the hipError_t
+template <auto Kernel>
+int drq_max_dynamic_lds(int bytes) {
+  static bool done[kMaxDevices] = {};
+  bool& d = done[drq_device()];
+  if (d) return DRQ_OK;
+  const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  d = e == hipSuccess;
+  return (int)e;
+}
+
+// f(std::integral_constant<int, H>) for the H of HS... that equals h; DRQ_EARG where none does
+template <int... HS, class F>
+int drq_dispatch(int h, F&& f) {
+  int rc = DRQ_EARG;
+  (void)((h == HS && ((rc = f(std::integral_constant<int, HS>{})), true)) || ...);
+  return rc;
 }
 
 // grid of a flat grid-stride kernel over n elements: one thread per element up to eight workgroups per CU

@@ -672,41 +672,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad3_kernel(WgradArgs a) {
   }
 }
 
-// Sums the per-block partial records in a fixed order and scatters to the canonical layouts.
-// Block = 64 record elements x 16 groups of partials (1024 threads).
-template <int CIN, bool SMALL>
-__global__ __launch_bounds__(1024) void conv3x3_wgrad_reduce_kernel(const float* part, int nblocks, float* dw,
-                                                                    float* db) {
-  constexpr int NT = SMALL ? 3 : 9;
-  constexpr int PART = NT * 1024 + 64;
-  __shared__ float sm[16][64];
-  const int e = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + e;        // PART is a multiple of 64
-  float s = 0.f;
-  for (int k = grp; k < nblocks; k += 16) s += part[(long)k * PART + i];
-  sm[grp][e] = s;
-  __syncthreads();
-  if (grp != 0) return;
-  float tot = 0.f;
-#pragma unroll
-  for (int g = 0; g < 16; ++g) tot += sm[g][e];
-  if (i < NT * 1024) {
-    const int t = i >> 10, r = (i >> 6) & 15, lane = i & 63;
-    const int col = lane & 31, half = lane >> 5;
-    const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (SMALL) {
-      if (col < CIN * 3) dw[(co * CIN + col / 3) * 9 + t * 3 + col % 3] = tot;
-    } else {
-      if (col < CIN) dw[(co * CIN + col) * 9 + t] = tot;
-    }
-  } else {
-    // bias partials: lane (cout, half); the two halves hold even / odd pixels
-    const float other = __shfl_xor(tot, 32);
-    if (e < 32) db[e] = tot + other;
-  }
-}
-
-// the same reduction for up to 4 layers in one launch (blockIdx.y = layer): the encoder backward defers the four
+// Sums the per-block partial records in a fixed order and scatters to the canonical layouts, for up to 4 layers in one
+// launch (blockIdx.y = layer; block = 64 record elements x 16 groups of partials): the encoder backward defers the four
 // per-layer reductions to its end (nothing reads dW/db before the optimiser step)
 struct ReduceJob {
   const float* part;
@@ -755,125 +722,90 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_reduce_multi_kernel(Reduce
   }
 }
 
-template <int CIN, int HIN, int STRIDE, int BLK, int TPW, bool MASK = false>
-int launch_conv_v(const ConvArgs& a, hipStream_t st) {
-  constexpr int HOUT = (HIN - 3) / STRIDE + 1;
-  const long ntiles = ((long)a.nb * HOUT * HOUT + 31) / 32;
-  long blocks = (ntiles + 8 * TPW - 1) / (8 * TPW);
-  const long cap = (long)BLK * drq_num_cus();
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+// f(Geom) for conv1 (9, 84, 2) or a 32 -> 32 stride-1 layer with hin among HS...; DRQ_EARG for anything else
+template <int CIN, int HIN, int STRIDE>
+struct Geom {
+  static constexpr int cin = CIN, hin = HIN, stride = STRIDE;
+};
+template <int... HS, class F>
+int conv_dispatch(int cin, int hin, int stride, F&& f) {
+  if (cin == 9 && hin == 84 && stride == 2) return f(Geom<9, 84, 2>{});
+  if (cin != 32 || stride != 1) return DRQ_EARG;
+  return drq_dispatch<HS...>(hin, [&](auto h) { return f(Geom<32, decltype(h)::value, 1>{}); });
+}
+
+template <class G>
+int launch_conv(G, const ConvArgs& a, hipStream_t st) {
+  const ConvPlan p = plan_conv_direct(drq_num_cus(), a.nb, G::hin, G::stride);
   // Pin the residency to exactly BLK workgroups per CU: registers and the static LDS alone would admit BLK+1, and
   // the dispatcher then packs BLK+1 on some CUs and leaves others short (a one-wave grid of equal-length
   // workgroups then runs at the pace of the over-filled CUs: measured -12 % on an MFMA-only probe).  Unused
   // dynamic LDS raises the group segment just past 160 KB / (BLK+1).
-  constexpr int NS = ((CIN + 1) / 2) * 9;
+  constexpr int BLK = kConvBlk, TPW = kConvTpw, NS = ((G::cin + 1) / 2) * 9;
   constexpr int static_lds = NS * 73 * 4 + 32 * 4;
   constexpr int want = 160 * 1024 / (BLK + 1) + 1024;
-  const int pad = want > static_lds ? ((want - static_lds + 255) & ~255) : 0;
-  hipLaunchKernelGGL((conv3x3_kernel<CIN, HIN, STRIDE, BLK, TPW, MASK>), dim3((unsigned)blocks), dim3(512), pad, st, a);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
-}
-
-template <int CIN, int HIN, int STRIDE>
-int launch_conv(const ConvArgs& a, hipStream_t st) {
-  if (a.mask) {
-    if constexpr (CIN == 32) return launch_conv_v<CIN, HIN, STRIDE, 2, 1, true>(a, st);
-    else return DRQ_EARG;
-  }
-  return launch_conv_v<CIN, HIN, STRIDE, 2, 1>(a, st);
+  constexpr int pad = want > static_lds ? ((want - static_lds + 255) & ~255) : 0;
+  const dim3 g((unsigned)p.grid), t(512);
+  if (!a.mask) hipLaunchKernelGGL((conv3x3_kernel<G::cin, G::hin, G::stride, BLK, TPW>), g, t, pad, st, a);
+  else if constexpr (G::cin == 32) hipLaunchKernelGGL((conv3x3_kernel<32, G::hin, G::stride, BLK, TPW, true>), g, t, pad, st, a);
+  else return DRQ_EARG;
+  return drq_launched();
 }
 
 // conv1 (9 -> 32, stride 2) runs conv3x3_wgrad_kernel, conv2..4 (32 -> 32, stride 1) the rolling-tile
-// conv3x3_wgrad3_kernel.  defer: run only the partial-sum kernel (records in ws, their count in *nblocks_out); the
-// caller reduces several layers with one launch of conv3x3_wgrad_reduce_multi_kernel
-template <int CIN, int HIN, int STRIDE>
-int launch_wgrad(const WgradArgs& a0, float* dw, float* db, float* ws, size_t ws_bytes, hipStream_t st,
-                 bool defer = false, int* nblocks_out = nullptr) {
-  using G = WgradGeom<CIN, HIN, STRIDE>;
+// conv3x3_wgrad3_kernel: partial records in a.part, one per workgroup
+template <class GE>
+int launch_wgrad(GE, const WgradArgs& a, const ConvPlan& p, hipStream_t st) {
+  using G = WgradGeom<GE::cin, GE::hin, GE::stride>;
   static_assert(4 * G::PART * 4 <= 160 * 1024, "reduction tile too large");
-  static_assert(G::PART % 64 == 0, "record size");
-  const long units = ((long)a0.nb * G::HOUT + 3) / 4;
-  // conv1 (SMALL): 63 MFMAs per output row against 38 staging loads + LDS writes that the wave cannot overlap with
-  // its own MFMAs; its tile is 15 KB per wave and it needs 180 VGPRs, so two workgroups share a CU and one's staging
-  // runs under the other's MFMAs
-  long blocks = (G::SMALL ? 2L : 1L) * drq_num_cus();
-  if (blocks > units) blocks = units;
-  if (blocks < 1) blocks = 1;
-  if ((size_t)blocks * G::PART * sizeof(float) > ws_bytes) return DRQ_EWS;
-  if (((size_t)ws & 15) != 0) return DRQ_EARG;          // partial records are written 16 bytes at a time
-  WgradArgs a = a0;
-  a.part = ws;
-  static bool attr_set_dev[kMaxDevices] = {};
-  bool& attr_set = attr_set_dev[drq_device()];
-  if constexpr (STRIDE == 1 && CIN == 32) {
-    constexpr int wave3 = 4 * CIN * G::XP + 2 * 32 * G::DP + 128;
+  static_assert(G::PART % 64 == 0 && G::PART == conv_part(G::SMALL), "record size");
+  const dim3 g((unsigned)p.grid), t(256);
+  if constexpr (GE::stride == 1 && GE::cin == 32) {
+    constexpr int wave3 = 4 * 32 * G::XP + 2 * 32 * G::DP + 128;
     constexpr int lds3 = (4 * wave3 > 4 * G::PART) ? 4 * wave3 : 4 * G::PART;
     static_assert(lds3 * 4 <= 160 * 1024, "rolling tile too large");
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad3_kernel<HIN>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds3 * 4);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_wgrad3_kernel<HIN>), dim3((unsigned)blocks), dim3(256), lds3 * 4, st, a);
+    if (const int rc = drq_max_dynamic_lds<conv3x3_wgrad3_kernel<GE::hin>>(lds3 * 4)) return rc;
+    hipLaunchKernelGGL((conv3x3_wgrad3_kernel<GE::hin>), g, t, lds3 * 4, st, a);
   } else {
     static_assert(4 * G::WAVE_LDS * 4 <= 160 * 1024, "LDS tile too large");
     constexpr int lds1 = (4 * G::WAVE_LDS > 4 * G::PART) ? 4 * G::WAVE_LDS : 4 * G::PART;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_kernel<CIN, HIN, STRIDE>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds1 * 4);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<CIN, HIN, STRIDE>), dim3((unsigned)blocks), dim3(256), lds1 * 4, st, a);
+    if (const int rc = drq_max_dynamic_lds<conv3x3_wgrad_kernel<GE::cin, GE::hin, GE::stride>>(lds1 * 4)) return rc;
+    hipLaunchKernelGGL((conv3x3_wgrad_kernel<GE::cin, GE::hin, GE::stride>), g, t, lds1 * 4, st, a);
   }
-  DRQ_LAUNCH_CHECK();
-  if (nblocks_out) *nblocks_out = (int)blocks;
-  if (defer) return DRQ_OK;
-  hipLaunchKernelGGL((conv3x3_wgrad_reduce_kernel<CIN, G::SMALL>), dim3(G::PART / 64), dim3(1024), 0, st,
-                     (const float*)ws, (int)blocks, dw, db);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  return drq_launched();
 }
 
 }  // namespace
 
 // ---- internal entry points of the step orchestration (step.hip): per-layer partial sums now, one reduction later
-int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, long dy_bs,
-                              long dy_cs, long dy_rs, long dy_off, float* part, size_t part_bytes, int* nblocks,
-                              hipStream_t st) {
+int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, ConvView dyv,
+                              float* part, size_t part_bytes, int* nblocks, hipStream_t st) {
   if (!x || !dy || !part || !nblocks || nb <= 0) return DRQ_EARG;
-  const size_t xb = (size_t)nb * cin * hin * hin * 4;
-  const size_t dyb = (size_t)nb * dy_bs * 4;
-  if (xb >= (1ull << 31) || dyb >= (1ull << 31) || dy_off < 0 || dy_bs <= 0) return DRQ_EARG;
-  WgradArgs a{x, dy, dy_bs, dy_cs, dy_rs, dy_off, nullptr, (unsigned)xb, (unsigned)dyb, nb};
-  if (cin == 9 && hin == 84 && stride == 2)
-    return launch_wgrad<9, 84, 2>(a, nullptr, nullptr, part, part_bytes, st, true, nblocks);
-  if (cin == 32 && stride == 1) {
-    if (hin == 41) return launch_wgrad<32, 41, 1>(a, nullptr, nullptr, part, part_bytes, st, true, nblocks);
-    if (hin == 39) return launch_wgrad<32, 39, 1>(a, nullptr, nullptr, part, part_bytes, st, true, nblocks);
-    if (hin == 37) return launch_wgrad<32, 37, 1>(a, nullptr, nullptr, part, part_bytes, st, true, nblocks);
-  }
-  return DRQ_EARG;
+  const size_t frame = (size_t)cin * hin * hin;
+  if (!conv_bytes_ok(nb, frame) || !view_ok(nb, dyv)) return DRQ_EARG;
+  const ConvPlan p = plan_wgrad_direct(drq_num_cus(), nb, cin, hin, stride, part_bytes);
+  if (p.rc) return p.rc;
+  if (((size_t)part & 15) != 0) return DRQ_EARG;          // partial records are written 16 bytes at a time
+  const WgradArgs a{x, dy, dyv.bs, dyv.cs, dyv.rs, dyv.off, part, conv_bytes(nb, frame), conv_bytes(nb, dyv.bs), nb};
+  *nblocks = p.records[0];
+  return conv_dispatch<41, 39, 37>(cin, hin, stride, [&](auto g) { return launch_wgrad(g, a, p, st); });
 }
 
 int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* nblocks, const int* cin,
                                    float* const* dw, float* const* db, hipStream_t st) {
   if (n <= 0 || n > 4 || !part || !nblocks || !cin || !dw || !db) return DRQ_EARG;
   ReduceJobs js{};
-  int maxpart = 0;
   for (int i = 0; i < n; ++i) {
     if (!part[i] || !dw[i] || !db[i] || nblocks[i] <= 0) return DRQ_EARG;
-    const int small = cin[i] * 3 <= 32;
-    js.j[i] = ReduceJob{part[i], dw[i], db[i], nblocks[i], cin[i], small};
-    const int p = (small ? 3 : 9) * 1024 + 64;
-    if (p > maxpart) maxpart = p;
+    js.j[i] = ReduceJob{part[i], dw[i], db[i], nblocks[i], cin[i], cin[i] * 3 <= 32};
   }
-  hipLaunchKernelGGL(conv3x3_wgrad_reduce_multi_kernel, dim3(maxpart / 64, n), dim3(1024), 0, st, js);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  const ConvPlan p = plan_reduce(n, cin);
+  hipLaunchKernelGGL(conv3x3_wgrad_reduce_multi_kernel, dim3(p.grid, p.grid_y), dim3(1024), 0, st, js);
+  return drq_launched();
+}
+
+int drq_conv3x3_wgrad_reduce_one(int rc, const float* part, int nblocks, int cin, float* dw, float* db, hipStream_t st) {
+  return rc != DRQ_OK ? rc : drq_conv3x3_wgrad_reduce_multi(1, &part, &nblocks, &cin, &dw, &db, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -883,18 +815,10 @@ int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* n
 DRQ_API int drq_conv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int nb, int cin, int hin,
                     int stride, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
   if (!x || !w || !y || nb <= 0) return DRQ_EARG;
-  const size_t xb = (size_t)nb * cin * hin * hin * 4;
-  if (xb >= (1ull << 31)) return DRQ_EARG;
-  const size_t yb = (size_t)nb * y_bs * 4;
-  if (yb >= (1ull << 31) || y_off < 0 || y_bs <= 0) return DRQ_EARG;
-  ConvArgs a{x, w, bias, nullptr, y, y_bs, y_cs, y_rs, y_off, (unsigned)xb, (unsigned)yb, 0u, nb, relu, 0};
-  if (cin == 9 && hin == 84 && stride == 2) return launch_conv<9, 84, 2>(a, st);
-  if (cin == 32 && stride == 1) {
-    if (hin == 41) return launch_conv<32, 41, 1>(a, st);
-    if (hin == 39) return launch_conv<32, 39, 1>(a, st);
-    if (hin == 37) return launch_conv<32, 37, 1>(a, st);
-  }
-  return DRQ_EARG;
+  const size_t frame = (size_t)cin * hin * hin;
+  if (!conv_bytes_ok(nb, frame) || !view_ok(nb, {y_bs, y_cs, y_rs, y_off})) return DRQ_EARG;
+  const ConvArgs a{x, w, bias, nullptr, y, y_bs, y_cs, y_rs, y_off, conv_bytes(nb, frame), conv_bytes(nb, y_bs), 0u, nb, relu, 0};
+  return conv_dispatch<41, 39, 37>(cin, hin, stride, [&](auto g) { return launch_conv(g, a, st); });
 }
 
 // dx = conv_transpose(dy, w) * (mask > 0): dy_pad is the pre-activation gradient stored zero-padded by 2
@@ -902,51 +826,31 @@ DRQ_API int drq_conv3x3_fwd(const float* x, const float* w, const float* bias, f
 DRQ_API int drq_conv3x3_dgrad(const float* dy_pad, const float* w, const float* mask, float* dx, int nb, int hout,
                       long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st) {
   if (!dy_pad || !w || !dx || nb <= 0) return DRQ_EARG;
-  const int hp = hout + 4;
-  const size_t xb = (size_t)nb * 32 * hp * hp * 4;
-  if (xb >= (1ull << 31)) return DRQ_EARG;
-  const size_t yb = (size_t)nb * dx_bs * 4;
-  const size_t mb = (size_t)nb * 32 * (hout + 2) * (hout + 2) * 4;
-  if (yb >= (1ull << 31) || dx_off < 0 || dx_bs <= 0) return DRQ_EARG;
-  ConvArgs a{dy_pad, w, nullptr, mask, dx, dx_bs, dx_cs, dx_rs, dx_off, (unsigned)xb, (unsigned)yb, (unsigned)mb,
-             nb, 0, 1};
-  if (hp == 39) return launch_conv<32, 39, 1>(a, st);
-  if (hp == 41) return launch_conv<32, 41, 1>(a, st);
-  if (hp == 43) return launch_conv<32, 43, 1>(a, st);
-  return DRQ_EARG;
+  const size_t hp = (size_t)hout + 4, hin = (size_t)hout + 2;
+  if (!conv_bytes_ok(nb, 32 * hp * hp) || !view_ok(nb, {dx_bs, dx_cs, dx_rs, dx_off})) return DRQ_EARG;
+  const ConvArgs a{dy_pad, w, nullptr, mask, dx, dx_bs, dx_cs, dx_rs, dx_off, conv_bytes(nb, 32 * hp * hp),
+                   conv_bytes(nb, dx_bs), conv_bytes(nb, 32 * hin * hin), nb, 0, 1};
+  return conv_dispatch<39, 41, 43>(32, hout + 4, 1, [&](auto g) { return launch_conv(g, a, st); });
 }
 
 // dw[32][cin][3][3], db[32] from the layer input x and the pre-activation gradient dy (strided view).
 DRQ_API int drq_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, int nb, int cin, int hin,
                       int stride, long dy_bs, long dy_cs, long dy_rs, long dy_off, float* ws, size_t ws_bytes,
                       hipStream_t st) {
-  if (!x || !dy || !dw || !db || !ws || nb <= 0) return DRQ_EARG;
-  const size_t xb = (size_t)nb * cin * hin * hin * 4;
-  const size_t dyb = (size_t)nb * dy_bs * 4;
-  if (xb >= (1ull << 31) || dyb >= (1ull << 31) || dy_off < 0 || dy_bs <= 0) return DRQ_EARG;
-  WgradArgs a{x, dy, dy_bs, dy_cs, dy_rs, dy_off, nullptr, (unsigned)xb, (unsigned)dyb, nb};
-  if (cin == 9 && hin == 84 && stride == 2) return launch_wgrad<9, 84, 2>(a, dw, db, ws, ws_bytes, st);
-  if (cin == 32 && stride == 1) {
-    if (hin == 41) return launch_wgrad<32, 41, 1>(a, dw, db, ws, ws_bytes, st);
-    if (hin == 39) return launch_wgrad<32, 39, 1>(a, dw, db, ws, ws_bytes, st);
-    if (hin == 37) return launch_wgrad<32, 37, 1>(a, dw, db, ws, ws_bytes, st);
-  }
-  return DRQ_EARG;
+  if (!dw || !db || !ws) return DRQ_EARG;
+  int nblocks = 0;
+  const int rc = drq_conv3x3_wgrad_partial(x, dy, nb, cin, hin, stride, {dy_bs, dy_cs, dy_rs, dy_off}, ws, ws_bytes, &nblocks, st);
+  return drq_conv3x3_wgrad_reduce_one(rc, ws, nblocks, cin, dw, db, st);
 }
 
 // The same gradients of the 32->32 layers in Winograd F(2x2,3x3) form (conv_wino_wgrad.hip): partial records in the
 // same format, the same fixed-order reduction.
 DRQ_API int drq_conv3x3_wgrad_wino(const float* x, const float* dy, float* dw, float* db, int nb, int hin, long dy_bs,
                                    long dy_cs, long dy_rs, long dy_off, float* ws, size_t ws_bytes, hipStream_t st) {
-  if (!x || !dy || !dw || !db || !ws || nb <= 0) return DRQ_EARG;
+  if (!dw || !db || !ws) return DRQ_EARG;
   int nblocks = 0;
-  const int rc = drq_conv3x3_wgrad_partial_wino(x, dy, nb, hin, dy_bs, dy_cs, dy_rs, dy_off, ws, ws_bytes, &nblocks, st);
-  if (rc != 0) return rc;
-  constexpr int PART = 9 * 1024 + 64;
-  hipLaunchKernelGGL((conv3x3_wgrad_reduce_kernel<32, false>), dim3(PART / 64), dim3(1024), 0, st, (const float*)ws,
-                     nblocks, dw, db);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  const int rc = drq_conv3x3_wgrad_partial_wino(x, dy, nb, hin, {dy_bs, dy_cs, dy_rs, dy_off}, ws, ws_bytes, &nblocks, st);
+  return drq_conv3x3_wgrad_reduce_one(rc, ws, nblocks, 32, dw, db, st);
 }
 
-DRQ_API size_t drq_conv3x3_wgrad_ws_bytes(void) { return (size_t)1024 * (9 * 1024 + 64) * sizeof(float); }
+DRQ_API size_t drq_conv3x3_wgrad_ws_bytes(void) { return (size_t)1024 * conv_part(false) * sizeof(float); }

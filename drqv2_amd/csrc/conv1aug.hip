@@ -26,7 +26,7 @@ namespace {
 
 constexpr int H = 84, C = 9, PAD = 4, S = 92, HW = H * H;
 constexpr int HO = 41, PO = HO * HO;
-constexpr int NBAND = 5;                 // output rows [0,9) [9,17) [17,25) [25,33) [33,41)
+constexpr int NBAND = kConv1Bands;       // output rows [0,9) [9,17) [17,25) [25,33) [33,41)
 constexpr int MAXR = 9;
 constexpr int NROWS = 2 * MAXR + 1;      // augmented rows a band needs (stride 2, 3 taps)
 constexpr int SROWS = NROWS + 2;         // source rows those touch (floor may land one lower, +1 for the second tap)
@@ -41,7 +41,7 @@ constexpr int U8_ALLOC = NDMA * 64;                       // the last instructio
 constexpr int NTHR = 256;                                 // 4 waves (512 with waves 4..7 augmenting only: stage 2 40 instead
                                                           // of 50 us, but the stage times add up either way: 90 vs 86 us)
 constexpr int NWAVE = NTHR / 64;
-constexpr int MAXU = 64;                                  // units per workgroup (shift table); the grid grows beyond it
+constexpr int MAXU = kConv1MaxU;                          // units per workgroup (shift table); the grid grows beyond it
 constexpr int FG = 3, GC = C / FG;       // frame groups of a stack, channels per group (frame_stack 3 of RGB frames)
 constexpr int LDS_BYTES = (XS_FLOATS + U8_ALLOC + H + (2 + FG) * MAXU) * 4;   // + base grid, shift table, frame table
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups share a CU's LDS");
@@ -462,30 +462,15 @@ int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, co
     a.wino_u = wino_u;
     a.n_rider = 6;
   }
-  static bool attr_set_dev[kMaxDevices] = {};
-  bool& attr_set = attr_set_dev[drq_device()];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv1_aug_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv1_aug_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)conv1_aug_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  const long units = (long)2 * n * NBAND;
-  long blocks = units;
-  const long cap = 2L * drq_num_cus();
-  if (blocks > cap) blocks = cap;
-  if (blocks * MAXU < units) blocks = (units + MAXU - 1) / MAXU;     // a workgroup's shift table holds MAXU units
-  blocks += a.n_rider;
-  if (bf_mma == 2) hipLaunchKernelGGL((conv1_aug_kernel<true, true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-  else if (bf_mma) hipLaunchKernelGGL((conv1_aug_kernel<true>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-  else hipLaunchKernelGGL((conv1_aug_kernel<false>), dim3((unsigned)blocks), dim3(NTHR), LDS_BYTES, st, a);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  const dim3 g((unsigned)plan_conv1_aug(drq_num_cus(), n, a.n_rider).grid), t(NTHR);
+  auto launch = [&](auto bf, auto yn) {
+    constexpr auto kernel = conv1_aug_kernel<decltype(bf)::value, decltype(yn)::value>;
+    if (const int rc = drq_max_dynamic_lds<kernel>(LDS_BYTES)) return rc;
+    hipLaunchKernelGGL(kernel, g, t, LDS_BYTES, st, a);
+    return drq_launched();
+  };
+  if (bf_mma == 2) return launch(std::true_type{}, std::true_type{});
+  return bf_mma ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
 }
 
 DRQ_API int drq_conv1_aug_fwd(const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,

@@ -61,15 +61,15 @@ struct ConvBfArgs {
 
 // A workgroup's unit is load -> barrier -> MFMAs -> stores, one after the other; the workgroups of a CU hide each
 // other's phases.  With the bf16 channel-contiguous input (ten 16-byte loads per thread) three per CU measure 12 %
-// faster than two; with fp32 input (77 dword loads per thread in flight, 162 registers) three are 9 % slower.
-constexpr int conv_bf_wgs(int lay) { return (lay & 1) ? 3 : 2; }
+// faster than two; with fp32 input (77 dword loads per thread in flight, 162 registers) three are 9 % slower: conv_bf_wgs
+// (conv_plan.h).
 constexpr int PIXP = 20;   // dwords per pixel in LDS: 16 (32 bf16 channels) + 4 pad
 
 template <int HIN, int LAY = 0>
 struct ConvBfGeom {
   static constexpr int HOUT = HIN - 2;
   static constexpr int WGS = conv_bf_wgs(LAY);
-  static constexpr int NPART = (WGS == 3 && HIN >= 43) ? 4 : 3;   // parts per sample: WGS images fit a CU's 160 KB of LDS
+  static constexpr int NPART = conv_bf_npart(LAY, HIN);           // parts per sample: WGS images fit a CU's 160 KB of LDS
   static constexpr int RP = (HOUT + NPART - 1) / NPART;           // output rows per part
   static constexpr int NIN = (RP + 2) * HIN;                      // staged pixels per part
   static constexpr int LDS_DWORDS = NIN * PIXP > 18 * 64 * 4 ? NIN * PIXP : 18 * 64 * 4;
@@ -222,25 +222,14 @@ __global__ __launch_bounds__(256, conv_bf_wgs(LAY)) void conv3x3_bf16_kernel(Con
   }
 }
 
-template <int HIN, bool MASK, int LAY = 0>
-int launch_conv_bf16(const ConvBfArgs& a, hipStream_t st) {
+template <int HIN, bool MASK, int LAY>
+int launch_conv_bf16(const ConvBfArgs& a, const ConvPlan& p, hipStream_t st) {
   using G = ConvBfGeom<HIN, LAY>;
   constexpr int lds = G::LDS_DWORDS * 4;
   static_assert(G::WGS * lds <= 160 * 1024, "workgroups per CU");
-  static bool attr_dev[kMaxDevices] = {};
-  bool& attr = attr_dev[drq_device()];
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_bf16_kernel<HIN, MASK, LAY>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  long blocks = (long)a.nb * G::NPART;
-  const long cap = (long)G::WGS * drq_num_cus();
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL((conv3x3_bf16_kernel<HIN, MASK, LAY>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  if (const int rc = drq_max_dynamic_lds<conv3x3_bf16_kernel<HIN, MASK, LAY>>(lds)) return rc;
+  hipLaunchKernelGGL((conv3x3_bf16_kernel<HIN, MASK, LAY>), dim3((unsigned)p.grid), dim3(256), lds, st, a);
+  return drq_launched();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -254,7 +243,7 @@ struct WgradBfArgs {
   int nb;
 };
 
-constexpr int WG_PART = 9 * 1024 + 64;   // floats per partial record: same layout as the fp32 kernels'
+constexpr int WG_PART = conv_part(false);   // floats per partial record: same layout as the fp32 kernels'
 
 constexpr int pitch4(int need) {          // smallest dword pitch >= need with pitch/4 odd: 16-byte aligned rows whose
   int p = (need + 3) / 4;                 // b128 reads by 16 neighbouring rows fall on 64 distinct banks
@@ -497,140 +486,96 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_bf16_kernel(WgradBfArgs 
     out[i] = (red[i] + red[WG_PART + i]) + (red[2 * WG_PART + i] + red[3 * WG_PART + i]);
 }
 
-template <int HIN, bool XNHWC = false, bool DYNHWC = false>
-int launch_wgrad_bf16(const WgradBfArgs& a0, float* ws, size_t ws_bytes, int* nblocks_out, hipStream_t st) {
+template <int HIN, bool XNHWC, bool DYNHWC>
+int launch_wgrad_bf16(const WgradBfArgs& a, const ConvPlan& p, hipStream_t st) {
   using G = WgradBfGeom<HIN>;
   constexpr int lds_dwords = 4 * G::WAVE_DWORDS > 4 * WG_PART ? 4 * G::WAVE_DWORDS : 4 * WG_PART;
   static_assert(lds_dwords * 4 <= 160 * 1024, "LDS");
-  const long units = (long)a0.nb * G::HOUT;
-  long blocks = drq_num_cus();
-  if (blocks * 4 > units) blocks = (units + 3) / 4;
-  if (blocks < 1) blocks = 1;
-  if ((size_t)blocks * WG_PART * sizeof(float) > ws_bytes) return DRQ_EWS;
-  WgradBfArgs a = a0;
-  a.part = ws;
-  static bool attr_dev[kMaxDevices] = {};
-  bool& attr = attr_dev[drq_device()];
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16_kernel<HIN, XNHWC, DYNHWC>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds_dwords * 4);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<HIN, XNHWC, DYNHWC>), dim3((unsigned)blocks), dim3(256), lds_dwords * 4, st, a);
-  DRQ_LAUNCH_CHECK();
-  if (nblocks_out) *nblocks_out = (int)blocks;
-  return DRQ_OK;
+  if (const int rc = drq_max_dynamic_lds<conv3x3_wgrad_bf16_kernel<HIN, XNHWC, DYNHWC>>(lds_dwords * 4)) return rc;
+  hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<HIN, XNHWC, DYNHWC>), dim3((unsigned)p.grid), dim3(256), lds_dwords * 4, st, a);
+  return drq_launched();
 }
 
 }  // namespace
 
 // ---- internal (step.hip) and C ABI: the same launches with the bf16 channel-contiguous layout on some operands -----
-// x: bf16 [nb][hin][hin][32] when lay & 1, else fp32 NCHW; y: bf16 [nb][hout][hout][32] when lay & 2 (the strides are
-// ignored), else fp32 with the given strides
+// x: bf16 [nb][hin][hin][32] when lay & 1, else fp32 NCHW; y: bf16 [nb][hout][hout][32] when lay & 2 (the view is
+// ignored), else fp32 with the given view
 int drq_conv3x3_fwd_bf16_lay(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
-                             long y_bs, long y_cs, long y_rs, long y_off, int lay, hipStream_t st) {
+                             ConvView yv, int lay, hipStream_t st) {
   if (!x || !w || !y || nb <= 0 || (lay & ~3)) return DRQ_EARG;
-  const int hout = hin - 2;
-  if (lay & 2) { y_bs = 16L * hout * hout; y_cs = 0; y_rs = 0; y_off = 0; }   // 64 bytes per pixel, in floats
-  const size_t yb = (size_t)nb * y_bs * 4;
-  if (yb >= (1ull << 31) || y_off < 0 || y_bs <= 0 || ((lay & 1) && ((uintptr_t)x & 15)) || ((lay & 2) && ((uintptr_t)y & 15)))
-    return DRQ_EARG;
-  ConvBfArgs a{(const float*)x, w, bias, nullptr, (float*)y, y_bs, y_cs, y_rs, y_off, (unsigned)yb, 0u, nb, relu, 0};
-#define DRQ_BF_FWD(H)                                            \
-  if (hin == H) {                                                \
-    if (lay == 0) return launch_conv_bf16<H, false, 0>(a, st);   \
-    if (lay == 1) return launch_conv_bf16<H, false, 1>(a, st);   \
-    if (lay == 2) return launch_conv_bf16<H, false, 2>(a, st);   \
-    return launch_conv_bf16<H, false, 3>(a, st);                 \
-  }
-  DRQ_BF_FWD(41) DRQ_BF_FWD(39) DRQ_BF_FWD(37)
-#undef DRQ_BF_FWD
-  return DRQ_EARG;
+  if (lay & 2) yv = {16L * (hin - 2) * (hin - 2), 0, 0, 0};   // 64 bytes per pixel, in floats
+  if (!view_ok(nb, yv) || ((lay & 1) && ((uintptr_t)x & 15)) || ((lay & 2) && ((uintptr_t)y & 15))) return DRQ_EARG;
+  const ConvBfArgs a{(const float*)x, w, bias, nullptr, (float*)y, yv.bs, yv.cs, yv.rs, yv.off, conv_bytes(nb, yv.bs), 0u,
+                     nb, relu, 0};
+  const ConvPlan p = plan_conv_bf16(drq_num_cus(), nb, hin, lay);
+  return drq_dispatch<41, 39, 37>(hin, [&](auto h) {
+    return drq_dispatch<0, 1, 2, 3>(lay, [&](auto l) { return launch_conv_bf16<decltype(h)::value, false, decltype(l)::value>(a, p, st); });
+  });
 }
 
 // lay bits: 1 = dy_pad is bf16 [nb][hout+4][hout+4][32] (zero border), 2 = dx is the interior of a bf16
-// [nb][hout+6][hout+6][32] buffer padded by 2 (the strides are ignored; the border is the caller's), 4 = the mask is bf16
+// [nb][hout+6][hout+6][32] buffer padded by 2 (the view is ignored; the border is the caller's), 4 = the mask is bf16
 // [nb][hout+2][hout+2][32]; a clear bit: fp32 NCHW as in drq_conv3x3_dgrad_bf16
 int drq_conv3x3_dgrad_bf16_lay(const void* dy_pad, const float* w, const void* mask, void* dx, int nb, int hout,
-                               long dx_bs, long dx_cs, long dx_rs, long dx_off, int lay, hipStream_t st) {
+                               ConvView dxv, int lay, hipStream_t st) {
   if (!dy_pad || !w || !dx || !mask || nb <= 0 || (lay & ~7)) return DRQ_EARG;
   const int hp = hout + 4, hin = hout + 2;
-  if (lay & 2) { dx_bs = 16L * (hin + 4) * (hin + 4); dx_cs = 0; dx_rs = 0; dx_off = 0; }
-  const size_t yb = (size_t)nb * dx_bs * 4;
-  const size_t mb = (size_t)nb * 32 * hin * hin * ((lay & 4) ? 2 : 4);
-  if (yb >= (1ull << 31) || mb >= (1ull << 31) || dx_off < 0 || dx_bs <= 0) return DRQ_EARG;
+  if (lay & 2) dxv = {16L * (hin + 4) * (hin + 4), 0, 0, 0};
+  const size_t mframe = (size_t)32 * hin * hin, melem = (lay & 4) ? 2 : 4;
+  if (!view_ok(nb, dxv) || !conv_bytes_ok(nb, mframe, melem)) return DRQ_EARG;
   if (((lay & 4) && ((uintptr_t)mask & 15)) || ((lay & 1) && ((uintptr_t)dy_pad & 15)) || ((lay & 2) && ((uintptr_t)dx & 15)))
     return DRQ_EARG;
-  ConvBfArgs a{(const float*)dy_pad, w, nullptr, (const float*)mask, (float*)dx, dx_bs, dx_cs, dx_rs, dx_off, (unsigned)yb,
-               (unsigned)mb, nb, 0, 1, (lay & 2) ? 2 : 0};
-#define DRQ_BF_DGRAD(H)                                         \
-  if (hp == H) {                                                \
-    switch (lay) {                                              \
-      case 0: return launch_conv_bf16<H, true, 0>(a, st);       \
-      case 4: return launch_conv_bf16<H, true, 4>(a, st);       \
-      case 5: return launch_conv_bf16<H, true, 5>(a, st);       \
-      case 6: return launch_conv_bf16<H, true, 6>(a, st);       \
-      case 7: return launch_conv_bf16<H, true, 7>(a, st);       \
-      default: return DRQ_EARG;                                 \
-    }                                                           \
-  }
-  DRQ_BF_DGRAD(39) DRQ_BF_DGRAD(41) DRQ_BF_DGRAD(43)
-#undef DRQ_BF_DGRAD
-  return DRQ_EARG;
+  const ConvBfArgs a{(const float*)dy_pad, w, nullptr, (const float*)mask, (float*)dx, dxv.bs, dxv.cs, dxv.rs, dxv.off,
+                     conv_bytes(nb, dxv.bs), conv_bytes(nb, mframe, melem), nb, 0, 1, (lay & 2) ? 2 : 0};
+  const ConvPlan p = plan_conv_bf16(drq_num_cus(), nb, hp, lay);
+  return drq_dispatch<39, 41, 43>(hp, [&](auto h) {
+    return drq_dispatch<0, 4, 5, 6, 7>(lay, [&](auto l) { return launch_conv_bf16<decltype(h)::value, true, decltype(l)::value>(a, p, st); });
+  });
 }
 
 // ---- C ABI (include/drqv2_hip.h), argument meaning as the fp32 entries of conv.hip ------------------------------
 DRQ_API int drq_conv3x3_fwd_bf16_nhwc(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
                                       int x_nhwc, int y_nhwc, hipStream_t st) {
-  const int hout = hin - 2;
-  return drq_conv3x3_fwd_bf16_lay(x, w, bias, y, nb, hin, relu, 32L * hout * hout, (long)hout * hout, hout, 0,
-                                  (x_nhwc ? 1 : 0) | (y_nhwc ? 2 : 0), st);
+  return drq_conv3x3_fwd_bf16_lay(x, w, bias, y, nb, hin, relu, ConvView::contiguous(hin - 2), (x_nhwc ? 1 : 0) | (y_nhwc ? 2 : 0), st);
 }
 
 DRQ_API int drq_conv3x3_dgrad_bf16_nhwc(const void* dy_pad, const float* w, const void* mask_nhwc, void* dx, int nb, int hout,
                                         int dy_nhwc, int dx_nhwc, long dx_bs, long dx_cs, long dx_rs, long dx_off,
                                         hipStream_t st) {
-  return drq_conv3x3_dgrad_bf16_lay(dy_pad, w, mask_nhwc, dx, nb, hout, dx_bs, dx_cs, dx_rs, dx_off,
+  return drq_conv3x3_dgrad_bf16_lay(dy_pad, w, mask_nhwc, dx, nb, hout, {dx_bs, dx_cs, dx_rs, dx_off},
                                     4 | (dy_nhwc ? 1 : 0) | (dx_nhwc ? 2 : 0), st);
 }
 
 DRQ_API int drq_conv3x3_fwd_bf16(const float* x, const float* w, const float* bias, float* y, int nb, int hin, int relu, long y_bs,
                          long y_cs, long y_rs, long y_off, hipStream_t st) {
-  return drq_conv3x3_fwd_bf16_lay(x, w, bias, y, nb, hin, relu, y_bs, y_cs, y_rs, y_off, 0, st);
+  return drq_conv3x3_fwd_bf16_lay(x, w, bias, y, nb, hin, relu, {y_bs, y_cs, y_rs, y_off}, 0, st);
 }
 
 DRQ_API int drq_conv3x3_dgrad_bf16(const float* dy_pad, const float* w, const float* mask, float* dx, int nb, int hout, long dx_bs,
                            long dx_cs, long dx_rs, long dx_off, hipStream_t st) {
-  return drq_conv3x3_dgrad_bf16_lay(dy_pad, w, mask, dx, nb, hout, dx_bs, dx_cs, dx_rs, dx_off, 0, st);
+  return drq_conv3x3_dgrad_bf16_lay(dy_pad, w, mask, dx, nb, hout, {dx_bs, dx_cs, dx_rs, dx_off}, 0, st);
 }
-
 
 // internal (step.hip): partial records only; one reduction launch serves all layers
 // lay bits: 1 = x is bf16 [nb][hin][hin][32] instead of fp32 NCHW; 2 = dy is the bf16 [nb][hin+2][hin+2][32] buffer
-// zero-padded by 2 (its base; the strides are ignored) instead of an fp32 strided view
-int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                       long dy_off, float* part, size_t part_bytes, int* nblocks, int lay,
-                                       hipStream_t st) {
+// zero-padded by 2 (its base; the view is ignored) instead of an fp32 strided view
+int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, int hin, ConvView dyv, float* part,
+                                       size_t part_bytes, int* nblocks, int lay, hipStream_t st) {
   if (!x || !dy || !part || !nblocks || nb <= 0 || (lay & ~3)) return DRQ_EARG;
-  if (!(lay & 2) && (dy_off < 0 || dy_bs <= 0)) return DRQ_EARG;
+  if (!(lay & 2) && (dyv.off < 0 || dyv.bs <= 0)) return DRQ_EARG;
   if (((size_t)part & 15) != 0 || ((lay & 1) && ((uintptr_t)x & 15)) || ((lay & 2) && ((uintptr_t)dy & 15))) return DRQ_EARG;
   if (lay == 2) return DRQ_EARG;                        // not instantiated: the update never has fp32 x beside bf16 dy
-  WgradBfArgs a{(const float*)x, (const float*)dy, dy_bs, dy_cs, dy_rs, dy_off, nullptr, nb};
-#define DRQ_BF_WGRAD(H)                                                                  \
-  if (hin == H) {                                                                        \
-    if (lay == 3) return launch_wgrad_bf16<H, true, true>(a, part, part_bytes, nblocks, st);  \
-    if (lay == 1) return launch_wgrad_bf16<H, true, false>(a, part, part_bytes, nblocks, st); \
-    return launch_wgrad_bf16<H>(a, part, part_bytes, nblocks, st);                       \
-  }
-  DRQ_BF_WGRAD(41) DRQ_BF_WGRAD(39) DRQ_BF_WGRAD(37)
-#undef DRQ_BF_WGRAD
-  return DRQ_EARG;
-}
-
-int drq_conv3x3_wgrad_partial_bf16(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st) {
-  return drq_conv3x3_wgrad_partial_bf16_lay(x, dy, nb, hin, dy_bs, dy_cs, dy_rs, dy_off, part, part_bytes, nblocks, 0, st);
+  const ConvPlan p = plan_wgrad_bf16(drq_num_cus(), nb, hin, part_bytes);
+  if (p.rc) return p.rc;
+  const WgradBfArgs a{(const float*)x, (const float*)dy, dyv.bs, dyv.cs, dyv.rs, dyv.off, part, nb};
+  *nblocks = p.records[0];
+  return drq_dispatch<41, 39, 37>(hin, [&](auto h) {
+    return drq_dispatch<0, 1, 3>(lay, [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      return launch_wgrad_bf16<decltype(h)::value, (L & 1) != 0, (L & 2) != 0>(a, p, st);
+    });
+  });
 }
 
 DRQ_API int drq_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw, float* db, int nb, int hin,
@@ -638,12 +583,8 @@ DRQ_API int drq_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw, f
                                               hipStream_t st) {
   if (!dw || !db || !ws) return DRQ_EARG;
   int nblk = 0;
-  const int rc = drq_conv3x3_wgrad_partial_bf16(x, dy, nb, hin, dy_bs, dy_cs, dy_rs, dy_off, ws, ws_bytes, &nblk, st);
-  if (rc != DRQ_OK) return rc;
-  const float* parts[1] = {ws};
-  const int cins[1] = {32};
-  float *dws[1] = {dw}, *dbs[1] = {db};
-  return drq_conv3x3_wgrad_reduce_multi(1, parts, &nblk, cins, dws, dbs, st);
+  const int rc = drq_conv3x3_wgrad_partial_bf16_lay(x, dy, nb, hin, {dy_bs, dy_cs, dy_rs, dy_off}, ws, ws_bytes, &nblk, 0, st);
+  return drq_conv3x3_wgrad_reduce_one(rc, ws, nblk, 32, dw, db, st);
 }
 
 DRQ_API int drq_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dy, float* dw, float* db, int nb, int hin,
@@ -651,11 +592,7 @@ DRQ_API int drq_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dy, floa
                                                    size_t ws_bytes, hipStream_t st) {
   if (!dw || !db || !ws) return DRQ_EARG;
   int nblk = 0;
-  const int rc = drq_conv3x3_wgrad_partial_bf16_lay(x_nhwc, dy, nb, hin, dy_bs, dy_cs, dy_rs, dy_off, ws, ws_bytes, &nblk,
+  const int rc = drq_conv3x3_wgrad_partial_bf16_lay(x_nhwc, dy, nb, hin, {dy_bs, dy_cs, dy_rs, dy_off}, ws, ws_bytes, &nblk,
                                                     dy_nhwc ? 3 : 1, st);
-  if (rc != DRQ_OK) return rc;
-  const float* parts[1] = {ws};
-  const int cins[1] = {32};
-  float *dws[1] = {dw}, *dbs[1] = {db};
-  return drq_conv3x3_wgrad_reduce_multi(1, parts, &nblk, cins, dws, dbs, st);
+  return drq_conv3x3_wgrad_reduce_one(rc, ws, nblk, 32, dw, db, st);
 }

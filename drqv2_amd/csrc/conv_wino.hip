@@ -309,64 +309,50 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
 }
 
 template <int HIN>
-int launch_wino(const WinoArgs& a0, hipStream_t st) {
-  WinoArgs a = a0;
-  a.stagger = kStagger;
-  constexpr int HOUT = HIN - 2, TH = (HOUT + 1) / 2;
-  const long nunit = ((long)a.nb * TH * TH + 15) / 16;
-  long blocks = (nunit + 3) / 4;
-  const long cap = 2L * drq_num_cus();
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  const dim3 g((unsigned)blocks), t(256);
+int launch_wino(const WinoArgs& a, const ConvPlan& p, hipStream_t st) {
+  const dim3 g((unsigned)p.grid), t(256);
   if (a.mask && a.relu) hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, true, true>), g, t, 0, st, a);
   else if (a.mask) hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, true, false>), g, t, 0, st, a);
   else if (a.relu) hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, true>), g, t, 0, st, a);
   else hipLaunchKernelGGL((conv3x3_wino_kernel<HIN, false, false>), g, t, 0, st, a);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  return drq_launched();
+}
+
+// x: the kernel's input of side hin -- the layer input, or (dgrad) the gradient zero-padded by 2, with the ReLU mask
+// of side hin - 2
+int wino_any(bool dgrad, const float* x, const float* w, const float* u_image, const float* bias, const float* mask,
+             float* y, int nb, int hin, int relu, const ConvView& yv, hipStream_t st) {
+  if (!x || !w || !y || nb <= 0) return DRQ_EARG;
+  const size_t frame = 32 * (size_t)hin * hin, mframe = 32 * ((size_t)hin - 2) * ((size_t)hin - 2);
+  if (!conv_bytes_ok(nb, frame) || !view_ok(nb, yv)) return DRQ_EARG;
+  const WinoArgs a{x, w, u_image, bias, mask, y, (int)yv.bs, (int)yv.cs, (int)yv.rs, (int)yv.off, conv_bytes(nb, frame),
+                   conv_bytes(nb, yv.bs), dgrad ? conv_bytes(nb, mframe) : 0u, nb, relu, dgrad, kStagger};
+  const ConvPlan p = plan_wino(drq_num_cus(), nb, hin);
+  auto go = [&](auto h) { return launch_wino<decltype(h)::value>(a, p, st); };
+  return dgrad ? drq_dispatch<39, 41, 43>(hin, go) : drq_dispatch<41, 39, 37>(hin, go);
 }
 
 }  // namespace
 
 // internal (step.hip): u_image = the layer's U image prepared by conv1_aug_kernel's rider for this update, or null
 int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,
-                             int hin, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
-  if (!x || !w || !y || nb <= 0) return DRQ_EARG;
-  const size_t xb = (size_t)nb * 32 * hin * hin * 4;
-  const size_t yb = (size_t)nb * y_bs * 4;
-  if (xb >= (1ull << 31) || yb >= (1ull << 31) || y_off < 0 || y_bs <= 0) return DRQ_EARG;
-  WinoArgs a{x, w, u_image, bias, nullptr, y, (int)y_bs, (int)y_cs, (int)y_rs, (int)y_off, (unsigned)xb, (unsigned)yb, 0u, nb, relu, 0, 0};
-  if (hin == 41) return launch_wino<41>(a, st);
-  if (hin == 39) return launch_wino<39>(a, st);
-  if (hin == 37) return launch_wino<37>(a, st);
-  return DRQ_EARG;
+                             int hin, int relu, ConvView yv, hipStream_t st) {
+  return wino_any(false, x, w, u_image, bias, nullptr, y, nb, hin, relu, yv, st);
 }
 
 int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float* u_image, const float* mask, float* dx,
-                               int nb, int hout, long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st) {
-  if (!dy_pad || !w || !dx || nb <= 0) return DRQ_EARG;
-  const int hp = hout + 4;
-  const size_t xb = (size_t)nb * 32 * hp * hp * 4;
-  const size_t yb = (size_t)nb * dx_bs * 4;
-  const size_t mb = (size_t)nb * 32 * (hout + 2) * (hout + 2) * 4;
-  if (xb >= (1ull << 31) || yb >= (1ull << 31) || dx_off < 0 || dx_bs <= 0) return DRQ_EARG;
-  WinoArgs a{dy_pad, w, u_image, nullptr, mask, dx, (int)dx_bs, (int)dx_cs, (int)dx_rs, (int)dx_off, (unsigned)xb, (unsigned)yb,
-             (unsigned)mb, nb, 0, 1, 0};
-  if (hp == 39) return launch_wino<39>(a, st);
-  if (hp == 41) return launch_wino<41>(a, st);
-  if (hp == 43) return launch_wino<43>(a, st);
-  return DRQ_EARG;
+                               int nb, int hout, ConvView dxv, hipStream_t st) {
+  return wino_any(true, dy_pad, w, u_image, nullptr, mask, dx, nb, hout + 4, 0, dxv, st);
 }
 
 // Same contract as drq_conv3x3_fwd (conv.hip) for cin = 32, stride 1, in Winograd form (rounding differs).
 DRQ_API int drq_conv3x3_fwd_wino(const float* x, const float* w, const float* bias, float* y, int nb, int hin, int relu,
                                  long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st) {
-  return drq_conv3x3_fwd_wino_pre(x, w, nullptr, bias, y, nb, hin, relu, y_bs, y_cs, y_rs, y_off, st);
+  return drq_conv3x3_fwd_wino_pre(x, w, nullptr, bias, y, nb, hin, relu, {y_bs, y_cs, y_rs, y_off}, st);
 }
 
 // Same contract as drq_conv3x3_dgrad (conv.hip) in Winograd form.
 DRQ_API int drq_conv3x3_dgrad_wino(const float* dy_pad, const float* w, const float* mask, float* dx, int nb, int hout,
                                    long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st) {
-  return drq_conv3x3_dgrad_wino_pre(dy_pad, w, nullptr, mask, dx, nb, hout, dx_bs, dx_cs, dx_rs, dx_off, st);
+  return drq_conv3x3_dgrad_wino_pre(dy_pad, w, nullptr, mask, dx, nb, hout, {dx_bs, dx_cs, dx_rs, dx_off}, st);
 }

@@ -264,107 +264,53 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_wino3_kernel(WW3Args g) 
   else ww_body<37>(g.l[2], b - g.beg[2], g.beg[3] - g.beg[2]);
 }
 
+constexpr int kWwLds = 4 * conv_part(false) * 4;   // bytes: the four waves' images of a record
+
 template <int HIN>
-int launch_ww(const WWArgs& a, int* nblocks, hipStream_t st) {
-  constexpr int PART = 9 * 1024 + 64;
-  constexpr int lds = 4 * PART * 4;
-  static bool attr_dev[kMaxDevices] = {};
-  bool& attr = attr_dev[drq_device()];
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_wino_kernel<HIN>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  constexpr int TH = (HIN - 1) / 2;
-  long blocks = drq_num_cus();
-  const long steps = ((long)a.nb * TH * TH + 3) / 4;
-  if (blocks * 4 > steps) blocks = (steps + 3) / 4;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((conv3x3_wgrad_wino_kernel<HIN>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-  DRQ_LAUNCH_CHECK();
-  *nblocks = (int)blocks;
-  return DRQ_OK;
+int launch_ww(const WWArgs& a, const ConvPlan& p, hipStream_t st) {
+  if (const int rc = drq_max_dynamic_lds<conv3x3_wgrad_wino_kernel<HIN>>(kWwLds)) return rc;
+  hipLaunchKernelGGL((conv3x3_wgrad_wino_kernel<HIN>), dim3((unsigned)p.grid), dim3(256), kWwLds, st, a);
+  return drq_launched();
+}
+
+// the kernel's arguments for one layer; false: an operand is missing or too large
+bool ww_args(WWArgs& a, const float* x, const float* dy, int nb, int hin, const ConvView& v, float* part) {
+  const size_t frame = 32 * (size_t)hin * hin;
+  if (!x || !dy || !part || !conv_bytes_ok(nb, frame) || !view_ok(nb, v)) return false;
+  a = WWArgs{x, dy, (int)v.bs, (int)v.cs, (int)v.rs, (int)v.off, part, conv_bytes(nb, frame), conv_bytes(nb, v.bs), nb};
+  return true;
 }
 
 }  // namespace
 
-// internal (step.hip): conv2, conv3, conv4 (hin 41, 39, 37) in one launch; x[l], dy[l], part[l] and the dY strides per
-// layer; nblocks[l] = records written for layer l
-int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const long* dy_bs,
-                                    const long* dy_cs, const long* dy_rs, const long* dy_off, float* const* part,
-                                    size_t part_bytes, int* nblocks, hipStream_t st) {
-  if (!x || !dy || !dy_bs || !dy_cs || !dy_rs || !dy_off || !part || !nblocks || nb <= 0) return DRQ_EARG;
-  constexpr int PART = 9 * 1024 + 64;
-  const int hins[3] = {41, 39, 37};
+// internal (step.hip): conv2, conv3, conv4 (hin 41, 39, 37) in one launch; x[l], dy[l], part[l] and the dY view per
+// layer; nblocks[l] = records written for layer l.  The caller asks plan_ww3 first: a batch it does not merge is refused
+int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const ConvView* dyv,
+                                    float* const* part, size_t part_bytes, int* nblocks, hipStream_t st) {
+  if (!x || !dy || !dyv || !part || !nblocks || nb <= 0) return DRQ_EARG;
   WW3Args g{};
-  long steps[3], tot = 0;
+  for (int l = 0; l < 3; ++l)
+    if (!ww_args(g.l[l], x[l], dy[l], nb, kEncH[l + 1], dyv[l], part[l]) || ((size_t)part[l] & 15)) return DRQ_EARG;
+  const ConvPlan p = plan_ww3(drq_num_cus(), nb, part_bytes);
+  if (p.rc) return p.rc;
   for (int l = 0; l < 3; ++l) {
-    const int hin = hins[l], th = (hin - 1) / 2;
-    if (!x[l] || !dy[l] || !part[l] || ((size_t)part[l] & 15)) return DRQ_EARG;
-    const size_t xb = (size_t)nb * 32 * hin * hin * 4, dyb = (size_t)nb * dy_bs[l] * 4;
-    if (xb >= (1ull << 31) || dyb >= (1ull << 31) || dy_off[l] < 0 || dy_bs[l] <= 0) return DRQ_EARG;
-    g.l[l] = WWArgs{x[l], dy[l], (int)dy_bs[l], (int)dy_cs[l], (int)dy_rs[l], (int)dy_off[l], part[l], (unsigned)xb,
-                    (unsigned)dyb, nb};
-    steps[l] = ((long)nb * th * th + 3) / 4;
-    tot += steps[l];
+    g.beg[l + 1] = p.beg[l + 1];
+    nblocks[l] = p.records[l];
   }
-  const int cus = drq_num_cus();
-  if (cus < 3 || tot < 3L * 4) return DRQ_EARG;          // tiny problems: the caller launches the layers one by one
-  // workgroups per layer proportional to its steps (at least one each), all of them resident at once
-  int nb_l[3], used = 0;
-  for (int l = 0; l < 3; ++l) {
-    long n = (steps[l] * cus + tot / 2) / tot;
-    if (n < 1) n = 1;
-    if (n * 4 > steps[l]) n = (steps[l] + 3) / 4;
-    nb_l[l] = (int)n;
-    used += nb_l[l];
-  }
-  while (used > cus) {                                   // rounding overshoot: take from the largest share
-    int m = 0;
-    for (int l = 1; l < 3; ++l) if (nb_l[l] > nb_l[m]) m = l;
-    --nb_l[m]; --used;
-  }
-  g.beg[0] = 0;
-  for (int l = 0; l < 3; ++l) {
-    g.beg[l + 1] = g.beg[l] + nb_l[l];
-    nblocks[l] = nb_l[l];
-    if ((size_t)nb_l[l] * PART * sizeof(float) > part_bytes) return DRQ_EWS;
-  }
-  constexpr int lds = 4 * PART * 4;
-  static bool attr_dev[kMaxDevices] = {};
-  bool& attr = attr_dev[drq_device()];
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_wino3_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(conv3x3_wgrad_wino3_kernel, dim3((unsigned)g.beg[3]), dim3(256), lds, st, g);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  if (const int rc = drq_max_dynamic_lds<conv3x3_wgrad_wino3_kernel>(kWwLds)) return rc;
+  hipLaunchKernelGGL(conv3x3_wgrad_wino3_kernel, dim3((unsigned)p.grid), dim3(256), kWwLds, st, g);
+  return drq_launched();
 }
 
 // internal (step.hip, conv.hip's public entry): partial records of the 32->32 weight gradient in Winograd form, same
 // record format and reduction as drq_conv3x3_wgrad_partial
-int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st) {
-  if (!x || !dy || !part || !nblocks || nb <= 0) return DRQ_EARG;
-  const size_t xb = (size_t)nb * 32 * hin * hin * 4;
-  const size_t dyb = (size_t)nb * dy_bs * 4;
-  if (xb >= (1ull << 31) || dyb >= (1ull << 31) || dy_off < 0 || dy_bs <= 0) return DRQ_EARG;
-  // The kernel reads row and column `hout` of every dy plane as the empty half of the last 2x2 tile: dy must be the
-  // interior of a zero-padded buffer (one more zero row and column at least), as the update stores its gradients.  A
-  // contiguous [nb][32][hout][hout] dy would silently wrap into the next row / plane: refused.
-  {
-    const int hout = hin - 2;
-    if (dy_rs < hout + 1 || dy_cs < (long)(hout + 1) * dy_rs) return DRQ_EARG;
-  }
-  if ((size_t)drq_num_cus() * (9 * 1024 + 64) * sizeof(float) > part_bytes) return DRQ_EWS;
+int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, ConvView dyv, float* part,
+                                   size_t part_bytes, int* nblocks, hipStream_t st) {
+  WWArgs a;
+  if (!nblocks || nb <= 0 || !ww_args(a, x, dy, nb, hin, dyv, part)) return DRQ_EARG;
+  const ConvPlan p = plan_ww(drq_num_cus(), nb, hin, dyv, part_bytes);
+  if (p.rc) return p.rc;
   if (((size_t)part & 15) != 0) return DRQ_EARG;
-  WWArgs a{x, dy, (int)dy_bs, (int)dy_cs, (int)dy_rs, (int)dy_off, part, (unsigned)xb, (unsigned)dyb, nb};
-  if (hin == 41) return launch_ww<41>(a, nblocks, st);
-  if (hin == 39) return launch_ww<39>(a, nblocks, st);
-  if (hin == 37) return launch_ww<37>(a, nblocks, st);
-  return DRQ_EARG;
+  *nblocks = p.records[0];
+  return drq_dispatch<41, 39, 37>(hin, [&](auto h) { return launch_ww<decltype(h)::value>(a, p, st); });
 }

@@ -4,6 +4,7 @@
 // (-z defs).  Grouped by defining file.
 #pragma once
 #include "common.h"
+#include "conv_plan.h"
 #include "gemm_plan.h"
 
 // ---- layernorm.hip
@@ -122,29 +123,41 @@ int drq_polout_l1_fwd(const float* p2, const float* w3, const float* b3, float* 
                       long lda_hi, const float* noise_lo, float* mu_lo, float* ha_lo, long lda_lo, int nheads,
                       const float* const* w, const float* const* b, float* const* y, hipStream_t st);
 
-// ---- conv1aug.hip: bf_mma selects the bf16-MFMA form of the layer's products; ring_first != NULL: obs == obs1 is a
+// ---- the convolution family (conv.hip, conv_wino.hip, conv_wino_wgrad.hip, conv_bf16.hip, conv1aug.hip).  conv_plan.h
+// holds the launch arithmetic: an entry checks its pointers, builds the ConvView of its strided operand, asks the planner
+// and hands the kernel's arguments and the plan to a launcher that only launches.
+static_assert(kConvOk == DRQ_OK && kConvEarg == DRQ_EARG && kConvEws == DRQ_EWS, "ConvPlan::rc is the entry's result");
+// conv1aug.hip: bf_mma selects the bf16-MFMA form of the layer's products; ring_first != NULL: obs == obs1 is a
 // ring of single frames (R rows x N environments), fidx0 / fidx1 the newest-frame slots of the stacks
 int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, const uint8_t* obs1, const float* shift1,
                           const float* base_grid, const float* w, const float* bias, float* xaug, float* y, int n,
                           int n_store, hipStream_t st, const float* const* wino_w, float* wino_u, const long* fidx0,
                           const long* fidx1, const uint8_t* ring_first, long ring_R, long ring_N);
-
-// ---- conv_wino.hip: the Winograd kernels with the layer's U image prepared by conv1_aug_kernel's rider
+// conv_wino.hip: the Winograd kernels with the layer's U image prepared by conv1_aug_kernel's rider
 int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,
-                             int hin, int relu, long y_bs, long y_cs, long y_rs, long y_off, hipStream_t st);
+                             int hin, int relu, ConvView yv, hipStream_t st);
 int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float* u_image, const float* mask, float* dx,
-                               int nb, int hout, long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st);
-
-// ---- conv_bf16.hip: the bf16 launches with activations in bf16 [frame][y][x][32] where the flags say so
+                               int nb, int hout, ConvView dxv, hipStream_t st);
+// conv_bf16.hip: the bf16 launches with activations in bf16 [frame][y][x][32] where the flags say so
 int drq_conv3x3_fwd_bf16_lay(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
-                             long y_bs, long y_cs, long y_rs, long y_off, int lay, hipStream_t st);
+                             ConvView yv, int lay, hipStream_t st);
 int drq_conv3x3_dgrad_bf16_lay(const void* dy_pad, const float* w, const void* mask, void* dx, int nb, int hout,
-                               long dx_bs, long dx_cs, long dx_rs, long dx_off, int lay, hipStream_t st);
-int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                       long dy_off, float* part, size_t part_bytes, int* nblocks, int lay,
-                                       hipStream_t st);
-int drq_conv3x3_wgrad_partial_bf16(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
+                               ConvView dxv, int lay, hipStream_t st);
+int drq_conv3x3_wgrad_partial_bf16_lay(const void* x, const void* dy, int nb, int hin, ConvView dyv, float* part,
+                                       size_t part_bytes, int* nblocks, int lay, hipStream_t st);
+// conv.hip: per-layer partial records; fixed-order reduction of the records of up to four layers; the tail of the public
+// weight-gradient entries: rc of their partial launch, then the reduction of its one job
+int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, ConvView dyv,
+                              float* part, size_t part_bytes, int* nblocks, hipStream_t st);
+int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* nblocks, const int* cin,
+                                   float* const* dw, float* const* db, hipStream_t st);
+int drq_conv3x3_wgrad_reduce_one(int rc, const float* part, int nblocks, int cin, float* dw, float* db, hipStream_t st);
+// conv_wino_wgrad.hip: the 32->32 layers' records in Winograd form (same format, same reduction); wino3: conv2..4 in one
+// launch where plan_ww3 merges them (DRQ_EARG where it does not)
+int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, ConvView dyv, float* part,
+                                   size_t part_bytes, int* nblocks, hipStream_t st);
+int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const ConvView* dyv,
+                                    float* const* part, size_t part_bytes, int* nblocks, hipStream_t st);
 
 // ---- act.hip: batched policy inference on launches of its own (drq_act_batch; the C entry lives in step.hip beside
 // the parameter layout).  ws holds drq_act_batch_ws_floats(n, F, H) floats; no state, no counter.
@@ -158,20 +171,6 @@ bool drq_act_batch_supported(int n, int C, int A, int F, int H);
 long drq_act_batch_ws_floats(int n, int F, int H);
 int drq_act_batch_launch(const ActWeights& p, int A, int F, int H, const uint8_t* obs, int n, const float* noise,
                          float std, float* mu_out, float* action_out, float* ws, hipStream_t st);
-
-// ---- conv.hip: per-layer partial records; fixed-order reduction of the records of up to four layers
-int drq_conv3x3_wgrad_partial(const float* x, const float* dy, int nb, int cin, int hin, int stride, long dy_bs,
-                              long dy_cs, long dy_rs, long dy_off, float* part, size_t part_bytes, int* nblocks,
-                              hipStream_t st);
-int drq_conv3x3_wgrad_reduce_multi(int n, const float* const* part, const int* nblocks, const int* cin,
-                                   float* const* dw, float* const* db, hipStream_t st);
-
-// ---- conv_wino_wgrad.hip: the 32->32 layers' records in Winograd form (same format, same reduction)
-int drq_conv3x3_wgrad_partial_wino(const float* x, const float* dy, int nb, int hin, long dy_bs, long dy_cs, long dy_rs,
-                                   long dy_off, float* part, size_t part_bytes, int* nblocks, hipStream_t st);
-int drq_conv3x3_wgrad_partial_wino3(const float* const* x, const float* const* dy, int nb, const long* dy_bs,
-                                    const long* dy_cs, const long* dy_rs, const long* dy_off, float* const* part,
-                                    size_t part_bytes, int* nblocks, hipStream_t st);
 
 // ---- vecstats.hip: the 64-byte header of the episode statistics (include/drqv2_hip.h, "episode statistics"), as the
 // device state and the host mirror hold it

@@ -312,17 +312,17 @@ int encoder_forward(const Ctx& c, const float* x, int nb, float* a1, float* a2, 
   for (int l = x ? 0 : 1; l < 4; ++l) {
     const int hin = kEncH[l], hout = kEncH[l + 1];
     if (timed && l == 1) CK(c.stamp(0));
+    const ConvView yv = ConvView::contiguous(hout);
     if (c.bf16() && l > 0)
-      CK(drq_conv3x3_fwd_bf16_lay(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, hin, 1, 32L * hout * hout,
-                                  (long)hout * hout, hout, 0, (x == nullptr && c.acts16()) ? (l < 3 ? 3 : 1) : 0, c.st));
+      CK(drq_conv3x3_fwd_bf16_lay(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, hin, 1, yv,
+                                  (x == nullptr && c.acts16()) ? (l < 3 ? 3 : 1) : 0, c.st));
     else if (l > 0)   // the 32->32 layers in Winograd F(2x2,3x3) form (conv_wino.hip); in the update (x == nullptr) the
                       // weight images come from the riders of the fused aug+conv1 launch
       CK(drq_conv3x3_fwd_wino_pre(in, c.p(P.enc_w[l]), x ? nullptr : c.ws(W_WINO_U) + (2L * (l - 1)) * 16384,
-                                  c.p(P.enc_b[l]), outs[l], nb, hin, 1, 32L * hout * hout, (long)hout * hout, hout, 0,
-                                  c.st));
+                                  c.p(P.enc_b[l]), outs[l], nb, hin, 1, yv, c.st));
     else
-      CK(drq_conv3x3_fwd(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, l == 0 ? c.s->C : 32, hin, l == 0 ? 2 : 1,
-                         1, 32L * hout * hout, (long)hout * hout, hout, 0, c.st));
+      CK(drq_conv3x3_fwd(in, c.p(P.enc_w[l]), c.p(P.enc_b[l]), outs[l], nb, c.s->C, hin, 2, 1, yv.bs, yv.cs, yv.rs, yv.off,
+                         c.st));
     if (timed && l == 1) CK(c.stamp(1));
     in = outs[l];
   }
@@ -576,66 +576,43 @@ int phase_conv_backward(const Ctx& c) {
   // at the end turns them into dW/db (nothing reads those before the optimiser step)
   float* cws = c.ws(W_CONV_WS);
   const size_t quarter = drq_conv3x3_wgrad_ws_bytes() / 4;
-  const float* parts[4];
+  const float *parts[4], *xs[4], *dys[4];
   int nblk[4], cins[4];
-  float *dws[4], *dbs[4];
+  float *dws[4], *dbs[4], *ps[4];
+  ConvView dyv[4];                           // every layer's gradient is the interior of a buffer zero-padded by 2
   // fp32: the input gradients first (a chain: dY4 -> dY3 -> dY2 -> dY1), then the weight gradients of conv2..4 in ONE
   // Winograd launch (each needs only its layer's dY and input) and conv1's; bf16: layer by layer as before
-  const bool merged = !c.bf16();
-  for (int l = 3; l >= 0; --l) {
-    const int hin = kEncH[l], hout = kEncH[l + 1], hp = hout + 4;
-    const float* dy = c.ws(dyid[l]);
-    float* part = cws + (size_t)l * (quarter / sizeof(float));
-    parts[l] = part; cins[l] = l == 0 ? C : 32; dws[l] = c.g(P.enc_w[l]); dbs[l] = c.g(P.enc_b[l]);
-    if (!merged) {
-      if (l > 0)
-        CK(drq_conv3x3_wgrad_partial_bf16_lay(c.ws(actid[l]), dy, B, hin, 32L * hp * hp, (long)hp * hp, hp, 2L * hp + 2,
-                                              part, quarter, &nblk[l],
-                                              (c.acts16() ? 1 : 0) | (c.grads16() && l < 3 ? 2 : 0), st));
-      else
-        CK(drq_conv3x3_wgrad_partial(c.ws(actid[l]), dy, B, C, hin, 2, 32L * hp * hp, (long)hp * hp, hp, 2L * hp + 2,
-                                     part, quarter, &nblk[l], st));
-    }
-    if (l >= 1) {
-      const int hpi = hin + 4;   // padded size of the next (shallower) gradient buffer
-      if (l == 2) CK(c.stamp(2));
-      if (c.bf16())
-        CK(drq_conv3x3_dgrad_bf16_lay(dy, c.p(P.enc_w[l]), c.ws(actid[l]), c.ws(dyid[l - 1]), B, hout, 32L * hpi * hpi,
-                                      (long)hpi * hpi, hpi, 2L * hpi + 2,
-                                      (c.acts16() ? 4 : 0) | (c.grads16() && l < 3 ? 1 : 0) | (c.grads16() && l > 1 ? 2 : 0),
-                                      st));
-      else
-        CK(drq_conv3x3_dgrad_wino_pre(dy, c.p(P.enc_w[l]), c.ws(W_WINO_U) + (2L * (l - 1) + 1) * 16384, c.ws(actid[l]),
-                                      c.ws(dyid[l - 1]), B, hout, 32L * hpi * hpi, (long)hpi * hpi, hpi, 2L * hpi + 2,
-                                      st));
-      if (l == 2) CK(c.stamp(3));
-    }
+  const bool wino = !c.bf16();
+  for (int l = 0; l < 4; ++l) {
+    xs[l] = c.ws(actid[l]); dys[l] = c.ws(dyid[l]); dyv[l] = ConvView::padded(kEncH[l + 1]);
+    parts[l] = ps[l] = cws + (size_t)l * (quarter / sizeof(float));
+    cins[l] = l == 0 ? C : 32; dws[l] = c.g(P.enc_w[l]); dbs[l] = c.g(P.enc_b[l]);
   }
-  if (merged) {
-    const float *xs[3], *dys[3];
-    float* ps[3];
-    long bs[3], cs[3], rs[3], off[3];
-    for (int k = 0; k < 3; ++k) {            // k = 0, 1, 2 -> layers 1, 2, 3 (conv2, conv3, conv4: hin 41, 39, 37)
-      const int l = k + 1, hp = kEncH[l + 1] + 4;
-      xs[k] = c.ws(actid[l]); dys[k] = c.ws(dyid[l]); ps[k] = const_cast<float*>(parts[l]);
-      bs[k] = 32L * hp * hp; cs[k] = (long)hp * hp; rs[k] = hp; off[k] = 2L * hp + 2;
-    }
-    int nb3[3];
+  for (int l = 3; l >= 1; --l) {
+    if (!wino)
+      CK(drq_conv3x3_wgrad_partial_bf16_lay(xs[l], dys[l], B, kEncH[l], dyv[l], ps[l], quarter, &nblk[l],
+                                            (c.acts16() ? 1 : 0) | (c.grads16() && l < 3 ? 2 : 0), st));
+    if (l == 2) CK(c.stamp(2));
+    if (!wino)   // dyv[l - 1]: the next (shallower) gradient buffer
+      CK(drq_conv3x3_dgrad_bf16_lay(dys[l], c.p(P.enc_w[l]), xs[l], c.ws(dyid[l - 1]), B, kEncH[l + 1], dyv[l - 1],
+                                    (c.acts16() ? 4 : 0) | (c.grads16() && l < 3 ? 1 : 0) | (c.grads16() && l > 1 ? 2 : 0),
+                                    st));
+    else
+      CK(drq_conv3x3_dgrad_wino_pre(dys[l], c.p(P.enc_w[l]), c.ws(W_WINO_U) + (2L * (l - 1) + 1) * 16384, xs[l],
+                                    c.ws(dyid[l - 1]), B, kEncH[l + 1], dyv[l - 1], st));
+    if (l == 2) CK(c.stamp(3));
+  }
+  if (wino) {
     CK(c.stamp(4));
-    int rc = drq_conv3x3_wgrad_partial_wino3(xs, dys, B, bs, cs, rs, off, ps, quarter, nb3, st);
-    if (rc == DRQ_EARG) {                    // tiny batch: one launch per layer
-      for (int k = 0; k < 3; ++k)
-        CK(drq_conv3x3_wgrad_partial_wino(xs[k], dys[k], B, kEncH[k + 1], bs[k], cs[k], rs[k], off[k], ps[k], quarter,
-                                          &nb3[k], st));
-    } else if (rc != 0) {
-      return rc;
-    }
+    // conv2..4 (layers 1..3) in one launch where the planner merges them, else (tiny batch) one launch per layer
+    if (plan_ww3(drq_num_cus(), B, quarter).merged)
+      CK(drq_conv3x3_wgrad_partial_wino3(xs + 1, dys + 1, B, dyv + 1, ps + 1, quarter, nblk + 1, st));
+    else
+      for (int l = 1; l < 4; ++l)
+        CK(drq_conv3x3_wgrad_partial_wino(xs[l], dys[l], B, kEncH[l], dyv[l], ps[l], quarter, &nblk[l], st));
     CK(c.stamp(5));
-    for (int k = 0; k < 3; ++k) nblk[k + 1] = nb3[k];
-    const int hp0 = kEncH[1] + 4;
-    CK(drq_conv3x3_wgrad_partial(c.ws(actid[0]), c.ws(dyid[0]), B, C, kEncH[0], 2, 32L * hp0 * hp0, (long)hp0 * hp0, hp0,
-                                 2L * hp0 + 2, const_cast<float*>(parts[0]), quarter, &nblk[0], st));
   }
+  CK(drq_conv3x3_wgrad_partial(xs[0], dys[0], B, C, kEncH[0], 2, dyv[0], ps[0], quarter, &nblk[0], st));
   CK(drq_conv3x3_wgrad_reduce_multi(4, parts, nblk, cins, dws, dbs, st));
   return 0;
 }

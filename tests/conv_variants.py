@@ -7,12 +7,18 @@ depend on the batch and on the CU count.  The functions below mirror, rule for r
   csrc/conv.hip             launch_conv_v(), launch_wgrad(), conv3x3_wgrad_reduce_multi_kernel (its record loop)
   csrc/conv_wino.hip        launch_wino() and the work split at the top of conv3x3_wino_kernel
   csrc/conv_wino_wgrad.hip  launch_ww(), drq_conv3x3_wgrad_partial_wino3(), the XCD remap of both kernels
-  csrc/conv_bf16.hip        launch_wgrad_bf16() (the record count only: it feeds the same reduce kernel)
+  csrc/conv_bf16.hip        launch_conv_bf16() (the grid), launch_wgrad_bf16() (the records it feeds the same reduce kernel)
+  csrc/conv1aug.hip         drq_conv1_aug_fwd_any() (the grid)
   csrc/step.hip             phase_encode() / phase_conv_backward(): which of these one update issues, with which batch
 
-(the 2 GiB operand-size refusals are left out: no test shape comes near them).  A change to one of those functions has
-to be repeated here; tests/test_cpu_conv_variants.py then says which decision is no longer taken on both sides by the
-rows of tests/test_hip_encoder_audit.py.
+(the 2 GiB operand-size refusals are left out: no test shape comes near them).  The host side of those functions now
+lives in csrc/conv_plan.h, and tests/test_cpu_conv_variants.py holds this module against it through
+tests/conv_plan_dump.cpp: the grid, the records and the merged-or-fallback choice of every function below, for batches
+1..4096, every instantiated geometry and eight CU counts.  A change to a planner that is not repeated here fails that
+sweep; the test then also says which decision is no longer taken on both sides by the rows of
+tests/test_hip_encoder_audit.py.  What a kernel decides for itself from its grid cannot be read from the host and stays
+restated here only: the Winograd kernel's unit split (wino.full_rounds, wino.left_over*), the XCD remaps (*.xcd_remap),
+conv_v.rounds>1, the ragged ends and the record loop of the reduce (reduce.*).
 
 Every function takes the CU count (default 256, drq_num_cus() on the MI355X) and returns a Launch: the kernel, its grid,
 the partial records it leaves for the reduce (None where there are none) and the decisions taken on the way
@@ -175,6 +181,31 @@ def launch_wgrad_bf16(nb, hin, cus=CUS):
     return Launch("conv3x3_wgrad_bf16_kernel", blocks, [blocks], dict(d))
 
 
+def launch_conv_bf16(nb, hin, lay=0, cus=CUS):
+    """launch_conv_bf16<HIN, MASK, LAY>: (sample, part of the output rows) units, three workgroups per CU with bf16
+    input (lay & 1), else two; hin is the kernel's input side as for launch_wino"""
+    d = _D()
+    wgs = 3 if lay & 1 else 2
+    blocks = nb * (4 if wgs == 3 and hin >= 43 else 3)
+    if d("conv_bf16.blocks>cap", blocks > wgs * cus):
+        blocks = wgs * cus
+    return Launch("conv3x3_bf16_kernel", max(blocks, 1), None, dict(d))
+
+
+# --------------------------------------------------------------------------------------------- csrc/conv1aug.hip
+def launch_conv1_aug(n, riders=0, cus=CUS):
+    """drq_conv1_aug_fwd_any: both views' (frame, band of output rows) units over two workgroups per CU; a workgroup's
+    shift table holds 64 units, so the grid grows beyond the cap instead; `riders` workgroups lead the grid"""
+    d = _D()
+    units = 2 * n * 5
+    blocks = units
+    if d("conv1_aug.blocks>cap", blocks > 2 * cus):
+        blocks = 2 * cus
+    if d("conv1_aug.table_full", blocks * 64 < units):
+        blocks = _cdiv(units, 64)
+    return Launch("conv1_aug_kernel", blocks + riders, None, dict(d))
+
+
 # ------------------------------------------------------------------------------------------------ csrc/step.hip
 def update_launches(B, dtype="fp32", cus=CUS):
     """The convolution launches of one update() at batch B that this module restates, as (stage, Launch) in issue order.
@@ -258,6 +289,9 @@ OP_TEST_ROWS = {
                "test_conv_kernels_at_training_batch_sizes",
                '[(9, 84, 2, 256), (32, 41, 1, 512), (32, 39, 1, 256), (32, 37, 1, 96)]'),
     "ww": ("test_conv_wgrad_winograd", '[(41, 5), (39, 2), (37, 7), (41, 1), (37, 64), (39, 256)]'),
+    # the public direct weight gradient ends in the multi-job reduce: conv1 at 11, 31, 52 and 328 records
+    "wgrad": ("test_conv_wgrad", '[(9, 84, 2, 3), (32, 41, 1, 5), (32, 39, 1, 2), (32, 37, 1, 7), (9, 84, 2, 1), '
+                                 '(9, 84, 2, 5), (9, 84, 2, 32)]'),
 }
 OP_DECISIONS = ("conv_v.blocks>cap", "conv_v.rounds>1", "conv_v.ragged_last_tile", "ww.blocks*4>steps", "ww.xcd_remap")
 

@@ -1,7 +1,11 @@
 """The batch sizes of the per-launch encoder audit (tests/test_hip_encoder_audit.py) take every decision of the
 convolution launch arithmetic restated in tests/conv_variants.py on both sides, except the sides no batch can reach on a
-256-CU device, which are listed and checked as such.  No GPU needed."""
+256-CU device, which are listed and checked as such; and that restatement agrees with the planner the library launches
+from (csrc/conv_plan.h, through tests/conv_plan_dump.cpp).  No GPU needed."""
 import os
+import subprocess
+
+import pytest
 
 from tests import conv_variants as cv
 
@@ -112,3 +116,88 @@ def test_the_other_launchers_are_covered_by_the_op_tests():
     seen = cv.decisions_of(cv.op_test_launches())
     assert set(seen) == set(cv.OP_DECISIONS)
     assert all(v == {True, False} for v in seen.values()), seen
+
+
+# ------------------------------------------------------------------------- the mirror against csrc/conv_plan.h
+@pytest.fixture(scope="module")
+def plan_dump(tmp_path_factory):
+    """tests/conv_plan_dump.cpp compiled for the host: lines of launches in; rc, grid, grid_y, three record counts, the
+    merged flag and the workspace bytes out"""
+    from drqv2_amd import build
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path_factory.mktemp("conv_plan") / "conv_plan_dump")
+    subprocess.check_call([build._hipcc(), "-x", "c++", "-std=c++17", "-Wall", "-Werror",
+                           os.path.join(here, "conv_plan_dump.cpp"), "-o", exe])
+
+    def run(lines):
+        out = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, check=True).stdout
+        return [[int(v) for v in ln.split()] for ln in out.splitlines()]
+    return run
+
+
+def _line(kind, cus, nb, hin=0, stride=1, cin=32, lay=0, ws=-1):
+    return "%s %d %d %d %d %d %d %d\n" % (kind, cus, nb, hin, stride, cin, lay, ws)
+
+
+SWEEP_CUS = (2, 3, 8, 32, 64, 128, 256, 304)
+DIRECT_GEOMS = [(9, 84, 2), (32, 41, 1), (32, 39, 1), (32, 37, 1)]   # (cin, hin, stride) of the direct kernels
+PART = {9: (3 * 1024 + 64) * 4, 32: (9 * 1024 + 64) * 4}             # bytes of a partial record by cin
+
+
+def sweep_cases(cus, batches):
+    """(input line, the mirror's Launch) for every host-side function of the mirror at every geometry its launcher is
+    instantiated for.  hin 43 is the padded gradient of conv2's input gradient."""
+    for nb in batches:
+        for cin, hin, stride in DIRECT_GEOMS + [(32, 43, 1)]:
+            yield _line("conv_v", cus, nb, hin, stride, cin), cv.launch_conv_v(nb, hin, stride, cus=cus)
+        for cin, hin, stride in DIRECT_GEOMS:
+            yield _line("wgrad", cus, nb, hin, stride, cin), cv.launch_wgrad(nb, cin, hin, stride, cus)
+        for hin in (41, 39, 37, 43):
+            yield _line("wino", cus, nb, hin), cv.launch_wino(nb, hin, cus)
+            for lay in (0, 1):
+                yield _line("conv_bf16", cus, nb, hin, lay=lay), cv.launch_conv_bf16(nb, hin, lay, cus)
+        for hin in (41, 39, 37):
+            yield _line("ww", cus, nb, hin), cv.launch_ww(nb, hin, cus)
+            yield _line("wgrad_bf16", cus, nb, hin), cv.launch_wgrad_bf16(nb, hin, cus)
+        yield _line("ww3", cus, nb), cv.wgrad_partial_wino3(nb, cus)
+        for riders in (0, 6):
+            yield _line("conv1_aug", cus, nb, lay=riders), cv.launch_conv1_aug(nb, riders, cus)
+    for cins in ([9], [32], [9, 32], [32, 32, 32], [9, 32, 32, 32]):
+        yield (_line("reduce", cus, len(cins), cin=cins[0]), cv.reduce_multi([1] * len(cins), cins))
+
+
+def test_the_mirror_agrees_with_the_planner(plan_dump):
+    """per launch: the grid, the records left per layer and the merged-or-fallback choice, for batches 1..4096 at eight
+    CU counts (2: the three-layer launch never merges; 32: its overshoot loop; 8..128: its remap).  The C++ is the
+    behaviour: a disagreement is a bug of the mirror."""
+    cases = [c for cus in SWEEP_CUS for c in sweep_cases(cus, range(1, 4097))]
+    got = plan_dump([c[0] for c in cases])
+    assert len(got) == len(cases) > 900000
+    wrong = []
+    for (line, la), (rc, grid, grid_y, r0, r1, r2, merged, _) in zip(cases, got):
+        if la.kernel == cv.EARG:
+            ok = rc == -1 and not merged
+        else:
+            want_grid = la.grid if isinstance(la.grid, tuple) else (la.grid, 1)
+            ok = rc == 0 and merged and (grid, grid_y) == want_grid and [r0, r1, r2] == (list(la.records or []) + [0] * 3)[:3]
+        if not ok:
+            wrong.append((line.strip(), la.kernel, la.grid, la.records, (rc, grid, grid_y, r0, r1, r2, merged)))
+    assert not wrong, (len(wrong), wrong[:10])
+
+
+def test_the_planner_sizes_and_refuses_workspaces(plan_dump):
+    """the mirror has no workspace, so these are direct: a weight gradient needs one record per workgroup and layer, the
+    single-layer Winograd one a record per CU whatever its grid (and a padded dy); one byte less is DRQ_EWS (-2); a
+    geometry without a kernel is DRQ_EARG (-1) before the workspace is looked at"""
+    rc = lambda lines: [(g[0], g[-1]) for g in plan_dump(lines)]
+    assert rc([_line("wgrad", 256, 5, 84, 2, 9, ws=52 * PART[9]), _line("wgrad", 256, 5, 84, 2, 9, ws=52 * PART[9] - 1),
+               _line("wgrad", 256, 5, 41, 1, 32, ws=49 * PART[32] - 1), _line("wgrad", 256, 5, 43, 1, 32, ws=0),
+               _line("wgrad", 256, 5, 84, 1, 9, ws=0)]) == [(0, 52 * PART[9]), (-2, 52 * PART[9]), (-2, 49 * PART[32]),
+                                                          (-1, 0), (-1, 0)]
+    assert cv.launch_ww(1, 41).grid == 25
+    assert rc([_line("ww", 256, 1, 41, ws=256 * PART[32]), _line("ww", 256, 1, 41, ws=256 * PART[32] - 1),
+               _line("ww_flat", 256, 1, 41)]) == [(0, 256 * PART[32]), (-2, 256 * PART[32]), (-1, 0)]
+    assert rc([_line("ww3", 256, 8, ws=94 * PART[32]), _line("ww3", 256, 8, ws=94 * PART[32] - 1),
+               _line("ww3", 2, 8, ws=0)]) == [(0, 94 * PART[32]), (-2, 94 * PART[32]), (-1, 0)]
+    assert rc([_line("wgrad_bf16", 256, 2, 41, ws=20 * PART[32]), _line("wgrad_bf16", 256, 2, 41, ws=20 * PART[32] - 1),
+               _line("wgrad_bf16", 256, 2, 43, ws=0)]) == [(0, 20 * PART[32]), (-2, 20 * PART[32]), (-1, 0)]

@@ -181,8 +181,9 @@ def test_conv_wgrad_winograd_refuses_a_contiguous_dy(ops):
     assert nerr(dw, ref) <= 3e-6
 
 
-@pytest.mark.parametrize("cin,hin,stride,nb", [(9, 84, 2, 3), (32, 41, 1, 5), (32, 39, 1, 2), (32, 37, 1, 7)])
+@pytest.mark.parametrize("cin,hin,stride,nb", [(9, 84, 2, 3), (32, 41, 1, 5), (32, 39, 1, 2), (32, 37, 1, 7), (9, 84, 2, 1), (9, 84, 2, 5), (9, 84, 2, 32)])
 def test_conv_wgrad(ops, cin, hin, stride, nb):
+    """conv1 at batches 1, 5 and 32 leaves 11, 52 and 328 records: the three regimes of the reduce's record loop"""
     hout = (hin - 3) // stride + 1
     x = rnd(nb, cin, hin, hin, seed=7)
     dy = rnd(nb, 32, hout, hout, seed=8)
