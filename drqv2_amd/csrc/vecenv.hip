@@ -30,26 +30,12 @@
 // drq_vec_reach_image writes the renderer-shaped uint8 [N][S][S][C] image of frames, S = 84 k: every pixel k x k times,
 // channels last, a fourth channel 255.  N x ceil(pieces / 1,024) workgroups of 256 threads, 16-byte stores, the source
 // bytes through the cache (a frame is 21 KB); k and C are template arguments, so the decode divides by constants.
-#include "common.h"
+#include "vecenv_common.h"      // the frame's geometry, reach_draw, clamp1: shared with veccartpole.hip
 #include "../../include/drqv2_hip.h"
 
 namespace {
 
-constexpr int kSide = 84;
-constexpr int kPlane = kSide * kSide;             // 7,056 bytes = 441 x 16
-constexpr int kFrame = 3 * kPlane;                // 21,168 bytes = 1,323 x 16
-constexpr int kPieces = kFrame / 16;
-constexpr int kThreads = 256;
 constexpr int kTargetR2 = 25, kAgentR2 = 16;
-
-// draw k of episode `episode` of environment e: uniform on the 2^24 grid of [0, 1), then into [-0.9, 0.9]
-__device__ __forceinline__ float reach_draw(unsigned seed, unsigned e, unsigned episode, unsigned k) {
-  const unsigned h = drq_fmix32(seed ^ e * 0x9E3779B9u ^ episode * 0x85EBCA6Bu ^ k * 0xC2B2AE35u);
-  const float u = (float)(h >> 8) * 5.9604644775390625e-8f;          // 2^-24: exact
-  return (u * 2.0f - 1.0f) * 0.9f;
-}
-
-__device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
 __device__ __forceinline__ int pixel_centre(float x) { return (int)floorf((x + 1.0f) * 41.5f + 0.5f); }
 

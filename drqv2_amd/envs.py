@@ -9,6 +9,12 @@ accelerates the point, and its velocity is in no single frame, so it is the one 
 stack.  Both take action_repeat (the ActionRepeatWrapper of dmc.py:35-50, inside the launch).  The tasks are specified to
 the bit in include/drqv2_hip.h ("device environment") and restated in numpy by tests/vec_env_oracle.py and
 tests/vec_tasks_oracle.py.  They are not benchmark tasks and say nothing about DMC.
+
+VecCartpole is a third task with a kernel of its own (csrc/veccartpole.hip, drq_vec_cartpole_step): a cart on a rail that
+carries a free pole, started hanging or near upright, in the image of the reference's cartpole_swingup and
+cartpole_balance (cfgs/task/easy.yaml) -- an action that acts through second-order coupled dynamics and an unstable
+equilibrium.  It shares _VecTask with the other two; what differs per task -- the entries, the state arrays and their
+arguments -- are _VecTask's hooks.  Specified in include/drqv2_hip.h ("Cartpole"), restated by tests/vec_cartpole_oracle.py.
 """
 import torch
 
@@ -55,7 +61,11 @@ class _VecTask:
     FRAME_SHAPE = (3, 84, 84)
     IMAGE_SIZES = (84, 168, 252, 336)
     TASK = TASK_ID = None       # the name in state dicts and tools; DRQ_TASK_* of include/drqv2_hip.h
-    _STATE = ("pos", "target", "t", "episode", "over")
+    _STATE = ("pos", "target", "t", "episode", "over")      # the state arrays, in the order of state() and state_dict()
+    _STATE_SPEC = {"pos": ((2,), torch.float32), "target": ((2,), torch.float32), "vel": ((2,), torch.float32),
+                   "t": ((), torch.int32), "episode": ((), torch.int32), "over": ((), torch.uint8)}
+    _MIN_ACTION_DIM = 2         # the columns of the action a step reads
+    vel = None                  # reach has no velocity: the library is handed NULL
 
     def __init__(self, num_envs, device, action_dim=2, episode_length=250, seed=0, action_repeat=1):
         if isinstance(action_repeat, bool) or not isinstance(action_repeat, int) \
@@ -63,17 +73,13 @@ class _VecTask:
             raise ValueError(f"action_repeat must be an int in 1 .. {MAX_ACTION_REPEAT}, got {action_repeat!r}")
         self.action_repeat = action_repeat
         self.N, self.A, self.episode_length = int(num_envs), int(action_dim), int(episode_length)
-        if self.N < 1 or self.A < 2 or self.episode_length < 1:
-            raise ValueError("num_envs and episode_length must be >= 1, action_dim >= 2")
+        if self.N < 1 or self.A < self._MIN_ACTION_DIM or self.episode_length < 1:
+            raise ValueError(f"num_envs and episode_length must be >= 1, action_dim >= {self._MIN_ACTION_DIM}")
         self.seed = int(seed) & 0xFFFFFFFF
         self.device = dev = torch.device(device)
-        N = self.N
-        self.pos = torch.zeros((N, 2), dtype=torch.float32, device=dev)
-        self.target = torch.zeros((N, 2), dtype=torch.float32, device=dev)
-        self.t = torch.zeros(N, dtype=torch.int32, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)       # uint32 on the device: state() views it so
-        self.over = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.vel = torch.zeros((N, 2), dtype=torch.float32, device=dev) if "vel" in self._STATE else None
+        for k in self._STATE:       # episode is uint32 on the device: state() views it so
+            shape, dtype = self._STATE_SPEC[k]
+            setattr(self, k, torch.zeros((self.N,) + shape, dtype=dtype, device=dev))
         self.last_substeps = None   # int32 [N] of the newest step() / reset()
         self._out = None            # two of (frame, reward, discount, first, substeps), then the index of the next
         self._frame = None          # the frames of the newest step() / reset()
@@ -116,13 +122,21 @@ class _VecTask:
     def _launch(self, action, reset_all):
         out = self._next_out()
         with torch.cuda.device(self.device):
-            launch("drq_vec_task_step", self.TASK_ID, ptr(self.pos), ptr(self.target), ptr(self.vel), ptr(self.t),
-                   ptr(self.episode), ptr(self.over), self.N, self.A, ptr(action), self.seed, self.episode_length,
-                   self.action_repeat, int(reset_all), *(ptr(o) for o in out), device=self.device)
+            self._step_launch(action, reset_all, out)
             if action is not None:  # a caller's tensor may be freed right after step(): the launch still reads it
                 action.record_stream(torch.cuda.current_stream())
         self._frame, self.last_substeps = out[0], out[4]
         return out[:4]
+
+    def _step_launch(self, action, reset_all, out):
+        """the task's step entry: the macro step (or the reset of all) of every environment into the output set `out`"""
+        launch("drq_vec_task_step", self.TASK_ID, ptr(self.pos), ptr(self.target), ptr(self.vel), ptr(self.t),
+               ptr(self.episode), ptr(self.over), self.N, self.A, ptr(action), self.seed, self.episode_length,
+               self.action_repeat, int(reset_all), *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        """the task's render entry: the frames of the states as they are into `frame`"""
+        launch("drq_vec_reach_render", ptr(self.pos), ptr(self.target), self.N, ptr(frame), device=self.device)
 
     def reset(self):
         """Starts a new episode in every environment (one launch) and returns its first frames, uint8 [N, 3, 84, 84].  The
@@ -153,7 +167,7 @@ class _VecTask:
 
     def _render(self):
         out = self._next_out()
-        launch("drq_vec_reach_render", ptr(self.pos), ptr(self.target), self.N, ptr(out[0]), device=self.device)
+        self._render_launch(out[0])
         self._frame = out[0]
         return out[0]
 
@@ -236,3 +250,47 @@ class VecPointMass(_VecTask):
     methods as VecReach; state() and state_dict() carry "vel" too."""
     TASK, TASK_ID = "pointmass", 1
     _STATE = _VecTask._STATE + ("vel",)
+
+
+class VecCartpole(_VecTask):
+    """N environments of the cartpole on the device: a cart on a rail carries a free pole, and action[:, 0] in [-1, 1]
+    pushes the cart with a force of 10 (NaN counts as 0; further columns are ignored).  swing_up=True starts every
+    episode with the pole hanging down (the reference's cartpole_swingup), swing_up=False with it near upright
+    (cartpole_balance): the first task here whose action acts through second-order coupled dynamics, with an unstable
+    equilibrium.  It is a task in the image of those two, not a port of them: the frictionless textbook equations
+    stepped by semi-implicit Euler at dt = 0.01, the pole's angle held as a unit vector so that a step is +, -, *, / and
+    sqrt alone, and DMC's reward product with rational sigmoids -- upright (c + 1) / 2, centred, small control, small
+    angular velocity, each in [0, 1].  Nothing it scores says anything about DMC.  The rule is in include/drqv2_hip.h
+    ("Cartpole") to the bit and restated in numpy by tests/vec_cartpole_oracle.py.
+
+        env = VecCartpole(num_envs=N, device="cuda", action_dim=1, episode_length=1000, seed=0, action_repeat=1,
+                          swing_up=True)
+
+    The discount is 1 on every row and only the time limit (t == episode_length, in simulator steps) ends an episode; the
+    rail ends at x = +-1.8 stop the cart as the point mass's walls do.  The frame shows the rail (blue), the cart (green)
+    and the pole (red, a capsule) at 20 pixels per unit, so the whole pole is in the picture for |x| <= 0.9; neither
+    velocity is in a frame, so the policy needs the frame stack.  Same methods and guarantees as VecReach (_VecTask
+    holds them): reset, step, render, image, state, state_dict, load_state_dict and last_substeps, two rotating output
+    sets, nothing waits for the GPU.  The state words are "phys", float32 [N, 5] = (x, xdot, cos, sin, omega), and t,
+    episode, over; the config of a state dict carries swing_up."""
+    TASK = "cartpole"
+    _STATE = ("phys", "t", "episode", "over")
+    _STATE_SPEC = dict(_VecTask._STATE_SPEC, phys=((5,), torch.float32))
+    _MIN_ACTION_DIM = 1
+
+    def __init__(self, num_envs, device, action_dim=1, episode_length=1000, seed=0, action_repeat=1, swing_up=True):
+        if not isinstance(swing_up, (bool, int)) or swing_up not in (0, 1):
+            raise ValueError(f"swing_up must be True or False, got {swing_up!r}")
+        self.swing_up = bool(swing_up)
+        super().__init__(num_envs, device, action_dim, episode_length, seed, action_repeat)
+
+    def _step_launch(self, action, reset_all, out):
+        launch("drq_vec_cartpole_step", ptr(self.phys), ptr(self.t), ptr(self.episode), ptr(self.over), self.N, self.A,
+               ptr(action), self.seed, self.episode_length, self.action_repeat, int(reset_all), int(self.swing_up),
+               *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        launch("drq_vec_cartpole_render", ptr(self.phys), self.N, ptr(frame), device=self.device)
+
+    def _config(self):
+        return dict(super()._config(), swing_up=self.swing_up)

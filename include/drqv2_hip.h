@@ -656,6 +656,69 @@ int drq_vec_reach_step(float* pos, float* target, int* t, unsigned* episode, uin
 int drq_vec_reach_render(const float* pos, const float* target, long N, uint8_t* frame, drq_stream_t stream);
 int drq_vec_reach_image(const uint8_t* frame, uint8_t* image, long N, int S, int C, drq_stream_t stream);
 
+/* Cartpole.  A third task of the device environment, with entries of its own: a cart on a rail carries a free pole, the
+ * action pushes the cart.  swing_up = 1 starts every episode with the pole hanging down (the reference's
+ * cartpole_swingup, cfgs/task/easy.yaml), swing_up = 0 with the pole near upright (cartpole_balance).  The action acts
+ * through second-order coupled dynamics, and upright is an unstable equilibrium.  These definitions are the contract; they
+ * are exact to the bit.  Every float operation below is ONE correctly rounded IEEE float32 operation (+, -, *, / or
+ * sqrt), in the written order, never fused; there is no sin, cos or exp anywhere: the pole's angle theta, measured from
+ * upright, is held as the unit vector (c, s) = (cos theta, sin theta).
+ * State per environment e: phys f32 [N][5] = (x, xdot, c, s, omega): the cart's position and velocity, the pole's unit
+ *   vector and angular velocity; t i32 [N], episode u32 [N], over u8 [N] as above.
+ * normalise(c, s):  n = sqrt(c * c + s * s);  c = c / n;  s = s / n;  then one correction by the defect of the length,
+ *   which leaves c * c + s * s within 1 ulp of 1 (the five operations before it leave it within 3):
+ *   split(a):  t = a * 4097;  hi = t - (t - a);  lo = a - hi              (Veltkamp: hi * hi, hi * lo, lo * lo are exact)
+ *   square(a): p = a * a;  q = hi * lo;  err = ((hi * hi - p) + (q + q)) + lo * lo      (Dekker: p + err = a * a exactly)
+ *   (pc, ec) = square(c);  (ps, es) = square(s);  d = (1 - pc) - ps if pc >= ps, otherwise d = (1 - ps) - pc;
+ *   d = d - (ec + es);  g = d * 0.5f;  c = c + c * g;  s = s + s * g.
+ * Reset of e (reset_all = 1, or over[e] == 1): episode += 1 (mod 2^32), t = 0, over = 0; two draws v_0, v_1 as above
+ *   (the same hash of (seed, e, episode, k), v = (u * 2 - 1) * 0.9f):
+ *   x = v_0 * 0.1f;  xdot = 0;  omega = 0;  c = -1 for swing_up, 1 for balance;  s = v_1 * 0.05f;  normalise(c, s).
+ *   Outputs first = 1, reward = 0, discount = 1, substeps = 0, the frame of the new state.  The action is not read.
+ * Sub-step, a the sanitised action (a = action[e][0]; NaN becomes 0, then the clamp to [-1, 1]; columns 1 .. A-1 are not
+ *   read).  dt = 0.01, force 10 a, cart mass 1, pole mass 0.1, pole half-length 0.5, g = 9.8; the frictionless equations:
+ *   F = a * 10;  t1 = omega * omega;  t1 = 0.05f * t1;  t1 = t1 * s;  temp = (F + t1) / 1.1f
+ *   num = 9.8f * s - c * temp                                  (two multiplies, then the subtraction)
+ *   q = c * c;  q = 0.1f * q;  q = q / 1.1f;  den = 1.3333334f - q;  den = 0.5f * den;  thacc = num / den
+ *   r = 0.05f * thacc;  r = r * c;  r = r / 1.1f;  xacc = temp - r
+ *   omega = clamp(omega + thacc * 0.01f, -32, 32);  xdot = clamp(xdot + xacc * 0.01f, -16, 16)        (semi-implicit Euler)
+ *   p = x + xdot * 0.01f;  p < -1.8f: x = -1.8f, xdot = 0;  p > 1.8f: x = 1.8f, xdot = 0;  otherwise x = p  (the rail ends)
+ *   h = omega * 0.01f;  c' = c - s * h;  s' = s + c * h  (both from the old c and s);  (c, s) = normalise(c', s')
+ *   t += 1;  over = 1 only when t == episode_length;  d_i = 1 always.  Every reachable state is finite: den >= 0.62,
+ *   |omega|, |xdot| and |x| are bounded, and n >= 1 up to rounding.
+ *   Reward r_i in [0, 1], of the new state and a -- DMC cartpole's product with rational sigmoids for its Gaussian ones:
+ *   up = (c + 1) * 0.5f;  ce = 1 / (1 + x * x);  ce = (1 + ce) * 0.5f;  co = (4 + (1 - a * a)) / 5
+ *   w = omega / 5;  sl = 1 / (1 + w * w);  sl = (1 + sl) * 0.5f;  r_i = ((up * ce) * co) * sl
+ * Macro step: the one of "Tasks and action repeat" with every d_i = 1: reward = reward + r_i for up to `repeat` sub-steps,
+ *   stopping after the one that set over; discount = 1, first = 0, substeps = the sub-steps executed.
+ * Frame of a state, u8 [3][84][84].  Coordinates are integers in 1/16 pixel; pixel (i, j) has its centre at
+ *   (16 j + 8, 16 i + 8).  320 units (20 pixels) are one unit of x and the pole's length, so the pole is fully visible
+ *   for |x| <= 0.9, half the rail.  The pivot is (X0, 672), the pole's tip (X1, Y1), each rounded once:
+ *   xs = x * 320;  X0 = (int)floorf(xs + 672.5f);  X1 = (int)floorf((xs + s * 320) + 672.5f);  Y1 = (int)floorf(672.5f - c * 320)
+ *   Everything after that is integer arithmetic.  Per pixel, with P = (16 j + 8, 16 i + 8), later rules drawn over earlier:
+ *   background 32 + ((i + j) >> 2) in all three channels;
+ *   the rail, i == 42 and |P.x - 672| <= 576, in (64, 64, 255);
+ *   the cart, |P.x - X0| <= 96 and |P.y - 672| <= 48, in (64, 255, 64);
+ *   the pole, a capsule of radius 24 around the segment pivot -- tip, in (255, 64, 64): with v = P - pivot, d = tip - pivot,
+ *     dot = v.d, dd = d.d (int32):  dot <= 0: |v|^2 <= 576;  dot >= dd: |P - tip|^2 <= 576;  otherwise
+ *     cross = v.x * d.y - v.y * d.x and cross * cross <= 576 * dd, both sides in int64 (cross^2 reaches about 10^12).
+ *   Shapes that leave the frame are clipped by the pixel loop itself.
+ *
+ * drq_vec_cartpole_step: one launch, N workgroups of 256 threads with the shape of drq_vec_task_step: every lane computes the
+ *   macro step in registers (the trip count is uniform across a workgroup), a workgroup barrier, one lane stores the state
+ *   and the scalars, all store the frame as 1,323 pieces of 16 bytes.  Writes every byte of frame, reward, discount, first,
+ *   substeps and the state, nothing else.  No LDS, no atomics, nothing crosses workgroups.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 1, repeat < 1
+ *   or > DRQ_TASK_MAX_REPEAT, episode_length < 1, reset_all or swing_up not 0 or 1, frame not 16-byte aligned, a float /
+ *   int array not 4-byte aligned.
+ * drq_vec_cartpole_render: the frames of the states as they are, by the frame rule above (the same device function): every
+ *   byte of frame, nothing else; phys is only read.  DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX,
+ *   frame not 16-byte aligned, phys not 4-byte aligned.  drq_vec_reach_image serves these frames as it serves any. */
+int drq_vec_cartpole_step(float* phys, int* t, unsigned* episode, uint8_t* over, long N, int A, const float* action,
+                          unsigned seed, int episode_length, int repeat, int reset_all, int swing_up, uint8_t* frame,
+                          float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
+int drq_vec_cartpole_render(const float* phys, long N, uint8_t* frame, drq_stream_t stream);
+
 /* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
  * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
  * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep

@@ -1,0 +1,290 @@
+"""The cartpole of the device environment (drq_vec_cartpole_step / _render, drqv2_amd.envs.VecCartpole): everything that
+needs no GPU.  The public surface and the DRQ_EARG cases (all are decided before any launch), the properties of the numpy
+restatement tests/vec_cartpole_oracle.py that make it a cartpole -- the unit vector stays one, upright is a fixed point,
+the mirror symmetry, the reward's range, the capsule against a float64 distance, no denormal in a long free run -- and
+the condition on the inputs of the GPU tests (tests/test_hip_vec_cartpole.py), which is a property of the oracle's runs
+alone."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from drqv2_amd import _lib
+from tests import abi
+from tests import vec_cartpole_oracle as O
+
+F = np.float32
+STEP, RENDER = "drq_vec_cartpole_step", "drq_vec_cartpole_render"
+ULP1 = 2.0 ** -23                   # the spacing of float32 at 1
+TINY = np.finfo(np.float32).tiny    # the smallest normal float32
+
+
+def same_bits(got, want, what):
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    assert got.tobytes() == want.tobytes(), what
+
+
+# ------------------------------------------------------------------------------------------------ public surface
+def test_header_prototypes_symbols_and_build_flags():
+    header = abi.text()
+    for name, nargs in ((STEP, 18), (RENDER, 4)):
+        abi.assert_prototype(name)
+        assert len(_lib.PROTOTYPES[name][1]) == nargs and name not in _lib.NO_STREAM and name in abi.stream_entries()
+        assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name)
+    for text in ("Cartpole.", "n = sqrt(c * c + s * s);  c = c / n;  s = s / n", "temp = (F + t1) / 1.1f",
+                 "den = 1.3333334f - q;  den = 0.5f * den;  thacc = num / den", "c' = c - s * h;  s' = s + c * h",
+                 "r_i = ((up * ce) * co) * sl", "cross * cross <= 576 * dd", "X0 = (int)floorf(xs + 672.5f)"):
+        assert text in header, text                                        # the rule is part of the contract
+    from drqv2_amd import build, envs
+    assert "veccartpole.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "veccartpole.hip"))
+    assert build.FILE_FLAGS["veccartpole.hip"] == ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
+    assert _lib.load().drq_abi_version() == 7                              # additive: the version stays
+    assert envs.VecCartpole.TASK == "cartpole" and issubclass(envs.VecCartpole, envs._VecTask)
+    with open(os.path.join(build.CSRC, "veccartpole.hip")) as f:
+        src = "\n".join(line.split("//")[0] for line in f.read().splitlines())     # the code without its comments
+    for banned in ("sinf", "cosf", "expf", "__shared__", "atomic"):        # no libm rounding, no LDS, no atomics
+        assert banned not in src, banned
+    assert "sqrtf" in src
+
+
+def test_refusals_that_need_no_gpu():
+    """every DRQ_EARG case is decided before any launch.  The pointers are made-up addresses with the required alignment:
+    a refused call never looks behind them.  (tests/test_hip_vec_cartpole.py repeats them on poisoned outputs.)"""
+    lib = _lib.load()
+    for a in O.refused_calls(0x10000, 0x20000, 0x30000, 0x40000):
+        assert lib.drq_vec_cartpole_step(*a, None) == -1, a
+    for a in O.refused_renders(0x10000, 0x30000):
+        assert lib.drq_vec_cartpole_render(*a, None) == -1, a
+    # the task entry still knows reach and the point mass only
+    assert lib.drq_vec_task_step(2, *([0x10000] * 6), 5, 2, 0x20000, 7, 9, 2, 0, 0x30000, *([0x40000] * 4), None) == -1
+
+
+# ------------------------------------------------------------------------------------------------ the class, no GPU
+def test_constructor_state_and_state_dict_without_a_device(tmp_path):
+    from drqv2_amd import checkpoint
+    from drqv2_amd.envs import VecCartpole, VecPointMass
+    env = VecCartpole(3, "cpu")
+    assert (env.A, env.episode_length, env.action_repeat, env.swing_up) == (1, 1000, 1, True)
+    for bad in (dict(action_dim=0), dict(num_envs=0), dict(episode_length=0)):
+        with pytest.raises(ValueError, match="action_dim >= 1"):
+            VecCartpole(**dict(dict(num_envs=3, device="cpu"), **bad))
+    for bad in (0, 17, True, 2.0):
+        with pytest.raises(ValueError, match="action_repeat"):
+            VecCartpole(3, "cpu", action_repeat=bad)
+    for bad in (2, "yes", None, 0.5):
+        with pytest.raises(ValueError, match="swing_up"):
+            VecCartpole(3, "cpu", swing_up=bad)
+    with pytest.raises(ValueError, match="action_dim >= 2"):               # the other tasks read two columns, as before
+        VecPointMass(3, "cpu", action_dim=1)
+    env = VecCartpole(3, "cpu", action_dim=2, episode_length=7, seed=1, action_repeat=2, swing_up=False)
+    for method in ("reset", "step", "render", "image", "state", "state_dict", "load_state_dict"):
+        assert callable(getattr(env, method)), method
+    assert env.last_substeps is None
+    with pytest.raises(_lib.DrqError, match="no CPU fallback"):
+        env.reset()
+    with pytest.raises(ValueError, match=r"step\(\): action"):
+        env.step(torch.zeros(3, 1))
+    s = env.state()
+    assert list(s) == ["phys", "t", "episode", "over"] and s["phys"].shape == (3, 5) and s["phys"].dtype == np.float32
+    assert s["episode"].dtype == np.uint32 and s["over"].dtype == np.uint8 and s["t"].dtype == np.int32
+    sd = env.state_dict()
+    assert sd["kind"] == "VecCartpole" and sd["config"] == {"N": 3, "A": 2, "episode_length": 7, "seed": 1, "task": "cartpole",
+                                                             "action_repeat": 2, "swing_up": False}
+    with pytest.raises(_lib.DrqError, match="GPU"):                        # the checks pass, then the device is refused
+        VecCartpole(3, "cpu", action_dim=2, episode_length=7, seed=1, action_repeat=2, swing_up=False).load_state_dict(sd)
+    with pytest.raises(ValueError, match=r"\bswing_up: saved False, here True"):
+        VecCartpole(3, "cpu", action_dim=2, episode_length=7, seed=1, action_repeat=2).load_state_dict(sd)
+    with pytest.raises(ValueError, match="kind"):
+        VecPointMass(3, "cpu", episode_length=7, seed=1, action_repeat=2).load_state_dict(sd)
+    with pytest.raises(ValueError, match="phys: no tensor saved"):
+        VecCartpole(3, "cpu", action_dim=2, episode_length=7, seed=1, action_repeat=2, swing_up=False).load_state_dict(
+            {k: v for k, v in sd.items() if k != "phys"})
+    # drqv2_amd.checkpoint takes the class with no special case: the file holds the dict as it is
+    env.phys[1, 4] = 0.25
+    path = str(tmp_path / "env.pt")
+    checkpoint.save(path, env=env, extra={"step": 4})
+    ck = torch.load(path, weights_only=True)
+    assert ck["env"]["kind"] == "VecCartpole" and ck["env"]["config"]["swing_up"] is False
+    assert torch.equal(ck["env"]["phys"], env.phys) and ck["extra"] == {"step": 4}
+
+
+# ------------------------------------------------------------------------------------------------ the oracle's properties
+def free_run(p, a, steps):
+    out = []
+    for _ in range(steps):
+        p, _ = O.substep(p, a)
+        out.append(p)
+    return out
+
+
+_HARD = {}
+
+
+def hard_run():
+    """8,000 sub-steps, computed once: from a hanging and from a nearly upright start, 2,000 under a push that changes
+    sides every 90 steps and 2,000 under one that follows the swing, so that the pole spins and the cart hits both rail
+    ends.  Every state, its action and whether a rail end was hit"""
+    if not _HARD:
+        rows = []
+        for start in ((F(0.01), F(0), *O.normalise(F(-1), F(0.03)), F(0)), (F(-0.02), F(0), *O.normalise(F(1), F(-0.02)), F(0))):
+            p = start
+            for i in range(4000):
+                a = F(1) if (i // 90) % 2 == 0 else F(-1)
+                if i >= 2000:
+                    a = F(1) if p[3] * p[4] >= 0 else F(-1)
+                p, hit = O.substep(p, a)
+                rows.append((p, a, hit))
+        _HARD["rows"] = rows
+    return _HARD["rows"]
+
+
+def test_every_reachable_state_is_finite_and_bounded_and_the_reward_in_range():
+    rows = hard_run()
+    for p, a, _ in rows:
+        assert all(np.isfinite(v) and v.dtype == np.float32 for v in p)
+        assert abs(p[2]) <= 1 and abs(p[3]) <= 1 and abs(p[0]) <= O.RAIL and abs(p[1]) <= O.MAX_XDOT and abs(p[4]) <= O.MAX_OMEGA
+        r = O.reward_of(p, a)
+        assert r.dtype == np.float32 and 0 <= r <= 1
+    assert {hit for _, _, hit in rows} == {-1, 0, 1} and max(abs(float(p[4])) for p, _, _ in rows) > 10
+
+
+def test_unit_vector_stays_within_2_ulp_of_one():
+    """c^2 + s^2, evaluated in float64, within 2 ulp of 1 (2 x 2^-23 = 2.38e-7) after every sub-step of hard_run().
+    The division by n = sqrt(c'^2 + s'^2) alone cannot hold that (five roundings: up to 3 ulp, and 2.38 ulp over these
+    8,000 states); the contract's correction by the exactly computed defect 1 - c^2 - s^2 leaves c and s the float32
+    nearest to the unit vector's components, so the square of the length is within 1 ulp of 1, up to terms of 2^-46"""
+    worst = max(abs(float(p[2]) ** 2 + float(p[3]) ** 2 - 1.0) for p, _, _ in hard_run())
+    print(f"worst |c^2 + s^2 - 1| = {worst:.3e} = {worst / ULP1:.2f} ulp of 1")
+    assert worst <= 2 * ULP1, worst / ULP1
+    assert worst <= 1.01 * ULP1, worst / ULP1          # what the correction gives, by the reasoning above
+
+
+def test_the_clamps_bound_omega_and_xdot():
+    p, _ = O.substep((F(0), F(15.99), F(0), F(1), F(31.99)), F(1))
+    assert p[4] == O.MAX_OMEGA and p[1] == O.MAX_XDOT
+    p, _ = O.substep((F(0), F(-15.99), F(0), F(-1), F(-31.99)), F(-1))
+    assert p[4] == -O.MAX_OMEGA and p[1] == -O.MAX_XDOT
+
+
+def test_reward_is_one_only_upright_centred_at_rest_without_control():
+    best = (F(0), F(0), F(1), F(0), F(0))
+    assert O.reward_of(best, F(0)) == 1
+    for worse, a in (((F(0.5), F(0), F(1), F(0), F(0)), F(0)), ((F(0), F(0), F(0.9), F(0.4), F(0)), F(0)),
+                     ((F(0), F(0), F(1), F(0), F(3)), F(0)), (best, F(0.5))):
+        assert 0 < O.reward_of(worse, a) < 1
+    assert O.reward_of((F(0), F(0), F(-1), F(0), F(0)), F(0)) == 0           # hanging
+
+
+def test_exactly_upright_with_zero_action_is_a_fixed_point():
+    for x in (F(0), F(0.37), F(-1.8)):
+        for a in (F(0), F(-0.0)):
+            p = (x, F(0), F(1), F(0), F(0))
+            for q in free_run(p, a, 50):
+                same_bits(np.array(q), np.array(p), (x, a))
+    # ... and an unstable one: the smallest tilt grows
+    q = free_run((F(0), F(0), *O.normalise(F(1), F(1e-3)), F(0)), F(0), 200)[-1]
+    assert q[3] > 0.05
+
+
+def test_the_mirror_state_under_the_mirror_action_gives_the_mirrored_trajectory_bit_for_bit():
+    r = np.random.RandomState(3)
+    mirror = lambda p: (-p[0], -p[1], p[2], -p[3], -p[4])
+    for start in ((F(0.3), F(-0.2), *O.normalise(F(-1), F(0.4)), F(1.5)), (F(-1.7), F(-3), *O.normalise(F(0.2), F(-1)), F(-7))):
+        p, m = start, mirror(start)
+        hits = 0
+        for i in range(600):
+            a = O.clamp1(F(r.uniform(-1.5, 1.5)))
+            p, hp = O.substep(p, a)
+            m, hm = O.substep(m, F(-a))
+            hits += hp != 0
+            assert hm == -hp
+            same_bits(np.array(m) + F(0), np.array(mirror(p)) + F(0), i)      # + 0: a rail end sets xdot = +0 on either side
+            same_bits(O.reward_of(m, F(-a)), O.reward_of(p, a), (i, "reward"))
+        assert hits >= 1
+
+
+def test_a_long_zero_action_run_carries_no_state_word_into_the_denormal_range():
+    """no damping term shrinks anything: 20,000 free sub-steps of four resets of either variant; every state word is zero
+    or at least the smallest normal float32"""
+    for swing in (True, False):
+        o = O.CartpoleOracle(4, seed=11, swing_up=swing)
+        o.frames = lambda: None
+        o.reset()
+        for e in range(4):
+            p = tuple(o.phys[e])
+            for q in free_run(p, F(0), 5000):
+                v = np.abs(np.array(q))
+                assert ((v == 0) | (v >= TINY)).all() and np.isfinite(v).all(), q
+
+
+def test_capsule_pixels_match_a_float64_distance_except_in_a_band_at_the_edge():
+    """The integer rule against the float64 distance of the pixel centre to the segment, for 200 random segments and the
+    degenerate ones: wherever the distance differs from the radius by more than 1e-6 units (a unit is 1/16 pixel; the
+    integer rule is exact, the band only covers the float64 rounding of the reference) the two agree; and a capsule
+    covers what a 1.5-pixel-wide pole should: between 2 r |d| and (2 r + 4) (|d| + 2 r) square units"""
+    r = np.random.RandomState(9)
+    segs = [(int(r.randint(-200, 1544)), 672, int(r.randint(-500, 1800)), int(r.randint(300, 1044))) for _ in range(200)]
+    segs += [(672, 672, 672, 352), (672, 672, 992, 672), (100, 672, 100, 672), (1300, 672, 1620, 672), (672, 672, 673, 672)]
+    for X0, Y0, X1, Y1 in segs:
+        got = O.capsule(X0, Y0, X1, Y1)
+        px, py = O._PX.astype(np.float64), O._PY.astype(np.float64)
+        dx, dy = float(X1 - X0), float(Y1 - Y0)
+        dd = dx * dx + dy * dy
+        u = np.clip(((px - X0) * dx + (py - Y0) * dy) / dd, 0, 1) if dd else np.zeros_like(px)
+        dist = np.hypot(px - (X0 + u * dx), py - (Y0 + u * dy))
+        sure = np.abs(dist - O.POLE_R) > 1e-6
+        assert (got[sure] == (dist <= O.POLE_R)[sure]).all(), (X0, Y0, X1, Y1)
+    frame = O.render(np.array([0, 0, 1, 0, 0], F))                          # upright at the centre: 20 pixels and a cap tall
+    pole = (frame[0] == 255)
+    rows, cols = np.nonzero(pole)
+    assert (rows.min(), rows.max()) == (21, 42) and (cols.min(), cols.max()) == (40, 43)
+    assert (frame[1] == 255).sum() > 0 and (frame[2] == 255).sum() > 0      # cart and rail are there, in their own channels
+    assert not ((frame[0] == 255) & (frame[1] == 255)).any() and frame.min() >= 32
+
+
+def test_the_pole_is_fully_visible_up_to_half_the_rail():
+    """|x| <= 0.9: the capsule's bounding box (end points +- the radius) lies inside the 1,344 units of the frame for every
+    direction of the pole; at the rail's end the cart is still in the picture"""
+    for x in (F(-0.9), F(0.9)):
+        for c, s in ((0, 1), (0, -1), (1, 0), (-1, 0), O.normalise(F(1), F(1)), O.normalise(F(-1), F(-1))):
+            X0, X1, Y1 = O.end_points(x, F(c), F(s))
+            assert 0 <= min(X0, X1) - O.POLE_R and max(X0, X1) + O.POLE_R <= 16 * 84
+            assert 0 <= Y1 - O.POLE_R and Y1 + O.POLE_R <= 16 * 84
+    for x in (-O.RAIL, O.RAIL):
+        X0 = O.end_points(x, F(1), F(0))[0]
+        assert 0 <= X0 - O.CART_HALF_W and X0 + O.CART_HALF_W <= 16 * 84
+
+
+# ------------------------------------------------------------------------------------------------ the shared drive
+def test_inputs_of_the_gpu_tests_cover_what_they_claim():
+    """The runs tests/test_hip_vec_cartpole.py compares on the GPU, on the oracle alone: together they hold a hit on the
+    left and on the right rail end, s changing sign through hanging and (the balance variant) through upright, a time
+    limit that cuts a repeat short, a reset row, a NaN action and an action beyond +-1; and the episodes of the short runs
+    do stagger"""
+    seen = dict.fromkeys(("hit_left", "hit_right", "through_hanging", "through_upright", "cut_by_limit", "full",
+                          "reset_rows"), 0)
+    upright_in_balance = nan = beyond = inf = 0
+    for cfg in O.PHYSICS:
+        run = O.physics_run(*cfg, frames=False)
+        for k in seen:
+            seen[k] += run[k]
+        if not cfg[3]:
+            upright_in_balance += run["through_upright"]
+        beyond += int((np.abs(np.stack(run["actions"])[:, :, 0]) > 1).sum())
+    for cfg in O.DRIVEN:
+        run = O.driven_run(*cfg, frames=False)
+        for k in seen:
+            seen[k] += run[k]
+        acts = np.stack(run["actions"])[:, :, 0]
+        assert np.isnan(acts).any() and np.isinf(acts).any() and (np.abs(acts[np.isfinite(acts)]) > 1).any(), cfg
+        nan, inf, beyond = nan + int(np.isnan(acts).sum()), inf + int(np.isinf(acts).sum()), beyond + 1
+        firsts = np.stack([o[3] for o in run["out"]])
+        # a repeat of 16 ends every episode of seven steps in its first row, whatever t was: only there all reset together
+        assert firsts.any() and (cfg[2] > O.EPISODE_LENGTH or not (firsts.all(1) | ~firsts.any(1)).all()), "no stagger"
+        assert run["reset_rows"] >= 1 and (cfg[2] == 1 or run["cut_by_limit"] >= 1), cfg
+        assert all((o[2] == 1).all() for o in run["out"])                  # the discount is 1 on every row
+    assert all(v >= 1 for v in seen.values()), seen
+    assert upright_in_balance >= 1 and nan >= 1 and inf >= 1 and beyond >= 1

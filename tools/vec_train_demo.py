@@ -1,6 +1,6 @@
 """The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
 
-  VecReach or VecPointMass (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecReach, VecPointMass or VecCartpole (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
   VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
 
 Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
@@ -8,7 +8,7 @@ return (and length) of the episodes that finished in every interval, from VecEpi
 uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--task reach|pointmass] [--action-repeat 1]
+  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup] [--action-repeat 1]
                                  [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
@@ -18,6 +18,8 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--explore-beta B [--explore-bits K]]
 
 --task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
+--task cartpole_balance and cartpole_swingup train on VecCartpole (swing_up False / True), whose step reads one action column
+(--action-dim 1 fits it; the reference configures action repeat 2 and episodes of 1,000 simulator steps for its cartpoles);
 --action-repeat K holds every action for up to K simulator steps inside the step launch.  Both apply to the training
 environment, the evaluation environment and the random baseline alike.  --episode-length counts simulator steps; the
 lengths that are printed count rows, i.e. agent steps.
@@ -64,18 +66,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
 import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
-from drqv2_amd.envs import VecPointMass, VecReach  # noqa: E402
+from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
-TASKS = {"reach": VecReach, "pointmass": VecPointMass}
+TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_balance": (VecCartpole, {"swing_up": False}),
+         "cartpole_swingup": (VecCartpole, {"swing_up": True})}
 
 
 def make_env(args, seed):
-    return TASKS[args.task](args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
-                            action_repeat=args.action_repeat)
+    cls, more = TASKS[args.task]
+    return cls(args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
+               action_repeat=args.action_repeat, **more)
 
 
 def random_baseline(args, episodes):
