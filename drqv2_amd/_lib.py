@@ -56,6 +56,7 @@ PROTOTYPES = {
     "drq_conv3x3_dgrad": (I, [P, P, P, P, I, I, L, L, L, L, P]),
     "drq_conv3x3_fwd_wino": (I, [P, P, P, P, I, I, I, L, L, L, L, P]),
     "drq_conv3x3_dgrad_wino": (I, [P, P, P, P, I, I, L, L, L, L, P]),
+    "drq_conv3x3_dgrad_wino_budget": (I, [P, P, P, P, I, I, L, L, L, L, I, P]),
     "drq_conv3x3_wgrad_wino": (I, [P, P, P, P, I, I, L, L, L, L, P, SZ, P]),
     "drq_conv3x3_wgrad": (I, [P, P, P, P, I, I, I, I, L, L, L, L, P, SZ, P]),
     "drq_conv3x3_wgrad_ws_bytes": (SZ, []),
@@ -135,6 +136,7 @@ PROTOTYPES = {
     "drq_step_ws_bytes": (SZ, [I, I, I, I, I]),
     "drq_step_ws_offset": (L, [I, I, I, I, I, I]),
     "drq_update_phase": (I, [C.POINTER(DrqStep), I]),
+    "drq_update_phase_overlap": (I, [C.POINTER(DrqStep), P, I]),
     "drq_update_phase_bc": (I, [C.POINTER(DrqStep), I, F]),
     "drq_update_phase_per": (I, [C.POINTER(DrqStep), I, P, P]),
     "drq_update_phase_frames": (I, [C.POINTER(DrqStep), I, P, L, L, P, P]),
@@ -154,11 +156,13 @@ PHASE_ENCODE, PHASE_CRITIC_HEADS, PHASE_CONV_BACKWARD, PHASE_ACTOR_FORWARD, PHAS
 PHASE_ENCODER_OPT, PHASE_ACTOR_OPT = 8, 9
 PHASE_CRITIC_OPT, PHASE_ACTOR_LOSS, PHASE_POLYAK, PHASE_REDRAW = 10, 11, 12, 13
 
+STEP_OVERLAP_ACTOR = 16   # DRQ_STEP_OVERLAP_ACTOR (DrqStep.flags)
+
 PARAM_LAYOUT_LEN = 59   # DRQ_PARAM_LAYOUT_LEN: the offsets drq_param_layout writes
 
 # the entries without a trailing drq_stream_t: they launch nothing, or their DrqStep carries the stream
 NO_STREAM = frozenset({"drq_abi_version", "drq_conv3x3_wgrad_ws_bytes", "drq_param_layout", "drq_step_ws_bytes",
-                       "drq_step_ws_offset", "drq_update_phase", "drq_update_phase_bc", "drq_update_phase_per",
+                       "drq_step_ws_offset", "drq_update_phase", "drq_update_phase_overlap", "drq_update_phase_bc", "drq_update_phase_per",
                        "drq_update_phase_frames", "drq_act_forward", "drq_act_ws_bytes"})
 
 _lib = None

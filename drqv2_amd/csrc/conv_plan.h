@@ -72,12 +72,59 @@ inline ConvPlan plan_wgrad_direct(int cus, int nb, int cin, int hin, int stride,
 }
 
 // conv3x3_wino_kernel (Winograd forward / input gradient): a wave takes units of 16 2x2 tiles, two workgroups per CU
-inline ConvPlan plan_wino(int cus, int nb, int hin) {
+inline long wino_units(int nb, int hin) { return ((long)nb * ((hin - 1) / 2) * ((hin - 1) / 2) + 15) / 16; }
+// budget: workgroup slots the launch may hold, 0 = all of them (two per CU: every caller but the overlapped update's
+// input gradients, which leave the rest to the launches of a second stream).  A budget counts in sixteens -- the grids
+// the kernel's XCD-aware order takes (wino_deal) -- and never enlarges a grid.
+inline ConvPlan plan_wino(int cus, int nb, int hin, int budget = 0) {
   ConvPlan p;
-  const int th = (hin - 1) / 2;
-  const long nunit = ((long)nb * th * th + 15) / 16;
-  p.grid = conv_grid((nunit + 3) / 4, 2L * cus);
+  long cap = 2L * cus;
+  if (budget > 0 && budget < cap) cap = budget < 16 ? 16 : budget & ~15;
+  p.grid = conv_grid((wino_units(nb, hin) + 3) / 4, cap);
   return p;
+}
+// slots the three input gradients of the overlapped update hold on a chip of `cus` CUs (DESIGN.md section 3, round 4:
+// chosen by the sweep of profiles/overlap_budget_sweep.txt); the budget is given in 512ths of the chip
+constexpr int kWinoOverlapBudget512 = 224;
+inline int wino_overlap_budget(int cus, int budget512 = kWinoOverlapBudget512) {
+  return (int)(2L * cus * budget512 / 512);
+}
+
+// What wave `wid` of workgroup `block` does in a conv3x3_wino_kernel launch of `grid` workgroups over nunit units; the
+// kernel and the host walk of the tests decode the same function.  Units are dealt round-robin: wave gw takes units
+// gw, gw + nwave, ... of the first q rounds.  The r = nunit - q*nwave units left over are cut in HALF-units (16 tiles
+// x one half of the output channels) wherever that lowers the busiest wave's load: with 2r <= nwave every left-over
+// unit goes to two neighbouring waves as two halves; with 2r > nwave the first nf = 2r - nwave waves take a whole
+// unit, every other wave a half.  Workgroup -> position in a round, XCD-aware (grids in sixteens): on each half of the
+// grid every XCD (block & 7) takes a contiguous eighth of the half's positions.  The map is a bijection of [0, grid)
+// for every such grid, so each unit and half-unit has exactly one owner whatever the grid; only the speed reasoning
+// (blocks b and b + grid/2 share a CU) is exact at grid = two per CU alone.
+#ifdef __HIPCC__
+#define CONV_PLAN_HD __host__ __device__
+#else
+#define CONV_PLAN_HD
+#endif
+struct WinoDeal {
+  int gw, nwave;        // this wave's position in a round, waves per round
+  int nfull;            // whole units: gw + i*nwave, i < nfull
+  bool has_half;        // ... then one half-unit:
+  int half_unit, half_h;   // its unit, its half of the output channels
+};
+CONV_PLAN_HD inline WinoDeal wino_deal(int grid, int block, int wid, int nunit) {
+  WinoDeal d;
+  const int hg = grid >> 1;
+  const int bh = block >= hg ? 1 : 0, bl = block - bh * hg;
+  const int lb = (grid & 15) ? block : bh * hg + (bl & 7) * (hg >> 3) + (bl >> 3);
+  d.gw = lb * 4 + wid;
+  d.nwave = grid * 4;
+  const int q = nunit / d.nwave, r = nunit - q * d.nwave;
+  const int nf = 2 * r > d.nwave ? 2 * r - d.nwave : 0;
+  d.nfull = q + (d.gw < nf ? 1 : 0);
+  const int hk = d.gw - nf;                                   // index among the half-units
+  d.has_half = hk >= 0 && hk < 2 * (r - nf);
+  d.half_unit = q * d.nwave + nf + (hk >> 1);
+  d.half_h = hk & 1;
+  return d;
 }
 
 // steps of four 2x2 tiles of the Winograd weight gradient

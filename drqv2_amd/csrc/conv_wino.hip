@@ -143,16 +143,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
   // share two of their four input rows.  With the plain order those re-reads came from eight different L2s (1.5x the
   // compulsory fabric traffic); here each half of the grid (one workgroup per CU) gives every XCD a contiguous
   // eighth of the round, and the two halves stay as they are (see the left-over rule below).
-  const int hg = (int)gridDim.x >> 1;
-  const int bh = (int)blockIdx.x >= hg ? 1 : 0, bl = (int)blockIdx.x - bh * hg;
-  const int lb = ((int)gridDim.x & 15) ? (int)blockIdx.x : bh * hg + (bl & 7) * (hg >> 3) + (bl >> 3);
-  const int gw = lb * 4 + wid;
-  const int q = nunit / nwave, r = nunit - q * nwave;
-  const int nf = 2 * r > nwave ? 2 * r - nwave : 0;
-  const int nfull = q + (gw < nf ? 1 : 0);
-  const int hk = gw - nf;                                   // index among the half-units
-  const bool has_half = hk >= 0 && hk < 2 * (r - nf);
-  const int half_unit = q * nwave + nf + (hk >> 1), half_h = hk & 1;
+  // The decode is wino_deal (conv_plan.h), which the host walks too.  A launch on a slot budget (plan_wino: a grid
+  // in sixteens below two per CU) takes the same per-half permutation with its own half: every unit still has one
+  // owner and its arithmetic does not depend on who that is, so the output is the same bit for bit; what no longer
+  // holds there is only the premise of the half-unit placement (the chip's second slots are not all taken).
+  const WinoDeal deal = wino_deal((int)gridDim.x, (int)blockIdx.x, wid, nunit);
+  const int gw = deal.gw;
+  const int nfull = deal.nfull;
+  const bool has_half = deal.has_half;
+  const int half_unit = deal.half_unit, half_h = deal.half_h;
   auto item_unit = [&](int i) { return i < nfull ? gw + i * nwave : half_unit; };   // i-th work item of this wave
   const int nitem = nfull + (has_half ? 1 : 0);
 
@@ -321,13 +320,13 @@ int launch_wino(const WinoArgs& a, const ConvPlan& p, hipStream_t st) {
 // x: the kernel's input of side hin -- the layer input, or (dgrad) the gradient zero-padded by 2, with the ReLU mask
 // of side hin - 2
 int wino_any(bool dgrad, const float* x, const float* w, const float* u_image, const float* bias, const float* mask,
-             float* y, int nb, int hin, int relu, const ConvView& yv, hipStream_t st) {
-  if (!x || !w || !y || nb <= 0) return DRQ_EARG;
+             float* y, int nb, int hin, int relu, const ConvView& yv, hipStream_t st, int budget = 0) {
+  if (!x || !w || !y || nb <= 0 || budget < 0) return DRQ_EARG;
   const size_t frame = 32 * (size_t)hin * hin, mframe = 32 * ((size_t)hin - 2) * ((size_t)hin - 2);
   if (!conv_bytes_ok(nb, frame) || !view_ok(nb, yv)) return DRQ_EARG;
   const WinoArgs a{x, w, u_image, bias, mask, y, (int)yv.bs, (int)yv.cs, (int)yv.rs, (int)yv.off, conv_bytes(nb, frame),
                    conv_bytes(nb, yv.bs), dgrad ? conv_bytes(nb, mframe) : 0u, nb, relu, dgrad, kStagger};
-  const ConvPlan p = plan_wino(drq_num_cus(), nb, hin);
+  const ConvPlan p = plan_wino(drq_num_cus(), nb, hin, budget);
   auto go = [&](auto h) { return launch_wino<decltype(h)::value>(a, p, st); };
   return dgrad ? drq_dispatch<39, 41, 43>(hin, go) : drq_dispatch<41, 39, 37>(hin, go);
 }
@@ -340,9 +339,10 @@ int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_imag
   return wino_any(false, x, w, u_image, bias, nullptr, y, nb, hin, relu, yv, st);
 }
 
+// budget: workgroup slots the launch may hold (plan_wino), 0 = the chip; the output does not depend on it
 int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float* u_image, const float* mask, float* dx,
-                               int nb, int hout, ConvView dxv, hipStream_t st) {
-  return wino_any(true, dy_pad, w, u_image, nullptr, mask, dx, nb, hout + 4, 0, dxv, st);
+                               int nb, int hout, ConvView dxv, hipStream_t st, int budget) {
+  return wino_any(true, dy_pad, w, u_image, nullptr, mask, dx, nb, hout + 4, 0, dxv, st, budget);
 }
 
 // Same contract as drq_conv3x3_fwd (conv.hip) for cin = 32, stride 1, in Winograd form (rounding differs).
@@ -355,4 +355,11 @@ DRQ_API int drq_conv3x3_fwd_wino(const float* x, const float* w, const float* bi
 DRQ_API int drq_conv3x3_dgrad_wino(const float* dy_pad, const float* w, const float* mask, float* dx, int nb, int hout,
                                    long dx_bs, long dx_cs, long dx_rs, long dx_off, hipStream_t st) {
   return drq_conv3x3_dgrad_wino_pre(dy_pad, w, nullptr, mask, dx, nb, hout, {dx_bs, dx_cs, dx_rs, dx_off}, st);
+}
+
+// drq_conv3x3_dgrad_wino on a budget of workgroup slots (0 = the chip): the same output bit for bit.
+DRQ_API int drq_conv3x3_dgrad_wino_budget(const float* dy_pad, const float* w, const float* mask, float* dx, int nb,
+                                          int hout, long dx_bs, long dx_cs, long dx_rs, long dx_off, int budget,
+                                          hipStream_t st) {
+  return drq_conv3x3_dgrad_wino_pre(dy_pad, w, nullptr, mask, dx, nb, hout, {dx_bs, dx_cs, dx_rs, dx_off}, st, budget);
 }

@@ -137,7 +137,7 @@ int drq_conv1_aug_fwd_any(int bf_mma, const uint8_t* obs, const float* shift, co
 int drq_conv3x3_fwd_wino_pre(const float* x, const float* w, const float* u_image, const float* bias, float* y, int nb,
                              int hin, int relu, ConvView yv, hipStream_t st);
 int drq_conv3x3_dgrad_wino_pre(const float* dy_pad, const float* w, const float* u_image, const float* mask, float* dx,
-                               int nb, int hout, ConvView dxv, hipStream_t st);
+                               int nb, int hout, ConvView dxv, hipStream_t st, int budget = 0);
 // conv_bf16.hip: the bf16 launches with activations in bf16 [frame][y][x][32] where the flags say so
 int drq_conv3x3_fwd_bf16_lay(const void* x, const float* w, const float* bias, void* y, int nb, int hin, int relu,
                              ConvView yv, int lay, hipStream_t st);

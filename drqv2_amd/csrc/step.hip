@@ -1,9 +1,12 @@
-// Whole-step orchestration of DrQV2Agent.update (drqv2.py:230-262) on one HIP stream.
+// Whole-step orchestration of DrQV2Agent.update (drqv2.py:230-262) on one HIP stream -- or, for the overlapped schedule
+// (DRQ_STEP_OVERLAP_ACTOR), on the caller's two.
 // Host code only: sequences the kernels of the conv, gemm, layernorm, qout, policy_out and optim files over a caller-owned
-// workspace.  No allocation, no synchronisation, no global state.
+// workspace.  No allocation, no synchronisation with the host; the only state is the overlapped schedule's pair of
+// events per device, created on first use.
 #include "common.h"
 #include "internal.h"
 #include "../../include/drqv2_hip.h"
+#include <mutex>
 
 namespace {
 
@@ -172,6 +175,7 @@ struct Ctx {
   ParamLayout P;
   WsLayout W;
   hipStream_t st;
+  hipStream_t side_st = nullptr;   // drq_update_phase_overlap's second stream, else null
   // phases 6 and 7 issued back to back by one call (single-GPU schedule): the actor loss then rides in the first
   // launch of the backward (drq_qout_bwd_actor) instead of a launch of its own.  A host that exchanges the metric
   // sums between the two phases calls them separately and keeps the separate loss launch.
@@ -565,7 +569,9 @@ int phase_critic_heads(const Ctx& c) {
 }
 
 // phase 5: encoder backward, conv4 .. conv1 (wgrad all, dgrad 4..2): leaves the encoder gradients
-int phase_conv_backward(const Ctx& c) {
+// igrad_budget: workgroup slots each Winograd input gradient may hold (plan_wino), 0 = the chip; the weight gradients
+// and the reduction keep their grids
+int phase_conv_backward(const Ctx& c, int igrad_budget = 0) {
   const DrqStep* s = c.s;
   const ParamLayout& P = c.P;
   const int B = s->B, C = s->C;
@@ -599,7 +605,7 @@ int phase_conv_backward(const Ctx& c) {
                                     st));
     else
       CK(drq_conv3x3_dgrad_wino_pre(dys[l], c.p(P.enc_w[l]), c.ws(W_WINO_U) + (2L * (l - 1) + 1) * 16384, xs[l],
-                                    c.ws(dyid[l - 1]), B, kEncH[l + 1], dyv[l - 1], st));
+                                    c.ws(dyid[l - 1]), B, kEncH[l + 1], dyv[l - 1], st, igrad_budget));
     if (l == 2) CK(c.stamp(3));
   }
   if (wino) {
@@ -776,6 +782,69 @@ int phase_both_opt(const Ctx& c) {      // encoder_opt.step() (:202) and actor_o
                         s->adam_m + a, s->adam_v + a, P.seg_len(SEG_ACTOR), s->step_actor, s->lr, s->gscale, c.st);
 }
 
+// ---- the overlapped schedule: phases 6-7 on a second stream beside phase 5 -------------------------------------
+// One pair of events per device, created on first use and kept: no timing, and no system-scope release when they
+// complete (they order two queues of one device; nothing on the host waits on them).  A pair of calls (record on one
+// stream, wait on the other) is made under the lock, so two host threads with updates on one device cannot wait on
+// each other's record.
+struct ForkJoin {
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+std::mutex g_fork_join_lock;
+int fork_join_events(ForkJoin** out) {
+  static ForkJoin table[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return DRQ_EARG;
+  ForkJoin& e = table[dev];
+  const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
+  if (!e.fork && hipEventCreateWithFlags(&e.fork, fl) != hipSuccess) { e.fork = nullptr; return DRQ_EARG; }
+  if (!e.join && hipEventCreateWithFlags(&e.join, fl) != hipSuccess) { e.join = nullptr; return DRQ_EARG; }
+  *out = &e;
+  return 0;
+}
+// everything issued on `from` so far is ordered before whatever is issued on `to` from here on
+int order_after(hipStream_t from, hipStream_t to, bool join) {
+  std::lock_guard<std::mutex> hold(g_fork_join_lock);
+  ForkJoin* e = nullptr;
+  CK(fork_join_events(&e));
+  const hipEvent_t ev = join ? e->join : e->fork;
+  if (hipEventRecord(ev, from) != hipSuccess || hipStreamWaitEvent(to, ev, 0) != hipSuccess) return DRQ_EARG;
+  return 0;
+}
+
+// The plain fp32 single-GPU update only; with the roofline's timing events (they are recorded on ONE stream and
+// bracket phases as consecutive spans of it) the serial schedule runs.
+bool overlap_actor(const Ctx& c, int phase) {
+  const DrqStep* s = c.s;
+  return phase == DRQ_PHASE_ALL && (s->flags & DRQ_STEP_OVERLAP_ACTOR) && c.side_st && c.side_st != c.st && !s->bf16 && !c.bc() && !c.per() && !c.ring_first && s->global_B == s->B &&
+         !(s->timing_events && s->timing_n > 0);
+}
+// slots of the three input gradients: the planner's choice, or the thirty-seconds of the chip an A/B run asks for
+int overlap_budget(const DrqStep* s) {
+  const int n32 = (s->flags >> 8) & 63;
+  return n32 ? wino_overlap_budget(drq_num_cus(), n32 > 32 ? 512 : n32 * 16) : wino_overlap_budget(drq_num_cus());
+}
+
+// Phases 5 | 6-7 of DRQ_PHASE_ALL.  Phase 4 has left on the main stream everything the actor update reads (the critic's
+// gradients, the features, the policy activations and the actor's draw); from there
+//   main: the three input gradients on their slot budget, then the weight gradients and the reduction at their grids
+//   side: critic_opt.step() + Polyak, the actor loss through the stepped critic, its backward (phases 6, 7)
+// and the side stream joins the main one before the update's last launch (phase_both_opt reads both gradient sets).
+// The two sides share no buffer that either writes (the audit table).  Both sides are
+// issued and the join is made whatever a launch returns, so that an error leaves no work behind the caller's back.
+int phases_backward_overlapped(const Ctx& c) {
+  const hipStream_t side_st = c.side_st;
+  CK(order_after(c.st, side_st, false));
+  Ctx side = c;
+  side.st = side_st;
+  side.side_st = nullptr;
+  const int rc_main = phase_conv_backward(c, overlap_budget(c.s));
+  int rc_side = phase_actor_forward(side);
+  if (rc_side == 0) rc_side = phase_actor_backward(side);
+  const int rc_join = order_after(side_st, c.st, true);
+  return rc_main ? rc_main : rc_side ? rc_side : rc_join;
+}
+
 // does a drq_update_phase call with id `phase` run the piece `part`?  The composite ids are spelled out here and
 // nowhere else; DRQ_PHASE_OPT is a piece of its own (phases 8 and 9 in one launch), which DRQ_PHASE_ALL ends with
 bool runs(int phase, int part) {
@@ -824,7 +893,7 @@ DRQ_API long drq_step_ws_offset(int B, int C, int A, int F, int H, int id) {
 
 namespace {
 int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_weight = nullptr, float* td_abs = nullptr,
-                 const uint8_t* ring_first = nullptr, long ring_R = 0, long ring_N = 0) {
+                 const uint8_t* ring_first = nullptr, long ring_R = 0, long ring_N = 0, hipStream_t side_st = nullptr) {
   CK(check_step(s));
   if (!s->obs || !s->next_obs || !s->action || !s->reward || !s->discount || !s->shift_obs || !s->shift_next ||
       !s->noise_critic || !s->noise_actor || !s->base_grid || !s->grads || !s->adam_m || !s->adam_v || !s->sums)
@@ -838,17 +907,22 @@ int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_we
   c.ring_first = ring_first;
   c.ring_R = ring_R;
   c.ring_N = ring_N;
+  c.side_st = side_st;
   if (runs(phase, DRQ_PHASE_ENCODE)) CK(phase_encode(c));
   if (runs(phase, DRQ_PHASE_CRITIC_HEADS)) {
     CK(c.stamp(6));
     CK(phase_critic_heads(c));
     CK(c.stamp(7));
   }
-  if (runs(phase, DRQ_PHASE_CONV_BACKWARD)) CK(phase_conv_backward(c));
-  if (runs(phase, DRQ_PHASE_ACTOR_FORWARD)) CK(phase_actor_forward(c));
-  if (runs(phase, DRQ_PHASE_ACTOR_BACKWARD)) {
-    CK(phase_actor_backward(c));
-    CK(c.stamp(9));
+  if (overlap_actor(c, phase)) {
+    CK(phases_backward_overlapped(c));
+  } else {
+    if (runs(phase, DRQ_PHASE_CONV_BACKWARD)) CK(phase_conv_backward(c));
+    if (runs(phase, DRQ_PHASE_ACTOR_FORWARD)) CK(phase_actor_forward(c));
+    if (runs(phase, DRQ_PHASE_ACTOR_BACKWARD)) {
+      CK(phase_actor_backward(c));
+      CK(c.stamp(9));
+    }
   }
   if (runs(phase, DRQ_PHASE_OPT)) CK(phase_both_opt(c));
   if (runs(phase, DRQ_PHASE_ENCODER_OPT)) CK(c.adam_segment(SEG_ENC, s->step_enc));      // encoder_opt.step() (:202)
@@ -870,6 +944,11 @@ int update_phase(const DrqStep* s, int phase, float bc_alpha, const float* is_we
 }  // namespace
 
 DRQ_API int drq_update_phase(const DrqStep* s, int phase) { return update_phase(s, phase, 0.f); }
+
+DRQ_API int drq_update_phase_overlap(const DrqStep* s, drq_stream_t side_stream, int phase) {
+  if (!side_stream) return DRQ_EARG;
+  return update_phase(s, phase, 0.f, nullptr, nullptr, nullptr, 0, 0, (hipStream_t)side_stream);
+}
 
 DRQ_API int drq_update_phase_bc(const DrqStep* s, int phase, float bc_alpha) {
   // single GPU only: lambda needs the GLOBAL sum of |min(q1,q2)| before any gradient exists

@@ -9,6 +9,8 @@ from . import _lib
 from ._lib import DrqStep, check, launch, ptr
 
 NETS = ("enc", "critic", "actor", "target")
+# StepEngine.overlap_actor as an engine starts (DESIGN.md section 3, round 4 holds the measurement that decided it)
+OVERLAP_ACTOR_DEFAULT = True
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -362,7 +364,12 @@ class StepEngine:
         self.profile_exchange = False   # bench.py: event pairs around every wait for a gradient exchange
         self.exchange_wait_us = {}      # bucket name -> [us the compute stream waited], see collect_exchange_waits()
         self._wait_events = []
-        self._side = None         # side stream of the metric-sums exchange
+        self._side = None         # side stream: of the metric-sums exchange (data parallel), of the overlapped update
+        # DrqStep.flags bit 16 for the plain single-GPU update(): the critic's optimiser step and the actor update on the
+        # side stream beside the encoder backward -- the serial update bit for bit
+        self.overlap_actor = OVERLAP_ACTOR_DEFAULT
+        self.overlap_budget32 = 0 # A/B runs: slots of the input gradients in 32nds of the chip, 0 = the library's choice
+        self._side_handle = None  # the side stream's hipStream_t, looked up once
         self._side_busy = False
         self.bf16 = False             # DrqStep.bf16: the update's convs / GEMMs on the bf16 MFMA (set_compute_dtype)
         self.store_aug_next = False   # verification: keep the next_obs view's encoder input too (DrqStep.store_aug_next)
@@ -751,7 +758,15 @@ class StepEngine:
         d.noise_critic, d.noise_actor = ptr(noise_critic), ptr(noise_actor)
         if self.pg is None:
             self._throttle(steps[2] & 0xFFFFFFFF)
-            self._phase(d, _lib.PHASE_ALL, per, ring)
+            if self.overlap_actor and per is None and ring is None and self.bc_alpha is None and not self.bf16:
+                if self._side_handle is None:
+                    self._side_handle = self._side_stream().cuda_stream
+                d.flags |= _lib.STEP_OVERLAP_ACTOR | ((int(self.overlap_budget32) & 63) << 8)
+                with torch.cuda.device(self.device):
+                    check(_lib.load().drq_update_phase_overlap(ctypes.byref(d), self._side_handle, _lib.PHASE_ALL),
+                          "drq_update_phase_overlap(-1)")
+            else:
+                self._phase(d, _lib.PHASE_ALL, per, ring)
             self.last_td_abs = per[1] if per is not None else None
             self._last_seq = steps[2] & 0xFFFFFFFF
         else:

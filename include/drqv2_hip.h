@@ -94,6 +94,12 @@ int drq_conv3x3_fwd_wino(const float* x, const float* w, const float* bias, floa
                          long y_bs, long y_cs, long y_rs, long y_off, drq_stream_t stream);
 int drq_conv3x3_dgrad_wino(const float* dy_pad, const float* w, const float* mask, float* dx, int nb, int hout,
                            long dx_bs, long dx_cs, long dx_rs, long dx_off, drq_stream_t stream);
+/* drq_conv3x3_dgrad_wino on a budget of workgroup slots: the launch takes at most `budget` workgroups (counted in
+ * sixteens, at least 16; 0 or more than two per CU = the whole chip, which is drq_conv3x3_dgrad_wino) and leaves the
+ * other slots of the chip to launches of other streams.  dx is the same bit for bit whatever the budget.  The
+ * overlapped schedule of the update (DRQ_STEP_OVERLAP_ACTOR) runs its three input gradients this way. */
+int drq_conv3x3_dgrad_wino_budget(const float* dy_pad, const float* w, const float* mask, float* dx, int nb, int hout,
+                                  long dx_bs, long dx_cs, long dx_rs, long dx_off, int budget, drq_stream_t stream);
 /* ... and their weight / bias gradient in the same form: the contract of drq_conv3x3_wgrad for cin = 32, stride 1, with
  * ONE more precondition: dy must be the interior of a ZERO-PADDED buffer (the kernel reads row and column `hout` of
  * every plane as the empty half of the last 2x2 tile), i.e. dy_rs >= hout+1, dy_cs >= (hout+1)*dy_rs and zeros there --
@@ -945,12 +951,23 @@ typedef struct {
                               * gradient to the next (of conv3's and conv2's outputs) stay fp32 instead of bf16 in that
                               * layout -- the same weight gradients bit for bit; the two bias gradients they feed then
                               * sum unrounded values.  A workspace must be zeroed when these two bits change between
-                              * updates (the zero borders of the padded buffers move).  0 = the production schedule. */
+                              * updates (the zero borders of the padded buffers move).
+                              * DRQ_STEP_OVERLAP_ACTOR (16, fp32, DRQ_PHASE_ALL of drq_update_phase_overlap only, which
+                              * brings the second stream): the critic's optimiser step and the actor update (phases
+                              * 6-7) are issued on that stream beside the encoder backward (phase 5), whose three
+                              * Winograd input gradients then leave a part of the chip's workgroup slots free.  The same
+                              * launches on the same operands: the update is the serial one bit for bit.  Ignored (the
+                              * serial schedule runs) with timing_events, bf16, and in every other phase id or entry.
+                              * DRQ_STEP_BUDGET(n) (bits 8-13, A/B measurements): with the bit above, the slots the
+                              * input gradients hold, n in 1..32 thirty-seconds of the chip's two slots per CU (n x 16 workgroups
+                              * on 256 CUs); 0 = the library's choice. */
 } DrqStep;
 #define DRQ_STEP_NO_ROW_FUSION 1
 #define DRQ_STEP_NO_GEMM3 2
 #define DRQ_STEP_BF16_FP32_ACTS 4
 #define DRQ_STEP_BF16_FP32_GRADS 8
+#define DRQ_STEP_OVERLAP_ACTOR 16
+#define DRQ_STEP_BUDGET(n) (((n) & 63) << 8)
 
 /* Parameter arena: tensors in parameters() order of encoder, critic, actor, critic_target, each start
  * aligned to 64 floats, each network's segment padded to a multiple of 512 floats (a segment is one optimiser
@@ -1000,6 +1017,14 @@ enum {
   DRQ_PHASE_CRITIC_OPT = 10, DRQ_PHASE_ACTOR_LOSS = 11, DRQ_PHASE_POLYAK = 12, DRQ_PHASE_REDRAW = 13
 };
 int drq_update_phase(const DrqStep* s, int phase);
+/* drq_update_phase with a second stream of the same device (side_stream, not NULL; if it is s->stream itself the
+ * serial schedule runs).  With
+ * DRQ_STEP_OVERLAP_ACTOR set in s->flags and phase = DRQ_PHASE_ALL the overlapped schedule runs (see the flag); every
+ * other call is drq_update_phase(s, phase).  The library orders side_stream after s->stream and joins it back into
+ * s->stream before the update's last launches with two events of its own (one pair per device, created on first use,
+ * no timing, no system-scope fence): when the call returns, everything it issued is ordered before whatever the
+ * caller puts on s->stream next, as in the serial schedule.  Nothing else may run on side_stream meanwhile. */
+int drq_update_phase_overlap(const DrqStep* s, drq_stream_t side_stream, int phase);
 /* The same update with the DrQ+BC actor loss (see the BC entries above), alpha finite and > 0: the critic step is
  * unchanged bit for bit; phases 6 / 11 and 7 issue the BC forms of the loss and of the policy output backward in place
  * of the plain ones, launch for launch.  a_beh is s->action as phase 4 consumed it (the copy phase 4 left in the
