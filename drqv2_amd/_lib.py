@@ -105,6 +105,7 @@ PROTOTYPES = {
     "drq_per_update": (I, [P, L, P, P, I, D, D, P]),
     "drq_vec_add": (I, [P, P, P, P, P, L, L, I, L, L, P, P, P, P, P, P]),
     "drq_vec_sample": (I, [P, P, P, P, L, L, I, L, L, L, P, I, I, I, F, P, P, P, P, P, P, P, P, P]),
+    "drq_vec_sample_mixed": (I, [P, P, P, P, L, L, L, I, L, L, L, L, P, I, I, I, I, F, P, P, P, P, P, P, P, P, P]),
     "drq_vec_per_advance": (I, [P, L, P, L, L, L, L, L, P]),
     "drq_vec_per_sample": (I, [P, L, P, P, P, P, L, L, I, L, L, L, P, I, I, F, D, P, P, P, P, P, P, P]),
     "drq_vec_per_update": (I, [P, L, P, L, L, L, L, L, P, P, I, D, D, P]),

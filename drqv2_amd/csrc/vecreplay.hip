@@ -115,6 +115,42 @@ __global__ __launch_bounds__(256) void vec_sample_kernel(VecSampleArgs a) {
   ring_emit_row(a.r, b, t, e, k);
 }
 
+// ---- the mixed draw: batch rows b < Bd from the demonstration partition, the others from the ring ------------------
+// (contract: include/drqv2_hip.h, "demonstrations in the step-major replay")  Two geometries over ONE allocation: the
+// ring's R rows, and behind them the partition's D rows, linear -- a VecRing of D rows whose drawable rows end nstep
+// before the Td rows filled never takes the modulo.  `demo` is `live` with every store pointer moved R N slots on, so
+// vec_choose, ring_window, ring_emit_row and the frame copy run on either as they stand; what a partition row has to
+// add is the R N its three indices lack to index the whole allocation, which the thread that stored them puts on.
+struct VecMixedArgs {
+  VecSampleArgs live;   // the ring
+  VecSampleArgs demo;   // the partition: the same u, outputs, B, K, nstep and gamma
+  long base;            // R N: the partition's first slot
+  int Bd;               // batch rows 0 .. Bd-1 come from the partition
+};
+
+__global__ __launch_bounds__(256) void vec_sample_mixed_kernel(VecMixedArgs m) {
+  const int which = m.live.obs_out ? blockIdx.y : 2;   // no output frames: the scalars only (grid.y == 1)
+  const int b = which < 2 ? blockIdx.x : blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= m.live.r.B) return;
+  const bool part = b < m.Bd;                          // uniform over a copy block
+  const VecSampleArgs& a = part ? m.demo : m.live;
+  long t, e;
+  const int k = vec_choose(a, b, t, e);
+  if (which < 2) {
+    const long p = ring_slot(a.r.g, k == 0 ? t : (which == 0 ? t - 1 : t + k - 1), e);
+    const uint4* src = reinterpret_cast<const uint4*>(a.frames + p * a.frame_bytes);
+    uint4* dst = reinterpret_cast<uint4*>((which == 0 ? a.obs_out : a.next_obs_out) + (long)b * a.frame_bytes);
+    const long n16 = a.frame_bytes >> 4;
+    for (long i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    return;
+  }
+  ring_emit_row(a.r, b, t, e, k);
+  if (part) {
+    const long B = a.r.B;
+    for (int q = 0; q < 3; ++q) a.r.idx_out[q * B + b] += m.base;   // this thread's own stores
+  }
+}
+
 // ---- prioritized sampling: the sum tree over the ring's slots -----------------------------------------------------
 __global__ __launch_bounds__(kPerThreads) void vec_per_advance_kernel(double* tree, long L, const uint8_t* first, long N,
                                                                       long enter_row, long leave_row) {
@@ -232,6 +268,43 @@ DRQ_API int drq_vec_sample(const uint8_t* first, const float* action, const floa
                   u, frames, obs_out, next_obs_out, frame_bytes, K};
   if (obs_out) hipLaunchKernelGGL(vec_sample_kernel, dim3(B, 3), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(vec_sample_kernel, dim3((B + 255) / 256, 1), dim3(256), 0, st, a);
+  DRQ_LAUNCH_CHECK();
+  return DRQ_OK;
+}
+
+DRQ_API int drq_vec_sample_mixed(const uint8_t* first, const float* action, const float* reward, const float* discount,
+                                 long R, long D, long N, int A, long frame_bytes, long lo, long hi, long Td,
+                                 const double* u, int B, int Bd, int K, int nstep, float gamma, long* idx_out,
+                                 float* act_out, float* rew_out, float* disc_out, int* steps_out, const uint8_t* frames,
+                                 uint8_t* obs_out, uint8_t* next_obs_out, drq_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!first || !action || !reward || !discount || !u || !idx_out || !act_out || !rew_out || !disc_out || !steps_out)
+    return DRQ_EARG;
+  if (R <= 0 || N <= 0 || A <= 0 || B <= 0 || K <= 0 || nstep <= 0 || frame_bytes <= 0 || frame_bytes % 16)
+    return DRQ_EARG;
+  if (D <= 0 || Td < 0 || Td > D || Bd < 0 || Bd > B) return DRQ_EARG;
+  // the slots of the whole allocation, times the widest row, stay inside a long
+  if (N > INT32_MAX || R > INT64_MAX - D || R + D > INT64_MAX / N || frame_bytes > INT64_MAX / ((R + D) * N) ||
+      A > INT64_MAX / ((R + D) * N))
+    return DRQ_EARG;
+  // the ring, if a row is drawn from it: drq_vec_sample's bounds
+  if (Bd < B && (lo < 1 || hi < lo || hi - lo + 1 + nstep > R)) return DRQ_EARG;
+  // the partition, if a row is drawn from it: rows 1 .. Td - nstep, whose windows end inside the Td rows filled
+  if (Bd > 0 && Td - nstep < 1) return DRQ_EARG;
+  const int given = (frames != nullptr) + (obs_out != nullptr) + (next_obs_out != nullptr);
+  if (given != 0 && given != 3) return DRQ_EARG;
+  if (((uintptr_t)frames | (uintptr_t)obs_out | (uintptr_t)next_obs_out) & 15) return DRQ_EARG;
+  const long base = R * N;
+  VecMixedArgs m{
+      VecSampleArgs{RingBatch{VecRing{first, R, N, 0, lo, hi}, action, reward, discount, idx_out, act_out, rew_out,
+                              disc_out, steps_out, A, B, nstep, gamma},
+                    u, frames, obs_out, next_obs_out, frame_bytes, K},
+      VecSampleArgs{RingBatch{VecRing{first + base, D, N, 0, 1, Td - nstep}, action + base * A, reward + base,
+                              discount + base, idx_out, act_out, rew_out, disc_out, steps_out, A, B, nstep, gamma},
+                    u, frames ? frames + base * frame_bytes : nullptr, obs_out, next_obs_out, frame_bytes, K},
+      base, Bd};
+  if (obs_out) hipLaunchKernelGGL(vec_sample_mixed_kernel, dim3(B, 3), dim3(256), 0, st, m);
+  else hipLaunchKernelGGL(vec_sample_mixed_kernel, dim3((B + 255) / 256, 1), dim3(256), 0, st, m);
   DRQ_LAUNCH_CHECK();
   return DRQ_OK;
 }

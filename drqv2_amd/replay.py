@@ -50,6 +50,11 @@ csrc/vecepisodes.hip, host planning in drqv2_amd/episodes.py).  What N environme
 reference's `<timestamp>_<idx>_<len>.npz` files, which make_replay_loader() and the reference's own tooling read; and a
 ring of any shape starts from such files or from episode dicts, laid out as lockstep rows and written with one launch per
 staging chunk instead of one add() per row.
+
+Demonstrations (new: VecDeviceReplay(demo_rows=D), add_demonstrations(), demo_fraction; drq_vec_sample_mixed in
+csrc/vecreplay.hip).  D rows behind the ring's last row, in the same allocation, hold demonstration episodes for the whole
+run: never evicted, filled by drq_vec_fill, and drawn from for a fixed share of every batch by one launch that writes slot
+indices into the whole allocation -- so update() and its kernels see an IndexedBatch like any other.
 """
 import collections
 import datetime
@@ -310,8 +315,9 @@ class BatchIterator:
         if per != (store.tree is not None) or not store.indexed:
             raise ValueError("BatchIterator.load_state_dict(): the saved batch is "
                              f"{'prioritized' if per else 'uniform'} and indexed, the store is not")
-        if B and not (0 <= int(index.min()) and int(index.max()) < store.R * store.N):
-            raise ValueError(f"BatchIterator.load_state_dict(): slots outside the ring of {store.R * store.N}")
+        slots = (store.R + store.D) * store.N       # a mixed batch names slots of the demonstration partition too
+        if B and not (0 <= int(index.min()) and int(index.max()) < slots):
+            raise ValueError(f"BatchIterator.load_state_dict(): slots outside the ring of {slots}")
         dev = store.device
         idx, steps, act, rew, disc = (sd[k].to(dev) for k in ("index", "steps", "action", "reward", "discount"))
         batch = store._batch(per, idx, act, rew, disc)
@@ -594,35 +600,58 @@ class VecDeviceReplay:
     PrioritizedBatch; its update_priorities(td_abs) is one launch (drq_vec_per_update) that writes only positions that
     are still drawable, and nothing at all once `guard_rows` rows were added since the draw (so guard_rows >= 1 is
     needed for priorities to be renewed at all).  If every drawable row is a reset row the tree is empty, which the host
-    cannot know: the batch then consists of steps-0 rows on slot(lo, 0) with weight 1."""
+    cannot know: the batch then consists of steps-0 rows on slot(lo, 0) with weight 1.
 
-    K = 4       # candidates per batch row (the columns of the u table)
+    Demonstrations (`demo_rows=D`, uniform stores only; the contract is in include/drqv2_hip.h, "demonstrations in the
+    step-major replay"): the five arrays hold (rows + D) N slots, the ring in the first rows N -- `frames`, `action`,
+    `reward`, `discount` and `first` stay those views -- and behind it a partition of D rows that is linear and never
+    evicted: demonstration row d of lane e in slot (rows + d) N + e.  add_demonstrations() appends episodes to it,
+    `demo_rows_filled` is Td, demo_bounds() its drawable rows (1, Td - nstep).  `demo_fraction` (a plain attribute in
+    [0, 1], read at every draw) makes the first Bd = int(B * demo_fraction + 0.5) rows of every batch demonstrations:
+    Bd = 0 is drq_vec_sample as ever, otherwise one launch of drq_vec_sample_mixed from the same u table; `last_demo_count`
+    is Bd.  A batch's `frames` is the whole allocation.  state_dict() saves Td, the fraction and the filled slots."""
+
+    K = 4      # candidates per batch row (the columns of the u table)
     _draw_copies = True     # a materialised batch's frames are copied by the draw itself (drq_vec_sample)
 
     def __init__(self, rows, num_envs, obs_shape, action_dim, nstep, discount, device, seed=None, indexed=True,
-                 guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
+                 guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6, demo_rows=0):
         """priority_alpha, priority_beta, priority_eps: as DeviceReplay's.  None = uniform sampling: no tree is
-        allocated and every draw and launch is what it was.  priority_beta is a plain attribute, read at every draw."""
+        allocated and every draw and launch is what it was.  priority_beta is a plain attribute, read at every draw.
+        demo_rows: D rows behind the ring that hold demonstrations for the whole run (class docstring); 0 = none, and
+        every allocation, launch, draw and saved state is what it was."""
         self.device = torch.device(device)
         self.obs_shape = tuple(int(s) for s in obs_shape)
         self.slot_shape = self.obs_shape           # what add() stores per environment; here the whole observation
         self.frame_bytes = self.stack_bytes = int(np.prod(self.obs_shape))     # bytes per slot, per observation
         self.R, self.N, self.A = int(rows), int(num_envs), int(action_dim)
         self.nstep, self.gamma, self.guard_rows = int(nstep), float(discount), int(guard_rows)
+        self.D = int(demo_rows)
         if self.frame_bytes <= 0 or self.frame_bytes % 16:
             raise ValueError("frame size must be a multiple of 16 bytes")
         if self.N < 1 or self.A < 1 or self.nstep < 1 or self.guard_rows < 0:
             raise ValueError("num_envs, action_dim and nstep must be >= 1, guard_rows >= 0")
         if self.R < self.nstep + self.guard_rows + 2:
             raise ValueError(f"rows {self.R}: at least nstep + guard_rows + 2 = {self.nstep + self.guard_rows + 2}")
-        dev, S = self.device, self.R * self.N
+        if self.D:
+            self._check_demo_rows(priority_alpha)
+        dev, S = self.device, (self.R + self.D) * self.N
         # zeros, not empty: slots no add() has reached are compared as part of the ring (two runs of one loop, a run
         # against its restored copy), and what the allocator hands back depends on whatever ran in the process before
-        self.frames = torch.zeros((S, self.frame_bytes), dtype=torch.uint8, device=dev)
-        self.action = torch.zeros((S, self.A), dtype=torch.float32, device=dev)
-        self.reward = torch.zeros((S,), dtype=torch.float32, device=dev)
-        self.discount = torch.ones((S,), dtype=torch.float32, device=dev)
-        self.first = torch.ones((S,), dtype=torch.uint8, device=dev)
+        whole = (torch.zeros((S, self.frame_bytes), dtype=torch.uint8, device=dev),
+                 torch.zeros((S, self.A), dtype=torch.float32, device=dev),
+                 torch.zeros((S,), dtype=torch.float32, device=dev),
+                 torch.ones((S,), dtype=torch.float32, device=dev),
+                 torch.ones((S,), dtype=torch.uint8, device=dev))
+        # the ring is the first R N slots of each array, the partition the D N behind them; without demonstrations
+        # the ring IS the allocation.  Everything that adds, exports or saves the ring works on these views
+        live = self.R * self.N
+        self.frames, self.action, self.reward, self.discount, self.first = (t[:live] if self.D else t for t in whole)
+        self._whole = dict(zip(self._RING, whole))
+        self._demo = {n: t[live:] for n, t in self._whole.items()}
+        self.demo_rows_filled = 0   # Td: rows of the partition that add_demonstrations() has written
+        self._demo_fraction = 0.0
+        self.last_demo_count = 0    # Bd of the newest batch: its rows 0 .. Bd-1 are demonstrations
         self.T = 0                  # rows added
         self.rng = np.random.RandomState(seed)
         self.indexed = bool(indexed)
@@ -642,9 +671,48 @@ class VecDeviceReplay:
         """(lo, hi): the drawable rows; hi < lo while there are none"""
         return max(1, self.T - self.R + 1 + self.guard_rows), self.T - self.nstep
 
+    MAX_INDEXED_UNITS = 2 ** 31 - 1     # the fused aug+conv1 launch names its source as the int 3 * slot + g, g = 0 .. 2
+
+    def _check_demo_rows(self, priority_alpha):
+        """the refusals of demo_rows != 0, each a ValueError that says why"""
+        D, R, N = self.D, self.R, self.N
+        if D < self.nstep + 2:
+            raise ValueError(f"demo_rows {D}: at least nstep + 2 = {self.nstep + 2} (a reset row, one transition and "
+                             "its window)")
+        if 3 * (R + D) * N > self.MAX_INDEXED_UNITS:
+            raise ValueError(f"demo_rows {D}: (rows + demo_rows) x num_envs = {(R + D) * N} slots; update() gathers an "
+                             "indexed batch by the 32-bit index 3 * slot + g (the fused aug+conv1 launch), which reaches "
+                             f"{self.MAX_INDEXED_UNITS // 3} slots")
+        if priority_alpha is not None:
+            raise ValueError("demo_rows with priority_alpha: the sum tree covers the ring only; prioritized mixed draws "
+                             "are not built")
+
+    @property
+    def demo_fraction(self):
+        """The share of every batch that is drawn from the demonstrations, read at every draw: of B rows the first
+        Bd = int(B * demo_fraction + 0.5) are.  In [0, 1] (ValueError), and 0 for a store without demo_rows."""
+        return self._demo_fraction
+
+    @demo_fraction.setter
+    def demo_fraction(self, value):
+        f = float(value)
+        if isinstance(value, bool) or not (0.0 <= f <= 1.0):
+            raise ValueError(f"demo_fraction {value!r}: a float in [0, 1]")
+        if f > 0.0 and not self.D:
+            raise ValueError(f"demo_fraction {value!r}: this store has no demonstration partition (demo_rows=0)")
+        self._demo_fraction = f
+
+    def demo_bounds(self):
+        """(lo, hi) = (1, Td - nstep): the drawable rows of the partition; hi < lo while there are none"""
+        return 1, self.demo_rows_filled - self.nstep
+
+    def demo_count(self, batch_size):
+        """Bd: how many rows of a batch of batch_size come from the demonstrations at the present demo_fraction"""
+        return int(int(batch_size) * self._demo_fraction + 0.5)
+
     def _batch(self, prioritized, idx, act, rew, disc):
-        """the indexed batch of a draw whose slots are idx [3][B]"""
-        return (_PrioritizedIndexed if prioritized else IndexedBatch)(self.frames, idx[0], act, rew, disc, idx[1])
+        """the indexed batch of a draw whose slots are idx [3][B]; its frames are the whole allocation"""
+        return (_PrioritizedIndexed if prioritized else IndexedBatch)(self._whole["frames"], idx[0], act, rew, disc, idx[1])
 
     def __len__(self):
         """drawable transitions, reset rows included: rows x environments"""
@@ -737,11 +805,16 @@ class VecDeviceReplay:
         shaped like DeviceReplay's.  One random_sample((B, K)) call on the store's RandomState per batch."""
         _on_gpu(self, "the step-major replay lives")
         lo, hi = self.bounds()
-        if hi < lo:
+        B, K, dev = int(batch_size), self.K, self.device
+        Bd = self.demo_count(B)
+        if Bd > 0 and self.demo_bounds()[1] < 1:
+            raise _lib.DrqError(f"replay: demo_fraction {self._demo_fraction} asks for {Bd} demonstration rows of {B}, "
+                                f"the partition holds {self.demo_rows_filled} rows and no drawable one (nstep "
+                                f"{self.nstep}): add_demonstrations() first")
+        if hi < lo and Bd < B:      # a batch of demonstrations alone needs no live row: pure pre-training
             raise _lib.DrqError(f"replay: {self.T} rows added, no drawable row yet (nstep {self.nstep})")
         if self.tree is not None:
-            return self._sample_prioritized(int(batch_size), lo, hi)
-        B, K, dev = int(batch_size), self.K, self.device
+            return self._sample_prioritized(B, lo, hi)
         f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         idx, act, rew, disc, steps, u, host = _rotating(self._bufs, B, lambda: (
             torch.empty((3, B), dtype=torch.int64, device=dev), f(B, self.A), f(B, 1), f(B, 1),
@@ -757,11 +830,19 @@ class VecDeviceReplay:
                 self._frames_out = {B: out}
             obs, nxt = out
         copies = not self.indexed and self._draw_copies
-        launch("drq_vec_sample", ptr(self.first), ptr(self.action), ptr(self.reward), ptr(self.discount), self.R, self.N,
-               self.A, self.frame_bytes, lo, hi, ptr(u), B, K, self.nstep, self.gamma, ptr(idx), ptr(act), ptr(rew),
-               ptr(disc), ptr(steps), ptr(self.frames) if copies else None, ptr(obs) if copies else None,
-               ptr(nxt) if copies else None, device=dev)
-        self.last_steps, self.last_index = steps, idx
+        if Bd == 0:
+            launch("drq_vec_sample", ptr(self.first), ptr(self.action), ptr(self.reward), ptr(self.discount), self.R,
+                   self.N, self.A, self.frame_bytes, lo, hi, ptr(u), B, K, self.nstep, self.gamma, ptr(idx), ptr(act),
+                   ptr(rew), ptr(disc), ptr(steps), ptr(self.frames) if copies else None, ptr(obs) if copies else None,
+                   ptr(nxt) if copies else None, device=dev)
+        else:
+            # rows 0 .. Bd-1 from the partition, the others from the ring: the same u table, one launch
+            w = self._whole
+            launch("drq_vec_sample_mixed", ptr(w["first"]), ptr(w["action"]), ptr(w["reward"]), ptr(w["discount"]), self.R,
+                   self.D, self.N, self.A, self.frame_bytes, lo, hi, self.demo_rows_filled, ptr(u), B, Bd, K, self.nstep,
+                   self.gamma, ptr(idx), ptr(act), ptr(rew), ptr(disc), ptr(steps), ptr(w["frames"]) if copies else None,
+                   ptr(obs) if copies else None, ptr(nxt) if copies else None, device=dev)
+        self.last_steps, self.last_index, self.last_demo_count = steps, idx, Bd
         batch = self._batch(False, idx, act, rew, disc)
         if self.indexed:
             return batch
@@ -809,9 +890,12 @@ class VecDeviceReplay:
     _RING = ("frames", "action", "reward", "discount", "first")
 
     def _config(self):
-        return {"R": self.R, "N": self.N, "A": self.A, "slot_shape": tuple(self.slot_shape), "nstep": self.nstep,
-                "gamma": self.gamma, "guard_rows": self.guard_rows, "indexed": self.indexed,
-                "priority_alpha": self.priority_alpha, "priority_eps": self.priority_eps}
+        cfg = {"R": self.R, "N": self.N, "A": self.A, "slot_shape": tuple(self.slot_shape), "nstep": self.nstep,
+               "gamma": self.gamma, "guard_rows": self.guard_rows, "indexed": self.indexed,
+               "priority_alpha": self.priority_alpha, "priority_eps": self.priority_eps}
+        if self.D:      # only then: the states of stores without demonstrations stay what they were, both ways
+            cfg["demo_rows"] = self.D
+        return cfg
 
     def state_dict(self, frames=True):
         """The store as a plain dict of CPU tensors and Python scalars: "format": 1, "kind" (the class), "config" (R, N, A,
@@ -820,7 +904,9 @@ class VecDeviceReplay:
         -- slot (t mod R) N + e holds row t, so the first min(T, R) N -- and, prioritized, the whole tree (double
         [2 leaves]; tree[0] is the running maximum).  frames=False leaves the five ring arrays out (the caller keeps the
         ring some other way).  The ring goes through host memory whole: frame_bytes per live slot.  This SYNCHRONISES
-        the store's device.  The rotating staging sets are not state."""
+        the store's device.  The rotating staging sets are not state.  A store with demo_rows adds "demo_rows" to the
+        configuration and saves "demo_rows_filled", "demo_fraction" and "demos": the first Td N slots of the partition's
+        five arrays under the ring's names (left out with frames=False); one without saves exactly the above."""
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         live = min(self.T, self.R) * self.N
@@ -833,6 +919,11 @@ class VecDeviceReplay:
                 sd[n] = host(getattr(self, n)[:live])
         if self.tree is not None:
             sd["tree"] = host(self.tree)
+        if self.D:
+            # demonstrations: Td, the fraction and -- with the ring -- the first Td N slots of the partition's arrays
+            sd["demo_rows_filled"], sd["demo_fraction"] = self.demo_rows_filled, self._demo_fraction
+            if frames:
+                sd["demos"] = {n: host(self._demo[n][:self.demo_rows_filled * self.N]) for n in self._RING}
         return sd
 
     def load_state_dict(self, sd, frames=True):
@@ -842,7 +933,10 @@ class VecDeviceReplay:
         means it: T, the generator and the tree are restored, the ring arrays stay as they are.  After a load the slots
         above the live ones hold what the constructor puts there, last_steps and last_index are None, and the staging
         sets are kept.  Works on a CPU store as well (no launch is involved)."""
-        check_state(self, sd, self._config())
+        cfg = self._config()
+        if not self.D and isinstance(sd, dict) and isinstance(sd.get("config"), dict) and "demo_rows" in sd["config"]:
+            cfg["demo_rows"] = 0        # a state with demonstrations into a store without: named like any other field
+        check_state(self, sd, cfg)
         T, live = sd.get("T"), sd.get("live_slots")
         if not isinstance(T, int) or T < 0 or live != min(T, self.R) * self.N:
             raise ValueError(f"{type(self).__name__}.load_state_dict(): T {T!r} and live_slots {live!r} do not fit a ring "
@@ -858,6 +952,19 @@ class VecDeviceReplay:
         if (not isinstance(rng, (tuple, list)) or len(rng) != 5 or not torch.is_tensor(rng[1]) or rng[1].numel() != 624
                 or not 0 <= int(rng[2]) <= 624):
             raise ValueError(f"{type(self).__name__}.load_state_dict(): no RandomState in the saved state")
+        if self.D:
+            Td, fraction = sd.get("demo_rows_filled"), sd.get("demo_fraction")
+            if (not isinstance(Td, int) or not 0 <= Td <= self.D or not isinstance(fraction, float)
+                    or not 0.0 <= fraction <= 1.0):
+                raise ValueError(f"{type(self).__name__}.load_state_dict(): demo_rows_filled {Td!r} and demo_fraction "
+                                 f"{fraction!r} do not fit a partition of {self.D} rows")
+            if frames:
+                demos = sd.get("demos")
+                if not isinstance(demos, dict):
+                    raise ValueError(f"{type(self).__name__}.load_state_dict(): the state holds no demonstrations")
+                check_state(self, {"format": sd["format"], "kind": sd["kind"], **{f"demos.{n}": demos.get(n) for n in self._RING}},
+                            tensors={f"demos.{n}": ((Td * self.N,) + tuple(self._demo[n].shape[1:]), self._demo[n].dtype)
+                                     for n in self._RING})
         if frames:
             for n in self._RING:
                 getattr(self, n)[:live].copy_(sd[n])
@@ -865,8 +972,19 @@ class VecDeviceReplay:
             self.reward[live:].zero_()
             self.discount[live:].fill_(1.0)
             self.first[live:].fill_(1)
+            if self.D:
+                filled, d = Td * self.N, self._demo
+                for n in self._RING:
+                    d[n][:filled].copy_(sd["demos"][n])
+                d["frames"][filled:].zero_()
+                d["action"][filled:].zero_()
+                d["reward"][filled:].zero_()
+                d["discount"][filled:].fill_(1.0)
+                d["first"][filled:].fill_(1)
         if self.tree is not None:
             self.tree.copy_(sd["tree"])
+        if self.D:
+            self.demo_rows_filled, self._demo_fraction = Td, fraction
         self.T, self.priority_beta = T, float(sd["priority_beta"])
         self.rng.set_state((rng[0], rng[1].numpy().astype(np.uint32), int(rng[2]), int(rng[3]), float(rng[4])))
         self.last_steps = self.last_index = None
@@ -973,10 +1091,10 @@ class VecDeviceReplay:
                              f"{list(obs.shape)}")
         return np.ascontiguousarray(obs)
 
-    def _checked_episode(self, ep, name, check):
+    def _checked_episode(self, ep, name, check, what="add_episodes()"):
         """an episode dict as planned_rows takes it, every field checked against the store: ValueError naming both"""
         def bad(field, why):
-            return ValueError(f"add_episodes(): {name}: {field}: {why}")
+            return ValueError(f"{what}: {name}: {field}: {why}")
         for field in ("observation", "action", "reward", "discount"):
             if field not in ep:
                 raise bad(field, "the episode has no such field")
@@ -1016,16 +1134,8 @@ class VecDeviceReplay:
         A look-ahead batch drawn before the call is stale, as after any `guard_rows` adds: make a new iterator.  Every
         environment ends on a finished episode (or a pad row), so the next live add() must be a reset row for every
         environment.  Returns a FillReport.  DrqError for a store on the CPU, after the checks."""
-        import replay_buffer as RB          # at call time: replay_buffer imports this module
-        if isinstance(source, (str, pathlib.Path)):
-            files = [fn for fn, _, _ in RB._episode_files(source)]
-            named = [(fn.name, RB.load_episode(fn)) for fn in files]
-        else:
-            named = [(f"episode {i}", ep) for i, ep in enumerate(source)]
-        eps = [self._checked_episode(ep, name, check) for name, ep in named]
-        lengths = [ep["frame"].shape[0] - 1 for ep in eps]
-        plan = _episodes.plan_fill(lengths, self.N)
-        L, N, A, R = plan.L, self.N, self.A, self.R
+        eps, lengths, plan = self._planned_episodes(source, check, "add_episodes()")
+        L, R = plan.L, self.R
         if L > R:
             raise ValueError(f"add_episodes(): {len(eps)} episodes need L = {L} rows per environment, the ring has R = {R}: "
                              "split the data or enlarge the ring")
@@ -1036,8 +1146,32 @@ class VecDeviceReplay:
         # a prioritized store: no row of a chunk may overwrite flags the tree still has to read for an earlier row of
         # it (the row that enters is nstep - 1 rows behind the one just written)
         cap = R - self.nstep if self.tree is not None else R
+
+        def rows_added(n):
+            for _ in range(n):
+                self._row_added()
+        self._fill_rows(plan, eps, cap, chunk_bytes, [getattr(self, n) for n in self._RING], R, lambda: self.T, rows_added)
+        return report
+
+    def _planned_episodes(self, source, check, what):
+        """(episodes, lengths, plan): what add_episodes() and add_demonstrations() take -- a directory of episode files
+        or episode dicts -- read, every episode checked against the store, and laid out as lockstep rows"""
+        import replay_buffer as RB          # at call time: replay_buffer imports this module
+        if isinstance(source, (str, pathlib.Path)):
+            files = [fn for fn, _, _ in RB._episode_files(source)]
+            named = [(fn.name, RB.load_episode(fn)) for fn in files]
+        else:
+            named = [(f"episode {i}", ep) for i, ep in enumerate(source)]
+        eps = [self._checked_episode(ep, name, check, what) for name, ep in named]
+        lengths = [ep["frame"].shape[0] - 1 for ep in eps]
+        return eps, lengths, _episodes.plan_fill(lengths, self.N)
+
+    def _fill_rows(self, plan, eps, cap, chunk_bytes, arrays, R, row_of, rows_added):
+        """The plan's L rows staged step-major through two pinned buffers used in turn, at most chunk_bytes and `cap` rows
+        a chunk, each written by one drq_vec_fill into `arrays` (frames, action, reward, discount, first of R rows) from
+        row row_of() on; rows_added(n) counts the n rows of a chunk."""
+        L, N, A, dev = plan.L, self.N, self.A, self.device
         rows = int(max(1, min(L, cap, int(chunk_bytes) // (N * (self.frame_bytes + 4 * A + 9)))))
-        dev = self.device
         mk = lambda pin: [torch.empty(s, dtype=d, device=None if pin else dev, pin_memory=pin) for s, d in (
             ((rows, N) + self.slot_shape, torch.uint8), ((rows, N, A), torch.float32), ((rows, N), torch.float32),
             ((rows, N), torch.float32), ((rows, N), torch.uint8))]
@@ -1053,13 +1187,41 @@ class VecDeviceReplay:
                     d[:n].copy_(p[:n], non_blocking=True)
                 done[k] = torch.cuda.Event()
                 done[k].record(stream)
-                launch("drq_vec_fill", ptr(self.frames), ptr(self.action), ptr(self.reward), ptr(self.discount),
-                       ptr(self.first), R, N, A, self.frame_bytes, self.T, n, *(ptr(d) for d in dv), device=dev)
-                for _ in range(n):
-                    self._row_added()
+                launch("drq_vec_fill", *(ptr(t) for t in arrays), R, N, A, self.frame_bytes, row_of(), n,
+                       *(ptr(d) for d in dv), device=dev)
+                rows_added(n)
             for ev in done:
                 if ev is not None:
                     ev.synchronize()
+
+    # ---- demonstrations ------------------------------------------------------------------
+    def add_demonstrations(self, source, check=True, chunk_bytes=256 << 20):
+        """Appends episodes to the demonstration partition (demo_rows > 0).  source, check and chunk_bytes are
+        add_episodes()': a directory of the reference's episode files or a list of episode dicts, every episode checked
+        against the store before anything is written (ValueError names the episode and the field), laid out as lockstep
+        rows by drqv2_amd.episodes.plan_fill -- each episode into the lane with the fewest rows, the shorter lanes padded
+        with reset rows -- and written by drq_vec_fill, called on the partition's base pointers with R = demo_rows, one
+        launch per staging chunk.  The L rows go behind the Td = demo_rows_filled rows already there and hold
+        drqv2_amd.episodes.planned_rows(plan, episodes, 0, L), bit for bit.  The partition never evicts:
+        Td + L > demo_rows is a ValueError before anything is written.  The ring, T and the RandomState are untouched,
+        and a batch drawn earlier stays valid: rows that were drawable are never written again.  Returns a FillReport
+        (rows = L; T does not grow).  DrqError for a store on the CPU, after the checks."""
+        if not self.D:
+            raise ValueError("add_demonstrations(): this store has no demonstration partition (demo_rows=0)")
+        eps, lengths, plan = self._planned_episodes(source, check, "add_demonstrations()")
+        L, D, Td = plan.L, self.D, self.demo_rows_filled
+        if Td + L > D:
+            raise ValueError(f"add_demonstrations(): {len(eps)} episodes need L = {L} rows per lane behind the {Td} already "
+                             f"filled, the partition has demo_rows = {D} and never evicts: enlarge it or pass fewer episodes")
+        _on_gpu(self, "the step-major replay lives")
+        report = FillReport(len(eps), sum(lengths), L, plan.pad_rows)
+        if L == 0:
+            return report
+
+        def rows_added(n):
+            self.demo_rows_filled += n
+        self._fill_rows(plan, eps, D, chunk_bytes, [self._demo[n] for n in self._RING], D, lambda: self.demo_rows_filled,
+                        rows_added)
         return report
 
 
@@ -1092,9 +1254,13 @@ class VecFrameReplay(VecDeviceReplay):
         return newest_frames(obs, check)
 
     def __init__(self, rows, num_envs, action_dim, nstep, discount, device, frame_shape=(3, 84, 84), seed=None,
-                 indexed=True, guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6):
+                 indexed=True, guard_rows=8, priority_alpha=None, priority_beta=0.4, priority_eps=1e-6, demo_rows=0):
         if tuple(int(s) for s in frame_shape) != (3, 84, 84):
             raise ValueError(f"frame_shape {tuple(frame_shape)}: the single-frame ring stacks three (3, 84, 84) frames")
+        if int(demo_rows):
+            raise ValueError(f"demo_rows {demo_rows}: a single-frame ring holds no demonstrations -- its stacks are put "
+                             "together modulo the ring's rows, which a partition behind them is not part of; use "
+                             "VecDeviceReplay")
         if int(rows) < int(nstep) + int(guard_rows) + 4:
             raise ValueError(f"rows {rows}: at least nstep + guard_rows + 4 = {int(nstep) + int(guard_rows) + 4}")
         super().__init__(rows, num_envs, frame_shape, action_dim, nstep, discount, device, seed=seed, indexed=indexed,

@@ -403,6 +403,32 @@ int drq_vec_sample(const uint8_t* first, const float* action, const float* rewar
                    long* idx_out, float* act_out, float* rew_out, float* disc_out, int* steps_out, const uint8_t* frames,
                    uint8_t* obs_out, uint8_t* next_obs_out, drq_stream_t stream);
 
+/* ---- demonstrations in the step-major replay: a frozen partition behind the ring and batches that mix the two (the
+ * symmetric sampling of RLPD, the demonstration buffer of DDPGfD).  New functionality; these definitions are the
+ * contract.
+ * The five arrays of "step-major replay" hold (R + D) N slots.  Rows 0 .. R-1 are the ring, as above: row t of
+ * environment e in slot (t mod R) N + e, and nothing that writes or reads the ring knows of the rest.  Rows R .. R+D-1
+ * are the PARTITION: linear, never wrapped, never evicted; demonstration row d of lane e lives in slot (R + d) N + e.
+ * Its rows are laid out like the ring's (first == 1: a reset or pad row; row 0 always is one) and written by
+ * drq_vec_fill called on the partition's base pointers (frames + R N frame_bytes, action + R N A, ...) with R = D and
+ * T = Td, the rows filled so far; Td <= D.  Its drawable rows are 1 .. Td - nstep.
+ *
+ * drq_vec_sample_mixed: one launch, shaped like drq_vec_sample, draws B transitions: batch rows b < Bd from the
+ *   partition, rows b >= Bd from the ring.  Every row is drq_vec_sample's row for its own geometry -- the ring with
+ *   (R, lo, hi), the partition with (D, 1, Td - nstep) -- from its own u[b][0 .. K): the K candidates, the walk along
+ *   candidate 0's lane, the steps = 0 row, the window, the n-step sum.  idx_out int64 [3][B] indexes the WHOLE allocation:
+ *   a ring row's three slots are < R N, a partition row's are R N + its slots in the partition; obs_out / next_obs_out,
+ *   if given, receive frames[idx_out[0][b]], frames[idx_out[1][b]].  Bd = 0 is drq_vec_sample on the ring, Bd = B a
+ *   draw from the partition alone, for which lo and hi are not read (no live row need exist).  Plain vector stores, no
+ *   atomics, nothing crosses workgroups.
+ *   DRQ_EARG, nothing written: everything drq_vec_sample refuses (the ring's lo / hi only when Bd < B); D <= 0, Td < 0,
+ *   Td > D, Bd < 0, Bd > B; Bd > 0 with Td - nstep < 1; Bd < B with no drawable ring row (hi < lo). */
+int drq_vec_sample_mixed(const uint8_t* first, const float* action, const float* reward, const float* discount, long R,
+                         long D, long N, int A, long frame_bytes, long lo, long hi, long Td, const double* u, int B,
+                         int Bd, int K, int nstep, float gamma, long* idx_out, float* act_out, float* rew_out,
+                         float* disc_out, int* steps_out, const uint8_t* frames, uint8_t* obs_out, uint8_t* next_obs_out,
+                         drq_stream_t stream);
+
 /* ---- prioritized step-major replay: proportional prioritization (the definitions of "proportional prioritized replay"
  * above) on the ring of "step-major replay".  New functionality; these definitions are the contract.
  * `tree` is the sum tree of drq_per_*: double [2 L], L the smallest power of two >= R N, the leaf of slot s at tree[L + s],

@@ -16,6 +16,7 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--export-dir DIR] [--prefill-dir DIR]
                                  [--eval-every STEPS [--eval-episodes K] [--video DIR]]
                                  [--explore-beta B [--explore-bits K]]
+                                 [--demos DIR [--demo-fraction 0.5] [--demo-rows D]]
 
 --task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
 --task cartpole_balance and cartpole_swingup train on VecCartpole (swing_up False / True), whose step reads one action column
@@ -52,6 +53,15 @@ statistics, and so every return that is printed, keep the environment's own rewa
 number of distinct codes counted so far, and the count table goes into the checkpoint.  Off by default, and the output is
 then unchanged.
 
+--demos DIR keeps the episodes of DIR (episode files, e.g. what --export-dir wrote) as demonstrations for the whole run
+and draws --demo-fraction of every batch from them (VecDeviceReplay(demo_rows=D), add_demonstrations(), demo_fraction;
+INTEGRATION.md, "Demonstrations").  Demonstrations need a ring of whole observations, so the loop then runs on a
+VecDeviceReplay of 9 x 84 x 84 stacks -- three times the bytes per slot -- which a VecFrameStack in front of add() puts
+together and act_batch() reads.  --demo-rows D sizes the partition; by default it is what the files need at N lanes.
+The fraction is held constant here; a loop that anneals it assigns store.demo_fraction before a draw.  Not combined with
+--dormant-every / --perturb-every (they gather a single-frame batch) or with checkpoints (the frame stack in front of
+the ring is not saved).  Off by default, and the output is then unchanged.
+
 This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
 updates; it is no benchmark and makes no claim about DMC.
 """
@@ -69,7 +79,7 @@ from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import SimHashBonus  # noqa: E402
-from drqv2_amd.replay import VecEpisodeStats, VecFrameReplay  # noqa: E402
+from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
 TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_balance": (VecCartpole, {"swing_up": False}),
@@ -137,7 +147,14 @@ def main():
     ap.add_argument("--explore-beta", type=float, default=0.0, metavar="B",
                     help="add the exploration bonus B / sqrt(count of the frame's SimHash code) to the ring's reward (0: off)")
     ap.add_argument("--explore-bits", type=int, default=None, metavar="K", help="bits of the SimHash code, 1 .. 24 (16)")
+    ap.add_argument("--demos", default=None, metavar="DIR", help="episode files kept as demonstrations for the whole run")
+    ap.add_argument("--demo-fraction", type=float, default=0.5, metavar="F", help="share of every batch drawn from them")
+    ap.add_argument("--demo-rows", type=int, default=None, metavar="D", help="rows of the partition (what DIR needs)")
     args = ap.parse_args()
+    if args.demos and (args.dormant_every or args.perturb_every or args.checkpoint):
+        raise SystemExit("--demos does not combine with --dormant-every, --perturb-every or --checkpoint")
+    if not args.demos and (args.demo_rows is not None or args.demo_fraction != 0.5):
+        raise SystemExit("--demo-fraction and --demo-rows need --demos DIR")
     if args.explore_bits is not None and not args.explore_beta:
         raise SystemExit("--explore-bits needs --explore-beta B")
     if args.video and not args.eval_every:
@@ -157,7 +174,24 @@ def main():
     agent = drqv2.DrQV2Agent((9, 84, 84), (A,), "cuda", args.lr, args.feature_dim, args.hidden_dim, 0.01, args.warmup, 1,
                              args.stddev, 0.3, False)
     env = make_env(args, args.seed)
-    store = VecFrameReplay(rows=args.rows, num_envs=N, action_dim=A, nstep=3, discount=0.99, device="cuda", seed=args.seed)
+    if args.demos:
+        import replay_buffer
+        from drqv2_amd.episodes import plan_fill
+        need = plan_fill([n for _, _, n in replay_buffer._episode_files(args.demos)], N).L
+        store = VecDeviceReplay(rows=args.rows, num_envs=N, obs_shape=(9, 84, 84), action_dim=A, nstep=3, discount=0.99,
+                                device="cuda", seed=args.seed, demo_rows=args.demo_rows or max(need, 5))
+        fill = store.add_demonstrations(args.demos)
+        store.demo_fraction = args.demo_fraction
+        print(f"demonstrations from {args.demos}: {fill.episodes} episodes, {fill.transitions} transitions in {fill.rows} of "
+              f"{store.D} rows ({fill.pad_rows} pad rows); {store.demo_count(args.batch)} of every {args.batch} batch rows",
+              flush=True)
+        # the ring holds whole observations: the stack is put together in front of add(), and act_batch() reads it there
+        stack = VecFrameStack(N, "cuda")
+        add_row = lambda frame, action, reward, discount, first: store.add(stack.push(frame, first), action, reward, discount, first)
+        observe = stack.observation
+    else:
+        store = VecFrameReplay(rows=args.rows, num_envs=N, action_dim=A, nstep=3, discount=0.99, device="cuda", seed=args.seed)
+        add_row, observe = store.add, store.observation
     store.batch_size = args.batch
     stats = VecEpisodeStats(N, "cuda", log_size=max(1024, 2 * N * args.report))
     it = iter(store)
@@ -192,14 +226,14 @@ def main():
         frame = env.reset()
         # the reset row of every environment, flagged as one: only row 0 of an empty ring is a reset row by itself, and
         # after a prefill this row must not continue the prefilled episodes
-        store.add(frame, zeros_NA, zeros_N, ones_N, torch.ones(N, dtype=torch.uint8, device="cuda"))
+        add_row(frame, zeros_NA, zeros_N, ones_N, torch.ones(N, dtype=torch.uint8, device="cuda"))
         stats.step(zeros_N)
     t0 = time.perf_counter()
     for step in range(start, args.steps):
-        action = agent.act_batch(store.observation(), step, False)   # [N, A], stays on the device
+        action = agent.act_batch(observe(), step, False)             # [N, A], stays on the device
         frame, reward, discount, first = env.step(action)
         # the ring learns from reward + bonus; the statistics keep the environment's own reward
-        store.add(frame, action, reward if bonus is None else bonus.step(frame, reward), discount, first)
+        add_row(frame, action, reward if bonus is None else bonus.step(frame, reward), discount, first)
         stats.step(reward, first)
         if step >= args.warmup:
             agent.update(it, step)
