@@ -190,6 +190,14 @@ class _VecTask:
         launch("drq_vec_reach_image", ptr(self._frame), ptr(out), self.N, size, channels, device=self.device)
         return out
 
+    def background_key(self):
+        """The background every task here draws behind its shapes, uint8 [3, 84, 84] on the environment's device: the
+        ramp 32 + ((i + j) >> 2) in all three channels (include/drqv2_hip.h, "device environment").  It is the `key` of
+        drqv2_amd.distract.FrameDistractor: a pixel of a frame that equals it is background."""
+        i = torch.arange(84, device=self.device)
+        ramp = (32 + ((i[:, None] + i[None, :]) >> 2)).to(torch.uint8)
+        return ramp.expand(self.FRAME_SHAPE).contiguous()
+
     def state(self):
         """Host copies of the state, for tests and debugging: {"pos": float32 [N, 2], "target": float32 [N, 2], "t": int32
         [N], "episode": uint32 [N], "over": uint8 [N]}, and "vel": float32 [N, 2] for the point mass.  This SYNCHRONISES:

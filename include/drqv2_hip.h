@@ -791,6 +791,72 @@ int drq_explore_simhash_step(const uint8_t* frame, long N, int bits, unsigned se
                              int* code_out, int* count_out, float* bonus_out, const float* reward, float* reward_out,
                              drq_stream_t stream);
 
+/* ---- distractions.  New functionality: the reference trains and evaluates on the clean frames of dm_control.  The
+ * Distracting Control Suite (Stone et al. 2021) and DMControl-GB (Hansen & Wang 2021) ask whether a pixel agent still
+ * works when the image changes in ways that do not matter, and perturb exactly three things: the background, the colours
+ * and the camera.  This applies the three to the frames of N lockstep environments as "device environment" writes them,
+ * where they are: one launch per step, no download, no host wait.  These definitions are the contract; they are exact to
+ * the bit.  All arithmetic is integer: uint32 where it says so, int32 otherwise.
+ * Inputs: frame_in u8 [N][3][84][84]; first u8 [N] or NULL = no flag set; key u8 [3][84][84] or NULL (the clean background
+ *   of the renderer); bank u8 [M][F][3][84][84] or NULL (M clips of F background frames).  State per environment e, read
+ *   and written: episode u32 [N], t u32 [N], both 0 before the first call.  Scalars: seed; reset_all, hold, dynamic (0 / 1);
+ *   camera P, 0 .. DRQ_DISTRACT_MAX_CAMERA (8); camera_period >= 1; color C, 0 .. DRQ_DISTRACT_MAX_COLOR (128); bg_mode
+ *   0 (none), 1 (noise), 2 (bank); bg_alpha a, 0 .. 256; M and F, 1 .. DRQ_DISTRACT_MAX_BANK (65,536), read in mode 2 only.
+ *   Output: frame_out u8 [N][3][84][84], which overlaps frame_in nowhere.
+ * State step of e, before anything is drawn (skipped with hold = 1, see below):
+ *   reset_all = 1 or first[e] != 0:  episode += 1 (mod 2^32), t = 0;   otherwise t += 1 (mod 2^32).
+ *   tau = dynamic ? (t & 0xFFFFF) : 0.
+ * Draws: draw(k) = fmix32(seed ^ e * 0x9E3779B9 ^ episode * 0x85EBCA6B ^ (256 + k) * 0xC2B2AE35) in uint32 arithmetic,
+ *   episode the new count, fmix32 the murmur3 finaliser of "device environment".  The offset 256 keeps these draws apart
+ *   from an environment's own draws k = 0, 1, ... under the same seed.
+ * Fold: tri(v, m) for v >= 0:  0 when m == 0;  otherwise r = v mod 2m and tri = r <= m ? r : 2m - r   (0 .. m and back).
+ * Camera: ox = tri(draw(0) % (2P + 1) + (draw(2) % 3) * (tau / camera_period), 2P) - P, and oy likewise from draw(1) and
+ *   draw(3): an offset in [-P, P] per axis that starts anywhere and sweeps at 0, 1 or 2 pixels per camera_period steps.
+ *   The source pixel of output pixel (i, j) = (row, column) is si = clamp(i + oy, 0, 83), sj = clamp(j + ox, 0, 83) (edge
+ *   replication), and s_c = frame_in[e][c][si][sj].
+ * Keying: the pixel is BACKGROUND iff key != NULL and s_c == key[c][si][sj] for all three channels c -- the comparison is
+ *   made at the source pixel, so the foreground moves with the camera.  With key == NULL every pixel is foreground, and
+ *   bg_mode must be 0.
+ * Foreground colour, per channel c:  gain_c = 256 - C + draw(4 + c) % (2C + 1);  off_c = (int)(draw(7 + c) % (C + 1)) - (C >> 1);
+ *   f_c = clamp(((s_c * gain_c + 128) >> 8) + off_c, 0, 255).
+ * Background value n_c at output pixel (i, j):
+ *   mode 0:  n_c = s_c.
+ *   mode 1:  value noise on a lattice of 12 pixels that drifts with tau.  vx = (int)(draw(11) % 5) - 2;  vy = (int)(draw(12) % 5) - 2;
+ *     X = j + tau * vx;  Y = i + tau * vy;  gx = floor(X / 12), fx = X - 12 gx, and gy, fy likewise from Y (X and Y can be
+ *     negative: the division rounds toward minus infinity, 0 <= fx, fy <= 11).
+ *     L(c, gy, gx) = fmix32(draw(10) ^ c * 0x9E3779B9 ^ (uint32)gy * 0x85EBCA6B ^ (uint32)gx * 0xC2B2AE35) >> 24
+ *     top = L(c, gy, gx) * (12 - fx) + L(c, gy, gx + 1) * fx;  bot = the same at gy + 1;
+ *     n_c = (top * (12 - fy) + bot * fy + 72) / 144      (at most (255 * 144 + 72) / 144 = 255)
+ *   mode 2:  the clip m = draw(10) % M, its frame f = tri(draw(11) % F + tau, F - 1) -- the clip is played forward and
+ *     backward in turn (ping-pong) from a drawn start;  n_c = bank[m][f][c][i][j].
+ * Blend: b_c = (a * n_c + (256 - a) * s_c + 128) >> 8.     Output: frame_out[e][c][i][j] = background ? b_c : f_c.
+ * Identity: camera = 0, color = 0, bg_mode = 0 writes frame_in back bit for bit (gain 256, offset 0, n_c = s_c), for any key
+ *   and any bg_alpha; so does bg_alpha = 0 in any mode with camera = 0 and color = 0.  The state words still step.
+ * hold = 1 draws the frame of the state AS IT IS: the state step is skipped, episode and t are read and not written, first
+ *   is not read, reset_all must be 0.  After a call that stepped, a hold call on the same frame_in writes the same
+ *   frame_out; it is what a restored environment shows before its next step (a checkpoint holds episode and t).
+ *
+ * drq_vec_distract: one launch, N workgroups of 256 threads, one per environment.  The state words and the flag are read
+ *   wave-uniformly, so the state step, the draws and every scalar derived from them are computed once per wave on the
+ *   scalar unit; the frame and the key test are staged in LDS as one dword per pixel (three aligned 16-byte loads of the
+ *   frame and three of the key per 16 pixels; pixel p at dword p + (p >> 4), which spreads a wave over all banks) beside
+ *   the 9 x 9 x 3 lattice values the window can touch in mode 1 (they are hashed once, not per pixel); a workgroup barrier;
+ *   one lane stores the state, all store the frame as 16-byte pieces, 16 pixels of all three channel planes per lane and
+ *   round.  No atomics, nothing crosses workgroups.  Writes every byte of frame_out and, without hold, episode[e] and t[e]
+ *   of every environment; nothing else.  The caller orders the launches on one stream.
+ *   DRQ_EARG, nothing launched: a null frame_in, frame_out, episode or t; N < 1 or > INT32_MAX; reset_all, hold or dynamic
+ *   not 0 or 1; hold with reset_all; camera, color or bg_alpha outside its range; camera_period < 1; bg_mode not 0, 1 or 2;
+ *   bg_mode != 0 without a key; bg_mode 2 without a bank or with M or F outside 1 .. 65,536; frame_out overlapping frame_in
+ *   (frame_out == frame_in included); frame_in, frame_out, key or (mode 2) bank not 16-byte aligned; episode or t not
+ *   4-byte aligned. */
+#define DRQ_DISTRACT_MAX_CAMERA 8
+#define DRQ_DISTRACT_MAX_COLOR 128
+#define DRQ_DISTRACT_MAX_BANK 65536
+int drq_vec_distract(const uint8_t* frame_in, const uint8_t* first, const uint8_t* key, const uint8_t* bank,
+                     unsigned* episode, unsigned* t, long N, unsigned seed, int reset_all, int hold, int camera,
+                     int camera_period, int color, int bg_mode, int bg_alpha, int dynamic, int M, int F,
+                     uint8_t* frame_out, drq_stream_t stream);
+
 /* ---- evaluation.  New functionality: the reference evaluates its one environment on the host -- the 9-channel
  * observation comes out of a FrameStackWrapper (dmc.py:87-109), the episodes are recorded by video.py (train.py:98-122).
  * For N lockstep environments whose frames are device tensors ("device environment") both are one launch each, and

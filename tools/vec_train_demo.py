@@ -17,6 +17,7 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--eval-every STEPS [--eval-episodes K] [--video DIR]]
                                  [--explore-beta B [--explore-bits K]]
                                  [--demos DIR [--demo-fraction 0.5] [--demo-rows D]]
+                                 [--distract SPEC [--distract-on train|eval|both]]
 
 --task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
 --task cartpole_balance and cartpole_swingup train on VecCartpole (swing_up False / True), whose step reads one action column
@@ -62,6 +63,14 @@ The fraction is held constant here; a loop that anneals it assigns store.demo_fr
 --dormant-every / --perturb-every (they gather a single-frame batch) or with checkpoints (the frame stack in front of
 the ring is not saved).  Off by default, and the output is then unchanged.
 
+--distract SPEC puts visual distractions over the frames (drqv2_amd.distract: VecDistract around the environment, one more
+launch per step, INTEGRATION.md, "Distractions"): SPEC is easy, medium or hard, or a list such as
+camera=4,color=32,background=noise (further: camera_period=K, alpha=A, dynamic=0|1); the key is the built-in tasks' own
+background.  --distract-on train applies them to the training environment and the random baseline, eval to the evaluation
+environment, both (the default) to all three: train-only and eval-only runs are the two halves of the DMControl-GB
+protocol, whose difference from a clean run is the generalisation gap.  The distractor's state goes into the checkpoint
+with the environment's.  Off by default, and the output is then unchanged.
+
 This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
 updates; it is no benchmark and makes no claim about DMC.
 """
@@ -76,6 +85,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
 import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
+from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
 from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import SimHashBonus  # noqa: E402
@@ -86,10 +96,14 @@ TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_bal
          "cartpole_swingup": (VecCartpole, {"swing_up": True})}
 
 
-def make_env(args, seed):
+def make_env(args, seed, role="train"):
+    """the environment of a role ("train": training and the random baseline; "eval"), distracted when --distract-on says so"""
     cls, more = TASKS[args.task]
-    return cls(args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
-               action_repeat=args.action_repeat, **more)
+    env = cls(args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
+              action_repeat=args.action_repeat, **more)
+    if args.distract and args.distract_on in (role, "both"):
+        env = VecDistract(env, FrameDistractor(args.envs, "cuda", seed=seed, key="env", **parse_spec(args.distract)))
+    return env
 
 
 def random_baseline(args, episodes):
@@ -150,7 +164,20 @@ def main():
     ap.add_argument("--demos", default=None, metavar="DIR", help="episode files kept as demonstrations for the whole run")
     ap.add_argument("--demo-fraction", type=float, default=0.5, metavar="F", help="share of every batch drawn from them")
     ap.add_argument("--demo-rows", type=int, default=None, metavar="D", help="rows of the partition (what DIR needs)")
+    ap.add_argument("--distract", default=None, metavar="SPEC",
+                    help="visual distractions: easy|medium|hard, or e.g. camera=4,color=32,background=noise")
+    ap.add_argument("--distract-on", choices=("train", "eval", "both"), default=None, help="which environments are distracted (both)")
     args = ap.parse_args()
+    if args.distract_on and not args.distract:
+        raise SystemExit("--distract-on needs --distract SPEC")
+    if args.distract:
+        args.distract_on = args.distract_on or "both"
+        try:
+            parse_spec(args.distract)
+        except ValueError as err:
+            raise SystemExit(f"--distract: {err}")
+        if args.distract_on == "eval" and not args.eval_every:
+            raise SystemExit("--distract-on eval needs --eval-every STEPS")
     if args.demos and (args.dormant_every or args.perturb_every or args.checkpoint):
         raise SystemExit("--demos does not combine with --dormant-every, --perturb-every or --checkpoint")
     if not args.demos and (args.demo_rows is not None or args.demo_fraction != 0.5):
@@ -170,6 +197,9 @@ def main():
           f"{args.steps} steps, warm-up {args.warmup}, "
           f"batch {args.batch}, lr {args.lr}, feature_dim {args.feature_dim}, hidden_dim {args.hidden_dim}, stddev "
           f"{args.stddev}, seed {args.seed}", flush=True)
+
+    if args.distract:
+        print(f"distractions on {args.distract_on}: {parse_spec(args.distract)}", flush=True)
 
     agent = drqv2.DrQV2Agent((9, 84, 84), (A,), "cuda", args.lr, args.feature_dim, args.hidden_dim, 0.01, args.warmup, 1,
                              args.stddev, 0.3, False)
@@ -203,7 +233,7 @@ def main():
 
     if args.eval_every:
         K = args.eval_episodes
-        eval_env = make_env(args, args.seed + 1)
+        eval_env = make_env(args, args.seed + 1, "eval")
         eval_stats = VecEpisodeStats(N, "cuda", log_size=max(1024, K * N), max_episodes_per_env=K)
         eval_stack, video = VecFrameStack(N, "cuda"), None
         if args.video:
