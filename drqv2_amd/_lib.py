@@ -228,6 +228,14 @@ def launch(name, *args, device=None):
     check(enqueue(name, *args, device=device), name)
 
 
+def device_index(device):
+    """`device` as tensors on it report theirs: "cuda" without an index is the current device"""
+    d = torch.device(device)
+    if d.type == "cuda" and d.index is None:
+        return torch.device("cuda", torch.cuda.current_device())
+    return d
+
+
 def ptr(t):
     """data pointer of a torch tensor (or None)."""
     return None if t is None else t.data_ptr()

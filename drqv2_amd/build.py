@@ -13,7 +13,9 @@ SOURCES = ["conv.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv1aug.hip", "
 # own normal_() kernel: -ffp-contract=on does (0 of 65,536 values differ; hipcc's default fast contraction: 15 %
 # differ in the last bit; contraction off: 0.7 %) -- tools/rng_flags_probe.py, and the engine's self test at run time
 # vecenv.hip: the environment's contract is single float32 operations in the written order (a numpy oracle holds it to the
-# bit), so nothing may be fused: a * 0.1f + pos as one fma rounds once where the contract rounds twice
+# bit), so nothing may be fused: a * 0.1f + pos as one fma rounds once where the contract rounds twice.  The reset draw
+# and the wrapper fold of the tasks' skeleton (csrc/vecenv_task.h) are under the same contract: every file that
+# instantiates the skeleton needs -ffp-contract=off
 # veccartpole.hip: the same contract for the cartpole, whose step divides and takes a square root as well: both correctly
 # rounded, stated here for the reason given for explore.hip
 # explore.hip: the bonus is beta / sqrt(count) with both operations correctly rounded (a numpy oracle holds it to the bit);

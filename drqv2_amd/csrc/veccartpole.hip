@@ -8,17 +8,11 @@
 // written order, so tests/vec_cartpole_oracle.py restates it in numpy to the bit.  This file is compiled with
 // -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt (build.py): nothing is fused, and / and sqrt are IEEE.
 //
-// drq_vec_cartpole_step is one launch of N workgroups of 256 threads, one per environment, the shape of
-// vec_task_step_kernel (vecenv.hip):
-//   state     every thread loads the eight state words of its environment and computes the reset or the macro step
-//             itself, in registers -- the same IEEE operations on the same operands in every lane, so all 256 agree, on
-//             the trip count of the sub-step loop too
-//   barrier   __syncthreads(): every lane has read the old state before thread 0 stores the new one and the scalars
-//   frame     1,323 pieces of 16 bytes, 5 or 6 per lane, consecutive lanes consecutive pieces; per pixel the background,
-//             the rail, the cart and the pole's capsule, in integers (int64 where the capsule's cross product is squared)
-// No LDS, no atomics, nothing crosses workgroups.  drq_vec_cartpole_render is the frame part alone.
-#include "vecenv_common.h"
-#include "../../include/drqv2_hip.h"
+// The macro step, the render kernel, the frame walker and the checks of the step entry are the skeleton's
+// (vecenv_task.h); this file holds the cartpole's policy: its five state words, its two draws, its physics, its reward
+// and its pixel rule -- per pixel the background, the rail, the cart and the pole's capsule, in integers (int64 where the
+// capsule's cross product is squared).
+#include "vecenv_task.h"
 
 namespace {
 
@@ -111,31 +105,64 @@ __device__ __forceinline__ float cartpole_reward(const Pole& p, float a) {
   return ((upright * centred) * control) * slow;
 }
 
-// The pixel rule: the frame of (x, c, s) into the 21,168 bytes at `frame`, by the 256 threads of a workgroup -- 1,323
-// pieces of 16 bytes, consecutive lanes consecutive pieces.  Coordinates are 1/16 pixel; pixel (i, j) has its centre at
-// (16 j + 8, 16 i + 8).  Shapes that leave the frame are clipped by the loop itself: it visits the frame's pixels only.
-__device__ __forceinline__ void cartpole_frame(float x, float c, float s, uint8_t* frame) {
-  const float xs = x * 320.0f;
-  const int X0 = (int)floorf(xs + 672.5f);
-  const int X1 = (int)floorf((xs + s * 320.0f) + 672.5f);
-  const int Y1 = (int)floorf(672.5f - c * 320.0f);
-  const int dx = X1 - X0, dy = Y1 - kCentre;
-  const int dd = dx * dx + dy * dy;
-  const long edge = (long)kPoleR2 * dd;
-  uint4* dst = reinterpret_cast<uint4*>(frame);
-  for (int v = threadIdx.x; v < kPieces; v += kThreads) {
-    const int o = 16 * v;
-    const int ch = o / kPlane, rem = o - ch * kPlane;
-    int i = rem / kSide, j = rem - i * kSide;
-    const unsigned pole_colour = ch == 0 ? 255u : 64u, cart_colour = ch == 1 ? 255u : 64u, rail_colour = ch == 2 ? 255u : 64u;
-    unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-      unsigned p = 32u + (unsigned)((i + j) >> 2);
+// The cartpole's policy.  swing_up is a launch argument, like everything else that decides a branch (vecenv_task.h).
+struct Cartpole {
+  struct Args {
+    float* phys;            // [N][5]: x, xdot, c, s, omega
+    int swing_up;
+  };
+  using State = Pole;
+  using Action = float;
+
+  static __device__ __forceinline__ State load(const Args& a, long e) {
+    const float* ph = a.phys + 5 * e;
+    return {ph[0], ph[1], ph[2], ph[3], ph[4]};
+  }
+
+  static __device__ __forceinline__ void reset(const Args& a, State& p, unsigned seed, unsigned e, unsigned episode) {
+    p.x = reach_draw(seed, e, episode, 0u) * 0.1f;
+    p.xdot = 0.0f;
+    p.c = a.swing_up ? -1.0f : 1.0f;
+    p.s = reach_draw(seed, e, episode, 1u) * 0.05f;
+    normalise(p.c, p.s);
+    p.omega = 0.0f;
+  }
+
+  static __device__ __forceinline__ Action sanitise(const float* row) { return sanitise1(row[0]); }
+
+  // The task never ends an episode itself and every d is 1, so the wrapper rule's r * discount is r * 1 = r and its
+  // discount * d is 1 * 1 = 1, both exact in float32 for every r: the macro step's reward is the plain sum of the r, and
+  // the discount stays 1.
+  static __device__ __forceinline__ Sub substep(const Args&, State& p, Action act) {
+    cartpole_substep(p, act);
+    return {cartpole_reward(p, act), 1.0f, false};
+  }
+
+  static __device__ __forceinline__ void store(const Args& a, long e, const State& p) {
+    float* out = a.phys + 5 * e;
+    out[0] = p.x;
+    out[1] = p.xdot;
+    out[2] = p.c;
+    out[3] = p.s;
+    out[4] = p.omega;
+  }
+
+  // The pixel rule: the frame of (x, c, s).  Coordinates are 1/16 pixel; pixel (i, j) has its centre at (16 j + 8,
+  // 16 i + 8).  Shapes that leave the frame are clipped by the walker itself: it visits the frame's pixels only.
+  static __device__ __forceinline__ void frame(const State& st, uint8_t* frame) {
+    const float xs = st.x * 320.0f;
+    const int X0 = (int)floorf(xs + 672.5f);
+    const int X1 = (int)floorf((xs + st.s * 320.0f) + 672.5f);
+    const int Y1 = (int)floorf(672.5f - st.c * 320.0f);
+    const int dx = X1 - X0, dy = Y1 - kCentre;
+    const int dd = dx * dx + dy * dy;
+    const long edge = (long)kPoleR2 * dd;
+    draw_frame(frame, [=](int ch, int i, int j) {
+      unsigned p = frame_background(i, j);
       const int px = 16 * j + 8, py = 16 * i + 8;
       const int rx = px - kCentre, vx = px - X0, vy = py - kCentre;
-      if (i == kRailRow && rx >= -kRailHalf && rx <= kRailHalf) p = rail_colour;
-      if (vx >= -kCartHalfW && vx <= kCartHalfW && vy >= -kCartHalfH && vy <= kCartHalfH) p = cart_colour;
+      if (i == kRailRow && rx >= -kRailHalf && rx <= kRailHalf) p = ch == 2 ? 255u : 64u;
+      if (vx >= -kCartHalfW && vx <= kCartHalfW && vy >= -kCartHalfH && vy <= kCartHalfH) p = ch == 1 ? 255u : 64u;
       const int dot = vx * dx + vy * dy;
       bool in;
       if (dot <= 0) {
@@ -147,93 +174,10 @@ __device__ __forceinline__ void cartpole_frame(float x, float c, float s, uint8_
         const long cross = (long)vx * dy - (long)vy * dx;
         in = cross * cross <= edge;
       }
-      if (in) p = pole_colour;
-      w[b >> 2] |= p << (8 * (b & 3));
-      if (++j == kSide) {
-        j = 0;
-        ++i;
-      }
-    }
-    dst[v] = make_uint4(w[0], w[1], w[2], w[3]);
+      return in ? (ch == 0 ? 255u : 64u) : p;
+    });
   }
-}
-
-struct CartpoleArgs {
-  float* phys;            // [N][5]: x, xdot, c, s, omega
-  int* t;
-  unsigned* episode;
-  uint8_t* over;
-  const float* action;    // [N][A]; null only with reset_all
-  uint8_t* frame;         // [N][3][84][84]
-  float* reward;
-  float* discount;
-  uint8_t* first;
-  int* substeps;
-  unsigned seed;
-  int A, episode_length, repeat, reset_all, swing_up;
 };
-
-// One macro step of every environment: the reset row, or up to `repeat` sub-steps folded by the wrapper rule
-// (dmc.py:40-50).  repeat, reset_all and swing_up are launch arguments and the state is the workgroup's own, so every
-// branch and the trip count of the loop are uniform across the 256 lanes.
-__global__ __launch_bounds__(kThreads) void vec_cartpole_step_kernel(CartpoleArgs a) {
-  const long e = blockIdx.x;
-  const float* ph = a.phys + 5 * e;
-  Pole p{ph[0], ph[1], ph[2], ph[3], ph[4]};
-  int t = a.t[e];
-  unsigned episode = a.episode[e];
-  unsigned over = a.over[e];
-  float reward = 0.0f, discount = 1.0f;
-  unsigned first;
-  int n = 0;
-  if (a.reset_all || over) {
-    episode += 1u;
-    t = 0;
-    over = 0u;
-    p.x = reach_draw(a.seed, (unsigned)e, episode, 0u) * 0.1f;
-    p.xdot = 0.0f;
-    p.c = a.swing_up ? -1.0f : 1.0f;
-    p.s = reach_draw(a.seed, (unsigned)e, episode, 1u) * 0.05f;
-    normalise(p.c, p.s);
-    p.omega = 0.0f;
-    first = 1u;
-  } else {
-    float act = a.action[e * a.A];
-    act = act != act ? 0.0f : clamp1(act);
-    do {
-      cartpole_substep(p, act);
-      t += 1;
-      const float r = cartpole_reward(p, act);
-      if (t == a.episode_length) over = 1u;
-      reward = reward + r;          // the wrapper rule with every d_i = 1: r * 1 = r, and the discount stays 1
-    } while (++n < a.repeat && !over);
-    first = 0u;
-  }
-  __syncthreads();            // every lane holds the old state: thread 0 may now replace it
-  if (threadIdx.x == 0) {
-    float* out = a.phys + 5 * e;
-    out[0] = p.x;
-    out[1] = p.xdot;
-    out[2] = p.c;
-    out[3] = p.s;
-    out[4] = p.omega;
-    a.t[e] = t;
-    a.episode[e] = episode;
-    a.over[e] = (uint8_t)over;
-    a.reward[e] = reward;
-    a.discount[e] = discount;
-    a.first[e] = (uint8_t)first;
-    a.substeps[e] = n;
-  }
-
-  cartpole_frame(p.x, p.c, p.s, a.frame + e * (long)kFrame);
-}
-
-// the frames of the states as they are: the frame part of the step kernel alone, same launch shape
-__global__ __launch_bounds__(kThreads) void vec_cartpole_render_kernel(const float* __restrict__ phys, uint8_t* frame) {
-  const long e = blockIdx.x;
-  cartpole_frame(phys[5 * e], phys[5 * e + 2], phys[5 * e + 3], frame + e * (long)kFrame);
-}
 
 }  // namespace
 
@@ -241,26 +185,13 @@ DRQ_API int drq_vec_cartpole_step(float* phys, int* t, unsigned* episode, uint8_
                                   unsigned seed, int episode_length, int repeat, int reset_all, int swing_up,
                                   uint8_t* frame, float* reward, float* discount, uint8_t* first, int* substeps,
                                   drq_stream_t stream) {
-  if (!phys || !t || !episode || !over || !frame || !reward || !discount || !first || !substeps) return DRQ_EARG;
-  if (N < 1 || N > INT32_MAX || A < 1 || episode_length < 1) return DRQ_EARG;
-  if (repeat < 1 || repeat > DRQ_TASK_MAX_REPEAT) return DRQ_EARG;
-  if ((reset_all != 0 && reset_all != 1) || (swing_up != 0 && swing_up != 1)) return DRQ_EARG;
-  if (!action && !reset_all) return DRQ_EARG;
-  if ((uintptr_t)frame & 15) return DRQ_EARG;
-  if (((uintptr_t)phys | (uintptr_t)t | (uintptr_t)episode | (uintptr_t)reward | (uintptr_t)discount |
-       (uintptr_t)substeps | (uintptr_t)action) & 3)
-    return DRQ_EARG;
-  CartpoleArgs a{phys,     t,     episode,  over, action, frame,          reward,
-                 discount, first, substeps, seed, A,      episode_length, repeat, reset_all, swing_up};
-  hipLaunchKernelGGL(vec_cartpole_step_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, a);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  if (!phys || ((uintptr_t)phys & 3) || (swing_up != 0 && swing_up != 1)) return DRQ_EARG;
+  const EnvIO io{t, episode, over, action, frame, reward, discount, first, substeps, seed, A, episode_length, repeat, reset_all};
+  if (!env_io_ok(io, N, 1)) return DRQ_EARG;
+  return launch_env_step<Cartpole>({phys, swing_up}, io, N, stream);
 }
 
 DRQ_API int drq_vec_cartpole_render(const float* phys, long N, uint8_t* frame, drq_stream_t stream) {
-  if (!phys || !frame || N < 1 || N > INT32_MAX) return DRQ_EARG;
-  if (((uintptr_t)frame & 15) || ((uintptr_t)phys & 3)) return DRQ_EARG;
-  hipLaunchKernelGGL(vec_cartpole_render_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, phys, frame);
-  DRQ_LAUNCH_CHECK();
-  return DRQ_OK;
+  if (!phys || ((uintptr_t)phys & 3)) return DRQ_EARG;
+  return launch_env_render<Cartpole>({const_cast<float*>(phys), 0}, N, frame, stream);      // only loaded
 }

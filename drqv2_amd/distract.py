@@ -118,7 +118,7 @@ class FrameDistractor:
                 raise ValueError(f"background: a bank holds at most {MAX_BANK} clips of {MAX_BANK} frames, got {tuple(b.shape[:2])}")
             if b.dtype != torch.uint8:
                 raise ValueError(f"background: a bank must be {torch.uint8}, got {b.dtype}")
-            if b.device != self._device_index():
+            if b.device != _lib.device_index(self.device):
                 raise ValueError(f"background: the bank is on {b.device}, the distractor on {dev}")
             if not b.is_contiguous():
                 raise ValueError("background: the bank must be contiguous (it is read in place, never copied)")
@@ -151,12 +151,6 @@ class FrameDistractor:
         camera, color, alpha = PRESETS[name]
         return {"camera": camera, "color": color, "background": "noise", "background_alpha": alpha}
 
-    def _device_index(self):
-        d = self.device
-        if d.type == "cuda" and d.index is None:
-            return torch.device("cuda", torch.cuda.current_device())
-        return d
-
     def _on_gpu(self):
         if self.device.type != "cuda":
             raise _lib.DrqError("the distractions live on the GPU: the HIP path has no CPU fallback")
@@ -167,7 +161,7 @@ class FrameDistractor:
         if not torch.is_tensor(key) or tuple(key.shape) != FRAME_SHAPE or key.dtype != torch.uint8:
             raise ValueError("key must be None, \"env\" or a uint8 tensor [3, 84, 84]" +
                              (f", got {key.dtype} {tuple(key.shape)}" if torch.is_tensor(key) else f", got {key!r}"))
-        if key.device != self._device_index():
+        if key.device != _lib.device_index(self.device):
             raise ValueError(f"key is on {key.device}, the distractor on {self.device}")
         self.key = key.contiguous().clone()
 
@@ -178,7 +172,7 @@ class FrameDistractor:
             raise ValueError(f"{what}(): {name} of shape {shape} required, got {tuple(t.shape)}")
         if t.dtype not in dtypes:
             raise ValueError(f"{what}(): {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-        if t.device != self._device_index():
+        if t.device != _lib.device_index(self.device):
             raise ValueError(f"{what}(): {name} is on {t.device}, the distractor on {self.device}")
         return t.contiguous()
 

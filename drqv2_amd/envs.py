@@ -85,12 +85,6 @@ class _VecTask:
         self._frame = None          # the frames of the newest step() / reset()
         self._images = {}           # (size, channels) -> [buffer, buffer, index of the next]
 
-    def _device_index(self):
-        d = self.device
-        if d.type == "cuda" and d.index is None:
-            return torch.device("cuda", torch.cuda.current_device())
-        return d
-
     def _on_gpu(self):
         if self.device.type != "cuda":
             raise _lib.DrqError("the device environment lives on the GPU: the HIP path has no CPU fallback")
@@ -103,7 +97,7 @@ class _VecTask:
             raise ValueError(f"step(): action of shape {(N, A)} required, got {tuple(action.shape)}")
         if action.dtype != torch.float32:
             raise ValueError(f"step(): action must be {torch.float32}, got {action.dtype}")
-        if action.device != self._device_index():
+        if action.device != _lib.device_index(self.device):
             raise ValueError(f"step(): action is on {action.device}, the environment on {self.device}")
         return action.contiguous()
 

@@ -53,7 +53,7 @@ class VecFrameStack:
     push() after it, the convention of VecFrameReplay.observation(); a caller that keeps one longer clones it.
     observation() returns the newest stack again without a launch."""
 
-    _row, _device_index = VecDeviceReplay._row, VecDeviceReplay._device_index      # add()'s checks and messages
+    _row = VecDeviceReplay._row      # add()'s checks and messages
 
     def __init__(self, num_envs, device):
         self.N = int(num_envs)
@@ -253,7 +253,7 @@ class VecVideo:
     are held, record() launches nothing and counts in `dropped`.  clear() starts over; clip() is the recorded part, a
     device view."""
 
-    _row, _device_index = VecDeviceReplay._row, VecDeviceReplay._device_index      # add()'s checks and messages
+    _row = VecDeviceReplay._row      # add()'s checks and messages
 
     def __init__(self, num_envs, device, envs=None, grid=None, scale=2, max_frames=512):
         self.N, self.scale, self.max_frames = int(num_envs), int(scale), int(max_frames)

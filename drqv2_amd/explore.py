@@ -56,12 +56,6 @@ class SimHashBonus:
         self.codes = self.counts = self.last_bonus = None      # of the newest step()
         self._out = None            # two of (codes, counts, bonus, reward + bonus), then the index of the next
 
-    def _device_index(self):
-        d = self.device
-        if d.type == "cuda" and d.index is None:
-            return torch.device("cuda", torch.cuda.current_device())
-        return d
-
     def _on_gpu(self):
         if self.device.type != "cuda":
             raise _lib.DrqError("the exploration bonus lives on the GPU: the HIP path has no CPU fallback")
@@ -73,7 +67,7 @@ class SimHashBonus:
             raise ValueError(f"step(): {name} of shape {shape} required, got {tuple(t.shape)}")
         if t.dtype != dtype:
             raise ValueError(f"step(): {name} must be {dtype}, got {t.dtype}")
-        if t.device != self._device_index():
+        if t.device != _lib.device_index(self.device):
             raise ValueError(f"step(): {name} is on {t.device}, the bonus on {self.device}")
         return t.contiguous()
 

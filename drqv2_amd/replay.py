@@ -728,17 +728,11 @@ class VecDeviceReplay:
             raise ValueError(f"add(): {name} of shape {shapes[0]} required, got {tuple(t.shape)}")
         if t.dtype not in dtypes:
             raise ValueError(f"add(): {name} must be {dtypes[0]}, got {t.dtype}")
-        if t.device.type != "cpu" and t.device != self._device_index():
+        if t.device.type != "cpu" and t.device != _lib.device_index(self.device):
             raise ValueError(f"add(): {name} is on {t.device}, the store on {self.device}")
         if t.dtype != dtypes[0]:
             t = t.to(dtypes[0])     # float64 / bool of the same device: a cast, no wait
         return t.contiguous()
-
-    def _device_index(self):
-        d = self.device
-        if d.type == "cuda" and d.index is None:
-            return torch.device("cuda", torch.cuda.current_device())
-        return d
 
     def _staged(self, k, t):
         """a host tensor -> the device, through the pinned buffer of argument k: a blocking copy, like add_episode's"""
@@ -1303,7 +1297,7 @@ class VecFrameReplay(VecDeviceReplay):
             raise ValueError(f"add_render(): image with 3 or 4 channels last required, got {t.shape[3]}")
         if t.dtype != torch.uint8:
             raise ValueError(f"add_render(): image must be {torch.uint8}, got {t.dtype}")
-        if t.device.type != "cpu" and t.device != self._device_index():
+        if t.device.type != "cpu" and t.device != _lib.device_index(self.device):
             raise ValueError(f"add_render(): image is on {t.device}, the store on {self.device}")
         t = t.contiguous()
         return t.clone() if t.data_ptr() % 4 else t        # a view that starts inside a dword: the kernel reads dwords
@@ -1429,7 +1423,7 @@ class VecEpisodeStats:
     snapshot of the newest mirror whose sequence word equals the number it was published with.  read() publishes and
     waits for that one.  episode_return / episode_length are the running device tensors, read-only by convention."""
 
-    _row, _device_index = VecDeviceReplay._row, VecDeviceReplay._device_index      # add()'s checks and messages
+    _row = VecDeviceReplay._row      # add()'s checks and messages
 
     def __init__(self, num_envs, device, log_size=1024, max_episodes_per_env=0):
         self.N, self.W, self.limit = int(num_envs), int(log_size), int(max_episodes_per_env)

@@ -23,12 +23,12 @@ from tests import vec_env_oracle as E
 from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned allocations, check() after every test)
 from tests.test_hip_entries import dev, p
 from tests.test_hip_vec_replay import raw
+from tests.vec_env_checks import OUT, entry_on_poisoned_memory, lib_fixture, same_bits, same_state
 
 pytestmark = pytest.mark.gpu
 L, SEED = O.EPISODE_LENGTH, O.SEED
-U8 = poison.sentinel_of(torch.uint8)
-OUT = ("frame", "reward", "discount", "first", "substeps")
 STATE = ("phys", "t", "episode", "over")
+lib = lib_fixture("drq_vec_cartpole_step", "the cartpole entries are missing")
 _RUNS = {}
 
 
@@ -37,26 +37,6 @@ def run_of(cfg):
     if cfg not in _RUNS:
         _RUNS[cfg] = O.driven_run(*cfg) if len(cfg) == 4 else O.physics_run(*cfg)
     return _RUNS[cfg]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from drqv2_amd import _lib
-    assert torch.cuda.is_available()
-    assert "drq_vec_cartpole_step" in _lib.PROTOTYPES, "the cartpole entries are missing"
-    return _lib.load()
-
-
-def same_bits(got, want, what):
-    want = np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
-
-
-def same_state(got, want, what):
-    assert got.keys() == want.keys(), what
-    for k in want:
-        same_bits(got[k], want[k], (what, k))
 
 
 def make(cfg, episode_length=L):
@@ -134,29 +114,16 @@ def test_step_entry_writes_every_output_byte_and_nothing_else(lib, N, A, swing):
     z = lambda shape, dt, name: dev(torch.zeros(shape, dtype=dt), name)
     state = {"phys": z((N, 5), torch.float32, "phys"), "t": z(N, torch.int32, "t"), "episode": z(N, torch.int32, "episode"),
              "over": z(N, torch.uint8, "over")}
-    for s in range(-1, 12):
-        outs = [poison.alloc((N, 3, 84, 84), torch.uint8, "cuda", name="frame"),
-                poison.alloc(N, torch.float32, "cuda", name="reward"), poison.alloc(N, torch.float32, "cuda", name="discount"),
-                poison.alloc(N, torch.uint8, "cuda", name="first"), poison.alloc(N, torch.int32, "cuda", name="substeps")]
-        action = None if s < 0 else dev(torch.from_numpy(run["actions"][s]), "action")
-        assert lib.drq_vec_cartpole_step(*(p(state[n]) for n in STATE), N, A, p(action), SEED, L, 2, int(s < 0), int(swing),
-                                         *(p(t) for t in outs), None) == 0
-        if s < 0:
-            state["t"].copy_(torch.from_numpy(run["state0"]["t"]))         # the stagger of the oracle's run
-        want = (run["frame0"], np.zeros(N, np.float32), np.ones(N, np.float32), np.ones(N, np.uint8),
-                np.zeros(N, np.int32)) if s < 0 else run["out"][s]
-        for name, t, w in zip(OUT, outs, want):
-            got = t.cpu().numpy()
-            same_bits(got, w, (s, name))
-            if got.dtype == np.uint8:
-                assert not (got == U8).any(), (s, name)
+
+    def render_beside(s, want):
         again = poison.alloc((N, 3, 84, 84), torch.uint8, "cuda", name="rendered")
         assert lib.drq_vec_cartpole_render(p(state["phys"]), N, p(again), None) == 0
         same_bits(again.cpu().numpy(), want[0], (s, "render"))
-        poison.check()
-        got = {n: state[n].cpu().numpy() for n in STATE}
-        got["episode"] = got["episode"].view(np.uint32)
-        same_state(got, run["state0"] if s < 0 else run["states"][s], s)
+
+    entry_on_poisoned_memory(lambda action, reset_all, outs: lib.drq_vec_cartpole_step(
+        *(p(state[n]) for n in STATE), N, A, action, SEED, L, 2, reset_all, int(swing), *outs, None), run, N,
+        state=state, compared=STATE, beside=render_beside,
+        after_reset=lambda: state["t"].copy_(torch.from_numpy(run["state0"]["t"])))      # the stagger of the oracle's run
 
 
 def test_every_argument_error_is_refused_and_nothing_is_written(lib):

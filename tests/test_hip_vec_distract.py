@@ -18,26 +18,11 @@ from tests import poison
 from tests import vec_distract_oracle as O
 from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned allocations, check() after every test)
 from tests.test_hip_entries import dev, p
+from tests.vec_env_checks import lib_fixture, same_bits, same_state
 
 pytestmark = pytest.mark.gpu
 MODES = ("none", "noise", "bank")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from drqv2_amd import _lib
-    assert torch.cuda.is_available()
-    assert "drq_vec_distract" in _lib.PROTOTYPES, "the distraction entry is missing"
-    return _lib.load()
-
-
-def same_bits(got, want, what):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere(got != want)
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}: got {got[tuple(bad[0])]}, "
-                             f"want {want[tuple(bad[0])]}")
+lib = lib_fixture("drq_vec_distract", "the distraction entry is missing")
 
 
 def u32(t):
@@ -234,8 +219,7 @@ def test_checkpoint_round_trip_continues_bit_for_bit(tmp_path):
     fresh = make_wrapped("reach", N)
     assert checkpoint.load(path, env=fresh) == {"step": 11}
     same_bits(fresh.render().cpu().numpy(), at_k, "render() after the restore is the frame of step k")
-    for k, v in fresh.state().items():
-        same_bits(v, saved[k], ("restored", k))
+    same_state(fresh.state(), saved, "restored")
     for s, a in enumerate(acts[11:]):
         for got, want in zip(fresh.step(a), w.step(a)):
             same_bits(got.cpu().numpy(), want.cpu().numpy(), (s, "after the restore"))

@@ -24,20 +24,14 @@ from tests import vec_stats_oracle as VS
 from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned allocations, check() after every test)
 from tests.test_hip_entries import dev, p, rs_
 from tests.test_hip_vec_replay import raw
+from tests.vec_env_checks import U8, entry_on_poisoned_memory, lib_fixture, same_bits, same_state, state_words
 
 pytestmark = pytest.mark.gpu
 L, STEPS = 5, 40
 CONFIGS = ((3, 2), (3, 6), (65, 2), (65, 6))
 SEED = 11
-U8 = poison.sentinel_of(torch.uint8)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from drqv2_amd import _lib
-    assert torch.cuda.is_available()
-    assert "drq_vec_reach_step" in _lib.PROTOTYPES, "the device-environment entries are missing"
-    return _lib.load()
+STATE = ("pos", "target", "t", "episode", "over")
+lib = lib_fixture("drq_vec_reach_step", "the device-environment entries are missing")
 
 
 def reference_run(N, A, seed=SEED, steps=STEPS, episode_length=L):
@@ -74,17 +68,6 @@ def covers(run):
             and bool((np.abs(np.nan_to_num(acts)) > 1).any()))
 
 
-def same_bits(got, want, what):
-    want = np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
-
-
-def same_state(got, want):
-    for k in ("pos", "target", "t", "episode", "over"):
-        same_bits(got[k], want[k], k)
-
-
 # ------------------------------------------------------------------------------------------------ VecReach against the oracle
 @pytest.mark.parametrize("N,A", CONFIGS)
 def test_vec_reach_matches_the_oracle_bit_for_bit(runs, N, A):
@@ -96,7 +79,7 @@ def test_vec_reach_matches_the_oracle_bit_for_bit(runs, N, A):
     frame = env.reset()
     assert frame.is_cuda and frame.dtype == torch.uint8 and tuple(frame.shape) == (N, 3, 84, 84)
     same_bits(frame.cpu().numpy(), run["frame0"], "first frame")
-    same_state(env.state(), run["state0"])
+    same_state(env.state(), run["state0"], keys=STATE)
     kept = []
     for s in range(STEPS):
         out = env.step(torch.from_numpy(run["actions"][s]).cuda())
@@ -108,7 +91,7 @@ def test_vec_reach_matches_the_oracle_bit_for_bit(runs, N, A):
             same_bits(kept[s - 1][0].cpu().numpy(), run["out"][s - 1][0], (s, "the frame of the step before"))
         if s >= 2:
             assert kept[s - 2][0].data_ptr() == out[0].data_ptr() and kept[s - 1][0].data_ptr() != out[0].data_ptr()
-    same_state(env.state(), run["state"])
+    same_state(env.state(), run["state"], keys=STATE)
 
 
 # ------------------------------------------------------------------------------------------------ the entry on poisoned memory
@@ -120,26 +103,13 @@ def test_reach_step_writes_every_output_byte_and_nothing_else(lib, runs, N, A):
     run = runs[N, A]
     z = lambda shape, dt: dev(torch.zeros(shape, dtype=dt))
     state = [z((N, 2), torch.float32), z((N, 2), torch.float32), z(N, torch.int32), z(N, torch.int32), z(N, torch.uint8)]
-    for s in range(-1, 12):
-        outs = [poison.alloc((N, 3, 84, 84), torch.uint8, "cuda", name="frame"),
-                poison.alloc(N, torch.float32, "cuda", name="reward"), poison.alloc(N, torch.float32, "cuda", name="discount"),
-                poison.alloc(N, torch.uint8, "cuda", name="first")]
-        action = None if s < 0 else dev(torch.from_numpy(run["actions"][s]), "action")
-        assert lib.drq_vec_reach_step(*(p(t) for t in state), N, A, p(action), SEED, L, int(s < 0), *(p(t) for t in outs),
-                                      None) == 0
-        want = (run["frame0"], np.zeros(N, np.float32), np.ones(N, np.float32), np.ones(N, np.uint8)) if s < 0 else run["out"][s]
-        for name, t, w in zip(("frame", "reward", "discount", "first"), outs, want):
-            got = t.cpu().numpy()
-            same_bits(got, w, (s, name))
-            if got.dtype == np.uint8:
-                assert not (got == U8).any(), (s, name)
-        poison.check()
-    got = [t.cpu().numpy() for t in state]
+    entry_on_poisoned_memory(lambda action, reset_all, outs: lib.drq_vec_reach_step(
+        *(p(t) for t in state), N, A, action, SEED, L, reset_all, *outs, None), run, N, substeps=False)
     o = E.ReachOracle(N, episode_length=L, seed=SEED)
     o.reset()
     for s in range(12):
         o.step(run["actions"][s])
-    same_state(dict(zip(("pos", "target", "t", "episode", "over"), got[:3] + [got[3].view(np.uint32), got[4]])), o.state())
+    same_state(state_words(dict(zip(STATE, state)), STATE), o.state(), keys=STATE)
 
 
 # ------------------------------------------------------------------------------------------------ the renderer-shaped image
@@ -226,7 +196,7 @@ def test_collection_loop_end_to_end():
     same_bits(store.discount[:held].cpu().numpy().reshape(T + 1, N), np.stack([w[2] for w in want]), "discount")
     same_bits(store.first[:held].cpu().numpy().reshape(T + 1, N), np.stack([w[3] for w in want]), "first")
     same_bits(store.action[N:held].cpu().numpy().reshape(T, N, A), np.stack(actions), "action")
-    same_state(env.state(), o.state())
+    same_state(env.state(), o.state(), keys=STATE)
     ws = so.snapshot()
     assert ws.episodes >= N and o.reached + o.timed_out >= ws.episodes           # every environment finished at least one
     assert snap.rows == T + 1 and snap.episodes == ws.episodes and snap.length_sum == ws.length_sum
@@ -250,7 +220,7 @@ def test_same_seed_same_bytes_other_seed_other_frame(runs):
         for x, y in zip(o0, o1):
             assert raw(x).tobytes() == raw(y).tobytes(), s
     s0, s1 = envs[0].state(), envs[1].state()
-    same_state(s0, s1)
+    same_state(s0, s1, keys=STATE)
     from drqv2_amd import _lib
     fresh = VecReach(N, "cuda", action_dim=A)
     with pytest.raises(_lib.DrqError, match="reset"):

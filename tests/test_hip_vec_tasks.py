@@ -28,22 +28,14 @@ from tests import vec_tasks_oracle as T
 from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned allocations, check() after every test)
 from tests.test_hip_entries import dev, p
 from tests.test_hip_vec_replay import raw
+from tests.vec_env_checks import OUT, alloc_outs, entry_on_poisoned_memory, lib_fixture, same_bits, same_state
 
 pytestmark = pytest.mark.gpu
 L, STEPS, SEED = 7, 40, 5
 CONFIGS = ((1, 2), (1, 6), (3, 2), (3, 6), (65, 2), (65, 6))
 REPEATS = (1, 2, 3, 4)
-U8 = poison.sentinel_of(torch.uint8)
-OUT = ("frame", "reward", "discount", "first", "substeps")
 STATE = ("pos", "target", "vel", "t", "episode", "over")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from drqv2_amd import _lib
-    assert torch.cuda.is_available()
-    assert "drq_vec_task_step" in _lib.PROTOTYPES, "the task entry is missing"
-    return _lib.load()
+lib = lib_fixture("drq_vec_task_step", "the task entry is missing")
 
 
 @pytest.fixture(scope="module")
@@ -61,18 +53,6 @@ def runs():
 def cls_of(task):
     from drqv2_amd import envs
     return {"reach": envs.VecReach, "pointmass": envs.VecPointMass}[task]
-
-
-def same_bits(got, want, what):
-    want = np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
-
-
-def same_state(got, want, what):
-    assert got.keys() == want.keys(), what
-    for k in want:
-        same_bits(got[k], want[k], (what, k))
 
 
 # ------------------------------------------------------------------------------------------------ the classes against the oracle
@@ -117,12 +97,9 @@ def test_task_reach_at_repeat_1_writes_the_bytes_of_the_old_entry(lib, runs):
                   dev(torch.from_numpy(s0["t"]), "t"), dev(torch.from_numpy(s0["episode"].view(np.int32)), "episode"),
                   dev(torch.from_numpy(s0["over"]), "over")]
     old, new = mk(), mk()
-    outs = lambda: [poison.alloc((N, 3, 84, 84), torch.uint8, "cuda", name="frame"),
-                    poison.alloc(N, torch.float32, "cuda", name="reward"), poison.alloc(N, torch.float32, "cuda", name="discount"),
-                    poison.alloc(N, torch.uint8, "cuda", name="first")]
     for s in range(16):
         action = dev(torch.from_numpy(run["actions"][s]), "action")
-        oo, on = outs(), outs()
+        oo, on = alloc_outs(N, substeps=False), alloc_outs(N, substeps=False)
         sub = poison.alloc(N, torch.int32, "cuda", name="substeps")
         assert lib.drq_vec_reach_step(*(p(t) for t in old), N, A, p(action), SEED, L, 0, *(p(t) for t in oo), None) == 0
         assert lib.drq_vec_task_step(0, p(new[0]), p(new[1]), None, *(p(t) for t in new[2:]), N, A, p(action), SEED, L, 1, 0,
@@ -151,24 +128,9 @@ def test_task_step_writes_every_output_byte_and_nothing_else(lib, runs, task, N,
              "vel": z((N, 2), torch.float32, "vel") if task == "pointmass"
              else poison.alloc((N, 2), torch.float32, "cuda", name="vel", kind="refused"),
              "t": z(N, torch.int32, "t"), "episode": z(N, torch.int32, "episode"), "over": z(N, torch.uint8, "over")}
-    for s in range(-1, 12):
-        outs = [poison.alloc((N, 3, 84, 84), torch.uint8, "cuda", name="frame"),
-                poison.alloc(N, torch.float32, "cuda", name="reward"), poison.alloc(N, torch.float32, "cuda", name="discount"),
-                poison.alloc(N, torch.uint8, "cuda", name="first"), poison.alloc(N, torch.int32, "cuda", name="substeps")]
-        action = None if s < 0 else dev(torch.from_numpy(run["actions"][s]), "action")
-        assert lib.drq_vec_task_step(T.TASKS.index(task), *(p(state[n]) for n in STATE), N, A, p(action), SEED, L, k,
-                                     int(s < 0), *(p(t) for t in outs), None) == 0
-        want = (run["frame0"], np.zeros(N, np.float32), np.ones(N, np.float32), np.ones(N, np.uint8),
-                np.zeros(N, np.int32)) if s < 0 else run["out"][s]
-        for name, t, w in zip(OUT, outs, want):
-            got = t.cpu().numpy()
-            same_bits(got, w, (s, name))
-            if got.dtype == np.uint8:
-                assert not (got == U8).any(), (s, name)
-        poison.check()
-        got = {n: state[n].cpu().numpy() for n in STATE if n != "vel" or task == "pointmass"}
-        got["episode"] = got["episode"].view(np.uint32)
-        same_state(got, run["state0"] if s < 0 else run["states"][s], s)
+    entry_on_poisoned_memory(lambda action, reset_all, outs: lib.drq_vec_task_step(
+        T.TASKS.index(task), *(p(state[n]) for n in STATE), N, A, action, SEED, L, k, reset_all, *outs, None), run, N,
+        state=state, compared=[n for n in STATE if n != "vel" or task == "pointmass"])
 
 
 def test_every_argument_error_is_refused_and_nothing_is_written(lib):
