@@ -122,6 +122,8 @@ PROTOTYPES = {
     "drq_vec_cartpole_render": (I, [P, L, P, P]),
     "drq_explore_simhash_step": (I, [P, L, I, C.c_uint, F, I, P, P, P, P, P, P, P]),
     "drq_vec_distract": (I, [P, P, P, P, P, P, L, C.c_uint, I, I, I, I, I, I, I, I, I, I, P, P]),
+    "drq_aug_overlay": (I, [P, P, P, P, L, I, I, I, P]),
+    "drq_aug_random_conv": (I, [P, P, P, L, I, P]),
     "drq_vec_stack_push": (I, [P, P, P, P, L, I, P]),
     "drq_vec_video_record": (I, [P, P, I, P, I, P, I, I, I, L, P]),
     "drq_vec_export_rows": (I, [P, P, P, P, L, L, I, L, I, P, I, P, P, P, P, P]),

@@ -857,7 +857,43 @@ int drq_vec_distract(const uint8_t* frame_in, const uint8_t* first, const uint8_
                      int camera_period, int color, int bg_mode, int bg_alpha, int dynamic, int M, int F,
                      uint8_t* frame_out, drq_stream_t stream);
 
-/* ---- evaluation.  New functionality: the reference evaluates its one environment on the host -- the 9-channel
+/* ---- strong augmentation.  New functionality: the reference's only augmentation is its random shift (drqv2.py:19-45).
+ * These are the two augmentations the methods of DMControl-GB (SVEA, SODA, "DrQ + aug"; Hansen & Wang 2021) are built
+ * from, on a batch of uint8 frame stacks: random_overlay blends the observation with an unrelated image, random_conv
+ * passes every frame through a random 3 x 3 convolution.  These definitions are the contract; both are exact to the bit.
+ * obs and out are u8 [B][C][84][84] with C in {3, 6, 9, 12}: a stack of C / 3 RGB frames, oldest first; frame g of sample b
+ * is channels 3g .. 3g + 2.  Each entry is one launch on the stream.
+ *
+ * drq_aug_overlay: bank u8 [M][3][84][84], idx i32 [B], alpha_q8 an int in 0 .. 256.  For sample b, frame g, colour channel c
+ *   and pixel p, with y = bank[clamp(idx[b], 0, M - 1)][c][p] and x = obs[b][3g + c][p]:
+ *     out[b][3g + c][p] = (x * (256 - alpha_q8) + y * alpha_q8 + 128) >> 8
+ *   in integer arithmetic.  alpha_q8 = 0 returns obs exactly, 256 the bank image exactly; the same bank image goes over
+ *   every frame of a stack, as DMControl-GB repeats it.  The clamp exists so that no value of idx can read outside the bank
+ *   (the index lives on the device and cannot be checked on the host without a wait).  out may be obs itself (in place).
+ *   A grid-stride walk over B x 3 x 441 pieces of 16 pixels; the bank piece is loaded once and reused over the C / 3 frames.
+ *   Writes every byte of out, nothing else.
+ *   DRQ_EARG, nothing launched: a null pointer; obs, out or bank not 16-byte aligned; idx not 4-byte aligned; B < 1;
+ *   B C 7,056 > INT32_MAX; C outside {3, 6, 9, 12}; M < 1; alpha_q8 outside 0 .. 256; out overlapping obs without being obs;
+ *   out overlapping the bank.
+ * drq_aug_random_conv: w f32 [B][3][3][3][3] = (sample, c_out, c_in, ky, kx): one filter bank per sample, applied to each of
+ *   its C / 3 frames with replicate padding.  For output channel co of frame g at (i, j) = (row, column):
+ *     acc = 0.0f;  for ci = 0 .. 2, ky = 0 .. 2, kx = 0 .. 2, in that order:  acc = acc + w[b][co][ci][ky][kx] * p,
+ *       p = (float)obs[b][3g + ci][clamp(i + ky - 1, 0, 83)][clamp(j + kx - 1, 0, 83)] * 0.003921568859368563f
+ *       (every * and + one float32 operation, nothing fused; the constant is 1 / 255 rounded to float32)
+ *     q = acc / (1.0f + fabsf(acc)), the division correctly rounded;  q = 0 if q != q
+ *     v = (0.5f + 0.5f * q) * 255.0f;   out[b][3g + co][i][j] = (uint8_t)(int)(v + 0.5f)
+ *   The squash is the rational sigmoid, in place of a transcendental, so that numpy reproduces it to the bit: this is in
+ *   the image of DMControl-GB's sigmoid(conv2d(x / 255)), not a port of it.  All-zero weights give 128 everywhere; an
+ *   infinite or NaN sum gives 128 as well (inf / inf is NaN).  One workgroup of 256 threads per (sample, frame): the three
+ *   input planes and the 81 weights are staged in LDS, a lane computes 16 consecutive pixels of all three output channels
+ *   and stores them as three 16-byte pieces.  Writes every byte of out, nothing else.
+ *   DRQ_EARG, nothing launched: a null pointer; obs or out not 16-byte aligned; w not 4-byte aligned; B < 1;
+ *   B C 7,056 > INT32_MAX; C outside {3, 6, 9, 12}; out overlapping obs (out == obs included: neighbours are read). */
+int drq_aug_overlay(const uint8_t* obs, const uint8_t* bank, const int* idx, uint8_t* out, long B, int C, int M,
+                    int alpha_q8, drq_stream_t stream);
+int drq_aug_random_conv(const uint8_t* obs, const float* w, uint8_t* out, long B, int C, drq_stream_t stream);
+
+/* ---- evaluation. New functionality: the reference evaluates its one environment on the host -- the 9-channel
  * observation comes out of a FrameStackWrapper (dmc.py:87-109), the episodes are recorded by video.py (train.py:98-122).
  * For N lockstep environments whose frames are device tensors ("device environment") both are one launch each, and
  * neither needs a ring of "single-frame step-major replay".  These definitions are the contract; everything is integer

@@ -18,6 +18,7 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--explore-beta B [--explore-bits K]]
                                  [--demos DIR [--demo-fraction 0.5] [--demo-rows D]]
                                  [--distract SPEC [--distract-on train|eval|both]]
+                                 [--svea overlay|conv [--svea-alpha 0.5] [--svea-bank 64]]
 
 --task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
 --task cartpole_balance and cartpole_swingup train on VecCartpole (swing_up False / True), whose step reads one action column
@@ -71,6 +72,13 @@ environment, both (the default) to all three: train-only and eval-only runs are 
 protocol, whose difference from a clean run is the generalisation gap.  The distractor's state goes into the checkpoint
 with the environment's.  Off by default, and the output is then unchanged.
 
+--svea overlay|conv trains with a strong augmentation the SVEA way (drqv2_amd.augment, INTEGRATION.md, "Strong
+augmentation (SVEA)"): every batch is drawn at half of --batch, materialised, and handed to the unchanged update() as
+svea_batch(batch, strong) -- the clean rows and their strongly augmented copies, --batch rows in all.  overlay blends
+with weight --svea-alpha an image of a procedurally made bank of --svea-bank images (noise_bank: nothing is shipped), conv
+is the random convolution.  The augmenter's state goes into the checkpoint.  With --distract SPEC --distract-on eval this
+is the DMControl-GB protocol with a method that is meant to close the gap.  Off by default, and the output is then unchanged.
+
 This is a demonstration that the pieces run together and of what the agent does on this toy task in a few thousand
 updates; it is no benchmark and makes no claim about DMC.
 """
@@ -85,6 +93,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import drqv2  # noqa: E402
 import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
+from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch  # noqa: E402
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
 from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
@@ -104,6 +113,23 @@ def make_env(args, seed, role="train"):
     if args.distract and args.distract_on in (role, "both"):
         env = VecDistract(env, FrameDistractor(args.envs, "cuda", seed=seed, key="env", **parse_spec(args.distract)))
     return env
+
+
+class SveaBatches:
+    """The iterator update() draws from under --svea: the store's batches, materialised and doubled by svea_batch().  The
+    look-ahead stays the store iterator's own (prefetch), so a checkpoint saves it as it always did."""
+
+    def __init__(self, it, strong):
+        self.it, self.strong = it, strong
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return svea_batch(next(self.it).materialize((9, 84, 84)), self.strong)
+
+    def prefetch(self):
+        self.it.prefetch()
 
 
 def random_baseline(args, episodes):
@@ -167,6 +193,9 @@ def main():
     ap.add_argument("--distract", default=None, metavar="SPEC",
                     help="visual distractions: easy|medium|hard, or e.g. camera=4,color=32,background=noise")
     ap.add_argument("--distract-on", choices=("train", "eval", "both"), default=None, help="which environments are distracted (both)")
+    ap.add_argument("--svea", choices=("overlay", "conv"), default=None, help="train on svea_batch() of a strong augmentation")
+    ap.add_argument("--svea-alpha", type=float, default=None, metavar="A", help="weight of the overlaid image, 0 .. 1 (0.5)")
+    ap.add_argument("--svea-bank", type=int, default=None, metavar="M", help="images of the procedural overlay bank (64)")
     args = ap.parse_args()
     if args.distract_on and not args.distract:
         raise SystemExit("--distract-on needs --distract SPEC")
@@ -178,6 +207,10 @@ def main():
             raise SystemExit(f"--distract: {err}")
         if args.distract_on == "eval" and not args.eval_every:
             raise SystemExit("--distract-on eval needs --eval-every STEPS")
+    if args.svea != "overlay" and (args.svea_alpha is not None or args.svea_bank is not None):
+        raise SystemExit("--svea-alpha and --svea-bank need --svea overlay")
+    if args.svea and (args.batch < 2 or args.batch % 2):
+        raise SystemExit("--svea doubles every batch: --batch must be even")
     if args.demos and (args.dormant_every or args.perturb_every or args.checkpoint):
         raise SystemExit("--demos does not combine with --dormant-every, --perturb-every or --checkpoint")
     if not args.demos and (args.demo_rows is not None or args.demo_fraction != 0.5):
@@ -222,9 +255,21 @@ def main():
     else:
         store = VecFrameReplay(rows=args.rows, num_envs=N, action_dim=A, nstep=3, discount=0.99, device="cuda", seed=args.seed)
         add_row, observe = store.add, store.observation
-    store.batch_size = args.batch
+    # under --svea the store draws half a batch: update() sees --batch rows, the clean half and the augmented half
+    store.batch_size = args.batch // 2 if args.svea else args.batch
     stats = VecEpisodeStats(N, "cuda", log_size=max(1024, 2 * N * args.report))
     it = iter(store)
+    strong, batches = None, it
+    if args.svea:
+        try:
+            strong = RandomConv("cuda", seed=args.seed) if args.svea == "conv" else RandomOverlay(
+                noise_bank(64 if args.svea_bank is None else args.svea_bank, seed=args.seed),
+                alpha=0.5 if args.svea_alpha is None else args.svea_alpha, device="cuda", seed=args.seed)
+        except ValueError as err:
+            raise SystemExit(f"--svea: {err}")
+        batches = SveaBatches(it, strong)
+        print(f"svea: {args.svea}" + (f", alpha_q8 {strong.alpha_q8}, a bank of {strong.M} images" if args.svea == "overlay" else "")
+              + f"; batches of {store.batch_size} drawn, {args.batch} rows per update", flush=True)
     bonus = SimHashBonus(N, "cuda", bits=args.explore_bits or 16, beta=args.explore_beta, seed=args.seed) \
         if args.explore_beta else None
     if bonus is not None:
@@ -244,6 +289,10 @@ def main():
     if args.resume:
         extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus)
         start, logged, updates, export_from = extra["step"], extra["logged"], extra["updates"], extra.get("export_from")
+        if strong is not None:
+            if not isinstance(extra.get("svea"), dict):
+                raise SystemExit(f"--resume: {args.checkpoint} was saved without --svea")
+            strong.load_state_dict(extra["svea"])
         print(f"resumed {args.checkpoint} at step {start}", flush=True)
     else:
         if args.prefill_dir:
@@ -266,7 +315,7 @@ def main():
         add_row(frame, action, reward if bonus is None else bonus.step(frame, reward), discount, first)
         stats.step(reward, first)
         if step >= args.warmup:
-            agent.update(it, step)
+            agent.update(batches, step)
             updates += 1
             show = args.dormant_every and updates % args.dormant_every == 0
             pull = args.perturb_every and updates % args.perturb_every == 0
@@ -314,7 +363,8 @@ def main():
                       f"({size / 1e6:.2f} MB) [save {time.perf_counter() - ts:.2f} s]", flush=True)
         if args.checkpoint_every and (step + 1) % args.checkpoint_every == 0:    # the end of an iteration: this WAITS
             checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus,
-                            extra={"step": step + 1, "logged": logged, "updates": updates, "export_from": export_from})
+                            extra=dict({"step": step + 1, "logged": logged, "updates": updates, "export_from": export_from},
+                                       **({} if strong is None else {"svea": strong.state_dict()})))
     snap = stats.read()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
