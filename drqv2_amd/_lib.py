@@ -120,6 +120,8 @@ PROTOTYPES = {
     "drq_vec_reach_image": (I, [P, P, L, I, I, P]),
     "drq_vec_cartpole_step": (I, [P, P, P, P, L, I, P, C.c_uint, I, I, I, I, P, P, P, P, P, P]),
     "drq_vec_cartpole_render": (I, [P, L, P, P]),
+    "drq_vec_reacher_step": (I, [P, P, P, P, P, L, I, P, C.c_uint, I, I, I, F, I, P, P, P, P, P, P]),
+    "drq_vec_reacher_render": (I, [P, P, L, F, P, P]),
     "drq_explore_simhash_step": (I, [P, L, I, C.c_uint, F, I, P, P, P, P, P, P, P]),
     "drq_vec_distract": (I, [P, P, P, P, P, P, L, C.c_uint, I, I, I, I, I, I, I, I, I, I, P, P]),
     "drq_aug_overlay": (I, [P, P, P, P, L, I, I, I, P]),

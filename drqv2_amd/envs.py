@@ -15,6 +15,12 @@ carries a free pole, started hanging or near upright, in the image of the refere
 cartpole_balance (cfgs/task/easy.yaml) -- an action that acts through second-order coupled dynamics and an unstable
 equilibrium.  It shares _VecTask with the other two; what differs per task -- the entries, the state arrays and their
 arguments -- are _VecTask's hooks.  Specified in include/drqv2_hip.h ("Cartpole"), restated by tests/vec_cartpole_oracle.py.
+
+VecReacher is a fourth (csrc/vecreacher.hip, drq_vec_reacher_step): a planar two-link arm driven by torques at the
+shoulder and the elbow, in the image of the reference's reacher_easy and reacher_hard -- the one task here with a sparse
+reward, 1 while the fingertip is inside the target disc and 0 otherwise, which is what the exploration bonus, the
+demonstrations, prioritized replay and the DrM blocks are for.  Specified in include/drqv2_hip.h ("Reacher"), restated by
+tests/vec_reacher_oracle.py.
 """
 import torch
 
@@ -296,3 +302,54 @@ class VecCartpole(_VecTask):
 
     def _config(self):
         return dict(super()._config(), swing_up=self.swing_up)
+
+
+class VecReacher(_VecTask):
+    """N environments of the reacher on the device: a planar arm of two links of 0.5, seen from above (no gravity), with
+    a point mass of 1 at the elbow and one at the fingertip.  action[:, 0] in [-1, 1] is the torque at the shoulder and
+    action[:, 1] the torque at the elbow, each times 2 (NaN counts as 0; further columns are ignored); both joints are
+    damped, coupled through the full inertia matrix and its Coriolis terms, and have no limits.  sparse=True pays 1 for
+    every simulator step whose fingertip is inside the target disc of radius target_radius and 0 otherwise: about 0.15 is
+    the reference's reacher_easy, about 0.05 its reacher_hard.  sparse=False pays 1 / (1 + 4 d^2) of the distance d
+    between fingertip and target instead: a dense shaping of the same geometry, for debugging and as the comparison arm
+    of a demo.  It is a task in the image of those two, not a port of them, and nothing it scores says anything about
+    DMC.  The rule is in include/drqv2_hip.h ("Reacher") to the bit and restated in numpy by tests/vec_reacher_oracle.py.
+
+        env = VecReacher(num_envs=N, device="cuda", action_dim=2, episode_length=1000, seed=0, action_repeat=1,
+                         target_radius=0.15, sparse=True)
+
+    The discount is 1 on every row and only the time limit (t == episode_length, in simulator steps) ends an episode, so
+    a macro step's sparse reward is an exact small integer.  A reset draws both joint angles and a target whose whole
+    disc the fingertip can cover.  The frame shows the target (green), the upper arm (blue), the forearm (red) and the
+    fingertip (yellow) at 36 pixels per unit, the shoulder in the middle; neither velocity is in a frame, so the policy
+    needs the frame stack.  Same methods and guarantees as VecReach (_VecTask holds them).  The state words are "phys",
+    float32 [N, 6] = (c1, s1, w1, c2, s2, w2) -- the shoulder's unit vector, the elbow's relative to the upper arm, the
+    angular velocities -- "target", float32 [N, 2], and t, episode, over; the config of a state dict carries
+    target_radius and sparse."""
+    TASK = "reacher"
+    _STATE = ("phys", "target", "t", "episode", "over")
+    _STATE_SPEC = dict(_VecTask._STATE_SPEC, phys=((6,), torch.float32))
+    MIN_TARGET_RADIUS, MAX_TARGET_RADIUS = 0.02, 0.3
+
+    def __init__(self, num_envs, device, action_dim=2, episode_length=1000, seed=0, action_repeat=1, target_radius=0.15,
+                 sparse=True):
+        if isinstance(target_radius, bool) or not isinstance(target_radius, (int, float)) \
+                or not self.MIN_TARGET_RADIUS <= target_radius <= self.MAX_TARGET_RADIUS:
+            raise ValueError(f"target_radius must be a number in {self.MIN_TARGET_RADIUS} .. {self.MAX_TARGET_RADIUS}, "
+                             f"got {target_radius!r}")
+        if not isinstance(sparse, (bool, int)) or sparse not in (0, 1):
+            raise ValueError(f"sparse must be True or False, got {sparse!r}")
+        self.target_radius, self.sparse = float(target_radius), bool(sparse)
+        super().__init__(num_envs, device, action_dim, episode_length, seed, action_repeat)
+
+    def _step_launch(self, action, reset_all, out):
+        launch("drq_vec_reacher_step", ptr(self.phys), ptr(self.target), ptr(self.t), ptr(self.episode), ptr(self.over),
+               self.N, self.A, ptr(action), self.seed, self.episode_length, self.action_repeat, int(reset_all),
+               self.target_radius, int(self.sparse), *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        launch("drq_vec_reacher_render", ptr(self.phys), ptr(self.target), self.N, self.target_radius, ptr(frame),
+               device=self.device)
+
+    def _config(self):
+        return dict(super()._config(), target_radius=self.target_radius, sparse=self.sparse)

@@ -751,6 +751,75 @@ int drq_vec_cartpole_step(float* phys, int* t, unsigned* episode, uint8_t* over,
                           float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
 int drq_vec_cartpole_render(const float* phys, long N, uint8_t* frame, drq_stream_t stream);
 
+/* Reacher.  A fourth task of the device environment, with entries of its own: a planar arm of two links, seen from above
+ * (no gravity), driven by a torque at the shoulder and one at the elbow; the fingertip must be brought into a target
+ * disc of radius target_radius.  sparse = 1 pays 1 while the fingertip is inside the disc and 0 otherwise -- in the image
+ * of the reference's reacher_easy and reacher_hard (the files under cfgs/task; target_radius about 0.15 and 0.05), not a port of
+ * them; sparse = 0 pays a dense shaping of the same distance.  These definitions are the contract; they are exact to the
+ * bit.  Every float operation below is ONE correctly rounded IEEE float32 operation (+, -, *, / or sqrt), in the written
+ * order, never fused; there is no sin, cos or exp anywhere: the shoulder's angle is held as the unit vector (c1, s1), the
+ * elbow's angle, relative to the upper arm, as (c2, s2).  normalise, the draws v_k and the sanitising are those above.
+ * State per environment e: phys f32 [N][6] = (c1, s1, w1, c2, s2, w2), w the angular velocities; target f32 [N][2];
+ *   t i32 [N], episode u32 [N], over u8 [N] as above.  0.02 <= target_radius <= 0.3.
+ * Geometry.  Both links have length 0.5:  c12 = c1 * c2 - s1 * s2;  s12 = s1 * c2 + c1 * s2  (the forearm's direction);
+ *   tip.x = 0.5f * c1 + 0.5f * c12;  tip.y = 0.5f * s1 + 0.5f * s12         (two multiplies, then the add, per component)
+ * direction(v), the unit vector of a draw v in [-0.9, 0.9]: a walk round the diamond |x| + |y| = 1, normalised:
+ *   u = clamp(v * 1.1111112f, -1, 1);  x = 1 - 2 * |u|;  y = 1 - |x|, negated for u < 0;
+ *   x * x + y * y < 0.25f: (1, 0)  (a degenerate pair; no point of the diamond is one);  otherwise normalise(x, y).
+ * Reset of e (reset_all = 1, or over[e] == 1): episode += 1 (mod 2^32), t = 0, over = 0; four draws v_0 .. v_3:
+ *   (c1, s1) = direction(v_0);  (c2, s2) = direction(v_1);  w1 = w2 = 0;
+ *   (gx, gy) = direction(v_2);  f = 0.5f + v_3 * 0.5f;  rho = (1 - target_radius) * f;  target = (rho * gx, rho * gy)
+ *   f is in [0.05, 0.95], so |target| + target_radius < 1: the whole disc lies where the fingertip can go.
+ *   Outputs first = 1, reward = 0, discount = 1, substeps = 0, the frame of the new state.  The action is not read.
+ * Sub-step, (a1, a2) the sanitised action (action[e][0] the shoulder's torque, action[e][1] the elbow's, each NaN to 0,
+ *   then the clamp to [-1, 1]; columns 2 .. A-1 are not read).  Two point masses of 1 at the ends of the links, dt = 0.01,
+ *   torque K = 2 per unit of action, viscous damping b = 0.5 at both joints:
+ *   M11 = 0.75f + 0.5f * c2;  M12 = 0.25f + 0.25f * c2;  h = 0.25f * s2                              (M22 = 0.25)
+ *   cor = (2 * w1) * w2 + w2 * w2
+ *   tau1 = (a1 * 2 - 0.5f * w1) + h * cor;  tau2 = (a2 * 2 - 0.5f * w2) - h * (w1 * w1)
+ *   det = M11 * 0.25f - M12 * M12                          (= 0.125 - 0.0625 c2^2 >= 0.0625 up to rounding: never near 0)
+ *   al1 = (0.25f * tau1 - M12 * tau2) / det;  al2 = (M11 * tau2 - M12 * tau1) / det
+ *   w1 = clamp(w1 + al1 * 0.01f, -16, 16);  w2 = clamp(w2 + al2 * 0.01f, -16, 16)                (semi-implicit Euler)
+ *   per joint, with its new w:  k = w * 0.01f;  k == 0: (c, s) stay as they are (an arm at rest stays at rest to the bit);
+ *   otherwise c' = c - s * k;  s' = s + c * k  (both from the old c and s);  (c, s) = normalise(c', s').  No joint limits.
+ *   t += 1;  over = 1 only when t == episode_length;  d_i = 1 always: the task never ends an episode itself.
+ *   Reward r_i of the new state:  dx = tip.x - target.x;  dy = tip.y - target.y;  d2 = dx * dx + dy * dy;
+ *   sparse:  r_i = d2 <= target_radius * target_radius ? 1 : 0;     dense:  r_i = 1 / (1 + 4 * d2), in (0, 1]
+ * Macro step: the one of "Tasks and action repeat" with every d_i = 1: reward = reward + r_i for up to `repeat` sub-steps,
+ *   stopping after the one that set over; discount = 1, first = 0, substeps = the sub-steps executed.  In the sparse form
+ *   the reward is an exact small integer, 0 .. repeat.
+ * Frame of a state, u8 [3][84][84].  Coordinates are integers in 1/16 pixel; pixel (i, j) has its centre at
+ *   (16 j + 8, 16 i + 8).  576 units (36 pixels) are one unit of length, y points up, the shoulder is at (672, 672): the
+ *   reach of the arm and the fingertip's radius stay inside the frame (672 - 576 - 32 >= 0).  Each coordinate is rounded once:
+ *   ax = c1 * 288;  ay = s1 * 288;  EX = (int)floorf(ax + 672.5f);  EY = (int)floorf(672.5f - ay)               (the elbow)
+ *   TX = (int)floorf((ax + c12 * 288) + 672.5f);  TY = (int)floorf(672.5f - (ay + s12 * 288))                   (the tip)
+ *   GX = (int)floorf(target.x * 576 + 672.5f);  GY = (int)floorf(672.5f - target.y * 576)                       (the target)
+ *   GR = (int)floorf(target_radius * 576 + 0.5f)
+ *   Everything after that is integer arithmetic.  Per pixel, with P = (16 j + 8, 16 i + 8), later rules drawn over earlier:
+ *   background 32 + ((i + j) >> 2) in all three channels;
+ *   the target, |P - G|^2 <= GR * GR, in (64, 255, 64);
+ *   the upper arm, the capsule of radius 24 around the segment shoulder -- elbow, in (64, 64, 255);
+ *   the forearm, the capsule of radius 24 around the segment elbow -- tip, in (255, 64, 64);
+ *   the fingertip, |P - T|^2 <= 1024, in (255, 255, 64).
+ *   A capsule is the cartpole's: with v = P - start, d = end - start, dot = v.d, dd = d.d (int32):  dot <= 0: |v|^2 <= 576;
+ *     dot >= dd: |P - end|^2 <= 576;  otherwise cross = v.x * d.y - v.y * d.x and cross * cross <= 576 * dd, in int64.
+ *   Neither velocity is in a frame.  A shape pixel holds 64 and 255 only and never three equal channels.
+ *
+ * drq_vec_reacher_step: one launch, N workgroups of 256 threads with the shape of drq_vec_cartpole_step.  Writes every byte
+ *   of frame, reward, discount, first, substeps and the state (phys and target), nothing else.  No LDS, no atomics.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 2, repeat < 1
+ *   or > DRQ_TASK_MAX_REPEAT, episode_length < 1, reset_all or sparse not 0 or 1, target_radius outside [0.02, 0.3] or
+ *   NaN, frame not 16-byte aligned, a float / int array not 4-byte aligned.
+ * drq_vec_reacher_render: the frames of the states as they are, by the frame rule above (the same device function): every
+ *   byte of frame, nothing else; phys and target are only read.  DRQ_EARG, nothing launched: a null pointer, N < 1 or
+ *   > INT32_MAX, target_radius as for the step, frame not 16-byte aligned, phys or target not 4-byte aligned. */
+int drq_vec_reacher_step(float* phys, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
+                         const float* action, unsigned seed, int episode_length, int repeat, int reset_all,
+                         float target_radius, int sparse, uint8_t* frame, float* reward, float* discount, uint8_t* first,
+                         int* substeps, drq_stream_t stream);
+int drq_vec_reacher_render(const float* phys, const float* target, long N, float target_radius, uint8_t* frame,
+                           drq_stream_t stream);
+
 /* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
  * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
  * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep

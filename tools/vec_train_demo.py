@@ -1,6 +1,6 @@
 """The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
 
-  VecReach, VecPointMass or VecCartpole (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecReach, VecPointMass, VecCartpole or VecReacher (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
   VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
 
 Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
@@ -8,7 +8,8 @@ return (and length) of the episodes that finished in every interval, from VecEpi
 uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup] [--action-repeat 1]
+  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard]
+                                 [--reward sparse|dense] [--action-repeat 1]
                                  [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
@@ -23,7 +24,11 @@ process: that is the baseline the training curve is read against, not a constant
 --task pointmass trains on the point mass, whose velocity is in no single frame (the frame stack is what shows it);
 --task cartpole_balance and cartpole_swingup train on VecCartpole (swing_up False / True), whose step reads one action column
 (--action-dim 1 fits it; the reference configures action repeat 2 and episodes of 1,000 simulator steps for its cartpoles);
---action-repeat K holds every action for up to K simulator steps inside the step launch.  Both apply to the training
+--task reacher_easy and reacher_hard train on VecReacher (target_radius 0.15 / 0.05), the one task here whose reward is
+sparse: 1 for every simulator step with the fingertip inside the target's disc, else 0 (the reference configures episodes of
+1,000 simulator steps for its reachers); --reward dense swaps in VecReacher's dense shaping of the same distance, the
+comparison arm;
+--action-repeat K holds every action for up to K simulator steps inside the step launch.  All of these apply to the training
 environment, the evaluation environment and the random baseline alike.  --episode-length counts simulator steps; the
 lengths that are printed count rows, i.e. agent steps.
 
@@ -95,21 +100,23 @@ import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch  # noqa: E402
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
-from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach  # noqa: E402
+from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach, VecReacher  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
 TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_balance": (VecCartpole, {"swing_up": False}),
-         "cartpole_swingup": (VecCartpole, {"swing_up": True})}
+         "cartpole_swingup": (VecCartpole, {"swing_up": True}), "reacher_easy": (VecReacher, {"target_radius": 0.15}),
+         "reacher_hard": (VecReacher, {"target_radius": 0.05})}
+REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: VecReacher's two forms
 
 
 def make_env(args, seed, role="train"):
     """the environment of a role ("train": training and the random baseline; "eval"), distracted when --distract-on says so"""
     cls, more = TASKS[args.task]
     env = cls(args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
-              action_repeat=args.action_repeat, **more)
+              action_repeat=args.action_repeat, **more, **REWARDS[args.reward])
     if args.distract and args.distract_on in (role, "both"):
         env = VecDistract(env, FrameDistractor(args.envs, "cuda", seed=seed, key="env", **parse_spec(args.distract)))
     return env
@@ -155,6 +162,7 @@ def random_baseline(args, episodes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=sorted(TASKS), default="reach")
+    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher tasks (sparse)")
     ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per action, 1 .. 16")
     ap.add_argument("--steps", type=int, default=20000, help="environment steps (each of all N environments)")
     ap.add_argument("--envs", type=int, default=16)
@@ -197,6 +205,8 @@ def main():
     ap.add_argument("--svea-alpha", type=float, default=None, metavar="A", help="weight of the overlaid image, 0 .. 1 (0.5)")
     ap.add_argument("--svea-bank", type=int, default=None, metavar="M", help="images of the procedural overlay bank (64)")
     args = ap.parse_args()
+    if args.reward and TASKS[args.task][0] is not VecReacher:
+        raise SystemExit("--reward needs --task reacher_easy or reacher_hard")
     if args.distract_on and not args.distract:
         raise SystemExit("--distract-on needs --distract SPEC")
     if args.distract:
@@ -226,7 +236,7 @@ def main():
     N, A = args.envs, args.action_dim
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed_all(args.seed)
-    print(f"{args.task}: N={N} environments, episode_length={args.episode_length}, action_repeat={args.action_repeat}, A={A}; "
+    print(f"{args.task}{' (' + args.reward + ' reward)' if args.reward else ''}: N={N} environments, episode_length={args.episode_length}, action_repeat={args.action_repeat}, A={A}; "
           f"{args.steps} steps, warm-up {args.warmup}, "
           f"batch {args.batch}, lr {args.lr}, feature_dim {args.feature_dim}, hidden_dim {args.hidden_dim}, stddev "
           f"{args.stddev}, seed {args.seed}", flush=True)
