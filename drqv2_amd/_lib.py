@@ -123,6 +123,8 @@ PROTOTYPES = {
     "drq_vec_reacher_step": (I, [P, P, P, P, P, L, I, P, C.c_uint, I, I, I, F, I, P, P, P, P, P, P]),
     "drq_vec_reacher_render": (I, [P, P, L, F, P, P]),
     "drq_explore_simhash_step": (I, [P, L, I, C.c_uint, F, I, P, P, P, P, P, P, P]),
+    "drq_explore_knn_ws_bytes": (SZ, [L, L, L]),
+    "drq_explore_knn": (I, [P, L, I, L, P, L, I, L, L, P, P, SZ, P]),
     "drq_vec_distract": (I, [P, P, P, P, P, P, L, C.c_uint, I, I, I, I, I, I, I, I, I, I, P, P]),
     "drq_aug_overlay": (I, [P, P, P, P, L, I, I, I, P]),
     "drq_aug_random_conv": (I, [P, P, P, L, I, P]),
@@ -169,7 +171,7 @@ PARAM_LAYOUT_LEN = 59   # DRQ_PARAM_LAYOUT_LEN: the offsets drq_param_layout wri
 # the entries without a trailing drq_stream_t: they launch nothing, or their DrqStep carries the stream
 NO_STREAM = frozenset({"drq_abi_version", "drq_conv3x3_wgrad_ws_bytes", "drq_param_layout", "drq_step_ws_bytes",
                        "drq_step_ws_offset", "drq_update_phase", "drq_update_phase_overlap", "drq_update_phase_bc", "drq_update_phase_per",
-                       "drq_update_phase_frames", "drq_act_forward", "drq_act_ws_bytes"})
+                       "drq_update_phase_frames", "drq_act_forward", "drq_act_ws_bytes", "drq_explore_knn_ws_bytes"})
 
 _lib = None
 

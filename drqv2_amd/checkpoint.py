@@ -14,7 +14,8 @@ for a seed, so the state is all there is to keep:
   env        VecReach / VecPointMass.state_dict(): the task, action_repeat and the state words of every environment (seven;
              nine with the point mass's velocity); the frames are drawn again from them
   stats      VecEpisodeStats.state_dict(): the running returns and lengths, the totals and the log
-  bonus      SimHashBonus.state_dict() (optional, `bonus=`): the count table of the exploration bonus in sparse form
+  bonus      SimHashBonus.state_dict() (optional, `bonus=`): the count table of the exploration bonus in sparse form; or
+             KnnBonus.state_dict(): the live rows of its feature table, the row counter and its RandomState
   rng        torch.get_rng_state() and torch.cuda.get_rng_state(device): update()'s draws and act_batch()'s noise
 
         for step in range(start, steps):

@@ -711,8 +711,11 @@ class VecDeviceReplay:
         return int(int(batch_size) * self._demo_fraction + 0.5)
 
     def _batch(self, prioritized, idx, act, rew, disc):
-        """the indexed batch of a draw whose slots are idx [3][B]; its frames are the whole allocation"""
-        return (_PrioritizedIndexed if prioritized else IndexedBatch)(self._whole["frames"], idx[0], act, rew, disc, idx[1])
+        """the indexed batch of a draw whose slots are idx [3][B]; its frames are the whole allocation, `slots` the
+        position slots of its transitions (idx[2]: what explore.KnnBonus looks up)"""
+        batch = (_PrioritizedIndexed if prioritized else IndexedBatch)(self._whole["frames"], idx[0], act, rew, disc, idx[1])
+        batch.slots = idx[2]
+        return batch
 
     def __len__(self):
         """drawable transitions, reset rows included: rows x environments"""
@@ -1271,8 +1274,10 @@ class VecFrameReplay(VecDeviceReplay):
         return max(1, self.T - self.R + 1 + self.guard_rows + 2), self.T - self.nstep
 
     def _batch(self, prioritized, idx, act, rew, disc):
-        return (_PrioritizedFrames if prioritized else FrameBatch)(self.frames, idx[0], act, rew, disc, idx[1], self.first,
-                                                                   self.R, self.N)
+        batch = (_PrioritizedFrames if prioritized else FrameBatch)(self.frames, idx[0], act, rew, disc, idx[1], self.first,
+                                                                    self.R, self.N)
+        batch.slots = idx[2]
+        return batch
 
     def add(self, frame, action, reward, discount, first=None):
         """As VecDeviceReplay.add(), with frame uint8 [N, 3, 84, 84]: the newest frame of every environment after the

@@ -860,7 +860,44 @@ int drq_explore_simhash_step(const uint8_t* frame, long N, int bits, unsigned se
                              int* code_out, int* count_out, float* bonus_out, const float* reward, float* reward_out,
                              drq_stream_t stream);
 
-/* ---- distractions.  New functionality: the reference trains and evaluates on the clean frames of dm_control.  The
+/* ---- k-NN bonus.  New functionality: a novelty measure in feature space beside the count of "exploration bonus".  RE3
+ * (Seo et al., ICML 2021) pays log(1 + ||y - y_kNN||), y the features of a fixed random encoder, the neighbours looked
+ * up among the rows of the replay when a batch is drawn.  This is the hot part: for B drawn rows of a feature table, the
+ * distance to the k-th nearest other row, without the B x M matrix of distances ever existing.  These definitions are the
+ * contract; the result is exact to the bit.
+ * Inputs: table f32 [S][d], row-major, 1 <= d <= DRQ_KNN_MAX_DIM (64); live, 0 <= live <= S: only rows < live exist;
+ *   slots int64 [B]; k, 1 <= k <= DRQ_KNN_MAX_K (8); stride >= 1 and 0 <= offset < stride.  Output: dist f32 [B].
+ *   candidates  the rows c = offset + j * stride with c < live, for j = 0, 1, ...
+ *   query       for b with s = slots[b]:  s < 0 or s >= live:  dist[b] = 0 and no row is read for it.  Otherwise q = table[s].
+ *   distance    for every candidate c != s:  D(c): acc = 0;  for i = 0 .. d-1 in that order:  t = q[i] - x[i];  acc = acc + t * t
+ *               with x = table[c].  Every -, * and + is one float32 operation, rounded on its own; nothing is fused or
+ *               reassociated.  A D that is NaN counts as +infinity.
+ *   result      fewer than k candidates other than s:  dist[b] = 0.  Otherwise dist[b] = sqrtf(the k-th smallest D),
+ *               correctly rounded (+infinity where that D is).  Ties need no rule: a value is returned, not an index.
+ *   No row >= live is ever read, whatever it holds.  The row itself is excluded by its index, not by its distance: a
+ *   duplicate of the query elsewhere in the table is a neighbour at distance 0.
+ * drq_explore_knn: two launches on the stream.  Partial lists: a grid of G x ceil(B / 256) workgroups of 256 threads; a lane
+ *   owns a query (its row in registers) and the sorted list of its 8 smallest D; the candidates are dealt in chunks of
+ *   DRQ_KNN_CHUNK (128) rows, chunk ch to workgroup ch mod G, and staged in LDS once per 256 queries, where every lane of
+ *   a wave reads the same address; G = min(chunks, max(1, 512 / ceil(B / 256))).  Each lane writes its list to
+ *   ws [B][G][8].  Merge: one wave per query folds the G lists into one and stores the result.  D is exact, min and max
+ *   are exact, so the bits do not depend on G, on the dealing or on the order of anything; no atomics.  Writes every
+ *   element of dist and the first B G 8 floats of ws, nothing else.  With no candidate at all only the merge is launched.
+ *   drq_explore_knn_ws_bytes(B, live, stride): the bytes of ws that serve every offset (0 for arguments the entry refuses,
+ *   and for live = 0).
+ *   DRQ_EARG, nothing launched: a null table, slots or dist; S < 1; d < 1 or > 64; live < 0 or > S; B < 1 or
+ *   > DRQ_KNN_MAX_QUERIES (2^20); k < 1 or > 8; stride < 1; offset < 0 or >= stride; table or dist not 4-byte aligned,
+ *   slots not 8-byte aligned, ws not 16-byte aligned.  DRQ_EWS, nothing launched: candidates exist and ws is null or
+ *   ws_bytes < B G 32. */
+#define DRQ_KNN_MAX_DIM 64
+#define DRQ_KNN_MAX_K 8
+#define DRQ_KNN_CHUNK 128
+#define DRQ_KNN_MAX_QUERIES 1048576
+size_t drq_explore_knn_ws_bytes(long B, long live, long stride);
+int drq_explore_knn(const float* table, long S, int d, long live, const int64_t* slots, long B, int k, long stride,
+                    long offset, float* dist, float* ws, size_t ws_bytes, drq_stream_t stream);
+
+/* ---- distractions. New functionality: the reference trains and evaluates on the clean frames of dm_control.  The
  * Distracting Control Suite (Stone et al. 2021) and DMControl-GB (Hansen & Wang 2021) ask whether a pixel agent still
  * works when the image changes in ways that do not matter, and perturb exactly three things: the background, the colours
  * and the camera.  This applies the three to the frames of N lockstep environments as "device environment" writes them,

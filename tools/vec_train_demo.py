@@ -17,6 +17,7 @@ process: that is the baseline the training curve is read against, not a constant
                                  [--export-dir DIR] [--prefill-dir DIR]
                                  [--eval-every STEPS [--eval-episodes K] [--video DIR]]
                                  [--explore-beta B [--explore-bits K]]
+                                 [--explore-knn-beta B [--explore-knn-k 3] [--explore-knn-candidates M]]
                                  [--demos DIR [--demo-fraction 0.5] [--demo-rows D]]
                                  [--distract SPEC [--distract-on train|eval|both]]
                                  [--svea overlay|conv [--svea-alpha 0.5] [--svea-bank 64]]
@@ -60,6 +61,14 @@ statistics, and so every return that is printed, keep the environment's own rewa
 number of distinct codes counted so far, and the count table goes into the checkpoint.  Off by default, and the output is
 then unchanged.
 
+--explore-knn-beta B adds RE3's state-entropy bonus (drqv2_amd.explore.KnnBonus, INTEGRATION.md, "k-NN bonus (RE3)") to the
+reward of every batch as it is handed to update(): B * log(1 + the distance to the --explore-knn-k'th nearest neighbour,
+3 by default, among the rows the ring holds), in the 50 features of a fixed random encoder (RandomFeatures) computed from
+the observation after every add().  --explore-knn-candidates M looks at every ceil(live / M)'th row only.  The ring, the
+statistics and every printed return keep the environment's reward; the report line then ends with the mean distance of
+the newest batch, and the feature table goes into the checkpoint.  Not combined with --explore-beta (one bonus per
+checkpoint) or --prefill-dir (prefilled rows have no features).  Off by default, and the output is then unchanged.
+
 --demos DIR keeps the episodes of DIR (episode files, e.g. what --export-dir wrote) as demonstrations for the whole run
 and draws --demo-fraction of every batch from them (VecDeviceReplay(demo_rows=D), add_demonstrations(), demo_fraction;
 INTEGRATION.md, "Demonstrations").  Demonstrations need a ring of whole observations, so the loop then runs on a
@@ -102,7 +111,7 @@ from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch 
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
 from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach, VecReacher  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
-from drqv2_amd.explore import SimHashBonus  # noqa: E402
+from drqv2_amd.explore import KnnBonus, RandomFeatures, SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
 
 
@@ -195,6 +204,10 @@ def main():
     ap.add_argument("--explore-beta", type=float, default=0.0, metavar="B",
                     help="add the exploration bonus B / sqrt(count of the frame's SimHash code) to the ring's reward (0: off)")
     ap.add_argument("--explore-bits", type=int, default=None, metavar="K", help="bits of the SimHash code, 1 .. 24 (16)")
+    ap.add_argument("--explore-knn-beta", type=float, default=0.0, metavar="B",
+                    help="add B * log1p(distance to the k-th nearest neighbour in random features) to every batch's reward (0: off)")
+    ap.add_argument("--explore-knn-k", type=int, default=None, metavar="K", help="which neighbour, 1 .. 8 (3)")
+    ap.add_argument("--explore-knn-candidates", type=int, default=None, metavar="M", help="look at about M rows of the ring (all)")
     ap.add_argument("--demos", default=None, metavar="DIR", help="episode files kept as demonstrations for the whole run")
     ap.add_argument("--demo-fraction", type=float, default=0.5, metavar="F", help="share of every batch drawn from them")
     ap.add_argument("--demo-rows", type=int, default=None, metavar="D", help="rows of the partition (what DIR needs)")
@@ -227,6 +240,10 @@ def main():
         raise SystemExit("--demo-fraction and --demo-rows need --demos DIR")
     if args.explore_bits is not None and not args.explore_beta:
         raise SystemExit("--explore-bits needs --explore-beta B")
+    if not args.explore_knn_beta and (args.explore_knn_k is not None or args.explore_knn_candidates is not None):
+        raise SystemExit("--explore-knn-k and --explore-knn-candidates need --explore-knn-beta B")
+    if args.explore_knn_beta and (args.explore_beta or args.prefill_dir):
+        raise SystemExit("--explore-knn-beta does not combine with --explore-beta or --prefill-dir")
     if args.video and not args.eval_every:
         raise SystemExit("--video needs --eval-every STEPS")
     if (args.checkpoint_every or args.resume) and not args.checkpoint:
@@ -277,13 +294,32 @@ def main():
                 alpha=0.5 if args.svea_alpha is None else args.svea_alpha, device="cuda", seed=args.seed)
         except ValueError as err:
             raise SystemExit(f"--svea: {err}")
-        batches = SveaBatches(it, strong)
+        batches = SveaBatches(it, strong)      # (its inner iterator becomes the k-NN bonus's below, when there is one)
         print(f"svea: {args.svea}" + (f", alpha_q8 {strong.alpha_q8}, a bank of {strong.M} images" if args.svea == "overlay" else "")
               + f"; batches of {store.batch_size} drawn, {args.batch} rows per update", flush=True)
     bonus = SimHashBonus(N, "cuda", bits=args.explore_bits or 16, beta=args.explore_beta, seed=args.seed) \
         if args.explore_beta else None
     if bonus is not None:
         print(f"exploration bonus: beta {bonus.beta}, {bonus.bits} bits", flush=True)
+    knn = features = None
+    if args.explore_knn_beta:
+        try:
+            knn = KnnBonus(store, dim=50, k=args.explore_knn_k or 3, beta=args.explore_knn_beta,
+                           candidates=args.explore_knn_candidates, seed=args.seed)
+        except ValueError as err:
+            raise SystemExit(f"--explore-knn-beta: {err}")
+        features = RandomFeatures((9, 84, 84), 50, "cuda", seed=args.seed)
+        # the bonus is applied when a batch is handed out; the look-ahead stays the store iterator's own
+        if strong is not None:
+            batches.it = knn.batches(it)
+        else:
+            batches = knn.batches(it)
+        print(f"k-NN bonus: beta {knn.beta}, k {knn.k}, candidates {knn.candidates or 'all'}, {knn.dim} random features", flush=True)
+        plain_add = add_row
+
+        def add_row(*row):
+            plain_add(*row)
+            knn.observe(features(observe()))
     zeros_NA, zeros_N, ones_N = torch.zeros(N, A, device="cuda"), torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
 
     if args.eval_every:
@@ -297,7 +333,7 @@ def main():
 
     start, logged, updates, export_from = 0, 0, 0, None
     if args.resume:
-        extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus)
+        extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus or knn)
         start, logged, updates, export_from = extra["step"], extra["logged"], extra["updates"], extra.get("export_from")
         if strong is not None:
             if not isinstance(extra.get("svea"), dict):
@@ -348,7 +384,9 @@ def main():
             print(f"step {step + 1:6d}  updates {updates:6d}  episodes {snap.episodes:6d} (+{len(new) + missed})  mean return "
                   f"{mean}  mean length {length}  return per step "
                   f"{(new['return'].sum() / max(1, new['length'].sum())):.3f}  [{time.perf_counter() - t0:.1f} s]"
-                  + ("" if bonus is None else f"  distinct codes {int(bonus.distinct())}"), flush=True)
+                  + ("" if bonus is None else f"  distinct codes {int(bonus.distinct())}")
+                  + ("" if knn is None or knn.last_dist is None else f"  mean k-NN distance {float(knn.last_dist.mean()):.4f}"),
+                  flush=True)
             if args.export_dir:                                      # this WAITS as well
                 rep = store.export_episodes(args.export_dir, start_row=export_from)
                 export_from = rep.next_row
@@ -372,7 +410,7 @@ def main():
                 print(f"step {step + 1:6d}  eval: {len(video)} images of {video.image_shape[1]} x {video.image_shape[0]} -> {path} "
                       f"({size / 1e6:.2f} MB) [save {time.perf_counter() - ts:.2f} s]", flush=True)
         if args.checkpoint_every and (step + 1) % args.checkpoint_every == 0:    # the end of an iteration: this WAITS
-            checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus,
+            checkpoint.save(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus or knn,
                             extra=dict({"step": step + 1, "logged": logged, "updates": updates, "export_from": export_from},
                                        **({} if strong is None else {"svea": strong.state_dict()})))
     snap = stats.read()
