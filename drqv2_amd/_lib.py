@@ -122,6 +122,9 @@ PROTOTYPES = {
     "drq_vec_cartpole_render": (I, [P, L, P, P]),
     "drq_vec_reacher_step": (I, [P, P, P, P, P, L, I, P, C.c_uint, I, I, I, F, I, P, P, P, P, P, P]),
     "drq_vec_reacher_render": (I, [P, P, L, F, P, P]),
+    "drq_vec_maze_step": (I, [P, P, P, P, P, P, L, I, P, C.c_uint, I, I, I, I, I, I, C.c_uint, I, P, P, P, P, P, P]),
+    "drq_vec_maze_render": (I, [P, P, P, L, I, P, P]),
+    "drq_vec_maze_geodesic": (I, [P, P, P, L, I, P, P]),
     "drq_explore_simhash_step": (I, [P, L, I, C.c_uint, F, I, P, P, P, P, P, P, P]),
     "drq_explore_knn_ws_bytes": (SZ, [L, L, L]),
     "drq_explore_knn": (I, [P, L, I, L, P, L, I, L, L, P, P, SZ, P]),

@@ -21,6 +21,13 @@ shoulder and the elbow, in the image of the reference's reacher_easy and reacher
 reward, 1 while the fingertip is inside the target disc and 0 otherwise, which is what the exploration bonus, the
 demonstrations, prioritized replay and the DrM blocks are for.  Specified in include/drqv2_hip.h ("Reacher"), restated by
 tests/vec_reacher_oracle.py.
+
+VecMaze is a fifth (csrc/vecmaze.hip, drq_vec_maze_step): a point in a square that walls cut into size x size cells must find
+the goal cell.  The walls are generated on the device at every reset -- a binary-tree maze put through one of the 8
+symmetries of the square, with loops opened on request -- fresh per episode or from a finite pool of `layouts` mazes that
+`layout_seed` names, so a user trains on K layouts and evaluates on others.  The reward sits behind walls: it is the task
+the exploration bonuses are for, and the one whose dynamics differ between episodes.  Specified in include/drqv2_hip.h
+("Maze"), restated by tests/vec_maze_oracle.py.
 """
 import torch
 
@@ -353,3 +360,91 @@ class VecReacher(_VecTask):
 
     def _config(self):
         return dict(super()._config(), target_radius=self.target_radius, sparse=self.sparse)
+
+
+class VecMaze(_VecTask):
+    """N environments of the maze on the device: the world [-1, 1]^2 is cut into size x size cells (size 3, 4, 6, 7 or 8),
+    and action[:, :2] in [-1, 1] moves a point by up to 0.05 per axis and simulator step (NaN counts as 0; further columns
+    are ignored), x first, then y.  A move towards a wall or the boundary stops 0.04 in front of it; no wall is crossed
+    and no corner is cut.  sparse=True pays 1 for every simulator step that ends in the goal cell and 0 otherwise;
+    sparse=False pays (size^2 - d) / size^2 of the geodesic distance d in cells instead, a dense shaping for debugging and
+    as the comparison arm of a demo.  The rule is in include/drqv2_hip.h ("Maze") to the bit and restated by
+    tests/vec_maze_oracle.py.
+
+        env = VecMaze(num_envs=N, device="cuda", action_dim=2, episode_length=200, seed=0, action_repeat=1, size=6,
+                      loops=0, layouts=0, layout_seed=0, sparse=True)
+
+    A reset draws the start cell, the goal cell (another one) and the walls, all on the device from a hash of (seed,
+    environment, episode): a spanning tree of the cells (connected by construction, size^2 - 1 open sides), one of the 8
+    symmetries of the square, and with loops = 1 .. 254 every wall still closed opened with probability loops / 256
+    (loops = 255 opens every wall: an empty room).
+    layouts = 0 generates a fresh maze every episode; layouts = K (up to 65,535) draws one of K mazes per episode, which
+    (layout_seed, index) name and all environments share -- another layout_seed is another pool, so
+
+        train = VecMaze(N, "cuda", layouts=16, layout_seed=0)
+        held_out = VecMaze(N, "cuda", layouts=16, layout_seed=1, seed=1)
+
+    differ in the mazes and in nothing else.  Start and goal are always drawn per episode.
+
+    The discount is 1 on every row and only the time limit (t == episode_length, in simulator steps) ends an episode, so a
+    macro step's sparse reward is an exact small integer.  The frame shows the goal cell (a green inset square), the
+    walls (white) and the agent (a magenta disc) over the ramp every task here draws.  geodesic() is the length in cells
+    of the shortest path that is left, for an evaluation to report beside the return.  Same methods and guarantees as
+    VecReach (_VecTask holds them).  The state words are "pos", float32 [N, 2]; "walls", int64 [N, 2] = the east and the
+    south board, cell (r, c) bit 8 r + c, read as unsigned on the device; "cells", int32 [N, 2] = start and goal, each
+    8 r + c; and t, episode, over.  The walls are state, so a checkpoint does not depend on the generator; the config of a
+    state dict carries size, loops, layouts, layout_seed and sparse."""
+    TASK = "maze"
+    _STATE = ("pos", "walls", "cells", "t", "episode", "over")
+    _STATE_SPEC = dict(_VecTask._STATE_SPEC, walls=((2,), torch.int64), cells=((2,), torch.int32))
+    SIZES = (3, 4, 6, 7, 8)
+    MAX_LOOPS, MAX_LAYOUTS = 255, 65535
+
+    def __init__(self, num_envs, device, action_dim=2, episode_length=200, seed=0, action_repeat=1, size=6, loops=0,
+                 layouts=0, layout_seed=0, sparse=True):
+        def whole(v):
+            return isinstance(v, int) and not isinstance(v, bool)
+        if not whole(size) or size not in self.SIZES:
+            raise ValueError(f"size must be one of {self.SIZES}, got {size!r}")
+        if not whole(loops) or not 0 <= loops <= self.MAX_LOOPS:
+            raise ValueError(f"loops must be an int in 0 .. {self.MAX_LOOPS}, got {loops!r}")
+        if not whole(layouts) or not 0 <= layouts <= self.MAX_LAYOUTS:
+            raise ValueError(f"layouts must be an int in 0 .. {self.MAX_LAYOUTS}, got {layouts!r}")
+        if not whole(layout_seed):
+            raise ValueError(f"layout_seed must be an int, got {layout_seed!r}")
+        if not isinstance(sparse, (bool, int)) or sparse not in (0, 1):
+            raise ValueError(f"sparse must be True or False, got {sparse!r}")
+        self.size, self.loops, self.layouts = size, loops, layouts
+        self.layout_seed, self.sparse = layout_seed & 0xFFFFFFFF, bool(sparse)
+        super().__init__(num_envs, device, action_dim, episode_length, seed, action_repeat)
+        self._geodesic = None       # two int32 [N] buffers used in turn, then the index of the next
+
+    def _step_launch(self, action, reset_all, out):
+        launch("drq_vec_maze_step", ptr(self.pos), ptr(self.walls), ptr(self.cells), ptr(self.t), ptr(self.episode),
+               ptr(self.over), self.N, self.A, ptr(action), self.seed, self.episode_length, self.action_repeat,
+               int(reset_all), self.size, self.loops, self.layouts, self.layout_seed, int(self.sparse),
+               *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        launch("drq_vec_maze_render", ptr(self.pos), ptr(self.walls), ptr(self.cells), self.N, self.size, ptr(frame),
+               device=self.device)
+
+    def geodesic(self):
+        """The geodesic distance in cells from the cell every agent is in to its goal cell, int32 [N] on the device: the
+        flood fill of the reward, one launch (drq_vec_maze_geodesic), nothing waits.  After reset() it is the length of
+        the optimal path of the episode; size^2 where walls written through load_state_dict() cut the goal off.  Two
+        buffers are used in turn, like the output sets."""
+        self._on_gpu()
+        if self._frame is None:
+            raise _lib.DrqError("geodesic(): call reset() or load_state_dict() first")
+        if self._geodesic is None:
+            self._geodesic = [torch.empty(self.N, dtype=torch.int32, device=self.device) for _ in range(2)] + [0]
+        out = self._geodesic[self._geodesic[2]]
+        self._geodesic[2] ^= 1
+        launch("drq_vec_maze_geodesic", ptr(self.walls), ptr(self.cells), ptr(self.pos), self.N, self.size, ptr(out),
+               device=self.device)
+        return out
+
+    def _config(self):
+        return dict(super()._config(), size=self.size, loops=self.loops, layouts=self.layouts,
+                    layout_seed=self.layout_seed, sparse=self.sparse)

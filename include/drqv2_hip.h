@@ -820,6 +820,97 @@ int drq_vec_reacher_step(float* phys, float* target, int* t, unsigned* episode, 
 int drq_vec_reacher_render(const float* phys, const float* target, long N, float target_radius, uint8_t* frame,
                            drq_stream_t stream);
 
+/* Maze.  A fifth task of the device environment, with entries of its own: a point in the square [-1, 1]^2, which walls cut
+ * into G x G cells, must find the goal cell.  The walls are generated on the device for every episode, fresh or from a
+ * finite pool of layouts, so the world itself differs between episodes and a reward sits behind walls.  These
+ * definitions are the contract; they are exact to the bit.  The generator, the flood fill, the sparse reward and the frame
+ * are integer arithmetic; every float operation below is ONE IEEE float32 operation (+, -, *, a compare or floorf; the
+ * dense reward has the one correctly rounded division), in the written order, never fused.
+ * Geometry.  G = size is 3, 4, 6, 7 or 8: the sizes that divide the 1344 sixteenths of a pixel of a frame side.  Cell
+ *   (r, c), row 0 at the top of the frame (y = 1), column 0 at the left (x = -1), is bit 8 r + c of a 64-bit board, stride 8
+ *   whatever G is.  The walls are two boards: east, bit (r, c) set = a wall between (r, c) and (r, c + 1), c <= G - 2;
+ *   south, bit (r, c) set = a wall between (r, c) and (r + 1, c), r <= G - 2.  The outer boundary is always wall; bits
+ *   outside these ranges are 0 as generated and are ignored when read.
+ *   hg = G * 0.5f (exact);  cw = 2 / G rounded once: 0.6666667f, 0.5f, 0.33333334f, 0.2857143f, 0.25f.
+ *   col(x) = clamp((int)floorf((x + 1) * hg), 0, G - 1);  row(y) = clamp((int)floorf((1 - y) * hg), 0, G - 1);
+ *   cell(pos) = 8 * row(y) + col(x).
+ * State per environment e: pos f32 [N][2]; walls u64 [N][2] = (east, south); cells i32 [N][2] = (start, goal), each
+ *   8 r + c; t i32 [N], episode u32 [N], over u8 [N] as above.  The walls are state: nothing re-derives them.
+ * The integer draw k of (s, e, episode):  h_k = fmix32(s ^ e * 0x9E3779B9 ^ episode * 0x85EBCA6B ^ k * 0xC2B2AE35), the
+ *   integer behind the draws v_k above.
+ * walls(s, e, episode), the generator:
+ *   every interior wall closed; then every cell but (0, G - 1) opens one passage, to the north or to the east: a cell of
+ *   row 0 to the east, a cell of column G - 1 to the north, any other cell (r, c) to the north when bit 8 r + c of the
+ *   64-bit word (h_4 << 32 | h_3) is set and to the east when it is clear.  (The binary tree: G * G - 1 open sides, every
+ *   cell connected to the top-right corner.)
+ *   then the symmetry sym = h_5 & 7, applied to the maze as a set of walls between cells, in this order:
+ *     sym & 1: the transpose, (r, c) -> (c, r);  sym & 2: the columns mirrored, (r, c) -> (r, G - 1 - c);
+ *     sym & 4: the rows mirrored, (r, c) -> (G - 1 - r, c)
+ *   then, for loops > 0, every wall still closed is opened when (h_k & 255) < loops, with k = 16 + 8 r + c for the east
+ *   wall of (r, c) and k = 80 + 8 r + c for its south wall, (r, c) in the board after the symmetry.  loops = 255 opens
+ *   every wall, whatever its draw: the one value for which the comparison is not the whole rule.
+ * Reset of e (reset_all = 1, or over[e] == 1): episode += 1 (mod 2^32), t = 0, over = 0; with the draws of (seed, e, episode):
+ *   i0 = h_0 mod G * G;  i1 = h_1 mod G * G;  i1 == i0: i1 = (i1 + 1) mod G * G;  a linear index i is the cell (i / G, i mod G);
+ *   start = cell i0, goal = cell i1;
+ *   layouts = 0: (east, south) = walls(seed, e, episode);  layouts = K > 0: (east, south) = walls(layout_seed, 0, h_2 mod K)
+ *   pos, the centre of the start cell (r, c):  x = ((float)c + 0.5f) * cw - 1;  y = 1 - ((float)r + 0.5f) * cw
+ *   Outputs first = 1, reward = 0, discount = 1, substeps = 0, the frame of the new state.  The action is not read.
+ * Sub-step, (ax, ay) the sanitised action (action[e][0 .. 1], each NaN to 0, then the clamp to [-1, 1]; columns 2 .. A-1
+ *   are not read).  x moves first, in the cell the point is in; then the cell is taken again and y moves:
+ *   move(p, d, wall_hi, edge_hi, wall_lo, edge_lo):  n = p + d;
+ *     d > 0 and wall_hi:  lim = edge_hi - 0.04f;  lim < p: lim = p;  n > lim: n = lim
+ *     d < 0 and wall_lo:  lim = edge_lo + 0.04f;  lim > p: lim = p;  n < lim: n = lim           (an open side does not clamp)
+ *   c = col(x), r = row(y);  x = move(x, ax * 0.05f, c == G - 1 or east bit (r, c), (float)(c + 1) * cw - 1,
+ *                                                      c == 0 or east bit (r, c - 1), (float)c * cw - 1)
+ *   c = col(x), r = row(y);  y = move(y, ay * 0.05f, r == 0 or south bit (r - 1, c), 1 - (float)r * cw,
+ *                                                      r == G - 1 or south bit (r, c), 1 - (float)(r + 1) * cw)
+ *   A move is along one axis inside one row or column and 0.05 is less than a cell minus both margins, so no wall is
+ *   crossed and no corner is cut: a move keeps the cell or enters the neighbour behind an open side.
+ *   t += 1;  over = 1 only when t == episode_length;  d_i = 1 always: the task never ends an episode itself.
+ *   Reward r_i of the new state:  sparse:  r_i = cell(pos) == goal ? 1 : 0, a compare of integers;
+ *   dense:  r_i = (float)(G * G - d) / (float)(G * G), d = geodesic(cell(pos), goal).
+ * geodesic(from, to), a flood fill on the boards:  reach = the bit of `from`;  d = 0;  while the bit of `to` is not in reach:
+ *   reach = reach | the cells east, west, south and north of a cell of reach through an open side (all four from the
+ *   old reach);  d += 1;  a fill that stops growing before it covers `to` gives d = G * G (only walls written by a
+ *   caller can cut a cell off).  Cells are taken & 63.
+ * Macro step: the one of "Tasks and action repeat" with every d_i = 1: reward = reward + r_i for up to `repeat` sub-steps,
+ *   stopping after the one that set over; discount = 1, first = 0, substeps = the sub-steps executed.  In the sparse form
+ *   the reward is an exact small integer, 0 .. repeat.
+ * Frame of a state, u8 [3][84][84].  Coordinates are integers in 1/16 pixel, y downwards; pixel (i, j) has its centre at
+ *   P = (16 j + 8, 16 i + 8);  W = 1344 / G is a cell's side, cell (r, c) the square [c W, (c + 1) W] x [r W, (r + 1) W].
+ *   Per pixel, later rules drawn over earlier:
+ *   background 32 + ((i + j) >> 2) in all three channels;
+ *   the goal cell (r, c), an inset square:  c W + W / 4 <= P.x < (c + 1) W - W / 4 and likewise P.y with r, in (64, 255, 64);
+ *   the walls, in (255, 255, 255): P within 12 in both coordinates of the nearest point of a closed segment -- for the wall
+ *     east of (r, c), x = (c + 1) W and r W <= y <= (r + 1) W:  |P.x - (c + 1) W| <= 12 and r W - 12 <= P.y <= (r + 1) W + 12;
+ *     for the wall south of (r, c) likewise with the axes exchanged; the four sides of the boundary are closed segments;
+ *   the agent, |P - A|^2 <= 729 (a radius of 0.04), in (255, 64, 255), with each coordinate rounded once:
+ *     A.x = (int)floorf(x * 672 + 672.5f);  A.y = (int)floorf(672.5f - y * 672)
+ *   A pixel holds 32 .. 73, 64 or 255.
+ *
+ * drq_vec_maze_step: one launch, N workgroups of 256 threads with the shape of drq_vec_cartpole_step; every lane computes
+ *   the reset or the macro step in registers.  Writes every byte of frame, reward, discount, first, substeps and the
+ *   state (pos, walls, cells), nothing else.  No LDS, no atomics.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 2, repeat < 1
+ *   or > DRQ_TASK_MAX_REPEAT, episode_length < 1, reset_all or sparse not 0 or 1, size not 3, 4, 6, 7 or 8, loops outside
+ *   0 .. 255, layouts outside 0 .. 65535, frame not 16-byte aligned, walls not 8-byte aligned, a float / int array not
+ *   4-byte aligned.
+ * drq_vec_maze_render: the frames of the states as they are, by the frame rule above (the same device function): every
+ *   byte of frame, nothing else; the state is only read.  DRQ_EARG, nothing launched: a null pointer, N < 1 or
+ *   > INT32_MAX, size as for the step, frame not 16-byte aligned, walls not 8-byte aligned, pos or cells not 4-byte aligned.
+ * drq_vec_maze_geodesic: out i32 [N] = geodesic(cell(pos), goal) per environment -- the length of the shortest path that is
+ *   left, for an evaluation to report beside the return.  One launch, one lane per environment; the state is only read.
+ *   DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX, size as for the step, walls not 8-byte aligned,
+ *   pos, cells or out not 4-byte aligned. */
+int drq_vec_maze_step(float* pos, uint64_t* walls, int* cells, int* t, unsigned* episode, uint8_t* over, long N, int A,
+                      const float* action, unsigned seed, int episode_length, int repeat, int reset_all, int size,
+                      int loops, int layouts, unsigned layout_seed, int sparse, uint8_t* frame, float* reward,
+                      float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
+int drq_vec_maze_render(const float* pos, const uint64_t* walls, const int* cells, long N, int size, uint8_t* frame,
+                        drq_stream_t stream);
+int drq_vec_maze_geodesic(const uint64_t* walls, const int* cells, const float* pos, long N, int size, int* out,
+                          drq_stream_t stream);
+
 /* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
  * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
  * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep

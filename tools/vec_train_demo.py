@@ -1,6 +1,6 @@
 """The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
 
-  VecReach, VecPointMass, VecCartpole or VecReacher (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecReach, VecPointMass, VecCartpole, VecReacher or VecMaze (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
   VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
 
 Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
@@ -8,8 +8,9 @@ return (and length) of the episodes that finished in every interval, from VecEpi
 uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard]
+  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small]
                                  [--reward sparse|dense] [--action-repeat 1]
+                                 [--maze-layouts K] [--maze-loops Q] [--maze-eval-layout-seed S]
                                  [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
                                  [--batch 256] [--lr 3e-4] [--feature-dim 50] [--hidden-dim 256] [--seed 0]
                                  [--checkpoint PATH [--checkpoint-every STEPS] [--resume]]
@@ -29,6 +30,13 @@ process: that is the baseline the training curve is read against, not a constant
 sparse: 1 for every simulator step with the fingertip inside the target's disc, else 0 (the reference configures episodes of
 1,000 simulator steps for its reachers); --reward dense swaps in VecReacher's dense shaping of the same distance, the
 comparison arm;
+--task maze and maze_small train on VecMaze (size 6 / 4): walls generated on the device at every reset, 1 for every simulator
+step in the goal cell, else 0; --reward dense swaps in the shaping by the geodesic distance.  --maze-layouts K draws every
+episode's walls from a pool of K mazes (0, the default: a fresh maze per episode), --maze-loops Q opens every remaining
+wall with probability Q / 256.  --maze-eval-layout-seed S builds the evaluation environment with layout_seed=S, another
+pool of the same size (the training pool is layout_seed 0): the evaluation lines are then held-out returns, and the
+report ends with the mean return of the last training interval beside the last held-out one.  It needs --maze-layouts K
+and --eval-every STEPS;
 --action-repeat K holds every action for up to K simulator steps inside the step launch.  All of these apply to the training
 environment, the evaluation environment and the random baseline alike.  --episode-length counts simulator steps; the
 lengths that are printed count rows, i.e. agent steps.
@@ -109,7 +117,7 @@ import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch  # noqa: E402
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
-from drqv2_amd.envs import VecCartpole, VecPointMass, VecReach, VecReacher  # noqa: E402
+from drqv2_amd.envs import VecCartpole, VecMaze, VecPointMass, VecReach, VecReacher  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import KnnBonus, RandomFeatures, SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
@@ -117,13 +125,16 @@ from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  #
 
 TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_balance": (VecCartpole, {"swing_up": False}),
          "cartpole_swingup": (VecCartpole, {"swing_up": True}), "reacher_easy": (VecReacher, {"target_radius": 0.15}),
-         "reacher_hard": (VecReacher, {"target_radius": 0.05})}
-REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: VecReacher's two forms
+         "reacher_hard": (VecReacher, {"target_radius": 0.05}), "maze": (VecMaze, {"size": 6}), "maze_small": (VecMaze, {"size": 4})}
+REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: the two forms of VecReacher and VecMaze
 
 
 def make_env(args, seed, role="train"):
     """the environment of a role ("train": training and the random baseline; "eval"), distracted when --distract-on says so"""
     cls, more = TASKS[args.task]
+    if cls is VecMaze:      # the pool of layouts: the evaluation's is another one under --maze-eval-layout-seed
+        held_out = role == "eval" and args.maze_eval_layout_seed is not None
+        more = dict(more, layouts=args.maze_layouts, loops=args.maze_loops, layout_seed=args.maze_eval_layout_seed if held_out else 0)
     env = cls(args.envs, "cuda", action_dim=args.action_dim, episode_length=args.episode_length, seed=seed,
               action_repeat=args.action_repeat, **more, **REWARDS[args.reward])
     if args.distract and args.distract_on in (role, "both"):
@@ -171,7 +182,11 @@ def random_baseline(args, episodes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=sorted(TASKS), default="reach")
-    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher tasks (sparse)")
+    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher and maze tasks (sparse)")
+    ap.add_argument("--maze-layouts", type=int, default=0, metavar="K", help="the mazes come from a pool of K layouts (0: a fresh maze per episode)")
+    ap.add_argument("--maze-loops", type=int, default=0, metavar="Q", help="open every remaining wall with probability Q / 256, 0 .. 255")
+    ap.add_argument("--maze-eval-layout-seed", type=int, default=None, metavar="S",
+                    help="evaluate on the pool of layout_seed S (training uses 0): held-out mazes")
     ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per action, 1 .. 16")
     ap.add_argument("--steps", type=int, default=20000, help="environment steps (each of all N environments)")
     ap.add_argument("--envs", type=int, default=16)
@@ -218,8 +233,14 @@ def main():
     ap.add_argument("--svea-alpha", type=float, default=None, metavar="A", help="weight of the overlaid image, 0 .. 1 (0.5)")
     ap.add_argument("--svea-bank", type=int, default=None, metavar="M", help="images of the procedural overlay bank (64)")
     args = ap.parse_args()
-    if args.reward and TASKS[args.task][0] is not VecReacher:
-        raise SystemExit("--reward needs --task reacher_easy or reacher_hard")
+    if args.reward and TASKS[args.task][0] not in (VecReacher, VecMaze):
+        raise SystemExit("--reward needs --task reacher_easy, reacher_hard, maze or maze_small")
+    if TASKS[args.task][0] is not VecMaze and (args.maze_layouts or args.maze_loops or args.maze_eval_layout_seed is not None):
+        raise SystemExit("--maze-layouts, --maze-loops and --maze-eval-layout-seed need --task maze or maze_small")
+    if not 0 <= args.maze_layouts <= VecMaze.MAX_LAYOUTS or not 0 <= args.maze_loops <= VecMaze.MAX_LOOPS:
+        raise SystemExit(f"--maze-layouts is 0 .. {VecMaze.MAX_LAYOUTS}, --maze-loops 0 .. {VecMaze.MAX_LOOPS}")
+    if args.maze_eval_layout_seed is not None and not (args.maze_layouts and args.eval_every):
+        raise SystemExit("--maze-eval-layout-seed needs --maze-layouts K and --eval-every STEPS")
     if args.distract_on and not args.distract:
         raise SystemExit("--distract-on needs --distract SPEC")
     if args.distract:
@@ -332,6 +353,7 @@ def main():
             video = VecVideo(N, "cuda", max_frames=K * (args.episode_length + 1) + 51)    # evaluate()'s max_steps, and row 0
 
     start, logged, updates, export_from = 0, 0, 0, None
+    last_train = last_eval = None      # the newest interval's mean training return and the newest evaluation's, for the maze's report
     if args.resume:
         extra = checkpoint.load(args.checkpoint, agent=agent, store=store, iterator=it, env=env, stats=stats, bonus=bonus or knn)
         start, logged, updates, export_from = extra["step"], extra["logged"], extra["updates"], extra.get("export_from")
@@ -380,6 +402,7 @@ def main():
             new, missed = snap.since(logged)
             logged = snap.episodes
             mean = f"{new['return'].mean():7.3f}" if len(new) else "    n/a"
+            last_train = float(new["return"].mean()) if len(new) else last_train
             length = f"{new['length'].mean():5.1f}" if len(new) else "  n/a"
             print(f"step {step + 1:6d}  updates {updates:6d}  episodes {snap.episodes:6d} (+{len(new) + missed})  mean return "
                   f"{mean}  mean length {length}  return per step "
@@ -399,6 +422,7 @@ def main():
             te = time.perf_counter()
             res = evaluate(agent, eval_env, K, step, stats=eval_stats, stack=eval_stack, video=video)
             rec = res.snapshot.records
+            last_eval = res.snapshot.mean_return
             print(f"step {step + 1:6d}  eval: {res.snapshot.episodes} episodes ({K} per environment) in {res.steps} steps: mean "
                   f"return {res.snapshot.mean_return:7.3f}  min {res.snapshot.min_return:7.3f}  max "
                   f"{res.snapshot.max_return:7.3f}  mean length {rec['length'].mean():5.1f}  "
@@ -419,6 +443,9 @@ def main():
     print(f"trained: {snap.episodes} episodes in {snap.rows - 1} steps x {N} environments, mean return over all of them "
           f"{snap.mean_return:.3f}, mean length {snap.mean_length:.1f}; {wall:.1f} s, {1e3 * wall / max(1, args.steps - start):.2f} ms per step",
           flush=True)
+    if args.maze_eval_layout_seed is not None and last_train is not None and last_eval is not None:
+        print(f"maze: {args.maze_layouts} training layouts (layout_seed 0): mean return of the last interval {last_train:.3f}; "
+              f"held-out layouts (layout_seed {args.maze_eval_layout_seed}): mean return of the last evaluation {last_eval:.3f}", flush=True)
     b_ret, b_len, b_steps = random_baseline(args, snap.episodes)
     print(f"baseline: uniform-random actions, the first {snap.episodes} episodes ({b_steps} steps): mean return {b_ret:.3f}, "
           f"mean length {b_len:.1f}, return per step {b_ret / b_len:.3f}", flush=True)
