@@ -159,7 +159,9 @@ PROTOTYPES = {
 }
 
 WS_IDS = ["AUG", "ACT1", "ACT2", "ACT3", "FEAT", "Z_NEXT", "Z_OBS", "HA_T", "HA_C", "H_AN", "H_AO", "Q", "TQ",
-          "DQ", "MU_O", "DY4", "DY3", "DY2", "DY1", "DZ_C", "DZ_A", "HA_C2", "P1", "P2", "C1", "C2"]
+          "DQ", "MU_O", "DY4", "DY3", "DY2", "DY1", "DZ_C", "DZ_A", "HA_C2", "P1", "P2", "C1", "C2",
+          "XHAT_C", "RSTD_C", "XHAT_A", "RSTD_A", "Z_C2", "HROWS", "P3", "Z4", "T1", "T2", "DC2", "DC1", "DHA", "DLN",
+          "DPRE", "DP2", "DP1", "DH_A", "DA"]
 
 # ids of drq_update_phase (the DRQ_PHASE_* enum of include/drqv2_hip.h, where each is described)
 PHASE_ALL, PHASE_CRITIC, PHASE_ACTOR, PHASE_OPT = -1, 0, 1, 2

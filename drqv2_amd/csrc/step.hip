@@ -5,6 +5,7 @@
 // events per device, created on first use.
 #include "common.h"
 #include "internal.h"
+#include "step_plan.h"
 #include "../../include/drqv2_hip.h"
 #include <mutex>
 
@@ -95,11 +96,13 @@ enum {
   W_DZ_C = DRQ_WS_DZ_C, W_DZ_A = DRQ_WS_DZ_A, W_HA_C2 = DRQ_WS_HA_C2,
   W_P1 = DRQ_WS_P1, W_P2 = DRQ_WS_P2,             // policy activations over 2B rows (obs, next)
   W_C1 = DRQ_WS_C1, W_C2 = DRQ_WS_C2,             // critic-Q hidden activations
-  W_XHAT_C = DRQ_WS_NBUF_PUBLIC, W_RSTD_C, W_XHAT_A, W_RSTD_A, W_Z_C2,
-  W_HROWS, W_P3, W_Z4,                            // actor trunk output / policy output over 2B rows
-  W_T1, W_T2,                                     // target-Q hidden activations, reused by the actor step
-  W_DC2, W_DC1, W_DHA, W_DLN, W_DPRE, W_DP2, W_DP1, W_DH_A, W_DA,
-  W_GEMM_WS, W_CONV_WS,
+  W_XHAT_C = DRQ_WS_XHAT_C, W_RSTD_C = DRQ_WS_RSTD_C, W_XHAT_A = DRQ_WS_XHAT_A, W_RSTD_A = DRQ_WS_RSTD_A,
+  W_Z_C2 = DRQ_WS_Z_C2,
+  W_HROWS = DRQ_WS_HROWS, W_P3 = DRQ_WS_P3, W_Z4 = DRQ_WS_Z4,   // actor trunk output / policy output over 2B rows
+  W_T1 = DRQ_WS_T1, W_T2 = DRQ_WS_T2,             // target-Q hidden activations, reused by the actor step
+  W_DC2 = DRQ_WS_DC2, W_DC1 = DRQ_WS_DC1, W_DHA = DRQ_WS_DHA, W_DLN = DRQ_WS_DLN, W_DPRE = DRQ_WS_DPRE,
+  W_DP2 = DRQ_WS_DP2, W_DP1 = DRQ_WS_DP1, W_DH_A = DRQ_WS_DH_A, W_DA = DRQ_WS_DA,
+  W_GEMM_WS = DRQ_WS_NBUF_PUBLIC, W_CONV_WS,      // these three stay private: drq_step_ws_offset does not serve them
   W_WINO_U,                                       // six Winograd weight images of the update: [layer 2..4][fwd, dgrad][16384]
   W_COUNT
 };
@@ -198,17 +201,11 @@ struct Ctx {
   const uint8_t* ring_first = nullptr;
   long ring_R = 0, ring_N = 0;
   // B rows fit the LDS of the Q-output backward kernels that compute a loss as well (drq_qout_bwd_td / _actor)
-  bool qout_loss_fits_lds() const { return ((size_t)s->B + 5 * 1024 + 16) * 4 <= 60 * 1024; }
+  bool qout_loss_fits_lds() const { return step_qout_loss_fits_lds(s->B); }
   bool actor_loss_fused() const { return fuse_actor_loss && qout_loss_fits_lds(); }
   // row-local stages fused with the first MLP layers (rowblock.hip): fp32, shapes its kernels take
-  bool fuse_rows() const {
-    // measured (tools/ab_flags.py, same process, interleaved): cheetah_run B=256 1021.9 us fused against 1024.2, but
-    // humanoid_run (F+A = 121: odd, dword weight loads, 128-long padded reduction) 540 against 508 us at B=32 and 1220
-    // against 1203 at B=256 -- the fused kernels are chains of dependent memory round trips like the launches they
-    // replace, and only win where every weight row can be fetched with 8- or 16-byte loads into a 64-long reduction
-    return !(s->flags & DRQ_STEP_NO_ROW_FUSION) && !s->bf16 && s->A <= 32 && s->F + s->A <= 64 && s->F % 2 == 0 &&
-           s->A % 2 == 0 && s->H % 256 == 0;
-  }
+  // (the predicates of this section live in step_plan.h, where a CPU test can see them)
+  bool fuse_rows() const { return step_fuse_rows(s->A, s->F, s->H, s->bf16, s->flags); }
   bool use_gemm3() const { return !(s->flags & DRQ_STEP_NO_GEMM3) && !s->bf16; }
   // slot idx of DrqStep.timing_events (bench.py's roofline), recorded when the host asked for that many
   int stamp(int idx) const {
@@ -285,7 +282,7 @@ struct Ctx {
   // The trunk's weight gradient dW = dz^T feat (+ bias gradient) with the LayerNorm parameter gradients of the same
   // trunk riding in the launch (one extra workgroup) when the dedicated kernel takes the shape; `ride` says whether
   // the LayerNorm backward left them out (ln_rides()).
-  bool ln_rides() const { return !bf16() && s->F <= 128 && (s->B == 128 || s->B == 256 || s->B == 512); }
+  bool ln_rides() const { return step_ln_rides(s->B, s->F, bf16()); }
   int trunk_wgrad(const float* dz, const float* feat, float* gw, float* gb, bool ride, const float* dln,
                   const float* xhat, float* dgamma, float* dbeta) const {
     const int B = s->B, F = s->F;
@@ -351,7 +348,7 @@ int policy_forward(const Ctx& c, const float* h, int rows, float* p1, float* p2,
   float *y0[1] = {p1}, *y1[1] = {p2}, *y2[1] = {p3};
   CK(c.fwd(1, x0, F, w0, b0, y0, H, rows, H, F, 1));
   CK(c.fwd(1, x1, H, w1, b1, y1, H, rows, H, H, 1));
-  if (A <= 64) {
+  if (step_out_layer_kernel(A)) {
     CK(drq_policy_out_fwd(p2, w2[0], b2[0], p3, rows, H, A, sample_from >= 0 ? noise : nullptr, s->std, s->clip, 1,
                           sample_from >= 0 ? sample_from : 0, nullptr, a_out, lda_out,
                           sample_from > 0 ? noise0 : nullptr, mu_out0, a_out0, lda_out0, c.st));
@@ -448,7 +445,7 @@ int phase_critic_heads(const Ctx& c) {
     // the critic's [h, action] input: the action columns ride along with problem 0 (drqv2.py:106)
     const float* tail[4] = {s->action, nullptr, nullptr, nullptr};
     const int tld[4] = {A, 0, 0, 0};
-    const bool with_tail = A <= 64;
+    const bool with_tail = step_out_layer_kernel(A);
     if (c.fuse_rows() && sk > 1) {
       // ... and the first layers ride along with the LayerNorm: both Q heads of the critic on [h, action], the policy's
       // first layer on the actor's 2B rows (rowblock.hip; one launch instead of three)
@@ -711,7 +708,7 @@ int phase_actor_backward(const Ctx& c) {
   const long BH = (long)B * H;
 
   // output layer backward in one kernel (dpre, dW3, db3, dp2) when dpre fits its LDS
-  const bool fused_head = A <= 32 && ((size_t)B * A + 4 * 1024) * 4 <= 60 * 1024;
+  const bool fused_head = step_fused_head(B, A);
   int sk_da = 1;
   // backward through the critic to the action only (critic weight grads are never used: SURVEY A7(iii))
   {

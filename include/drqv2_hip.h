@@ -1311,6 +1311,21 @@ enum {
   DRQ_WS_DY4, DRQ_WS_DY3, DRQ_WS_DY2, DRQ_WS_DY1, DRQ_WS_DZ_C, DRQ_WS_DZ_A, DRQ_WS_HA_C2,
   DRQ_WS_P1, DRQ_WS_P2,   /* policy hidden activations (post-ReLU), [2B][H]: rows [0,B) obs, [B,2B) next_obs */
   DRQ_WS_C1, DRQ_WS_C2,   /* critic Q hidden activations (post-ReLU) of the critic loss, [2 heads][B][H] */
+  /* the head section's other buffers, for the per-launch audit (tests/test_hip_head_audit.py).  The ids are appended:
+   * the ones above keep their values; the workspace layout does not depend on the order of the ids. */
+  DRQ_WS_XHAT_C, DRQ_WS_RSTD_C, DRQ_WS_XHAT_A, DRQ_WS_RSTD_A,   /* LayerNorm's normalised rows [B][F] and 1/sigma [B] */
+  DRQ_WS_Z_C2,            /* the stepped critic's trunk output of the actor loss [B][F] (when no split-K records) */
+  DRQ_WS_HROWS,           /* actor trunk output after LayerNorm+tanh, [2B][F]: rows [0,B) obs, [B,2B) next_obs */
+  DRQ_WS_P3,              /* policy output before the tanh, [2B][A] */
+  DRQ_WS_Z4,              /* the four trunk outputs of phase 4, [4][B][F] (when no split-K records) */
+  DRQ_WS_T1, DRQ_WS_T2,   /* target Q hidden activations [2][B][H]; phase 6 reuses them for the stepped critic */
+  DRQ_WS_DC2, DRQ_WS_DC1, /* gradients of the Q hidden layers [2][B][H] */
+  DRQ_WS_DHA,             /* gradient of the critic's [h, action] input per head, [2][B][F+A] (when no records) */
+  DRQ_WS_DLN,             /* gradient of LayerNorm's output [B][F] */
+  DRQ_WS_DPRE,            /* gradient of the policy output before the tanh [B][A] (unfused output-layer backward) */
+  DRQ_WS_DP2, DRQ_WS_DP1, /* gradients of the policy hidden layers [B][H] */
+  DRQ_WS_DH_A,            /* gradient of the actor trunk output [B][F] (when no records) */
+  DRQ_WS_DA,              /* gradient of the action per Q head, [2][B][A] (when no records) */
   DRQ_WS_NBUF_PUBLIC
 };
 
