@@ -28,6 +28,13 @@ symmetries of the square, with loops opened on request -- fresh per episode or f
 `layout_seed` names, so a user trains on K layouts and evaluates on others.  The reward sits behind walls: it is the task
 the exploration bonuses are for, and the one whose dynamics differ between episodes.  Specified in include/drqv2_hip.h
 ("Maze"), restated by tests/vec_maze_oracle.py.
+
+VecCatch is a sixth (csrc/veccatch.hip, drq_vec_catch_step): a cup driven in the plane, a ball tied to it by a string that is
+either slack or taut, and three capsules that the ball collides with, in the image of the reference's cup_catch
+(cfgs/task/cup_catch.yaml) -- the one task here with a unilateral constraint, contacts between moving bodies and dynamics
+that switch regime inside an episode, and a sparse reward that needs a timed sequence: swing the ball up, then get the cup
+under it.  Specified in include/drqv2_hip.h ("Catch"), restated by tests/vec_catch_oracle.py, which also holds a scripted
+controller that solves it.
 """
 import torch
 
@@ -360,6 +367,57 @@ class VecReacher(_VecTask):
 
     def _config(self):
         return dict(super()._config(), target_radius=self.target_radius, sparse=self.sparse)
+
+
+class VecCatch(_VecTask):
+    """N environments of the catch on the device: in the world [-1, 1]^2 with gravity 4 along -y a cup -- a floor of width
+    cup_width and two walls of height 0.15, three capsules of radius 0.02 -- is driven by action[:, 0:2] in [-1, 1] per
+    axis with momentum, as the point mass is (v = v * 0.9 + a * 0.3, at most 1.5; a stop at +-0.4 zeroes the axis; NaN
+    counts as 0; further columns are ignored).  A ball of radius 0.05 hangs from the middle of the cup's inside floor on a
+    tether of length 0.5: inside that length the string is slack and the ball flies free, at that length it is pulled
+    back inelastically; the ball collides with the three capsules without restitution.  sparse=True pays 1 for every
+    simulator step whose ball centre is inside the cup -- between the walls, above the floor, below the rim -- and 0
+    otherwise; sparse=False pays 1 / (1 + 4 d^2) of the distance d between the ball and the middle of the cup's interior
+    instead, the reacher's shaping.  cup_width is the difficulty: 0.3 leaves the ball of diameter 0.1 an opening of 0.26,
+    0.18 one of 0.14.  It is a task in the image of DMC's ball-in-cup (the reference's cup_catch), not a port of it, and
+    nothing it scores says anything about DMC.  The rule is in include/drqv2_hip.h ("Catch") to the bit and restated in
+    numpy by tests/vec_catch_oracle.py, whose expert() swings the ball up and catches it.
+
+        env = VecCatch(num_envs=N, device="cuda", action_dim=2, episode_length=1000, seed=0, action_repeat=1,
+                       cup_width=0.3, sparse=True)
+
+    The discount is 1 on every row and only the time limit (t == episode_length, in simulator steps) ends an episode, so
+    a macro step's sparse reward is an exact small integer.  A reset draws the cup's position and hangs the ball at rest
+    at the tether's length, a little off the vertical.  The frame is the world at 42 pixels per unit: the tether (cyan),
+    the left wall (blue), the right wall (magenta), the floor (green) and the ball (yellow); no velocity is in a frame, so
+    the policy needs the frame stack.  Same methods and guarantees as VecReach (_VecTask holds them).  The state words are
+    "phys", float32 [N, 8] = (cx, cy, vcx, vcy, bx, by, vbx, vby) -- the cup's position and velocity, the ball's -- and t,
+    episode, over; the config of a state dict carries cup_width and sparse."""
+    TASK = "catch"
+    _STATE = ("phys", "t", "episode", "over")
+    _STATE_SPEC = dict(_VecTask._STATE_SPEC, phys=((8,), torch.float32))
+    MIN_CUP_WIDTH, MAX_CUP_WIDTH = 0.16, 0.4
+
+    def __init__(self, num_envs, device, action_dim=2, episode_length=1000, seed=0, action_repeat=1, cup_width=0.3,
+                 sparse=True):
+        if isinstance(cup_width, bool) or not isinstance(cup_width, (int, float)) \
+                or not self.MIN_CUP_WIDTH <= cup_width <= self.MAX_CUP_WIDTH:
+            raise ValueError(f"cup_width must be a number in {self.MIN_CUP_WIDTH} .. {self.MAX_CUP_WIDTH}, got {cup_width!r}")
+        if not isinstance(sparse, (bool, int)) or sparse not in (0, 1):
+            raise ValueError(f"sparse must be True or False, got {sparse!r}")
+        self.cup_width, self.sparse = float(cup_width), bool(sparse)
+        super().__init__(num_envs, device, action_dim, episode_length, seed, action_repeat)
+
+    def _step_launch(self, action, reset_all, out):
+        launch("drq_vec_catch_step", ptr(self.phys), ptr(self.t), ptr(self.episode), ptr(self.over), self.N, self.A,
+               ptr(action), self.seed, self.episode_length, self.action_repeat, int(reset_all), self.cup_width,
+               int(self.sparse), *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        launch("drq_vec_catch_render", ptr(self.phys), self.N, self.cup_width, ptr(frame), device=self.device)
+
+    def _config(self):
+        return dict(super()._config(), cup_width=self.cup_width, sparse=self.sparse)
 
 
 class VecMaze(_VecTask):

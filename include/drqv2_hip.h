@@ -911,6 +911,85 @@ int drq_vec_maze_render(const float* pos, const uint64_t* walls, const int* cell
 int drq_vec_maze_geodesic(const uint64_t* walls, const int* cells, const float* pos, long N, int size, int* out,
                           drq_stream_t stream);
 
+/* Catch.  A sixth task of the device environment, with entries of its own: a cup is driven in the plane, a ball hangs from
+ * it on a string that is either slack or taut, and the ball must be swung up and caught.  sparse = 1 pays 1 while the ball's
+ * centre is inside the cup and 0 otherwise -- in the image of the reference's cup_catch (cfgs/task/cup_catch.yaml, DMC's
+ * ball-in-cup), not a port of it; sparse = 0 pays a dense shaping of the distance to the cup's interior.  The one task here
+ * with a unilateral constraint (the string pulls and never pushes), contacts between moving bodies and dynamics that
+ * switch regime inside an episode.  These definitions are the contract; they are exact to the bit.  Every float operation
+ * below is ONE correctly rounded IEEE float32 operation (+, -, *, / or sqrt), in the written order, never fused.  The draws
+ * v_k and the sanitising are those above.
+ * World: the square [-1, 1]^2, y upwards, gravity 4 along -y, dt = 0.01.
+ * State per environment e: phys f32 [N][8] = (cx, cy, vcx, vcy, bx, by, vbx, vby): the cup's position (the middle of its
+ *   floor's segment) and velocity, the ball's centre and velocity; t i32 [N], episode u32 [N], over u8 [N] as above.  The
+ *   geometry is launch arguments and constants:  0.16 <= cup_width <= 0.4;  hw = cup_width * 0.5f.
+ * Geometry.  The cup is three capsules of radius 0.02 that move with it: the left wall, the segment (cx - hw, cy) --
+ *   (cx - hw, cy + 0.15f); the right wall, the same at cx + hw; the floor, (cx - hw, cy) -- (cx + hw, cy).  The ball is a
+ *   disc of radius 0.05, so ball and capsule touch at 0.07.  The tether has length 0.5 and is tied to the anchor
+ *   (cx, ay), ay = cy + 0.02f: the middle of the cup's inside floor.  The cup's range is |cx|, |cy| <= 0.4.
+ *   0.4 + 0.02 + 0.5 + 0.05 <= 1 on both axes: the ball stays in the world, which has no walls.
+ *   No tunnelling: the ball's speed is at most 4, the cup's at most 1.5 per axis, and (4 + 1.5 * sqrt(2)) * 0.01 < 0.07.
+ * Reset of e (reset_all = 1, or over[e] == 1): episode += 1 (mod 2^32), t = 0, over = 0; three draws v_0 .. v_2:
+ *   cx = v_0 * 0.4f;  cy = v_1 * 0.4f;  ay = cy + 0.02f;  o = v_2 * 0.25f;  n = sqrt(o * o + 1);
+ *   bx = cx + (o / n) * 0.5f;  by = ay - (1 / n) * 0.5f   (the ball hangs at the tether's length, a little off the vertical)
+ *   every velocity 0.  Outputs first = 1, reward = 0, discount = 1, substeps = 0, the frame of the new state.  The
+ *   action is not read.
+ * Sub-step, (a1, a2) the sanitised action (action[e][0] drives the cup along x, action[e][1] along y, each NaN to 0, then
+ *   the clamp to [-1, 1]; columns 2 .. A-1 are not read), in this order:
+ *   1. the cup, x with a1, then y with a2:  v = clamp(v * 0.9f + a * 0.3f, -1.5f, 1.5f);  q = c + v * 0.01f;
+ *      q < -0.4f: c = -0.4f, v = 0;  q > 0.4f: c = 0.4f, v = 0;  otherwise c = q               (a stop at either end)
+ *   2. the ball's free flight:  vby = vby - 0.04f;  s2 = vbx * vbx + vby * vby;
+ *      s2 > 16: k = 4 / sqrt(s2);  vbx = vbx * k;  vby = vby * k                                  (the clamp on its speed)
+ *      bx = bx + vbx * 0.01f;  by = by + vby * 0.01f                                               (semi-implicit Euler)
+ *   3. the tether, with the cup of step 1:  ay = cy + 0.02f;  dx = bx - cx;  dy = by - ay;  d2 = dx * dx + dy * dy;
+ *      d2 > 0.25f: d = sqrt(d2);  nx = dx / d;  ny = dy / d;  bx = cx + nx * 0.5f;  by = ay + ny * 0.5f;
+ *        vn = (vbx - vcx) * nx + (vby - vcy) * ny;  vn > 0: vbx = vbx - vn * nx;  vby = vby - vn * ny
+ *      (back onto the circle, the outward part of the velocity relative to the cup removed: inelastic).  Otherwise the
+ *      string is slack and does nothing.
+ *   4. the contacts, left wall, right wall, floor, each with the ball as the one before left it:
+ *      xl = cx - hw;  xr = cx + hw;  top = cy + 0.15f;  T, the closest point of the segment, is a clamp:
+ *      left wall T = (xl, clamp(by, cy, top));  right wall T = (xr, clamp(by, cy, top));  floor T = (clamp(bx, xl, xr), cy)
+ *      contact(T):  ex = bx - T.x;  ey = by - T.y;  e2 = ex * ex + ey * ey;  e2 < 0.0049f:
+ *        e2 == 0: (nx, ny) = (0, 1)  (the centre on the segment: pushed upwards);  otherwise e = sqrt(e2);  nx = ex / e;  ny = ey / e
+ *        bx = T.x + nx * 0.07f;  by = T.y + ny * 0.07f;                                    (out along the normal to touching)
+ *        vn = (vbx - vcx) * nx + (vby - vcy) * ny;  vn < 0: vbx = vbx - vn * nx;  vby = vby - vn * ny      (restitution 0)
+ *      A ball in contact is within 0.31 of the anchor, so no contact stretches the tether again.
+ *   t += 1;  over = 1 only when t == episode_length;  d_i = 1 always: the task never ends an episode itself.
+ *   Reward r_i of the new state:  ux = bx - cx;  inner = hw - 0.02f;
+ *   sparse:  r_i = (ux >= -inner and ux <= inner and by >= cy + 0.02f and by <= cy + 0.15f) ? 1 : 0   (between the walls,
+ *   above the floor, below the rim);     dense:  uy = by - (cy + 0.085f);  d2 = ux * ux + uy * uy;  r_i = 1 / (1 + 4 * d2)
+ * Macro step: the one of "Tasks and action repeat" with every d_i = 1: reward = reward + r_i for up to `repeat` sub-steps,
+ *   stopping after the one that set over; discount = 1, first = 0, substeps = the sub-steps executed.  In the sparse form
+ *   the reward is an exact small integer, 0 .. repeat.
+ * Frame of a state, u8 [3][84][84].  Coordinates are integers in 1/16 pixel; pixel (i, j) has its centre at
+ *   (16 j + 8, 16 i + 8).  672 units (42 pixels) are one unit of length, y points up, the world's centre is at (672, 672):
+ *   the frame is the world, and every shape of every reachable state stays inside it (the cup: 0.4 + 0.2 + 0.02 <= 1; the
+ *   ball: 0.4 + 0.02 + 0.5 + 0.05 <= 1).  X(x) = (int)floorf(x * 672 + 672.5f);  Y(y) = (int)floorf(672.5f - y * 672); each
+ *   coordinate is rounded once:  LX = X(cx - hw);  RX = X(cx + hw);  CY = Y(cy);  TY = Y(cy + 0.15f);  AX = X(cx);
+ *   AY = Y(cy + 0.02f);  BX = X(bx);  BY = Y(by).  Everything after that is integer arithmetic.  Per pixel, with
+ *   P = (16 j + 8, 16 i + 8), later rules drawn over earlier:
+ *   background 32 + ((i + j) >> 2) in all three channels;
+ *   the tether, the capsule of radius 10 around the segment A -- B (the cartpole's capsule: the cross product squared in
+ *     int64; a segment of length 0 is a disc), in (64, 255, 255);
+ *   the left wall, |P - (LX, clamp(P.y, TY, CY))|^2 <= 169, in (64, 64, 255);
+ *   the right wall, |P - (RX, clamp(P.y, TY, CY))|^2 <= 169, in (255, 64, 255);
+ *   the floor, |P - (clamp(P.x, LX, RX), CY)|^2 <= 169, in (64, 255, 64);
+ *   the ball, |P - B|^2 <= 1156, in (255, 255, 64).
+ *   No velocity is in a frame.  A shape pixel holds 64 and 255 only and never three equal channels.
+ *
+ * drq_vec_catch_step: one launch, N workgroups of 256 threads with the shape of drq_vec_cartpole_step.  Writes every byte of
+ *   frame, reward, discount, first, substeps and the state (phys), nothing else.  No LDS, no atomics.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 2, repeat < 1
+ *   or > DRQ_TASK_MAX_REPEAT, episode_length < 1, reset_all or sparse not 0 or 1, cup_width outside [0.16, 0.4] or NaN,
+ *   frame not 16-byte aligned, a float / int array not 4-byte aligned.
+ * drq_vec_catch_render: the frames of the states as they are, by the frame rule above (the same device function): every
+ *   byte of frame, nothing else; phys is only read.  DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX,
+ *   cup_width as for the step, frame not 16-byte aligned, phys not 4-byte aligned. */
+int drq_vec_catch_step(float* phys, int* t, unsigned* episode, uint8_t* over, long N, int A, const float* action,
+                       unsigned seed, int episode_length, int repeat, int reset_all, float cup_width, int sparse,
+                       uint8_t* frame, float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
+int drq_vec_catch_render(const float* phys, long N, float cup_width, uint8_t* frame, drq_stream_t stream);
+
 /* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
  * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
  * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep

@@ -1,6 +1,6 @@
 """The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
 
-  VecReach, VecPointMass, VecCartpole, VecReacher or VecMaze (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecReach, VecPointMass, VecCartpole, VecReacher, VecMaze or VecCatch (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
   VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
 
 Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
@@ -8,7 +8,7 @@ return (and length) of the episodes that finished in every interval, from VecEpi
 uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small]
+  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small|catch|catch_hard]
                                  [--reward sparse|dense] [--action-repeat 1]
                                  [--maze-layouts K] [--maze-loops Q] [--maze-eval-layout-seed S]
                                  [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
@@ -37,6 +37,9 @@ wall with probability Q / 256.  --maze-eval-layout-seed S builds the evaluation 
 pool of the same size (the training pool is layout_seed 0): the evaluation lines are then held-out returns, and the
 report ends with the mean return of the last training interval beside the last held-out one.  It needs --maze-layouts K
 and --eval-every STEPS;
+--task catch and catch_hard train on VecCatch (cup_width 0.3 / 0.18): a ball on a tether must be swung up and caught in a
+driven cup, 1 for every simulator step with the ball in the cup, else 0 (the reference configures episodes of 1,000
+simulator steps for its cup_catch); --reward dense swaps in the shaping by the distance to the cup's interior;
 --action-repeat K holds every action for up to K simulator steps inside the step launch.  All of these apply to the training
 environment, the evaluation environment and the random baseline alike.  --episode-length counts simulator steps; the
 lengths that are printed count rows, i.e. agent steps.
@@ -117,7 +120,7 @@ import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch  # noqa: E402
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
-from drqv2_amd.envs import VecCartpole, VecMaze, VecPointMass, VecReach, VecReacher  # noqa: E402
+from drqv2_amd.envs import VecCartpole, VecCatch, VecMaze, VecPointMass, VecReach, VecReacher  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import KnnBonus, RandomFeatures, SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
@@ -125,8 +128,9 @@ from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  #
 
 TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_balance": (VecCartpole, {"swing_up": False}),
          "cartpole_swingup": (VecCartpole, {"swing_up": True}), "reacher_easy": (VecReacher, {"target_radius": 0.15}),
-         "reacher_hard": (VecReacher, {"target_radius": 0.05}), "maze": (VecMaze, {"size": 6}), "maze_small": (VecMaze, {"size": 4})}
-REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: the two forms of VecReacher and VecMaze
+         "reacher_hard": (VecReacher, {"target_radius": 0.05}), "maze": (VecMaze, {"size": 6}), "maze_small": (VecMaze, {"size": 4}),
+         "catch": (VecCatch, {"cup_width": 0.3}), "catch_hard": (VecCatch, {"cup_width": 0.18})}
+REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: the two forms of VecReacher, VecMaze and VecCatch
 
 
 def make_env(args, seed, role="train"):
@@ -182,7 +186,7 @@ def random_baseline(args, episodes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=sorted(TASKS), default="reach")
-    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher and maze tasks (sparse)")
+    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher, maze and catch tasks (sparse)")
     ap.add_argument("--maze-layouts", type=int, default=0, metavar="K", help="the mazes come from a pool of K layouts (0: a fresh maze per episode)")
     ap.add_argument("--maze-loops", type=int, default=0, metavar="Q", help="open every remaining wall with probability Q / 256, 0 .. 255")
     ap.add_argument("--maze-eval-layout-seed", type=int, default=None, metavar="S",
@@ -233,8 +237,8 @@ def main():
     ap.add_argument("--svea-alpha", type=float, default=None, metavar="A", help="weight of the overlaid image, 0 .. 1 (0.5)")
     ap.add_argument("--svea-bank", type=int, default=None, metavar="M", help="images of the procedural overlay bank (64)")
     args = ap.parse_args()
-    if args.reward and TASKS[args.task][0] not in (VecReacher, VecMaze):
-        raise SystemExit("--reward needs --task reacher_easy, reacher_hard, maze or maze_small")
+    if args.reward and TASKS[args.task][0] not in (VecReacher, VecMaze, VecCatch):
+        raise SystemExit("--reward needs --task reacher_easy, reacher_hard, maze, maze_small, catch or catch_hard")
     if TASKS[args.task][0] is not VecMaze and (args.maze_layouts or args.maze_loops or args.maze_eval_layout_seed is not None):
         raise SystemExit("--maze-layouts, --maze-loops and --maze-eval-layout-seed need --task maze or maze_small")
     if not 0 <= args.maze_layouts <= VecMaze.MAX_LAYOUTS or not 0 <= args.maze_loops <= VecMaze.MAX_LOOPS:
