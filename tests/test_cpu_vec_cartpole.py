@@ -14,17 +14,13 @@ import torch
 from drqv2_amd import _lib
 from tests import abi
 from tests import vec_cartpole_oracle as O
+from tests import vec_skeleton_oracle as S
+from tests.vec_skeleton_oracle import same_bits
 
 F = np.float32
 STEP, RENDER = "drq_vec_cartpole_step", "drq_vec_cartpole_render"
 ULP1 = 2.0 ** -23                   # the spacing of float32 at 1
 TINY = np.finfo(np.float32).tiny    # the smallest normal float32
-
-
-def same_bits(got, want, what):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
 
 
 # ------------------------------------------------------------------------------------------------ public surface
@@ -54,42 +50,30 @@ def test_refusals_that_need_no_gpu():
     """every DRQ_EARG case is decided before any launch.  The pointers are made-up addresses with the required alignment:
     a refused call never looks behind them.  (tests/test_hip_vec_cartpole.py repeats them on poisoned outputs.)"""
     lib = _lib.load()
-    for a in O.refused_calls(0x10000, 0x20000, 0x30000, 0x40000):
-        assert lib.drq_vec_cartpole_step(*a, None) == -1, a
-    for a in O.refused_renders(0x10000, 0x30000):
-        assert lib.drq_vec_cartpole_render(*a, None) == -1, a
+    S.all_refused(((lib.drq_vec_cartpole_step, O.refused_calls(0x10000, 0x20000, 0x30000, 0x40000)),
+                   (lib.drq_vec_cartpole_render, O.refused_renders(0x10000, 0x30000))))
     # the task entry still knows reach and the point mass only
     assert lib.drq_vec_task_step(2, *([0x10000] * 6), 5, 2, 0x20000, 7, 9, 2, 0, 0x30000, *([0x40000] * 4), None) == -1
 
 
 # ------------------------------------------------------------------------------------------------ the class, no GPU
 def test_constructor_state_and_state_dict_without_a_device(tmp_path):
-    from drqv2_amd import checkpoint
     from drqv2_amd.envs import VecCartpole, VecPointMass
     env = VecCartpole(3, "cpu")
     assert (env.A, env.episode_length, env.action_repeat, env.swing_up) == (1, 1000, 1, True)
     for bad in (dict(action_dim=0), dict(num_envs=0), dict(episode_length=0)):
         with pytest.raises(ValueError, match="action_dim >= 1"):
             VecCartpole(**dict(dict(num_envs=3, device="cpu"), **bad))
-    for bad in (0, 17, True, 2.0):
-        with pytest.raises(ValueError, match="action_repeat"):
-            VecCartpole(3, "cpu", action_repeat=bad)
     for bad in (2, "yes", None, 0.5):
         with pytest.raises(ValueError, match="swing_up"):
             VecCartpole(3, "cpu", swing_up=bad)
     with pytest.raises(ValueError, match="action_dim >= 2"):               # the other tasks read two columns, as before
         VecPointMass(3, "cpu", action_dim=1)
     env = VecCartpole(3, "cpu", action_dim=2, episode_length=7, seed=1, action_repeat=2, swing_up=False)
-    for method in ("reset", "step", "render", "image", "state", "state_dict", "load_state_dict"):
-        assert callable(getattr(env, method)), method
-    assert env.last_substeps is None
-    with pytest.raises(_lib.DrqError, match="no CPU fallback"):
-        env.reset()
     with pytest.raises(ValueError, match=r"step\(\): action"):
         env.step(torch.zeros(3, 1))
     s = env.state()
     assert list(s) == ["phys", "t", "episode", "over"] and s["phys"].shape == (3, 5) and s["phys"].dtype == np.float32
-    assert s["episode"].dtype == np.uint32 and s["over"].dtype == np.uint8 and s["t"].dtype == np.int32
     sd = env.state_dict()
     assert sd["kind"] == "VecCartpole" and sd["config"] == {"N": 3, "A": 2, "episode_length": 7, "seed": 1, "task": "cartpole",
                                                              "action_repeat": 2, "swing_up": False}
@@ -102,13 +86,9 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
     with pytest.raises(ValueError, match="phys: no tensor saved"):
         VecCartpole(3, "cpu", action_dim=2, episode_length=7, seed=1, action_repeat=2, swing_up=False).load_state_dict(
             {k: v for k, v in sd.items() if k != "phys"})
-    # drqv2_amd.checkpoint takes the class with no special case: the file holds the dict as it is
-    env.phys[1, 4] = 0.25
-    path = str(tmp_path / "env.pt")
-    checkpoint.save(path, env=env, extra={"step": 4})
-    ck = torch.load(path, weights_only=True)
-    assert ck["env"]["kind"] == "VecCartpole" and ck["env"]["config"]["swing_up"] is False
-    assert torch.equal(ck["env"]["phys"], env.phys) and ck["extra"] == {"step": 4}
+    # what no task decides: action_repeat, the methods, no CPU fallback, the skeleton's words, the checkpoint file
+    ck = S.class_without_a_device(VecCartpole, env, tmp_path, ("phys", (1, 4), 0.25), bad_repeats=(0, 17, True, 2.0))
+    assert ck["env"]["config"]["swing_up"] is False
 
 
 # ------------------------------------------------------------------------------------------------ the oracle's properties
@@ -210,8 +190,7 @@ def test_a_long_zero_action_run_carries_no_state_word_into_the_denormal_range():
     """no damping term shrinks anything: 20,000 free sub-steps of four resets of either variant; every state word is zero
     or at least the smallest normal float32"""
     for swing in (True, False):
-        o = O.CartpoleOracle(4, seed=11, swing_up=swing)
-        o.frames = lambda: None
+        o = O.CartpoleOracle(4, seed=11, swing_up=swing, frames=False)
         o.reset()
         for e in range(4):
             p = tuple(o.phys[e])
@@ -268,14 +247,14 @@ def test_inputs_of_the_gpu_tests_cover_what_they_claim():
                           "reset_rows"), 0)
     upright_in_balance = nan = beyond = inf = 0
     for cfg in O.PHYSICS:
-        run = O.physics_run(*cfg, frames=False)
+        run = S.run_of(O, cfg, frames=False)
         for k in seen:
             seen[k] += run[k]
         if not cfg[3]:
             upright_in_balance += run["through_upright"]
         beyond += int((np.abs(np.stack(run["actions"])[:, :, 0]) > 1).sum())
     for cfg in O.DRIVEN:
-        run = O.driven_run(*cfg, frames=False)
+        run = S.run_of(O, cfg, frames=False)
         for k in seen:
             seen[k] += run[k]
         acts = np.stack(run["actions"])[:, :, 0]

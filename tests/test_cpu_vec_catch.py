@@ -14,25 +14,16 @@ import torch
 from drqv2_amd import _lib
 from tests import abi
 from tests import vec_catch_oracle as O
+from tests import vec_skeleton_oracle as S
+from tests.vec_skeleton_oracle import same_bits
 
 F = np.float32
 STEP, RENDER = "drq_vec_catch_step", "drq_vec_catch_render"
 
 
-def same_bits(got, want, what):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
-
-
-_RUNS = {}
-
-
 def run_of(cfg):
     """the oracle's run of a configuration of O.DRIVEN or O.PHYSICS without its frames: computed once, never modified"""
-    if cfg not in _RUNS:
-        _RUNS[cfg] = O.driven_run(*cfg, frames=False) if len(cfg) == 4 else O.physics_run(*cfg, frames=False)
-    return _RUNS[cfg]
+    return S.run_of(O, cfg, frames=False)
 
 
 # ------------------------------------------------------------------------------------------------ public surface
@@ -72,10 +63,7 @@ def test_refusals_that_need_no_gpu():
     a refused call never looks behind them.  (tests/test_hip_vec_catch.py repeats them on poisoned outputs.)"""
     lib = _lib.load()
     calls, renders = O.refused_calls(0x10000, 0x20000, 0x30000, 0x40000), O.refused_renders(0x10000, 0x30000)
-    for a in calls:
-        assert lib.drq_vec_catch_step(*a, None) == -1, a
-    for a in renders:
-        assert lib.drq_vec_catch_render(*a, None) == -1, a
+    S.all_refused(((lib.drq_vec_catch_step, calls), (lib.drq_vec_catch_render, renders)))
     ok = [0x10000, 0x10100, 0x10200, 0x10300, 5, 2, 0x20000, 7, 9, 2, 0, 0.3, 1, 0x30000, 0x40000, 0x40100, 0x40200, 0x40300]
     sub = lambda k, v: ok[:k] + [v] + ok[k + 1:]
     for a in ([None] + ok[1:], sub(0, 0x10002), sub(5, 1), sub(9, 0), sub(9, 17), sub(10, 2), sub(6, None), sub(11, 0.1599),
@@ -88,7 +76,6 @@ def test_refusals_that_need_no_gpu():
 
 # ------------------------------------------------------------------------------------------------ the class, no GPU
 def test_constructor_state_and_state_dict_without_a_device(tmp_path):
-    from drqv2_amd import checkpoint
     from drqv2_amd.envs import VecCartpole, VecCatch
     env = VecCatch(3, "cpu")
     assert (env.A, env.episode_length, env.action_repeat, env.cup_width, env.sparse) == (2, 1000, 1, 0.3, True)
@@ -100,23 +87,14 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
     for bad in (2, "yes", None, 0.5):
         with pytest.raises(ValueError, match="sparse"):
             VecCatch(3, "cpu", sparse=bad)
-    for bad in (0, 17, True):
-        with pytest.raises(ValueError, match="action_repeat"):
-            VecCatch(3, "cpu", action_repeat=bad)
     for width in (0.16, 0.4):                                              # both ends are valid (on the device: the GPU test's poses)
         assert VecCatch(3, "cpu", cup_width=width).cup_width == width
     kw = dict(action_dim=3, episode_length=7, seed=1, action_repeat=2, cup_width=0.18, sparse=False)
     env = VecCatch(3, "cpu", **kw)
-    for method in ("reset", "step", "render", "image", "background_key", "state", "state_dict", "load_state_dict"):
-        assert callable(getattr(env, method)), method
-    assert env.last_substeps is None
-    with pytest.raises(_lib.DrqError, match="no CPU fallback"):
-        env.reset()
     with pytest.raises(ValueError, match=r"step\(\): action"):
         env.step(torch.zeros(3, 2))
     s = env.state()
     assert list(s) == ["phys", "t", "episode", "over"] and s["phys"].shape == (3, 8) and s["phys"].dtype == np.float32
-    assert s["episode"].dtype == np.uint32 and s["over"].dtype == np.uint8 and s["t"].dtype == np.int32
     sd = env.state_dict()
     assert sd["kind"] == "VecCatch" and sd["config"] == {"N": 3, "A": 3, "episode_length": 7, "seed": 1, "task": "catch",
                                                           "action_repeat": 2, "cup_width": 0.18, "sparse": False}
@@ -130,13 +108,9 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
         VecCartpole(3, "cpu", action_dim=3, episode_length=7, seed=1, action_repeat=2).load_state_dict(sd)
     with pytest.raises(ValueError, match="phys: no tensor saved"):
         VecCatch(3, "cpu", **kw).load_state_dict({k: v for k, v in sd.items() if k != "phys"})
-    # drqv2_amd.checkpoint takes the class with no special case: the file holds the dict as it is
-    env.phys[1, 5] = 0.25
-    path = str(tmp_path / "env.pt")
-    checkpoint.save(path, env=env, extra={"step": 4})
-    ck = torch.load(path, weights_only=True)
-    assert ck["env"]["kind"] == "VecCatch" and ck["env"]["config"]["cup_width"] == 0.18
-    assert ck["env"]["config"]["sparse"] is False and torch.equal(ck["env"]["phys"], env.phys) and ck["extra"] == {"step": 4}
+    # what no task decides: action_repeat, the methods, no CPU fallback, the skeleton's words, the checkpoint file
+    ck = S.class_without_a_device(VecCatch, env, tmp_path, ("phys", (1, 5), 0.25), methods=("background_key",))
+    assert ck["env"]["config"]["cup_width"] == 0.18 and ck["env"]["config"]["sparse"] is False
 
 
 # ------------------------------------------------------------------------------------------------ the conditions on the constants
@@ -271,7 +245,7 @@ def test_inputs_of_the_gpu_tests_cover_what_they_claim():
     for phys, width in O.POSES:
         O.check_state(tuple(phys), O.half_width(width))
         frame = O.render(phys, width)
-        shape = (frame != O._BACKGROUND).any(0)
+        shape = (frame != O.BACKGROUND).any(0)
         assert set(np.unique(frame[:, shape])) == {64, 255} and not (frame == 0xA5).any()
         assert not ((frame[0] == frame[1]) & (frame[1] == frame[2]))[shape].any()
         assert not shape[0].any() and not shape[-1].any() and not shape[:, 0].any() and not shape[:, -1].any()   # all inside
@@ -286,9 +260,9 @@ def test_inputs_of_the_gpu_tests_cover_what_they_claim():
     assert {(float(p[0]), float(p[1])) for p, _ in O.POSES} >= {(F(x).item(), F(y).item()) for x in (-0.4, 0.4) for y in (-0.4, 0.4)}
     assert {w for _, w in O.POSES} >= {O.MIN_WIDTH, O.HARD_WIDTH, O.WIDTH, O.MAX_WIDTH}
     # ... and every frame of a physics run and a driven run: inside, and never the key
-    for run in (O.physics_run(*O.PHYSICS[0]), O.driven_run(*O.DRIVEN[-1])):
+    for run in (S.run_of(O, O.PHYSICS[0]), S.run_of(O, O.DRIVEN[-1])):
         for out in run["out"]:
-            shape = (out[0] != O._BACKGROUND).any(1)
+            shape = (out[0] != O.BACKGROUND).any(1)
             assert not shape[:, 0].any() and not shape[:, -1].any() and not shape[:, :, 0].any() and not shape[:, :, -1].any()
             f = out[0].transpose(1, 0, 2, 3)
             assert not ((f[0] == f[1]) & (f[1] == f[2]))[shape].any()

@@ -18,18 +18,16 @@ import torch
 from drqv2_amd import _lib
 from tests import abi
 from tests import vec_maze_oracle as O
+from tests import vec_skeleton_oracle as S
 
 F = np.float32
 STEP, RENDER, GEODESIC = "drq_vec_maze_step", "drq_vec_maze_render", "drq_vec_maze_geodesic"
-_RUNS = {}
 
 
 def run_of(cfg):
     """the oracle's run of a configuration of O.DRIVEN, O.VARIANTS or O.PUSHED without its frames: computed once, never
     modified"""
-    if cfg not in _RUNS:
-        _RUNS[cfg] = O.pushed_run(*cfg, frames=False) if cfg in O.PUSHED else O.driven_run(*cfg, frames=False)
-    return _RUNS[cfg]
+    return S.run_of(O, cfg, frames=False)
 
 
 def bfs(G, east, south, source):
@@ -89,12 +87,7 @@ def test_refusals_that_need_no_gpu():
     lib = _lib.load()
     calls = O.refused_calls(0x10000, 0x20000, 0x30000, 0x40000)
     renders, geodesics = O.refused_renders(0x10000, 0x30000), O.refused_geodesics(0x10000, 0x40000)
-    for a in calls:
-        assert lib.drq_vec_maze_step(*a, None) == -1, a
-    for a in renders:
-        assert lib.drq_vec_maze_render(*a, None) == -1, a
-    for a in geodesics:
-        assert lib.drq_vec_maze_geodesic(*a, None) == -1, a
+    S.all_refused(((lib.drq_vec_maze_step, calls), (lib.drq_vec_maze_render, renders), (lib.drq_vec_maze_geodesic, geodesics)))
     ok = [0x10000, 0x10100, 0x10200, 0x10300, 0x10400, 0x10500, 5, 2, 0x20000, 7, 9, 2, 0, 6, 0, 0, 3, 1, 0x30000, 0x40000,
           0x40100, 0x40200, 0x40300]
     sub = lambda k, v: ok[:k] + [v] + ok[k + 1:]
@@ -286,13 +279,13 @@ def test_inputs_of_the_gpu_tests_cover_what_they_claim():
     for G, pos, walls, cells in O.POSES:
         w = (O.as_u64(walls[0]), O.as_u64(walls[1]))
         frame = O.render(G, pos, w, cells)
-        shape = (frame != O._BACKGROUND).any(0)
+        shape = (frame != O.BACKGROUND).any(0)
         assert set(np.unique(frame[:, shape])) == {64, 255} and not (frame == 0xA5).any()
         assert set(np.unique(frame)) <= set(range(32, 74)) | {255}
         colours = {tuple(v) for v in frame[:, shape].T}
         assert O.WALL_RGB in colours and O.AGENT_RGB in colours
         assert shape[0].all() and shape[-1].all() and shape[:, 0].all() and shape[:, -1].all()     # the boundary is wall
-        assert not (frame == O._BACKGROUND).all(0)[shape].any()               # never VecDistract's background key
+        assert not (frame == O.BACKGROUND).all(0)[shape].any()               # never VecDistract's background key
 
 
 # ------------------------------------------------------------------------------------------------ the class, no GPU
@@ -306,25 +299,20 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
         VecMaze(3, "cpu", action_dim=1)
     for name, bads in (("size", (2, 5, 9, 6.0, "6", None, True)), ("loops", (-1, 256, 0.5, None, True)),
                        ("layouts", (-1, 65536, 2.0, None, False)), ("layout_seed", (1.5, "a", None)),
-                       ("sparse", (2, "yes", None, 0.5)), ("action_repeat", (0, 17, True))):
+                       ("sparse", (2, "yes", None, 0.5))):
         for bad in bads:
             with pytest.raises(ValueError, match=name):
                 VecMaze(3, "cpu", **{name: bad})
     kw = dict(action_dim=3, episode_length=7, seed=1, action_repeat=2, size=8, loops=96, layouts=4, layout_seed=-1, sparse=False)
     env = VecMaze(3, "cpu", **kw)
-    for method in ("reset", "step", "render", "image", "background_key", "state", "state_dict", "load_state_dict", "geodesic"):
-        assert callable(getattr(env, method)), method
-    assert env.last_substeps is None
-    for call in (env.reset, env.geodesic):
-        with pytest.raises(_lib.DrqError, match="no CPU fallback"):
-            call()
+    with pytest.raises(_lib.DrqError, match="no CPU fallback"):
+        env.geodesic()
     with pytest.raises(ValueError, match=r"step\(\): action"):
         env.step(torch.zeros(3, 2))
     s = env.state()
     assert list(s) == ["pos", "walls", "cells", "t", "episode", "over"]
     assert s["pos"].shape == s["walls"].shape == s["cells"].shape == (3, 2)
     assert (s["pos"].dtype, s["walls"].dtype, s["cells"].dtype) == (np.float32, np.int64, np.int32)
-    assert s["episode"].dtype == np.uint32 and s["over"].dtype == np.uint8 and s["t"].dtype == np.int32
     sd = env.state_dict()
     assert sd["kind"] == "VecMaze" and sd["config"] == {
         "N": 3, "A": 3, "episode_length": 7, "seed": 1, "task": "maze", "action_repeat": 2, "size": 8, "loops": 96,
@@ -344,13 +332,11 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
     with pytest.raises(ValueError, match="walls: saved torch.int32"):
         VecMaze(3, "cpu", **kw).load_state_dict(dict(sd, walls=sd["walls"].int()))
     # drqv2_amd.checkpoint takes the class with no special case: the file holds the dict as it is, bit 63 included
-    env.walls[1, 0] = -2 ** 63
+    # (with it, what no task decides: action_repeat, the methods, no CPU fallback, the skeleton's words)
     env.cells[2, 1] = 63
+    ck = S.class_without_a_device(VecMaze, env, tmp_path, ("walls", (1, 0), -2 ** 63), methods=("background_key", "geodesic"))
+    assert ck["env"]["config"] == sd["config"] and ck["env"]["walls"].dtype == torch.int64
     path = str(tmp_path / "env.pt")
-    checkpoint.save(path, env=env, extra={"step": 4})
-    ck = torch.load(path, weights_only=True)
-    assert ck["env"]["kind"] == "VecMaze" and ck["env"]["config"] == sd["config"] and ck["extra"] == {"step": 4}
-    assert torch.equal(ck["env"]["walls"], env.walls) and ck["env"]["walls"].dtype == torch.int64
     assert torch.equal(ck["env"]["cells"], env.cells) and int(ck["env"]["walls"][1, 0]) == -2 ** 63
     with pytest.raises(_lib.DrqError, match="GPU"):                        # load() reaches the environment with the dict intact
         checkpoint.load(path, env=VecMaze(3, "cpu", **kw))

@@ -14,26 +14,17 @@ import torch
 from drqv2_amd import _lib
 from tests import abi
 from tests import vec_reacher_oracle as O
+from tests import vec_skeleton_oracle as S
+from tests.vec_skeleton_oracle import same_bits
 
 F = np.float32
 STEP, RENDER = "drq_vec_reacher_step", "drq_vec_reacher_render"
 ULP1 = 2.0 ** -23                   # the spacing of float32 at 1
 
 
-def same_bits(got, want, what):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
-
-
-_RUNS = {}
-
-
 def run_of(cfg):
     """the oracle's run of a configuration of O.DRIVEN or O.PHYSICS without its frames: computed once, never modified"""
-    if cfg not in _RUNS:
-        _RUNS[cfg] = O.driven_run(*cfg, frames=False) if len(cfg) == 4 else O.physics_run(*cfg, frames=False)
-    return _RUNS[cfg]
+    return S.run_of(O, cfg, frames=False)
 
 
 # ------------------------------------------------------------------------------------------------ public surface
@@ -71,10 +62,7 @@ def test_refusals_that_need_no_gpu():
     a refused call never looks behind them.  (tests/test_hip_vec_reacher.py repeats them on poisoned outputs.)"""
     lib = _lib.load()
     calls, renders = O.refused_calls(0x10000, 0x20000, 0x30000, 0x40000), O.refused_renders(0x10000, 0x30000)
-    for a in calls:
-        assert lib.drq_vec_reacher_step(*a, None) == -1, a
-    for a in renders:
-        assert lib.drq_vec_reacher_render(*a, None) == -1, a
+    S.all_refused(((lib.drq_vec_reacher_step, calls), (lib.drq_vec_reacher_render, renders)))
     ok = [0x10000, 0x10100, 0x10200, 0x10300, 0x10400, 5, 2, 0x20000, 7, 9, 2, 0, 0.15, 1, 0x30000, 0x40000, 0x40100,
           0x40200, 0x40300]
     sub = lambda k, v: ok[:k] + [v] + ok[k + 1:]
@@ -90,7 +78,6 @@ def test_refusals_that_need_no_gpu():
 
 # ------------------------------------------------------------------------------------------------ the class, no GPU
 def test_constructor_state_and_state_dict_without_a_device(tmp_path):
-    from drqv2_amd import checkpoint
     from drqv2_amd.envs import VecCartpole, VecReacher
     env = VecReacher(3, "cpu")
     assert (env.A, env.episode_length, env.action_repeat, env.target_radius, env.sparse) == (2, 1000, 1, 0.15, True)
@@ -102,22 +89,13 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
     for bad in (2, "yes", None, 0.5):
         with pytest.raises(ValueError, match="sparse"):
             VecReacher(3, "cpu", sparse=bad)
-    for bad in (0, 17, True):
-        with pytest.raises(ValueError, match="action_repeat"):
-            VecReacher(3, "cpu", action_repeat=bad)
     kw = dict(action_dim=3, episode_length=7, seed=1, action_repeat=2, target_radius=0.05, sparse=False)
     env = VecReacher(3, "cpu", **kw)
-    for method in ("reset", "step", "render", "image", "background_key", "state", "state_dict", "load_state_dict"):
-        assert callable(getattr(env, method)), method
-    assert env.last_substeps is None
-    with pytest.raises(_lib.DrqError, match="no CPU fallback"):
-        env.reset()
     with pytest.raises(ValueError, match=r"step\(\): action"):
         env.step(torch.zeros(3, 2))
     s = env.state()
     assert list(s) == ["phys", "target", "t", "episode", "over"] and s["phys"].shape == (3, 6) and s["target"].shape == (3, 2)
     assert s["phys"].dtype == s["target"].dtype == np.float32
-    assert s["episode"].dtype == np.uint32 and s["over"].dtype == np.uint8 and s["t"].dtype == np.int32
     sd = env.state_dict()
     assert sd["kind"] == "VecReacher" and sd["config"] == {"N": 3, "A": 3, "episode_length": 7, "seed": 1, "task": "reacher",
                                                             "action_repeat": 2, "target_radius": 0.05, "sparse": False}
@@ -131,13 +109,9 @@ def test_constructor_state_and_state_dict_without_a_device(tmp_path):
         VecCartpole(3, "cpu", action_dim=3, episode_length=7, seed=1, action_repeat=2).load_state_dict(sd)
     with pytest.raises(ValueError, match="target: no tensor saved"):
         VecReacher(3, "cpu", **kw).load_state_dict({k: v for k, v in sd.items() if k != "target"})
-    # drqv2_amd.checkpoint takes the class with no special case: the file holds the dict as it is
-    env.phys[1, 5] = 0.25
-    path = str(tmp_path / "env.pt")
-    checkpoint.save(path, env=env, extra={"step": 4})
-    ck = torch.load(path, weights_only=True)
-    assert ck["env"]["kind"] == "VecReacher" and ck["env"]["config"]["target_radius"] == 0.05
-    assert ck["env"]["config"]["sparse"] is False and torch.equal(ck["env"]["phys"], env.phys) and ck["extra"] == {"step": 4}
+    # what no task decides: action_repeat, the methods, no CPU fallback, the skeleton's words, the checkpoint file
+    ck = S.class_without_a_device(VecReacher, env, tmp_path, ("phys", (1, 5), 0.25), methods=("background_key",))
+    assert ck["env"]["config"]["target_radius"] == 0.05 and ck["env"]["config"]["sparse"] is False
 
 
 # ------------------------------------------------------------------------------------------------ the oracle's properties
@@ -275,7 +249,7 @@ def test_inputs_of_the_gpu_tests_cover_what_they_claim():
         both = O.disc(GX, GY, GR) & O.capsule(O.CENTRE, O.CENTRE, EX, EY, O.ARM_R)
         under += bool(both.any() and (O.disc(GX, GY, GR) & ~both).any() and not O.disc(TX, TY, O.TIP_R)[O.disc(GX, GY, GR)].any())
         frame = O.render(phys, target, radius)
-        shape = (frame != O._BACKGROUND).any(0)
+        shape = (frame != O.BACKGROUND).any(0)
         assert set(np.unique(frame[:, shape])) == {64, 255} and not (frame == 0xA5).any()
         assert not ((frame[0] == frame[1]) & (frame[1] == frame[2]))[shape].any()     # never VecDistract's background key
         assert not shape[0].any() and not shape[-1].any() and not shape[:, 0].any() and not shape[:, -1].any()   # all inside

@@ -13,17 +13,13 @@ import torch
 from drqv2_amd import _lib
 from tests import abi
 from tests import vec_env_oracle as E
+from tests import vec_skeleton_oracle as S
 from tests import vec_tasks_oracle as T
+from tests.vec_skeleton_oracle import same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "drq_vec_task_step"
 F = np.float32
-
-
-def same_bits(got, want, what):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), what
 
 
 def same_state(got, want, what):
@@ -98,6 +94,15 @@ def test_reach_at_repeat_k_is_the_single_step_oracle_folded_by_the_wrapper_rule(
             same_state(new.state(), one.state(), (seed, s))
         assert new.t[0] <= L
     assert cut_target >= 1 and cut_limit >= 1 and full >= 1, "the fold must have stopped early both ways"
+    # No task's d is other than 1 before its last sub-step, so no run above multiplies a reward by a discount below 1.  A
+    # rule that halves it, on the same skeleton: reward = 1 + 1/2 + .. + 2^-(k-1), discount = 2^-k, both exact
+    class Halving(S.SkeletonOracle):
+        new_episode = sanitise = lambda self, *a: None
+        substep = lambda self, e, act: (F(1), F(0.5), False)
+    o = Halving(1, L, 0, k, frames=False)
+    o.reset()
+    _, reward, discount, first, n = o.step(np.zeros((1, A), F))
+    assert (reward[0], discount[0], first[0], n[0]) == (2 - 0.5 ** (k - 1), 0.5 ** k, 0, k)
 
 
 # ------------------------------------------------------------------------------------------------ the oracle, point mass
@@ -159,7 +164,7 @@ def test_inputs_of_the_gpu_tests_cover_what_they_claim():
     for task in T.TASKS:
         for N, A in CONFIGS:
             for k in REPEATS:
-                run = T.driven_run(task, N, A, k, SEED, STEPS, L, frames=False)
+                run = S.run_of(T, (task, N, A, k, SEED, STEPS, L), frames=False)
                 assert T.covers(run, task, k), (task, N, A, k)
 
 
@@ -190,8 +195,7 @@ def test_refusals_that_need_no_gpu():
     """every DRQ_EARG case is decided before any launch.  The pointers are made-up addresses with the required alignment:
     a refused call never looks behind them.  (tests/test_hip_vec_tasks.py repeats them on poisoned outputs.)"""
     lib = _lib.load()
-    for a in T.refused_calls(0x10000, 0x20000, 0x30000, 0x40000):
-        assert lib.drq_vec_task_step(*a, None) == -1, a
+    S.all_refused(((lib.drq_vec_task_step, T.refused_calls(0x10000, 0x20000, 0x30000, 0x40000)),))
 
 
 # ------------------------------------------------------------------------------------------------ the classes, no GPU

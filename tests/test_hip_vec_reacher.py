@@ -14,30 +14,20 @@ steps no joint leaves its quadrant: two long episodes at repeat 16 (vec_reacher_
 turn both joints through all four and run into the clamp of w.  The poses (vec_reacher_oracle.POSES) are where the pixel
 rule can go wrong.  The oracle's runs are made once, shared and never modified; what they cover is asserted without a GPU
 by tests/test_cpu_vec_reacher.py."""
+import types
+
 import numpy as np
 import pytest
 import torch
 
-from tests import poison
-from tests import vec_env_oracle as E
+from tests import vec_env_checks as C
 from tests import vec_reacher_oracle as O
 from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned allocations, check() after every test)
-from tests.test_hip_entries import dev, p
-from tests.test_hip_vec_replay import raw
-from tests.vec_env_checks import OUT, entry_on_poisoned_memory, lib_fixture, same_bits, same_state
+from tests.vec_env_checks import run_of, same_bits
 
 pytestmark = pytest.mark.gpu
 L, SEED = O.EPISODE_LENGTH, O.SEED
-STATE = ("phys", "target", "t", "episode", "over")
-lib = lib_fixture("drq_vec_reacher_step", "the reacher entries are missing")
-_RUNS = {}
-
-
-def run_of(cfg):
-    """the oracle's run of a configuration of O.DRIVEN or O.PHYSICS: computed once, on first use, shared, never modified"""
-    if cfg not in _RUNS:
-        _RUNS[cfg] = O.driven_run(*cfg) if len(cfg) == 4 else O.physics_run(*cfg)
-    return _RUNS[cfg]
+lib = C.lib_fixture("drq_vec_reacher_step", "the reacher entries are missing")
 
 
 def make(cfg, episode_length=L, radius=O.DRIVEN_RADIUS):
@@ -47,27 +37,13 @@ def make(cfg, episode_length=L, radius=O.DRIVEN_RADIUS):
                       target_radius=radius, sparse=sparse)
 
 
-def stagger(env, run):
-    """the state the oracle's run starts from (its staggered t, the spinning arms of the physics runs) into an environment
-    that has just been reset, through load_state_dict(), as a user of the class would write it"""
-    sd = env.state_dict()
-    for k in ("phys", "target", "t"):
-        sd[k] = torch.from_numpy(run["state0"][k])
-    env.load_state_dict(sd)
-
-
-def start(env, run):
-    env.reset()
-    stagger(env, run)
-
-
-def follow(env, run, first, last):
-    for s in range(first, last):
-        out = env.step(torch.from_numpy(run["actions"][s]).cuda())
-        assert len(out) == 4 and [t.dtype for t in out] == [torch.uint8, torch.float32, torch.float32, torch.uint8]
-        for name, t, want in zip(OUT, out + (env.last_substeps,), run["out"][s]):
-            same_bits(t.cpu().numpy(), want, (s, name))
-        same_state(env.state(), run["states"][s], s)
+T = types.SimpleNamespace(
+    O=O, kind="VecReacher", make=make, words=(("phys", (6,), torch.float32), ("target", (2,), torch.float32)),
+    staggered=("phys", "target", "t"), also=None,
+    step=lambda lib, cfg, state, action, reset_all, outs: lib.drq_vec_reacher_step(
+        *state.values(), cfg[0], cfg[1], action, SEED, L, cfg[2], reset_all, O.DRIVEN_RADIUS, int(cfg[3]), *outs, None),
+    render=lambda lib, cfg, state, frame: lib.drq_vec_reacher_render(state["phys"], state["target"], cfg[0], O.DRIVEN_RADIUS,
+                                                                     frame, None))
 
 
 # ------------------------------------------------------------------------------------------------ the class against the oracle
@@ -75,34 +51,18 @@ def follow(env, run, first, last):
 def test_env_matches_the_oracle_bit_for_bit(cfg):
     """reset(), then 40 macro steps at episode_length 7: frame, reward, discount, first, last_substeps and state() after
     every step; the two output sets are used in turn"""
-    run = run_of(cfg)
-    N = cfg[0]
-    env = make(cfg)
-    frame = env.reset()
-    same_bits(frame.cpu().numpy(), run["frame0"], "first frame")
-    same_bits(env.last_substeps.cpu().numpy(), np.zeros(N, np.int32), "substeps of the reset")
-    stagger(env, run)
-    same_state(env.state(), run["state0"], "reset")
-    same_bits(env.render().cpu().numpy(), run["frame0"], "the frame does not depend on t")
-    kept = []
-    for s in range(O.STEPS):
-        follow(env, run, s, s + 1)
-        kept.append(env.last_substeps)
-        if s >= 1:      # two output sets in turn: the set of the step before is intact, the one before that is reused
-            same_bits(kept[s - 1].cpu().numpy(), run["out"][s - 1][4], (s, "the substeps of the step before"))
-        if s >= 2:
-            assert kept[s - 2].data_ptr() == kept[s].data_ptr() != kept[s - 1].data_ptr()
+    C.env_matches_the_oracle(T, cfg)
 
 
 @pytest.mark.parametrize("cfg", O.PHYSICS, ids=lambda c: "sparse" if c[3] else "dense")
 def test_long_episode_matches_the_oracle_through_all_quadrants_and_the_clamp(cfg):
     """60 macro steps of 16 simulator steps in one episode: two arms driven round, two thrown into the clamp of w"""
-    run = run_of(cfg)
+    run = run_of(O, cfg)
     assert run["quadrants"][0] == run["quadrants"][1] == {0, 1, 2, 3} and run["clamped"] >= 1
     env = make(cfg, episode_length=cfg[5], radius=O.PHYSICS_RADIUS)
-    start(env, run)
+    C.start(T, env, run)
     same_bits(env.render().cpu().numpy(), run["frame0"], "first frame")
-    follow(env, run, 0, cfg[4])
+    C.follow(T, env, run, 0, cfg[4])
 
 
 def test_poses_render_as_the_oracle_draws_them():
@@ -129,38 +89,15 @@ def test_step_entry_writes_every_output_byte_and_nothing_else(lib, N, A, sparse)
     then 12 steps into fresh poisoned outputs each; drq_vec_reacher_render beside every one.  The outputs equal the
     oracle's, which never holds the byte sentinel 0xA5 (a frame is 32 .. 73, 64 or 255, a flag 0 or 1) nor the 4-byte one,
     so every byte was written; check() finds the guard bands of outputs, state and action untouched"""
-    cfg = (N, A, 2, sparse)
-    run = run_of(cfg)
-    radius = O.DRIVEN_RADIUS
-    z = lambda shape, dt, name: dev(torch.zeros(shape, dtype=dt), name)
-    state = {"phys": z((N, 6), torch.float32, "phys"), "target": z((N, 2), torch.float32, "target"),
-             "t": z(N, torch.int32, "t"), "episode": z(N, torch.int32, "episode"), "over": z(N, torch.uint8, "over")}
-
-    def render_beside(s, want):
-        again = poison.alloc((N, 3, 84, 84), torch.uint8, "cuda", name="rendered")
-        assert lib.drq_vec_reacher_render(p(state["phys"]), p(state["target"]), N, radius, p(again), None) == 0
-        same_bits(again.cpu().numpy(), want[0], (s, "render"))
-
-    entry_on_poisoned_memory(lambda action, reset_all, outs: lib.drq_vec_reacher_step(
-        *(p(state[n]) for n in STATE), N, A, action, SEED, L, 2, reset_all, radius, int(sparse), *outs, None), run, N,
-        state=state, compared=STATE, beside=render_beside,
-        after_reset=lambda: state["t"].copy_(torch.from_numpy(run["state0"]["t"])))      # the stagger of the oracle's run
+    C.step_entry_on_poisoned_memory(T, lib, (N, A, 2, sparse))
 
 
 def test_every_argument_error_is_refused_and_nothing_is_written(lib):
     """the DRQ_EARG cases (tests/vec_reacher_oracle.refused_calls / refused_renders, all held to return the error without
     a GPU by tests/test_cpu_vec_reacher.py) on real allocations full of the sentinel: the error, and check() finds every
     byte of the state, the action, the frame and the scalar outputs still poison"""
-    al = lambda nbytes, name: poison.alloc(nbytes, torch.uint8, "cuda", name=name, kind="refused")
-    state, action, frame, scalars = al(0x500, "state"), al(0x100, "action"), al(5 * 3 * 84 * 84, "frame"), al(0x400, "scalars")
-    calls = O.refused_calls(p(state), p(action), p(frame), p(scalars))
-    for a in calls:
-        assert lib.drq_vec_reacher_step(*a, None) == -1, a
-    renders = O.refused_renders(p(state), p(frame))
-    for a in renders:
-        assert lib.drq_vec_reacher_render(*a, None) == -1, a
-    assert len(calls) == 44 and len(renders) == 13
-    poison.check()
+    C.refused_on_poisoned_memory(0x500, lambda S0, ACT, FR, SC: ((lib.drq_vec_reacher_step, O.refused_calls(S0, ACT, FR, SC), 44),
+                                                                  (lib.drq_vec_reacher_render, O.refused_renders(S0, FR), 13)))
 
 
 # ------------------------------------------------------------------------------------------------ frames, images, checkpoints
@@ -169,35 +106,11 @@ def test_state_dict_into_a_fresh_environment_image_and_the_ring():
     takes the next 5 steps to the bit.  image() of it at 168 x 168 x 4 is the oracle's frame with every pixel twice in
     both directions.  One VecFrameReplay.add() of the reset row and one of a step, then observation(): the stack a frame
     stacker would hold.  A dict of another radius or reward form is refused, with the field named"""
-    from drqv2_amd.replay import VecFrameReplay
     cfg = (5, 4, 2, False)
-    run = run_of(cfg)
-    N, A = cfg[:2]
-    env = make(cfg)
-    start(env, run)
-    follow(env, run, 0, 9)
-    want = run["out"][8][0]
-    sd = env.state_dict()
-    assert sd["kind"] == "VecReacher" and sd["config"]["sparse"] is False and sd["config"]["target_radius"] == O.DRIVEN_RADIUS
-    assert tuple(sd["phys"].shape) == (N, 6) and tuple(sd["target"].shape) == (N, 2)
-    fresh = make(cfg)
-    fresh.load_state_dict(sd)
-    same_bits(fresh.render().cpu().numpy(), want, "the frame of the restored state")
-    same_state(fresh.state(), run["states"][8], "restored")
-    same_bits(fresh.image(168, 4).cpu().numpy(), E.replicate(want, 168, 4), "image()")
-    ring = VecFrameReplay(16, N, A, 3, 0.99, "cuda", seed=1)
-    zeros, ones = torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
-    ring.add(fresh.render(), torch.zeros(N, A, device="cuda"), zeros, ones, torch.ones(N, dtype=torch.uint8, device="cuda"))
-    action = torch.from_numpy(run["actions"][9]).cuda()
-    frame, reward, discount, first = fresh.step(action)
-    ring.add(frame, torch.nan_to_num(action).clamp(-1, 1), reward, discount, first)
-    newest, reset_row = run["out"][9][0], run["out"][9][3].astype(bool)[:, None, None, None]
-    stack = np.concatenate([np.where(reset_row, newest, want)] * 2 + [newest], axis=1)      # a reset row fills the stack
-    same_bits(ring.observation().cpu().numpy(), stack, "observation()")
-    same_state(fresh.state(), run["states"][9], "after the step")
-    follow(fresh, run, 10, 14)
+    sd = C.state_dict_image_and_ring(T, cfg)
+    assert sd["config"]["sparse"] is False and sd["config"]["target_radius"] == O.DRIVEN_RADIUS
     with pytest.raises(ValueError, match=r"\bsparse: saved False, here True"):
-        make((N, A, 2, True)).load_state_dict(sd)
+        make((5, 4, 2, True)).load_state_dict(sd)
     with pytest.raises(ValueError, match=r"\btarget_radius: saved 0.3, here 0.15"):
         make(cfg, radius=0.15).load_state_dict(sd)
 
@@ -208,73 +121,26 @@ def test_checkpoint_round_trip_continues_bit_for_bit(tmp_path):
     target_radius and sparse, and an environment of another radius refuses it"""
     from drqv2_amd import checkpoint
     cfg = (3, 2, 2, True)
-    run = run_of(cfg)
-    env = make(cfg)
-    start(env, run)
-    follow(env, run, 0, 6)
-    path = str(tmp_path / "env.pt")
-    checkpoint.save(path, env=env, extra={"step": 6})
-    saved = env.state()
-    assert np.abs(saved["phys"][:, 2]).max() > 0 and 0 < int(saved["t"].max()) < L, "the save must fall inside an episode, in motion"
-    config = torch.load(path, weights_only=True)["env"]["config"]
-    assert config["target_radius"] == O.DRIVEN_RADIUS and config["sparse"] is True
-    with pytest.raises(ValueError, match="target_radius"):
-        checkpoint.load(path, env=make(cfg, radius=0.05))
-    fresh = make(cfg)
-    assert checkpoint.load(path, env=fresh) == {"step": 6}
-    same_state(fresh.state(), run["states"][5], "restored")
-    assert raw(fresh.render()).tobytes() == run["out"][5][0].tobytes()
-    follow(fresh, run, 6, 16)
-    follow(env, run, 6, 16)
-    same_state(fresh.state(), env.state(), "after 10 steps")
+
+    def between(path, saved):
+        assert np.abs(saved["phys"][:, 2]).max() > 0 and 0 < int(saved["t"].max()) < L, "the save must fall inside an episode, in motion"
+        config = torch.load(path, weights_only=True)["env"]["config"]
+        assert config["target_radius"] == O.DRIVEN_RADIUS and config["sparse"] is True
+        with pytest.raises(ValueError, match="target_radius"):
+            checkpoint.load(path, env=make(cfg, radius=0.05))
+
+    C.checkpoint_round_trip(T, cfg, tmp_path, 6, 10, between)
 
 
 def test_distractions_and_the_exploration_bonus_take_the_class():
     """N = 3: reset() and one step of VecDistract(env, distractor) against the distraction oracle applied to the reacher
     oracle's frames -- no shape pixel is the background key -- and SimHashBonus of the plain frames and the sparse reward
     against its own oracle"""
-    from drqv2_amd.distract import FrameDistractor, VecDistract
-    from drqv2_amd.explore import SimHashBonus
-    from tests import simhash_oracle as S
-    from tests import vec_distract_oracle as D
-    cfg = (3, 2, 2, True)
-    run = run_of(cfg)
-    N = cfg[0]
-    kw = dict(seed=5, camera=8, camera_period=1, color=48)
-    wrapped = VecDistract(make(cfg), FrameDistractor(N, "cuda", background="noise", background_alpha=200, key="env", **kw))
-    o = D.DistractOracle(N, bg_mode=1, bg_alpha=200, key=D.ramp(), **kw)
-    same_bits(wrapped.reset().cpu().numpy(), o.apply(run["frame0"], reset_all=True), "reset")
-    stagger(wrapped.env, run)
-    frame, reward, discount, first = wrapped.step(torch.from_numpy(run["actions"][0]).cuda())
-    want = run["out"][0]
-    same_bits(frame.cpu().numpy(), o.apply(want[0], want[3]), "the distracted frame")
-    for got, w, what in ((reward, want[1], "reward"), (discount, want[2], "discount"), (first, want[3], "first"),
-                         (wrapped.last_substeps, want[4], "substeps")):
-        same_bits(got.cpu().numpy(), w, what)
-    o.require_branches("background", "foreground")
-    bonus, so = SimHashBonus(N, "cuda", bits=16, beta=0.5, seed=4), S.SimHashOracle(16, 0.5, 4)
-    plain = make(cfg)
-    start(plain, run)
-    for s in range(2):
-        frame, reward = plain.step(torch.from_numpy(run["actions"][s]).cuda())[:2]
-        ret = bonus.step(frame, reward)
-        code, count, extra, total = so.step(run["out"][s][0], run["out"][s][1])[:4]
-        for got, w, what in ((bonus.codes, code, "codes"), (bonus.counts, count, "counts"), (bonus.last_bonus, extra, "bonus"),
-                             (ret, total, "reward + bonus")):
-            same_bits(got.cpu().numpy(), w, (s, what))
+    C.distractions_and_the_exploration_bonus(T, (3, 2, 2, True))
 
 
 def test_evaluate_frame_stack_and_video_take_the_class():
     """evaluate() runs one episode of each of N = 3 environments of 7 simulator steps at repeat 2 (4 rows each) with a
     VecVideo beside it, as it does for the other tasks; a sparse return is a whole number of at most 7"""
-    import drqv2
-    from drqv2_amd.evaluate import VecVideo, evaluate
-    cfg = (3, 2, 2, True)
-    torch.manual_seed(3)
-    agent = drqv2.DrQV2Agent((9, 84, 84), (2,), "cuda", 1e-3, 50, 64, 0.01, 8, 1, "0.5", 0.3, True)
-    video = VecVideo(3, "cuda", max_frames=64)
-    res = evaluate(agent, make(cfg), 1, poll_every=4, video=video)
-    snap = res.snapshot
-    assert snap.complete and snap.episodes == 3 and sorted(snap.records["env"].tolist()) == [0, 1, 2]
-    assert (snap.records["length"] == -(-L // 2)).all() and len(video) >= 5
+    snap = C.evaluate_and_video(T, (3, 2, 2, True))
     assert (snap.records["return"] == np.round(snap.records["return"])).all() and 0 <= snap.min_return <= snap.max_return <= L

@@ -28,7 +28,8 @@ from tests import vec_tasks_oracle as T
 from tests.poison import poisoned_ops  # noqa: F401  (autouse: poisoned allocations, check() after every test)
 from tests.test_hip_entries import dev, p
 from tests.test_hip_vec_replay import raw
-from tests.vec_env_checks import OUT, alloc_outs, entry_on_poisoned_memory, lib_fixture, same_bits, same_state
+from tests.vec_env_checks import (OUT, alloc_outs, entry_on_poisoned_memory, lib_fixture, refused_on_poisoned_memory, run_of,
+                                  same_bits, same_state)
 
 pytestmark = pytest.mark.gpu
 L, STEPS, SEED = 7, 40, 5
@@ -41,13 +42,7 @@ lib = lib_fixture("drq_vec_task_step", "the task entry is missing")
 @pytest.fixture(scope="module")
 def runs():
     """the oracle's runs: each computed once, on first use, shared and never modified"""
-    cache = {}
-
-    def get(task, N, A, k):
-        if (task, N, A, k) not in cache:
-            cache[task, N, A, k] = T.driven_run(task, N, A, k, SEED, STEPS, L)
-        return cache[task, N, A, k]
-    return get
+    return lambda task, N, A, k: run_of(T, (task, N, A, k, SEED, STEPS, L))
 
 
 def cls_of(task):
@@ -137,13 +132,7 @@ def test_every_argument_error_is_refused_and_nothing_is_written(lib):
     """the DRQ_EARG cases (tests/vec_tasks_oracle.refused_calls, all held to return the error without a GPU by
     tests/test_cpu_vec_tasks.py) on real allocations full of the sentinel: the error, and check() finds every byte of
     the state, the action, the frame and the four scalar outputs still poison"""
-    al = lambda nbytes, name: poison.alloc(nbytes, torch.uint8, "cuda", name=name, kind="refused")
-    state, action, frame, scalars = al(0x600, "state"), al(0x100, "action"), al(5 * 3 * 84 * 84, "frame"), al(0x400, "scalars")
-    calls = T.refused_calls(p(state), p(action), p(frame), p(scalars))
-    for a in calls:
-        assert lib.drq_vec_task_step(*a, None) == -1, a
-    assert len(calls) == 54
-    poison.check()
+    refused_on_poisoned_memory(0x600, lambda S0, ACT, FR, SC: ((lib.drq_vec_task_step, T.refused_calls(S0, ACT, FR, SC), 54),))
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints

@@ -17,21 +17,21 @@ hash and the draws are those of tests/vec_env_oracle.py.
              rail end: x = +-1.8, xdot = 0; h = omega 0.01; (c, s) = normalise(c - s h, s + c h); t += 1; over at the limit
   reward     up = (c + 1) 0.5; ce = (1 + 1 / (1 + x x)) 0.5; co = (4 + (1 - a a)) / 5; w = omega / 5;
              sl = (1 + 1 / (1 + w w)) 0.5; r = ((up ce) co) sl
-  macro step a = action[e, 0] sanitised once (NaN -> 0, clamp to [-1, 1]); reward = reward + r_i for up to `repeat`
-             sub-steps, stopping after the one that set over; discount = 1, first = 0, substeps = the sub-steps executed
+  macro step the skeleton's (tests/vec_skeleton_oracle.py); a = action[e, 0] sanitised once (NaN -> 0, clamp to [-1, 1]);
+             d_i = 1, and the task never ends an episode
   frame      in 1/16 pixel, pixel (i, j) centred at (16 j + 8, 16 i + 8): X0 = floor(x 320 + 672.5), X1 = floor((x 320 + s 320)
              + 672.5), Y1 = floor(672.5 - c 320); background, rail, cart, the pole's capsule of radius 24 (render below)
 """
 import numpy as np
 
-from tests.vec_env_oracle import F, M32, SIDE, clamp1, draw
+from tests import vec_skeleton_oracle as S
+from tests.vec_env_oracle import BACKGROUND, F, SIDE, clamp1, draw  # noqa: F401  (clamp1: for the property tests)
 
 RAIL, MAX_XDOT, MAX_OMEGA = F(1.8), F(16), F(32)
 DT = F(0.01)
 CENTRE, RAIL_ROW, RAIL_HALF, CART_HALF_W, CART_HALF_H, POLE_R = 672, 42, 576, 96, 48, 24
 POLE_RGB, CART_RGB, RAIL_RGB = (255, 64, 64), (64, 255, 64), (64, 64, 255)
 _II, _JJ = np.meshgrid(np.arange(SIDE), np.arange(SIDE), indexing="ij")
-_BACKGROUND = (32 + ((_II + _JJ) >> 2)).astype(np.uint8)
 _PX, _PY = (16 * _JJ + 8).astype(np.int64), (16 * _II + 8).astype(np.int64)
 
 
@@ -136,7 +136,7 @@ def capsule(X0, Y0, X1, Y1, r=POLE_R):
 def render(phys):
     """the frame of one state"""
     X0, X1, Y1 = end_points(phys[0], phys[2], phys[3])
-    frame = np.stack([_BACKGROUND] * 3)
+    frame = np.stack([BACKGROUND] * 3)
     rail = (_II == RAIL_ROW) & (np.abs(_PX - CENTRE) <= RAIL_HALF)
     cart = (np.abs(_PX - X0) <= CART_HALF_W) & (np.abs(_PY - CENTRE) <= CART_HALF_H)
     for m, rgb in ((rail, RAIL_RGB), (cart, CART_RGB), (capsule(X0, CENTRE, X1, Y1), POLE_RGB)):
@@ -145,111 +145,54 @@ def render(phys):
     return frame
 
 
-class CartpoleOracle:
-    def __init__(self, num_envs, episode_length=1000, seed=0, repeat=1, swing_up=True):
-        assert 1 <= int(repeat) <= 16
-        self.N, self.episode_length, self.seed = int(num_envs), int(episode_length), int(seed) & M32
-        self.repeat, self.swing_up = int(repeat), bool(swing_up)
-        self.phys = np.zeros((self.N, 5), F)
-        self.t = np.zeros(self.N, np.int32)
-        self.episode = np.zeros(self.N, np.uint32)
-        self.over = np.zeros(self.N, np.uint8)
-        # what a run met: hits of either rail end, sign changes of s while hanging (c < 0) and while upright (c > 0),
-        # rows cut short by the time limit, full rows, reset rows
-        self.hit_left = self.hit_right = self.through_hanging = self.through_upright = 0
-        self.cut_by_limit = self.full = self.reset_rows = 0
+class CartpoleOracle(S.SkeletonOracle):
+    WORDS = (("phys", (5,), F),)
 
-    def _reset_one(self, e):
-        ep = (int(self.episode[e]) + 1) & M32
-        self.episode[e], self.t[e], self.over[e] = ep, 0, 0
+    def __init__(self, num_envs, episode_length=1000, seed=0, repeat=1, swing_up=True, frames=True):
+        super().__init__(num_envs, episode_length, seed, repeat, frames)
+        self.swing_up = bool(swing_up)
+        # what a run met: hits of either rail end, sign changes of s while hanging (c < 0) and while upright (c > 0)
+        self.hit_left = self.hit_right = self.through_hanging = self.through_upright = 0
+
+    def new_episode(self, e, ep):
         c, s = normalise(F(-1) if self.swing_up else F(1), F(draw(self.seed, e, ep, 1) * F(0.05)))
         self.phys[e] = (F(draw(self.seed, e, ep, 0) * F(0.1)), 0, c, s, 0)
 
-    def frames(self):
-        return np.stack([render(self.phys[e]) for e in range(self.N)])
+    def sanitise(self, row):
+        return S.sanitise(row[0])
 
-    def reset(self):
-        for e in range(self.N):
-            self._reset_one(e)
-        return self.frames()
+    def frame(self, e):
+        return render(self.phys[e])
 
-    def step(self, action):
-        """action: float32 [N, A], A >= 1 -> (frame, reward, discount, first, substeps)"""
-        action = np.asarray(action, F)
-        reward, discount, first = np.zeros(self.N, F), np.ones(self.N, F), np.zeros(self.N, np.uint8)
-        substeps = np.zeros(self.N, np.int32)
-        for e in range(self.N):
-            if self.over[e]:
-                self._reset_one(e)
-                first[e] = 1
-                self.reset_rows += 1
-                continue
-            a = F(0) if np.isnan(action[e, 0]) else clamp1(action[e, 0])
-            p = tuple(self.phys[e])
-            for _ in range(self.repeat):
-                s_before = p[3]
-                p, hit = substep(p, a)
-                self.hit_left += hit < 0
-                self.hit_right += hit > 0
-                if (s_before < 0) != (p[3] < 0) and s_before != 0 and p[3] != 0:
-                    if p[2] < 0:
-                        self.through_hanging += 1
-                    else:
-                        self.through_upright += 1
-                self.t[e] += 1
-                reward[e] = F(reward[e] + reward_of(p, a))
-                substeps[e] += 1
-                if self.t[e] == self.episode_length:
-                    self.over[e] = 1
-                    break
-            self.phys[e] = p
-            if substeps[e] == self.repeat:
-                self.full += 1
+    def substep(self, e, a):
+        s_before = self.phys[e, 3]
+        p, hit = substep(tuple(self.phys[e]), a)
+        self.hit_left += hit < 0
+        self.hit_right += hit > 0
+        if (s_before < 0) != (p[3] < 0) and s_before != 0 and p[3] != 0:
+            if p[2] < 0:
+                self.through_hanging += 1
             else:
-                self.cut_by_limit += 1
-        return self.frames(), reward, discount, first, substeps
+                self.through_upright += 1
+        self.phys[e] = p
+        return reward_of(p, a), F(1), False
 
-    def state(self):
-        return {"phys": self.phys.copy(), "t": self.t.copy(), "episode": self.episode.copy(), "over": self.over.copy()}
 
+_SEEN = ("hit_left", "hit_right", "through_hanging", "through_upright", "cut_by_limit", "full", "reset_rows")
 
 # ---- the driven run the CPU and the GPU tests share ---------------------------------------------------------------
 STEPS, EPISODE_LENGTH, SEED = 40, 7, 5
 DRIVEN = tuple((N, A, k, swing) for (N, A) in ((3, 1), (5, 3)) for k in (1, 2, 16) for swing in (True, False))
 
 
-def wild_actions(r, N, A, s):
-    """row s of actions from RandomState r: uniform in [-2, 2], so the clamp is hit; one component in sixteen NaN, one in
-    eight +-inf"""
-    a = r.uniform(-2, 2, (N, A)).astype(F)
-    kind = r.randint(0, 16, (N, A))
-    a[kind == 0] = np.nan
-    a[kind == 1] = np.inf
-    a[kind == 2] = -np.inf
-    return a
-
-
 def driven_run(N, A, repeat, swing_up, seed=SEED, steps=STEPS, episode_length=EPISODE_LENGTH, frames=True):
-    """the oracle driven for `steps` macro steps by wild_actions: the actions it was given, everything it returned (the
-    frames only if asked for: they are most of the time) and the state after every step.  Only the time limit ends an
-    episode, so environments reset together would stay in step for ever: after the reset, t of environment e is set to
-    e mod episode_length ("state0" holds it; a user of the class does the same through load_state_dict()), and the
-    resets stagger from then on"""
+    """the oracle driven for `steps` macro steps by S.wild_actions from the staggered reset (S.stagger): the actions it was
+    given, everything it returned (the frames only if asked for) and the state after every step"""
     r = np.random.RandomState(seed * 100003 + N * 101 + A * 17 + repeat * 3 + int(swing_up))
-    o = CartpoleOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, swing_up=swing_up)
-    if not frames:
-        o.frames = lambda: None
-    frame0 = o.reset()
-    o.t[:] = np.arange(N) % episode_length
-    run = {"frame0": frame0, "state0": o.state(), "actions": [], "out": [], "states": []}
-    for s in range(steps):
-        a = wild_actions(r, N, A, s)
-        run["actions"].append(a)
-        run["out"].append(o.step(a))
-        run["states"].append(o.state())
-    for k in ("hit_left", "hit_right", "through_hanging", "through_upright", "cut_by_limit", "full", "reset_rows"):
-        run[k] = getattr(o, k)
-    return run
+    o = CartpoleOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, swing_up=swing_up, frames=frames)
+    o.reset()
+    S.stagger(o)
+    return S.record(o, steps, lambda s: S.wild_actions(r, N, A), _SEEN)
 
 
 # The physics drive: the driven runs above have episodes of seven simulator steps, in which no cart reaches a rail end
@@ -272,18 +215,14 @@ def physics_actions(N, A, s, swing_up):
 
 
 def physics_run(N, A, repeat, swing_up, steps, episode_length, seed=SEED, frames=True):
-    o = CartpoleOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, swing_up=swing_up)
-    if not frames:
-        o.frames = lambda: None
-    run = {"frame0": o.reset(), "state0": o.state(), "actions": [], "out": [], "states": []}
-    for s in range(steps):
-        a = physics_actions(N, A, s, swing_up)
-        run["actions"].append(a)
-        run["out"].append(o.step(a))
-        run["states"].append(o.state())
-    for k in ("hit_left", "hit_right", "through_hanging", "through_upright", "cut_by_limit", "full", "reset_rows"):
-        run[k] = getattr(o, k)
-    return run
+    o = CartpoleOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, swing_up=swing_up, frames=frames)
+    o.reset()
+    return S.record(o, steps, lambda s: physics_actions(N, A, s, swing_up), _SEEN)
+
+
+def run(cfg, frames=True):
+    """the run of a configuration of DRIVEN or PHYSICS"""
+    return driven_run(*cfg, frames=frames) if len(cfg) == 4 else physics_run(*cfg, frames=frames)
 
 
 # ---- the argument lists drq_vec_cartpole_step refuses: shared by the CPU and the GPU test ------------------------------
@@ -293,18 +232,11 @@ def refused_calls(S0, ACT, FR, SC):
     #     phys t          episode     over        N  A  action seed L repeat reset swing frame
     ok = [S0, S0 + 0x100, S0 + 0x200, S0 + 0x300, 5, 1, ACT, 7, 9, 2, 0, 1, FR,
           SC, SC + 0x100, SC + 0x200, SC + 0x300]                         # reward discount first substeps
-    sub = lambda k, v, base=ok: base[:k] + [v] + base[k + 1:]
-    bad = [sub(k, None) for k in (0, 1, 2, 3, 6, 12, 13, 14, 15, 16)]      # every pointer; action: no reset_all
-    for k, vals in ((4, (0, -1, 2 ** 31)), (5, (0, -2)), (8, (0, -5)), (9, (0, -1, 17, 2 ** 31 - 1)), (10, (2, -1)),
-                    (11, (2, -1))):                                        # N, A, episode_length, repeat, reset_all, swing_up
-        bad += [sub(k, v) for v in vals]
-    bad += [sub(12, FR + m) for m in (1, 4, 8)]                            # frame not 16-byte aligned
-    bad += [sub(k, ok[k] + 2) for k in (0, 1, 2, 6, 13, 14, 16)]           # a float / int array not 4-byte aligned
+    bad = S.refused_steps(ok, "w w w b N A action - L repeat reset - frame w w b w", {11: (2, -1)})      # swing_up
     assert len(bad) == 10 + 15 + 3 + 7
     return bad
 
 
 def refused_renders(S0, FR):
     """the argument lists drq_vec_cartpole_render must refuse: (phys, N, frame)"""
-    return [[None, 3, FR], [S0, 3, None], [S0, 0, FR], [S0, -1, FR], [S0, 2 ** 31, FR], [S0, 3, FR + 4], [S0, 3, FR + 8],
-            [S0 + 2, 3, FR]]
+    return S.refused_reads([S0, 3, FR], "w N frame", {})

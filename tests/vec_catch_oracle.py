@@ -17,8 +17,8 @@ draws are those of tests/vec_env_oracle.py; the tether's capsule is the cartpole
              t += 1; over at the limit
   reward     ux = bx - cx; sparse: -(hw - 0.02) <= ux <= hw - 0.02 and cy + 0.02 <= by <= cy + 0.15 ? 1 : 0;
              dense: uy = by - (cy + 0.085); 1 / (1 + 4 (ux ux + uy uy))
-  macro step ax, ay = action[e, 0:2] sanitised once; reward = reward + r_i for up to `repeat` sub-steps, stopping after
-             the one that set over; discount = 1, first = 0, substeps = the sub-steps executed
+  macro step the skeleton's (tests/vec_skeleton_oracle.py); ax, ay = action[e, 0:2] sanitised once; d_i = 1, and the task
+             never ends an episode
   frame      in 1/16 pixel, 672 to the unit, the world's centre at (672, 672), y upwards (render below)
 
 Beside the rule: the runs, poses and refused argument lists the CPU and the GPU tests share, and expert(), the scripted
@@ -26,7 +26,9 @@ controller that makes the task solvable."""
 import numpy as np
 
 from tests.vec_cartpole_oracle import capsule, clamp_to
-from tests.vec_env_oracle import F, M32, SIDE, clamp1, draw
+from tests import vec_skeleton_oracle as S
+from tests.vec_env_oracle import BACKGROUND, F, SIDE, draw
+from tests.vec_skeleton_oracle import sanitise
 
 DT, GDT, DRAG, GAIN = F(0.01), F(0.04), F(0.9), F(0.3)            # GDT: gravity 4 times dt
 MAX_CUP_V, MAX_BALL_V, MAX_BALL_V2 = F(1.5), F(4), F(16)
@@ -38,15 +40,10 @@ MIN_WIDTH, MAX_WIDTH, WIDTH, HARD_WIDTH = 0.16, 0.4, 0.3, 0.18
 CENTRE, CUP_R, BALL_PIX, TETHER_R = 672, 13, 34, 10
 TETHER_RGB, LEFT_RGB, RIGHT_RGB, FLOOR_RGB, BALL_RGB = (64, 255, 255), (64, 64, 255), (255, 64, 255), (64, 255, 64), (255, 255, 64)
 _II, _JJ = np.meshgrid(np.arange(SIDE), np.arange(SIDE), indexing="ij")
-_BACKGROUND = (32 + ((_II + _JJ) >> 2)).astype(np.uint8)
 _PX, _PY = (16 * _JJ + 8).astype(np.int64), (16 * _II + 8).astype(np.int64)
 
 EVENTS = ("taut", "slack", "left_inside", "left_outside", "right_inside", "right_outside", "floor", "degenerate",
           "stop_x_lo", "stop_x_hi", "stop_y_lo", "stop_y_hi", "clamp_cup_x", "clamp_cup_y", "clamp_ball")
-
-
-def sanitise(v):
-    return F(0) if np.isnan(v) else clamp1(v)
 
 
 def half_width(width):
@@ -194,7 +191,7 @@ def masks(phys, width):
 
 def render(phys, width):
     """the frame of one state"""
-    frame = np.stack([_BACKGROUND] * 3)
+    frame = np.stack([BACKGROUND] * 3)
     for m, rgb in masks(phys, width):
         for ch in range(3):
             frame[ch][m] = rgb[ch]
@@ -217,75 +214,40 @@ def check_state(p, hw):
     assert abs(cx) + float(hw) + float(CAPSULE_R) <= 1, p
 
 
-class CatchOracle:
-    def __init__(self, num_envs, episode_length=1000, seed=0, repeat=1, cup_width=WIDTH, sparse=True):
-        assert 1 <= int(repeat) <= 16
-        self.N, self.episode_length, self.seed = int(num_envs), int(episode_length), int(seed) & M32
-        self.repeat, self.width, self.sparse = int(repeat), F(cup_width), bool(sparse)
+class CatchOracle(S.SkeletonOracle):
+    WORDS = (("phys", (8,), F),)
+
+    def __init__(self, num_envs, episode_length=1000, seed=0, repeat=1, cup_width=WIDTH, sparse=True, frames=True):
+        super().__init__(num_envs, episode_length, seed, repeat, frames)
+        self.width, self.sparse = F(cup_width), bool(sparse)
         self.hw = half_width(self.width)
-        self.phys = np.zeros((self.N, 8), F)
-        self.t = np.zeros(self.N, np.int32)
-        self.episode = np.zeros(self.N, np.uint32)
-        self.over = np.zeros(self.N, np.uint8)
         # what a run met: the events of substep(), sub-steps with and without reward, the longest run of consecutive
-        # sub-steps with the ball on the floor, rows cut short by the time limit, full rows, reset rows
+        # sub-steps with the ball on the floor
         self.events = dict.fromkeys(EVENTS, 0)
         self.rewarded = self.unrewarded = self.longest_rest = 0
         self._rest = np.zeros(self.N, np.int64)
-        self.cut_by_limit = self.full = self.reset_rows = 0
 
-    def _reset_one(self, e):
-        ep = (int(self.episode[e]) + 1) & M32
-        self.episode[e], self.t[e], self.over[e] = ep, 0, 0
+    def new_episode(self, e, ep):
         self.phys[e] = reset_state(self.seed, e, ep)
         check_state(self.phys[e], self.hw)
 
-    def frames(self):
-        return np.stack([render(self.phys[e], self.width) for e in range(self.N)])
+    def sanitise(self, row):
+        return sanitise(row[0]), sanitise(row[1])
 
-    def reset(self):
-        for e in range(self.N):
-            self._reset_one(e)
-        return self.frames()
+    def frame(self, e):
+        return render(self.phys[e], self.width)
 
-    def step(self, action):
-        """action: float32 [N, A], A >= 2 -> (frame, reward, discount, first, substeps)"""
-        action = np.asarray(action, F)
-        reward, discount, first = np.zeros(self.N, F), np.ones(self.N, F), np.zeros(self.N, np.uint8)
-        substeps = np.zeros(self.N, np.int32)
-        for e in range(self.N):
-            if self.over[e]:
-                self._reset_one(e)
-                first[e] = 1
-                self.reset_rows += 1
-                continue
-            a1, a2 = sanitise(action[e, 0]), sanitise(action[e, 1])
-            p = tuple(self.phys[e])
-            for _ in range(self.repeat):
-                floor = self.events["floor"]
-                p, _ = substep(p, a1, a2, self.hw, self.events)
-                check_state(p, self.hw)
-                self._rest[e] = self._rest[e] + 1 if self.events["floor"] > floor else 0
-                self.longest_rest = max(self.longest_rest, int(self._rest[e]))
-                self.t[e] += 1
-                r = reward_of(p, self.hw, self.sparse)
-                hit = in_cup(p, self.hw)
-                self.rewarded += hit
-                self.unrewarded += not hit
-                reward[e] = F(reward[e] + r)
-                substeps[e] += 1
-                if self.t[e] == self.episode_length:
-                    self.over[e] = 1
-                    break
-            self.phys[e] = p
-            if substeps[e] == self.repeat:
-                self.full += 1
-            else:
-                self.cut_by_limit += 1
-        return self.frames(), reward, discount, first, substeps
-
-    def state(self):
-        return {"phys": self.phys.copy(), "t": self.t.copy(), "episode": self.episode.copy(), "over": self.over.copy()}
+    def substep(self, e, a):
+        floor = self.events["floor"]
+        p, _ = substep(tuple(self.phys[e]), *a, self.hw, self.events)
+        check_state(p, self.hw)
+        self._rest[e] = self._rest[e] + 1 if self.events["floor"] > floor else 0
+        self.longest_rest = max(self.longest_rest, int(self._rest[e]))
+        hit = in_cup(p, self.hw)
+        self.rewarded += hit
+        self.unrewarded += not hit
+        self.phys[e] = p
+        return reward_of(p, self.hw, self.sparse), F(1), False
 
 
 _SEEN = ("events", "rewarded", "unrewarded", "longest_rest", "cut_by_limit", "full", "reset_rows")
@@ -295,42 +257,14 @@ STEPS, EPISODE_LENGTH, SEED = 40, 7, 5
 DRIVEN = tuple((N, A, k, sparse) for (N, A) in ((3, 2), (5, 4)) for k in (1, 2, 16) for sparse in (True, False))
 
 
-def wild_actions(r, N, A):
-    """a row of actions from RandomState r: uniform in [-2, 2], so the clamp is hit; one component in sixteen NaN, one in
-    eight +-inf"""
-    a = r.uniform(-2, 2, (N, A)).astype(F)
-    kind = r.randint(0, 16, (N, A))
-    a[kind == 0] = np.nan
-    a[kind == 1] = np.inf
-    a[kind == 2] = -np.inf
-    return a
-
-
-def _run(o, steps, actions):
-    run = {"frame0": o.frames(), "state0": o.state(), "actions": [], "out": [], "states": []}
-    for s in range(steps):
-        a = actions(s)
-        run["actions"].append(a)
-        run["out"].append(o.step(a))
-        run["states"].append(o.state())
-    for k in _SEEN:
-        run[k] = getattr(o, k)
-    return run
-
-
 def driven_run(N, A, repeat, sparse, seed=SEED, steps=STEPS, episode_length=EPISODE_LENGTH, frames=True):
-    """the oracle driven for `steps` macro steps by wild_actions: the actions it was given, everything it returned (the
-    frames only if asked for: they are most of the time) and the state after every step.  Only the time limit ends an
-    episode, so environments reset together would stay in step for ever: after the reset, t of environment e is set to
-    e mod episode_length ("state0" holds it; a user of the class does the same through load_state_dict()), and the
-    resets stagger from then on"""
+    """the oracle driven for `steps` macro steps by S.wild_actions from the staggered reset (S.stagger): the actions it was
+    given, everything it returned (the frames only if asked for) and the state after every step"""
     r = np.random.RandomState(seed * 100003 + N * 101 + A * 17 + repeat * 3 + int(sparse))
-    o = CatchOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, sparse=sparse)
-    if not frames:
-        o.frames = lambda: None
+    o = CatchOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, sparse=sparse, frames=frames)
     o.reset()
-    o.t[:] = np.arange(N) % episode_length
-    return _run(o, steps, lambda s: wild_actions(r, N, A))
+    S.stagger(o)
+    return S.record(o, steps, lambda s: S.wild_actions(r, N, A), _SEEN)
 
 
 # The physics drive: seven simulator steps from a hanging ball at rest meet a slack or a taut tether and nothing else.  These
@@ -360,13 +294,16 @@ def physics_actions(N, A, s):
 
 
 def physics_run(N, A, repeat, sparse, steps, episode_length, seed=SEED, frames=True):
-    o = CatchOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, sparse=sparse)
-    if not frames:
-        o.frames = lambda: None
+    o = CatchOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, sparse=sparse, frames=frames)
     o.reset()
     for e, p in physics_start().items():
         o.phys[e] = p
-    return _run(o, steps, lambda s: physics_actions(N, A, s))
+    return S.record(o, steps, lambda s: physics_actions(N, A, s), _SEEN)
+
+
+def run(cfg, frames=True):
+    """the run of a configuration of DRIVEN or PHYSICS"""
+    return driven_run(*cfg, frames=frames) if len(cfg) == 4 else physics_run(*cfg, frames=frames)
 
 
 # ---- the poses the frame is compared at: (phys, cup_width) ------------------------------------------------------------------
@@ -433,25 +370,20 @@ def episode(seed, e, ep, policy, steps=1000, cup_width=WIDTH, sparse=True):
 
 
 # ---- the argument lists drq_vec_catch_step refuses: shared by the CPU and the GPU test -------------------------------------
+_BAD_WIDTHS = (0.1599, 0.401, float("nan"), 0.0, -0.3, float("inf"))
+
+
 def refused_calls(S0, ACT, FR, SC):
     """the argument lists drq_vec_catch_step must refuse, around one well-formed list over the four given base addresses
     (state arrays 0x100 apart from S0, the action, the frame, the scalar outputs 0x100 apart from SC)"""
     #     phys t          episode     over        N  A  action seed L repeat reset width sparse frame
     ok = [S0, S0 + 0x100, S0 + 0x200, S0 + 0x300, 5, 2, ACT, 7, 9, 2, 0, 0.3, 1, FR,
           SC, SC + 0x100, SC + 0x200, SC + 0x300]                          # reward discount first substeps
-    sub = lambda k, v, base=ok: base[:k] + [v] + base[k + 1:]
-    bad = [sub(k, None) for k in (0, 1, 2, 3, 6, 13, 14, 15, 16, 17)]      # every pointer; action: no reset_all
-    for k, vals in ((4, (0, -1, 2 ** 31)), (5, (1, 0, -2)), (8, (0, -5)), (9, (0, -1, 17, 2 ** 31 - 1)), (10, (2, -1)),
-                    (11, (0.1599, 0.401, float("nan"), 0.0, -0.3, float("inf"))), (12, (2, -1))):
-        bad += [sub(k, v) for v in vals]                                   # N, A, episode_length, repeat, reset_all, width, sparse
-    bad += [sub(13, FR + m) for m in (1, 4, 8)]                            # frame not 16-byte aligned
-    bad += [sub(k, ok[k] + 2) for k in (0, 1, 2, 6, 14, 15, 17)]           # a float / int array not 4-byte aligned
+    bad = S.refused_steps(ok, "w w w b N A action - L repeat reset - - frame w w b w", {11: _BAD_WIDTHS, 12: (2, -1)})
     assert len(bad) == 10 + 22 + 3 + 7
     return bad
 
 
 def refused_renders(S0, FR):
     """the argument lists drq_vec_catch_render must refuse: (phys, N, cup_width, frame)"""
-    return [[None, 3, 0.3, FR], [S0, 3, 0.3, None], [S0, 0, 0.3, FR], [S0, -1, 0.3, FR], [S0, 2 ** 31, 0.3, FR],
-            [S0, 3, 0.3, FR + 4], [S0, 3, 0.3, FR + 8], [S0 + 2, 3, 0.3, FR], [S0, 3, 0.1599, FR], [S0, 3, 0.401, FR],
-            [S0, 3, float("nan"), FR], [S0, 3, float("inf"), FR]]
+    return S.refused_reads([S0, 3, 0.3, FR], "w N - frame", {2: (0.1599, 0.401, float("nan"), float("inf"))})

@@ -19,7 +19,7 @@ M32 = 0xFFFFFFFF
 SIDE = 84
 TARGET_RGB, AGENT_RGB = (64, 255, 64), (255, 64, 64)
 _II, _JJ = np.meshgrid(np.arange(SIDE), np.arange(SIDE), indexing="ij")
-_BACKGROUND = (32 + ((_II + _JJ) >> 2)).astype(np.uint8)
+BACKGROUND = (32 + ((_II + _JJ) >> 2)).astype(np.uint8)
 
 
 def fmix32(h):
@@ -57,7 +57,7 @@ def disc(cx, cy, r2):
 
 def render(pos, target):
     """the frame of one state"""
-    frame = np.stack([_BACKGROUND] * 3)
+    frame = np.stack([BACKGROUND] * 3)
     for (x, y), r2, rgb in ((target, 25, TARGET_RGB), (pos, 16, AGENT_RGB)):
         m = disc(centre(x), centre(y), r2)
         for c in range(3):

@@ -1,8 +1,9 @@
 """numpy / Python-int restatement of the device environment's maze (a helper module: not collected).  The contract is the
 comment of include/drqv2_hip.h ("device environment", "Maze"), stated here once more: the draws, the generator, the
 symmetries, the loops and the pools on sets of walls between cells (no bit tricks: the device's boards are compared with
-these sets), the sub-step on np.float32 scalars, one rounding per operation in the written order, the wrapper fold, the
-flood fill on Python integers and the pixel rule as rectangles around segments.  The hash is tests/vec_env_oracle.py's.
+these sets), the sub-step on np.float32 scalars, one rounding per operation in the written order, the flood fill on Python
+integers and the pixel rule as rectangles around segments.  The hash is tests/vec_env_oracle.py's; the macro step is the
+skeleton's (tests/vec_skeleton_oracle.py): d_i = 1, and the task never ends an episode.
 
   boards     cell (r, c) is bit 8 r + c; east bit (r, c): a wall between (r, c) and (r, c + 1); south bit: (r, c) | (r + 1, c)
   draws      h_k = fmix32(s ^ e 0x9E3779B9 ^ episode 0x85EBCA6B ^ k 0xC2B2AE35)
@@ -18,19 +19,15 @@ flood fill on Python integers and the pixel rule as rectangles around segments. 
 """
 import numpy as np
 
-from tests.vec_env_oracle import F, M32, SIDE, clamp1, fmix32
+from tests import vec_skeleton_oracle as S
+from tests.vec_env_oracle import BACKGROUND, F, M32, SIDE, fmix32
+from tests.vec_skeleton_oracle import sanitise
 
 SIZES = (3, 4, 6, 7, 8)
 MOVE, MARGIN = F(0.05), F(0.04)
 UNITS, WALL_T, AGENT_R2 = 1344, 12, 729
 GOAL_RGB, WALL_RGB, AGENT_RGB = (64, 255, 64), (255, 255, 255), (255, 64, 255)
-_II, _JJ = np.meshgrid(np.arange(SIDE), np.arange(SIDE), indexing="ij")
-_BACKGROUND = (32 + ((_II + _JJ) >> 2)).astype(np.uint8)
 _P = 16 * np.arange(SIDE) + 8                      # a pixel's centre along either axis
-
-
-def sanitise(v):
-    return F(0) if np.isnan(v) else clamp1(v)
 
 
 def hdraw(seed, e, episode, k):
@@ -249,7 +246,7 @@ def render(G, pos, walls, cells):
     inset = lambda k: (_P >= k * W + W // 4) & (_P < (k + 1) * W - W // 4)
     AX, AY = agent_centre(pos)
     agent = ((_P - AX) ** 2)[None, :] + ((_P - AY) ** 2)[:, None] <= AGENT_R2
-    frame = np.stack([_BACKGROUND] * 3)
+    frame = np.stack([BACKGROUND] * 3)
     for m, rgb in ((inset(gr)[:, None] & inset(gc)[None, :], GOAL_RGB), (wall_mask(G, walls), WALL_RGB), (agent, AGENT_RGB)):
         for ch in range(3):
             frame[ch][m] = rgb[ch]
@@ -265,79 +262,49 @@ def as_u64(v):
     return int(np.array(v, np.int64).view(np.uint64))
 
 
-class MazeOracle:
-    def __init__(self, num_envs, episode_length=200, seed=0, repeat=1, size=6, loops=0, layouts=0, layout_seed=0, sparse=True):
-        assert 1 <= int(repeat) <= 16 and size in SIZES and 0 <= loops <= 255 and 0 <= layouts <= 65535
-        self.N, self.episode_length, self.seed = int(num_envs), int(episode_length), int(seed) & M32
-        self.repeat, self.G, self.loops, self.layouts = int(repeat), int(size), int(loops), int(layouts)
+def geodesics_of(G, state):
+    """the flood fill's distance from every environment's cell to its goal, of the state words `state`: int32 [N]"""
+    return np.array([geodesic(G, (as_u64(w[0]), as_u64(w[1])), cell_of(G, pos), int(cells[1]))
+                     for pos, w, cells in zip(state["pos"], state["walls"], state["cells"])], np.int32)
+
+
+class MazeOracle(S.SkeletonOracle):
+    WORDS = (("pos", (2,), F), ("walls", (2,), np.int64), ("cells", (2,), np.int32))
+
+    def __init__(self, num_envs, episode_length=200, seed=0, repeat=1, size=6, loops=0, layouts=0, layout_seed=0, sparse=True,
+                 frames=True):
+        assert size in SIZES and 0 <= loops <= 255 and 0 <= layouts <= 65535
+        super().__init__(num_envs, episode_length, seed, repeat, frames)
+        self.G, self.loops, self.layouts = int(size), int(loops), int(layouts)
         self.layout_seed, self.sparse = int(layout_seed) & M32, bool(sparse)
-        self.pos = np.zeros((self.N, 2), F)
-        self.walls = np.zeros((self.N, 2), np.int64)
-        self.cells = np.zeros((self.N, 2), np.int32)
-        self.t = np.zeros(self.N, np.int32)
-        self.episode = np.zeros(self.N, np.uint32)
-        self.over = np.zeros(self.N, np.uint8)
-        # what a run met: every axis move as (cell before, cell after, side cut, walls), sub-steps in the goal cell,
-        # rows cut short by the time limit, full rows, reset rows
+        # what a run met: every axis move as (cell before, cell after, side cut, walls), sub-steps in the goal cell
         self.moves = []
-        self.in_goal = self.cut_by_limit = self.full = self.reset_rows = 0
+        self.in_goal = 0
 
     def walls_of(self, e):
         return as_u64(self.walls[e, 0]), as_u64(self.walls[e, 1])
 
-    def _reset_one(self, e):
-        ep = (int(self.episode[e]) + 1) & M32
-        self.episode[e], self.t[e], self.over[e] = ep, 0, 0
+    def geodesics(self):
+        return geodesics_of(self.G, self.state())
+
+    def new_episode(self, e, ep):
         pos, walls, cells = reset_state(self.seed, e, ep, self.G, self.loops, self.layouts, self.layout_seed)
         self.pos[e], self.cells[e] = pos, cells
         self.walls[e] = [as_i64(w) for w in walls]
 
-    def frames(self):
-        return np.stack([render(self.G, self.pos[e], self.walls_of(e), self.cells[e]) for e in range(self.N)])
+    def sanitise(self, row):
+        return sanitise(row[0]), sanitise(row[1])
 
-    def geodesics(self):
-        return np.array([geodesic(self.G, self.walls_of(e), cell_of(self.G, self.pos[e]), int(self.cells[e, 1]))
-                         for e in range(self.N)], np.int32)
+    def frame(self, e):
+        return render(self.G, self.pos[e], self.walls_of(e), self.cells[e])
 
-    def reset(self):
-        for e in range(self.N):
-            self._reset_one(e)
-        return self.frames()
-
-    def step(self, action):
-        """action: float32 [N, A], A >= 2 -> (frame, reward, discount, first, substeps)"""
-        action = np.asarray(action, F)
-        reward, discount, first = np.zeros(self.N, F), np.ones(self.N, F), np.zeros(self.N, np.uint8)
-        substeps = np.zeros(self.N, np.int32)
-        for e in range(self.N):
-            if self.over[e]:
-                self._reset_one(e)
-                first[e] = 1
-                self.reset_rows += 1
-                continue
-            ax, ay = sanitise(action[e, 0]), sanitise(action[e, 1])
-            pos, walls, goal = tuple(self.pos[e]), self.walls_of(e), int(self.cells[e, 1])
-            for _ in range(self.repeat):
-                pos, trace = substep(self.G, pos, walls, ax, ay)
-                self.moves += [m + (walls,) for m in trace]
-                self.t[e] += 1
-                r = reward_of(self.G, pos, walls, goal, self.sparse)
-                self.in_goal += cell_of(self.G, pos) == goal
-                reward[e] = F(reward[e] + r)
-                substeps[e] += 1
-                if self.t[e] == self.episode_length:
-                    self.over[e] = 1
-                    break
-            self.pos[e] = pos
-            if substeps[e] == self.repeat:
-                self.full += 1
-            else:
-                self.cut_by_limit += 1
-        return self.frames(), reward, discount, first, substeps
-
-    def state(self):
-        return {"pos": self.pos.copy(), "walls": self.walls.copy(), "cells": self.cells.copy(), "t": self.t.copy(),
-                "episode": self.episode.copy(), "over": self.over.copy()}
+    def substep(self, e, a):
+        walls, goal = self.walls_of(e), int(self.cells[e, 1])
+        pos, trace = substep(self.G, tuple(self.pos[e]), walls, *a)
+        self.moves += [m + (walls,) for m in trace]
+        self.in_goal += cell_of(self.G, pos) == goal
+        self.pos[e] = pos
+        return reward_of(self.G, pos, walls, goal, self.sparse), F(1), False
 
 
 _SEEN = ("moves", "in_goal", "cut_by_limit", "full", "reset_rows")
@@ -375,8 +342,7 @@ def controller_action(G, pos, walls, goal):
 
 def controlled_returns(size, N=4, episodes=2, episode_length=200, seed=0, controlled=True):
     """the sparse return of every episode of a run under the controller (or under the zero action): [N x episodes]"""
-    o = MazeOracle(N, episode_length=episode_length, seed=seed, size=size)
-    o.frames = lambda: None
+    o = MazeOracle(N, episode_length=episode_length, seed=seed, size=size, frames=False)
     o.reset()
     returns, total = [], np.zeros(N)
     while len(returns) < N * episodes:
@@ -402,28 +368,10 @@ VARIANTS = ((3, 2, 2, True, 8, 0, 2, 77), (5, 4, 2, False, 8, 96, 0, 0))
 PUSHED = ((5, 2, 16, True, 3, 24, 1000), (5, 2, 16, False, 8, 24, 1000))
 
 
-def wild_actions(r, N, A):
-    """a row of actions from RandomState r: uniform in [-2, 2], so the clamp is hit; one component in sixteen NaN, one in
-    eight +-inf"""
-    a = r.uniform(-2, 2, (N, A)).astype(F)
-    kind = r.randint(0, 16, (N, A))
-    a[kind == 0] = np.nan
-    a[kind == 1] = np.inf
-    a[kind == 2] = -np.inf
-    return a
-
-
 def _run(o, steps, actions):
-    run = {"frame0": o.frames(), "state0": o.state(), "geodesic0": o.geodesics(), "actions": [], "out": [], "states": [],
-           "geodesics": []}
-    for s in range(steps):
-        a = actions(s)
-        run["actions"].append(a)
-        run["out"].append(o.step(a))
-        run["states"].append(o.state())
-        run["geodesics"].append(o.geodesics())
-    for k in _SEEN:
-        run[k] = getattr(o, k)
+    """S.record, and the geodesic distances of the first state and of the state after every step"""
+    run = S.record(o, steps, actions, _SEEN)
+    run["geodesic0"], run["geodesics"] = geodesics_of(o.G, run["state0"]), [geodesics_of(o.G, st) for st in run["states"]]
     return run
 
 
@@ -431,20 +379,16 @@ def driven_run(N, A, repeat, sparse, size, loops=0, layouts=0, layout_seed=0, se
                episode_length=EPISODE_LENGTH, frames=True):
     """The oracle driven for `steps` macro steps: the actions it was given, everything it returned (the frames only if
     asked for: they are most of the time), the state and the geodesic distances after every step.  Half of the action
-    rows of an environment are wild_actions, half the controller's times 1.5 (beyond the clamp), so that in episodes of
-    seven steps walls are met and goals are entered.  Only the time limit ends an episode, so environments reset
-    together would stay in step for ever: after the reset, t of environment e is set to e mod episode_length ("state0"
-    holds it; a user of the class does the same through load_state_dict()), and the resets stagger from then on"""
+    rows of an environment are S.wild_actions, half the controller's times 1.5 (beyond the clamp), so that in episodes of
+    seven steps walls are met and goals are entered.  The reset is staggered (S.stagger)"""
     r = np.random.RandomState(seed * 100003 + N * 101 + A * 17 + repeat * 3 + int(sparse) + size * 1009 + loops + layouts)
     o = MazeOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, size=size, loops=loops, layouts=layouts,
-                   layout_seed=layout_seed, sparse=sparse)
-    if not frames:
-        o.frames = lambda: None
+                   layout_seed=layout_seed, sparse=sparse, frames=frames)
     o.reset()
-    o.t[:] = np.arange(N) % episode_length
+    S.stagger(o)
 
     def actions(s):
-        a = wild_actions(r, N, A)
+        a = S.wild_actions(r, N, A)
         for e in np.flatnonzero(r.randint(0, 2, N)):
             if not o.over[e]:
                 a[e, :2] = np.array(controller_action(size, o.pos[e], o.walls_of(e), int(o.cells[e, 1])), F) * F(1.5)
@@ -458,9 +402,7 @@ _PUSHES = ((1, 1), (1, -1), (-1, -1), (-1, 1), (1, 0), (0, 1), (-1, 0), (0, -1))
 def pushed_run(N, A, repeat, sparse, size, steps, episode_length, seed=SEED, frames=True):
     """one long episode under actions that hold a direction, diagonal or along an axis, for three macro steps of `repeat`
     simulator steps and lie beyond the clamp: every environment is pushed into walls and corners and slides along them"""
-    o = MazeOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, size=size, loops=64, sparse=sparse)
-    if not frames:
-        o.frames = lambda: None
+    o = MazeOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, size=size, loops=64, sparse=sparse, frames=frames)
     o.reset()
 
     def actions(s):
@@ -469,6 +411,11 @@ def pushed_run(N, A, repeat, sparse, size, steps, episode_length, seed=SEED, fra
             a[e, :2] = np.array(_PUSHES[(e + s // 3) % 8], F) * F(1.5)
         return a
     return _run(o, steps, actions)
+
+
+def run(cfg, frames=True):
+    """the run of a configuration of DRIVEN, VARIANTS or PUSHED"""
+    return pushed_run(*cfg, frames=frames) if cfg in PUSHED else driven_run(*cfg, frames=frames)
 
 
 # ---- the poses the frame, the move and the flood fill are compared at: (size, pos, walls, cells) -------------------------------
@@ -510,31 +457,17 @@ def refused_calls(S0, ACT, FR, SC):
     #     pos walls       cells       t           episode     over        N  A  action seed L repeat reset size loops layouts
     ok = [S0, S0 + 0x100, S0 + 0x200, S0 + 0x300, S0 + 0x400, S0 + 0x500, 5, 2, ACT, 7, 9, 2, 0, 6, 0, 0,
           3, 1, FR, SC, SC + 0x100, SC + 0x200, SC + 0x300]         # layout_seed sparse frame reward discount first substeps
-    sub = lambda k, v, base=ok: base[:k] + [v] + base[k + 1:]
-    bad = [sub(k, None) for k in (0, 1, 2, 3, 4, 5, 8, 18, 19, 20, 21, 22)]     # every pointer; action: no reset_all
-    for k, vals in ((6, (0, -1, 2 ** 31)), (7, (1, 0, -2)), (10, (0, -5)), (11, (0, -1, 17, 2 ** 31 - 1)), (12, (2, -1)),
-                    (13, (0, 1, 2, 5, 9, 16, -3)), (14, (-1, 256)), (15, (-1, 65536)), (17, (2, -1))):
-        bad += [sub(k, v) for v in vals]              # N, A, episode_length, repeat, reset_all, size, loops, layouts, sparse
-    bad += [sub(18, FR + m) for m in (1, 4, 8)]                                 # frame not 16-byte aligned
-    bad += [sub(1, ok[1] + 4)]                                                  # walls not 8-byte aligned
-    bad += [sub(k, ok[k] + 2) for k in (0, 1, 2, 3, 4, 8, 19, 20, 22)]          # a float / int array not 4-byte aligned
+    bad = S.refused_steps(ok, "w w8 w w w b N A action - L repeat reset - - - - - frame w w b w",
+                          {13: (0, 1, 2, 5, 9, 16, -3), 14: (-1, 256), 15: (-1, 65536), 17: (2, -1)})     # size, loops, layouts, sparse
     assert len(bad) == 12 + 27 + 3 + 1 + 9
     return bad
 
 
 def refused_renders(S0, FR):
     """the argument lists drq_vec_maze_render must refuse: (pos, walls, cells, N, size, frame)"""
-    W0, C0 = S0 + 0x100, S0 + 0x200
-    return [[None, W0, C0, 3, 6, FR], [S0, None, C0, 3, 6, FR], [S0, W0, None, 3, 6, FR], [S0, W0, C0, 3, 6, None],
-            [S0, W0, C0, 0, 6, FR], [S0, W0, C0, -1, 6, FR], [S0, W0, C0, 2 ** 31, 6, FR], [S0, W0, C0, 3, 6, FR + 4],
-            [S0, W0, C0, 3, 6, FR + 8], [S0 + 2, W0, C0, 3, 6, FR], [S0, W0 + 4, C0, 3, 6, FR], [S0, W0, C0 + 2, 3, 6, FR],
-            [S0, W0, C0, 3, 5, FR], [S0, W0, C0, 3, 0, FR], [S0, W0, C0, 3, 9, FR]]
+    return S.refused_reads([S0, S0 + 0x100, S0 + 0x200, 3, 6, FR], "w w8 w N - frame", {4: (5, 0, 9)})
 
 
 def refused_geodesics(S0, OUT):
     """the argument lists drq_vec_maze_geodesic must refuse: (walls, cells, pos, N, size, out)"""
-    W0, C0 = S0 + 0x100, S0 + 0x200
-    return [[None, C0, S0, 3, 6, OUT], [W0, None, S0, 3, 6, OUT], [W0, C0, None, 3, 6, OUT], [W0, C0, S0, 3, 6, None],
-            [W0, C0, S0, 0, 6, OUT], [W0, C0, S0, -1, 6, OUT], [W0, C0, S0, 2 ** 31, 6, OUT], [W0 + 4, C0, S0, 3, 6, OUT],
-            [W0, C0 + 2, S0, 3, 6, OUT], [W0, C0, S0 + 2, 3, 6, OUT], [W0, C0, S0, 3, 6, OUT + 2], [W0, C0, S0, 3, 5, OUT],
-            [W0, C0, S0, 3, 2, OUT], [W0, C0, S0, 3, 10, OUT]]
+    return S.refused_reads([S0 + 0x100, S0 + 0x200, S0, 3, 6, OUT], "w8 w w N - w", {4: (5, 2, 10)})

@@ -14,26 +14,23 @@ hash and the draws are those of tests/vec_env_oracle.py, normalise() is the cart
              per joint k = w 0.01; k != 0: (c, s) = normalise(c - s k, s + c k); t += 1; over at the limit
   reward     c12 = c1 c2 - s1 s2; s12 = s1 c2 + c1 s2; tip = (0.5 c1 + 0.5 c12, 0.5 s1 + 0.5 s12); d = tip - target;
              d2 = dx dx + dy dy; sparse: d2 <= radius radius ? 1 : 0; dense: 1 / (1 + 4 d2)
-  macro step a1, a2 = action[e, 0:2] sanitised once; reward = reward + r_i for up to `repeat` sub-steps, stopping after
-             the one that set over; discount = 1, first = 0, substeps = the sub-steps executed
+  macro step the skeleton's (tests/vec_skeleton_oracle.py); a1, a2 = action[e, 0:2] sanitised once; d_i = 1, and the task
+             never ends an episode
   frame      in 1/16 pixel, 576 to the unit, the shoulder at (672, 672), y upwards (render below)
 """
 import numpy as np
 
 from tests.vec_cartpole_oracle import capsule, clamp_to, normalise
-from tests.vec_env_oracle import F, M32, SIDE, clamp1, draw
+from tests import vec_skeleton_oracle as S
+from tests.vec_env_oracle import BACKGROUND, F, SIDE, clamp1, draw
+from tests.vec_skeleton_oracle import sanitise
 
 K, B = F(2), F(0.5)
 DT, MAX_W = F(0.01), F(16)
 CENTRE, ARM_R, TIP_R = 672, 24, 32
 TARGET_RGB, UPPER_RGB, FORE_RGB, TIP_RGB = (64, 255, 64), (64, 64, 255), (255, 64, 64), (255, 255, 64)
 _II, _JJ = np.meshgrid(np.arange(SIDE), np.arange(SIDE), indexing="ij")
-_BACKGROUND = (32 + ((_II + _JJ) >> 2)).astype(np.uint8)
 _PX, _PY = (16 * _JJ + 8).astype(np.int64), (16 * _II + 8).astype(np.int64)
-
-
-def sanitise(v):
-    return F(0) if np.isnan(v) else clamp1(v)
 
 
 def direction(v):
@@ -129,7 +126,7 @@ def disc(X, Y, r):
 def render(phys, target, radius):
     """the frame of one state"""
     EX, EY, TX, TY, GX, GY, GR = points(phys, target, F(radius))
-    frame = np.stack([_BACKGROUND] * 3)
+    frame = np.stack([BACKGROUND] * 3)
     for m, rgb in ((disc(GX, GY, GR), TARGET_RGB), (capsule(CENTRE, CENTRE, EX, EY, ARM_R), UPPER_RGB),
                    (capsule(EX, EY, TX, TY, ARM_R), FORE_RGB), (disc(TX, TY, TIP_R), TIP_RGB)):
         for ch in range(3):
@@ -141,72 +138,35 @@ def quadrant(c, s):
     return (0 if c >= 0 else 1) if s >= 0 else (3 if c >= 0 else 2)
 
 
-class ReacherOracle:
-    def __init__(self, num_envs, episode_length=1000, seed=0, repeat=1, target_radius=0.15, sparse=True):
-        assert 1 <= int(repeat) <= 16
-        self.N, self.episode_length, self.seed = int(num_envs), int(episode_length), int(seed) & M32
-        self.repeat, self.radius, self.sparse = int(repeat), F(target_radius), bool(sparse)
-        self.phys = np.zeros((self.N, 6), F)
-        self.target = np.zeros((self.N, 2), F)
-        self.t = np.zeros(self.N, np.int32)
-        self.episode = np.zeros(self.N, np.uint32)
-        self.over = np.zeros(self.N, np.uint8)
-        # what a run met: sub-steps with and without reward, clamps of w, the quadrants either joint's vector was in,
-        # rows cut short by the time limit, full rows, reset rows
+class ReacherOracle(S.SkeletonOracle):
+    WORDS = (("phys", (6,), F), ("target", (2,), F))
+
+    def __init__(self, num_envs, episode_length=1000, seed=0, repeat=1, target_radius=0.15, sparse=True, frames=True):
+        super().__init__(num_envs, episode_length, seed, repeat, frames)
+        self.radius, self.sparse = F(target_radius), bool(sparse)
+        # what a run met: sub-steps with and without reward, clamps of w, the quadrants either joint's vector was in
         self.rewarded = self.unrewarded = self.clamped = 0
         self.quadrants = (set(), set())
-        self.cut_by_limit = self.full = self.reset_rows = 0
 
-    def _reset_one(self, e):
-        ep = (int(self.episode[e]) + 1) & M32
-        self.episode[e], self.t[e], self.over[e] = ep, 0, 0
+    def new_episode(self, e, ep):
         self.phys[e], self.target[e] = reset_state(self.seed, e, ep, self.radius)
 
-    def frames(self):
-        return np.stack([render(self.phys[e], self.target[e], self.radius) for e in range(self.N)])
+    def sanitise(self, row):
+        return sanitise(row[0]), sanitise(row[1])
 
-    def reset(self):
-        for e in range(self.N):
-            self._reset_one(e)
-        return self.frames()
+    def frame(self, e):
+        return render(self.phys[e], self.target[e], self.radius)
 
-    def step(self, action):
-        """action: float32 [N, A], A >= 2 -> (frame, reward, discount, first, substeps)"""
-        action = np.asarray(action, F)
-        reward, discount, first = np.zeros(self.N, F), np.ones(self.N, F), np.zeros(self.N, np.uint8)
-        substeps = np.zeros(self.N, np.int32)
-        for e in range(self.N):
-            if self.over[e]:
-                self._reset_one(e)
-                first[e] = 1
-                self.reset_rows += 1
-                continue
-            a1, a2 = sanitise(action[e, 0]), sanitise(action[e, 1])
-            p, target = tuple(self.phys[e]), tuple(self.target[e])
-            for _ in range(self.repeat):
-                p, cut = substep(p, a1, a2)
-                self.clamped += cut
-                self.quadrants[0].add(quadrant(p[0], p[1]))
-                self.quadrants[1].add(quadrant(p[3], p[4]))
-                self.t[e] += 1
-                r = reward_of(p, target, self.radius, self.sparse)
-                self.rewarded += r > 0 if self.sparse else 0
-                self.unrewarded += r == 0
-                reward[e] = F(reward[e] + r)
-                substeps[e] += 1
-                if self.t[e] == self.episode_length:
-                    self.over[e] = 1
-                    break
-            self.phys[e] = p
-            if substeps[e] == self.repeat:
-                self.full += 1
-            else:
-                self.cut_by_limit += 1
-        return self.frames(), reward, discount, first, substeps
-
-    def state(self):
-        return {"phys": self.phys.copy(), "target": self.target.copy(), "t": self.t.copy(), "episode": self.episode.copy(),
-                "over": self.over.copy()}
+    def substep(self, e, a):
+        p, cut = substep(tuple(self.phys[e]), *a)
+        self.clamped += cut
+        self.quadrants[0].add(quadrant(p[0], p[1]))
+        self.quadrants[1].add(quadrant(p[3], p[4]))
+        r = reward_of(p, tuple(self.target[e]), self.radius, self.sparse)
+        self.rewarded += r > 0 if self.sparse else 0
+        self.unrewarded += r == 0
+        self.phys[e] = p
+        return r, F(1), False
 
 
 _SEEN = ("rewarded", "unrewarded", "clamped", "quadrants", "cut_by_limit", "full", "reset_rows")
@@ -217,42 +177,15 @@ DRIVEN_RADIUS = 0.3         # the largest: in episodes of seven steps a fingerti
 DRIVEN = tuple((N, A, k, sparse) for (N, A) in ((3, 2), (5, 4)) for k in (1, 2, 16) for sparse in (True, False))
 
 
-def wild_actions(r, N, A):
-    """a row of actions from RandomState r: uniform in [-2, 2], so the clamp is hit; one component in sixteen NaN, one in
-    eight +-inf"""
-    a = r.uniform(-2, 2, (N, A)).astype(F)
-    kind = r.randint(0, 16, (N, A))
-    a[kind == 0] = np.nan
-    a[kind == 1] = np.inf
-    a[kind == 2] = -np.inf
-    return a
-
-
-def _run(o, steps, actions):
-    run = {"frame0": o.frames(), "state0": o.state(), "actions": [], "out": [], "states": []}
-    for s in range(steps):
-        a = actions(s)
-        run["actions"].append(a)
-        run["out"].append(o.step(a))
-        run["states"].append(o.state())
-    for k in _SEEN:
-        run[k] = getattr(o, k)
-    return run
-
-
 def driven_run(N, A, repeat, sparse, seed=SEED, steps=STEPS, episode_length=EPISODE_LENGTH, frames=True):
-    """the oracle driven for `steps` macro steps by wild_actions: the actions it was given, everything it returned (the
-    frames only if asked for: they are most of the time) and the state after every step.  Only the time limit ends an
-    episode, so environments reset together would stay in step for ever: after the reset, t of environment e is set to
-    e mod episode_length ("state0" holds it; a user of the class does the same through load_state_dict()), and the
-    resets stagger from then on"""
+    """the oracle driven for `steps` macro steps by S.wild_actions from the staggered reset (S.stagger): the actions it was
+    given, everything it returned (the frames only if asked for) and the state after every step"""
     r = np.random.RandomState(seed * 100003 + N * 101 + A * 17 + repeat * 3 + int(sparse))
-    o = ReacherOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, target_radius=DRIVEN_RADIUS, sparse=sparse)
-    if not frames:
-        o.frames = lambda: None
+    o = ReacherOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, target_radius=DRIVEN_RADIUS, sparse=sparse,
+                      frames=frames)
     o.reset()
-    o.t[:] = np.arange(N) % episode_length
-    return _run(o, steps, lambda s: wild_actions(r, N, A))
+    S.stagger(o)
+    return S.record(o, steps, lambda s: S.wild_actions(r, N, A), _SEEN)
 
 
 # The physics drive: in seven simulator steps from rest no joint leaves its quadrant and no velocity comes near the
@@ -273,13 +206,17 @@ def physics_actions(N, A, s):
 
 
 def physics_run(N, A, repeat, sparse, steps, episode_length, seed=SEED, frames=True):
-    o = ReacherOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, target_radius=PHYSICS_RADIUS, sparse=sparse)
-    if not frames:
-        o.frames = lambda: None
+    o = ReacherOracle(N, episode_length=episode_length, seed=seed, repeat=repeat, target_radius=PHYSICS_RADIUS, sparse=sparse,
+                      frames=frames)
     o.reset()
     for e, sgn in ((2, F(1)), (3, F(-1))):
         o.phys[e] = (F(1), F(0), F(15.9) * sgn, F(0), -sgn, F(15.9) * sgn)
-    return _run(o, steps, lambda s: physics_actions(N, A, s))
+    return S.record(o, steps, lambda s: physics_actions(N, A, s), _SEEN)
+
+
+def run(cfg, frames=True):
+    """the run of a configuration of DRIVEN or PHYSICS"""
+    return driven_run(*cfg, frames=frames) if len(cfg) == 4 else physics_run(*cfg, frames=frames)
 
 
 # ---- the poses the frame is compared at: (phys, target, target_radius) ----------------------------------------------------
@@ -339,21 +276,12 @@ def refused_calls(S0, ACT, FR, SC):
     #     phys target     t           episode     over        N  A  action seed L repeat reset radius sparse frame
     ok = [S0, S0 + 0x100, S0 + 0x200, S0 + 0x300, S0 + 0x400, 5, 2, ACT, 7, 9, 2, 0, 0.15, 1, FR,
           SC, SC + 0x100, SC + 0x200, SC + 0x300]                         # reward discount first substeps
-    sub = lambda k, v, base=ok: base[:k] + [v] + base[k + 1:]
-    bad = [sub(k, None) for k in (0, 1, 2, 3, 4, 7, 14, 15, 16, 17, 18)]   # every pointer; action: no reset_all
-    for k, vals in ((5, (0, -1, 2 ** 31)), (6, (1, 0, -2)), (9, (0, -5)), (10, (0, -1, 17, 2 ** 31 - 1)), (11, (2, -1)),
-                    (12, (0.0199, 0.301, float("nan"), 0.0, -0.15, float("inf"))), (13, (2, -1))):
-        bad += [sub(k, v) for v in vals]                                   # N, A, episode_length, repeat, reset_all, radius, sparse
-    bad += [sub(14, FR + m) for m in (1, 4, 8)]                            # frame not 16-byte aligned
-    bad += [sub(k, ok[k] + 2) for k in (0, 1, 2, 3, 7, 15, 16, 18)]        # a float / int array not 4-byte aligned
+    bad = S.refused_steps(ok, "w w w w b N A action - L repeat reset - - frame w w b w",
+                          {12: (0.0199, 0.301, float("nan"), 0.0, -0.15, float("inf")), 13: (2, -1)})      # radius, sparse
     assert len(bad) == 11 + 22 + 3 + 8
     return bad
 
 
 def refused_renders(S0, FR):
     """the argument lists drq_vec_reacher_render must refuse: (phys, target, N, target_radius, frame)"""
-    T0 = S0 + 0x100
-    return [[None, T0, 3, 0.15, FR], [S0, None, 3, 0.15, FR], [S0, T0, 3, 0.15, None], [S0, T0, 0, 0.15, FR],
-            [S0, T0, -1, 0.15, FR], [S0, T0, 2 ** 31, 0.15, FR], [S0, T0, 3, 0.15, FR + 4], [S0, T0, 3, 0.15, FR + 8],
-            [S0 + 2, T0, 3, 0.15, FR], [S0, T0 + 2, 3, 0.15, FR], [S0, T0, 3, 0.0199, FR], [S0, T0, 3, 0.301, FR],
-            [S0, T0, 3, float("nan"), FR]]
+    return S.refused_reads([S0, S0 + 0x100, 3, 0.15, FR], "w w N - frame", {3: (0.0199, 0.301, float("nan"))})
