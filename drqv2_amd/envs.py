@@ -35,6 +35,12 @@ either slack or taut, and three capsules that the ball collides with, in the ima
 that switch regime inside an episode, and a sparse reward that needs a timed sequence: swing the ball up, then get the cup
 under it.  Specified in include/drqv2_hip.h ("Catch"), restated by tests/vec_catch_oracle.py, which also holds a scripted
 controller that solves it.
+
+VecWalker is a seventh (csrc/vecwalker.hip, drq_vec_walker_step): a planar legged runner of six particles and five rods
+under position-based dynamics, with four muscles and a ground with friction, in the image of the reference's walker_stand,
+walker_walk, walker_run and cheetah_run -- the one locomotion task here: ground contact, four actuators, an unbounded
+coordinate that the camera follows, and a reward on speed.  Specified in include/drqv2_hip.h ("Walker"), restated by
+tests/vec_walker_oracle.py, which also holds a scripted open-loop gait that makes it run.
 """
 import torch
 
@@ -418,6 +424,55 @@ class VecCatch(_VecTask):
 
     def _config(self):
         return dict(super()._config(), cup_width=self.cup_width, sparse=self.sparse)
+
+
+class VecWalker(_VecTask):
+    """N environments of the walker on the device: a planar legged runner above a ground at y = 0 with gravity 10 along
+    -y, in a world that is unbounded in x (periodic with period 4).  The body is six unit point masses -- shoulder, hip,
+    front knee, front foot, back knee, back foot -- held by five rigid rods (a torso of 0.4 with a leg of two limbs of
+    0.25 at either end) under position-based dynamics.  action[:, 0:4] in [-1, 1] sets the target lengths of four muscles,
+    each a distance across a joint: front hip, front knee, back hip, back knee (NaN counts as 0; further columns are
+    ignored).  A muscle closes half its error per sweep up to a force limit; hard limits on the same distances keep every
+    joint away from straight and from folded.  The ground stops a particle at y = 0 and leaves it a tenth of its
+    horizontal velocity, which is the friction the body pushes on.  speed = 0 pays stand, the torso's height (0 at 0.1,
+    1 from 0.2) times its uprightness; speed > 0 pays stand * (1 + 5 * move) / 6 with move = clamp(v / speed, 0, 1) of the
+    torso's forward velocity, the form of DMC's walker.  WALK_SPEED is about what a scripted open-loop gait reaches,
+    RUN_SPEED twice that.  It is a task in the image of DMC's walker and cheetah (the reference's walker_stand,
+    walker_walk, walker_run and cheetah_run), not a port of them, and nothing it scores says anything about DMC.  The
+    rule is in include/drqv2_hip.h ("Walker") to the bit and restated in numpy by tests/vec_walker_oracle.py, whose gait()
+    makes the body run.
+
+        env = VecWalker(num_envs=N, device="cuda", action_dim=4, episode_length=1000, seed=0, action_repeat=1, speed=0.3)
+
+    The discount is 1 on every row and only the time limit (t == episode_length, in simulator steps) ends an episode: a
+    fallen body lies there until then.  A reset draws a standing pose, the torso a little tilted.  The camera follows the
+    torso's middle at 42 pixels per unit: the ramp background stays fixed to the frame, the ground is a band of green and
+    blue stripes fixed to the world, the back leg is magenta, the torso red, the front leg cyan; no velocity is in a
+    frame -- it shows in how the ground scrolls -- so the policy needs the frame stack.  Same methods and guarantees as
+    VecReach (_VecTask holds them).  The state words are "phys", float32 [N, 24] = (x, y, vx, vy) of each of the six
+    particles, and t, episode, over; the config of a state dict carries speed."""
+    TASK = "walker"
+    _MIN_ACTION_DIM = 4
+    _STATE = ("phys", "t", "episode", "over")
+    _STATE_SPEC = dict(_VecTask._STATE_SPEC, phys=((24,), torch.float32))
+    MAX_SPEED, WALK_SPEED, RUN_SPEED = 2.0, 0.3, 0.6
+
+    def __init__(self, num_envs, device, action_dim=4, episode_length=1000, seed=0, action_repeat=1, speed=WALK_SPEED):
+        if isinstance(speed, bool) or not isinstance(speed, (int, float)) or not 0 <= speed <= self.MAX_SPEED:
+            raise ValueError(f"speed must be a number in 0 .. {self.MAX_SPEED}, got {speed!r}")
+        self.speed = float(speed)
+        super().__init__(num_envs, device, action_dim, episode_length, seed, action_repeat)
+
+    def _step_launch(self, action, reset_all, out):
+        launch("drq_vec_walker_step", ptr(self.phys), ptr(self.t), ptr(self.episode), ptr(self.over), self.N, self.A,
+               ptr(action), self.seed, self.episode_length, self.action_repeat, int(reset_all), self.speed,
+               *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        launch("drq_vec_walker_render", ptr(self.phys), self.N, ptr(frame), device=self.device)
+
+    def _config(self):
+        return dict(super()._config(), speed=self.speed)
 
 
 class VecMaze(_VecTask):

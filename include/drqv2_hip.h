@@ -990,6 +990,92 @@ int drq_vec_catch_step(float* phys, int* t, unsigned* episode, uint8_t* over, lo
                        uint8_t* frame, float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
 int drq_vec_catch_render(const float* phys, long N, float cup_width, uint8_t* frame, drq_stream_t stream);
 
+/* Walker.  A seventh task of the device environment, with entries of its own: a planar legged runner -- a torso with a
+ * two-link leg at either end -- moves through an unbounded world by pushing on a ground with friction.  speed = 0 pays for
+ * standing, speed > 0 for standing and moving forward at that speed -- in the image of the reference's walker_stand /
+ * walker_walk / walker_run and cheetah_run (cfgs/task/, DMC's planar runners), not a port of them.  The one task here with
+ * ground contact, four actuators, a reward on velocity and a camera that follows the body.  The body is particles and rods
+ * under position-based dynamics, which needs no mass-matrix solve and no trigonometry.  These definitions are the
+ * contract; they are exact to the bit.  Every float operation below is ONE correctly rounded IEEE float32 operation (+, -,
+ * *, / or sqrt), in the written order (a + b * c + d * e is (a + b * c) + d * e), never fused.  The draws v_k and the
+ * sanitising are those above.
+ * World: the half plane y >= 0 above a ground, y upwards, gravity 10 along -y, dt = 0.01; periodic in x with period 4.
+ * Body: six unit point masses, particle 0 the shoulder, 1 the hip, 2 the front knee, 3 the front foot, 4 the back knee, 5
+ *   the back foot; forward is +x and the shoulder is in front.  Five rods (i, j, length): torso (0, 1, 0.4f); front thigh
+ *   (0, 2, 0.25f); front shin (2, 3, 0.25f); back thigh (1, 4, 0.25f); back shin (4, 5, 0.25f).  Four muscles, each the
+ *   distance across a joint, (i, j, mid, half, lo, hi): front hip (1, 2, 0.46f, 0.1f, 0.3f, 0.6f); front knee
+ *   (0, 3, 0.34f, 0.06f, 0.25f, 0.43f); back hip (0, 4, 0.46f, 0.1f, 0.3f, 0.6f); back knee (1, 5, 0.34f, 0.06f, 0.25f,
+ *   0.43f).  [lo, hi] is what a sweep projects the distance into; after a step every muscle distance is inside the joint's
+ *   hard limits [lo - 0.005, hi + 0.005], which keep every joint away from straight and from folded.
+ * State per environment e: phys f32 [N][24], phys[4 i .. 4 i + 3] = (x_i, y_i, vx_i, vy_i) of particle i; t i32 [N],
+ *   episode u32 [N], over u8 [N] as above.  speed is a launch argument, 0 <= speed <= 2.
+ *   A phys written from outside (a restored checkpoint) is trusted as the other tasks' state is: its coordinates must be
+ *   finite and in the range the rule keeps them in, |x_i| <= 2.71 and 0 <= y_i <= 4; beyond it the frame's integers are
+ *   not defined.
+ * Reset of e (reset_all = 1, or over[e] == 1): episode += 1 (mod 2^32), t = 0, over = 0; five draws v_0 .. v_4:
+ *   tilt = v_0 * 0.05f;  n = sqrt(tilt * tilt + 1);  ux = 1 / n;  uy = tilt / n;
+ *   d0 = 0.46f + v_1 * 0.025f;  d1 = 0.34f + v_2 * 0.015f;  d2 = 0.46f + v_3 * 0.025f;  d3 = 0.34f + v_4 * 0.015f;
+ *   x_0 = ux * 0.2f;  y_0 = uy * 0.2f;  x_1 = -x_0;  y_1 = -y_0;  px = uy;  py = -ux;   (the torso's normal, downwards)
+ *   knee(B, D, dist):  al = (0.0625f - dist * dist + 0.4f * 0.4f) / 0.8f;  h = sqrt(0.0625f - al * al);
+ *     K.x = B.x + al * D.x + h * px;  K.y = B.y + al * D.y + h * py
+ *   foot(B, K, dist):  wx = (K.x - B.x) / 0.25f;  wy = (K.y - B.y) / 0.25f;  dd = dist * dist;  al = dd / 0.5f;
+ *     h = sqrt(dd - al * al);  F.x = B.x + al * wx + h * wy;  F.y = B.y + al * wy - h * wx
+ *   P_2 = knee(P_0, (-ux, -uy), d0);  P_3 = foot(P_0, P_2, d1);  P_4 = knee(P_1, (ux, uy), d2);  P_5 = foot(P_1, P_4, d3);
+ *   low = min(y_2, y_3, y_4, y_5);  every y_i = y_i - low  (the lowest knee or foot on the ground);  every velocity 0.
+ *   Outputs first = 1, reward = 0, discount = 1, substeps = 0, the frame of the new state.  The action is not read.
+ * Sub-step, (a_0 .. a_3) the sanitised action (action[e][m] drives muscle m, front hip, front knee, back hip, back knee,
+ *   each NaN to 0, then the clamp to [-1, 1]; columns 4 .. A-1 are not read), in this order:
+ *   1. every particle i = 0 .. 5:  vx = vx * 0.9f;  vy = vy * 0.9f - 0.1f;  ox = x;  oy = y;  x = x + vx * 0.01f;
+ *      y = y + vy * 0.01f                                                  (drag, gravity, the old position kept, the advance)
+ *   2. the targets:  T_m = mid_m + a_m * half_m
+ *   3. eight sweeps s = 0 .. 7, each: muscle 0, 1, 2, 3; the rods torso, front thigh, front shin, back thigh, back shin; the
+ *      ground.  A constraint between i and j:  dx = x_j - x_i;  dy = y_j - y_i;  d2 = dx * dx + dy * dy;
+ *        d2 == 0: d = 0, (nx, ny) = (0, 1)   (a fixed normal);  otherwise d = sqrt(d2);  nx = dx / d;  ny = dy / d
+ *        and, for its correction c:  h = c * 0.5f;  hx = nx * h;  hy = ny * h;  x_i = x_i + hx;  y_i = y_i + hy;
+ *        x_j = x_j - hx;  y_j = y_j - hy                                                 (split equally between its ends)
+ *      muscle m:  c = 0;  s < 4: c = clamp((d - T_m) * 0.5f, -0.004f, 0.004f)    (soft; the clamp is the force limit; the
+ *        last four sweeps only hold the limits);  q = d - c;  q < lo_m: c = d - lo_m;  else q > hi_m: c = d - hi_m
+ *      rod:  c = d - length
+ *      ground, every particle:  y < 0: y = 0
+ *   4. every particle:  vx = (x - ox) * 100;  vy = (y - oy) * 100;  y == 0: vx = vx * 0.1f   (friction: the ground leaves a
+ *      tenth of the horizontal velocity);  s2 = vx * vx + vy * vy;  s2 > 4: k = 2 / sqrt(s2);  vx = vx * k;  vy = vy * k
+ *   5. the wrap:  mid = (x_0 + x_1) * 0.5f;  mid >= 2: every x_i = x_i - 4;  else mid < -2: every x_i = x_i + 4
+ *   t += 1;  over = 1 only when t == episode_length;  d_i = 1 always: the task never ends an episode itself, and a fallen
+ *   body lies there until the time limit.
+ *   Reward r_i of the new state:  height = (y_0 + y_1) * 0.5f;  upright = (x_0 - x_1) * 2.5f;  clamp01(v) = clamp(v, 0, 1);
+ *   stand = clamp01((height - 0.1f) * 10) * clamp01((upright - 0.5f) * 2.5f);  speed == 0: r_i = stand;  otherwise
+ *   v = (vx_0 + vx_1) * 0.5f;  move = clamp01(v / speed);  r_i = stand * (1 + 5 * move) / 6.   The body stands at a height
+ *   of 0.25; walker_walk is speed 0.3, about what a scripted open-loop gait reaches, walker_run speed 0.6.
+ * Macro step: the one of "Tasks and action repeat" with every d_i = 1.
+ * Frame of a state, u8 [3][84][84].  Coordinates are integers in 1/16 pixel; pixel (i, j) has its centre at
+ *   (16 j + 8, 16 i + 8).  672 units (42 pixels) are one unit of length, y points up and the ground line y = 0 is at 1008.
+ *   The camera's x is the torso's middle, as an integer:  C = (int)floorf((x_0 + x_1) * 0.5f * 672);
+ *   X_i = (int)floorf(x_i * 672 + 0.5f) - C + 672;  Y_i = (int)floorf(1008.5f - y_i * 672).  Everything after that is
+ *   integer arithmetic.  Every particle is within 0.2 + 0.5 of the camera up to the rods' 1 %, so inside the frame's half
+ *   width 1; |x_i| <= 2 + 0.71 by the wrap, so every integer is below 2^12 in magnitude whatever the episode's length.
+ *   Per pixel, with P = (16 j + 8, 16 i + 8), later rules drawn over earlier:
+ *   background 32 + ((i + j) >> 2) in all three channels, fixed to the frame;
+ *   the ground, P.y > 1008: with w = P.x - 672 + C the world's coordinate and m = w mod 336 in 0 .. 335 (the floor modulo,
+ *     also of a negative w), m < 168 in (64, 255, 64), otherwise (64, 64, 255): stripes of 0.25 fixed to the world;
+ *   the back thigh P_1 -- P_4 and the back shin P_4 -- P_5 in (255, 64, 255);  the torso P_0 -- P_1 in (255, 64, 64);  the
+ *   front thigh P_0 -- P_2 and the front shin P_2 -- P_3 in (64, 255, 255): capsules of radius 18 (the cartpole's capsule:
+ *   the cross product squared in int64; a segment of length 0 is a disc).
+ *   No velocity is in a frame: it shows in how the ground scrolls between stacked frames.  A shape pixel holds 64 and 255
+ *   only and never three equal channels.
+ *
+ * drq_vec_walker_step: one launch, N workgroups of 256 threads with the shape of drq_vec_cartpole_step.  Writes every byte
+ *   of frame, reward, discount, first, substeps and the state (phys), nothing else.  No LDS, no atomics.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 4, repeat < 1
+ *   or > DRQ_TASK_MAX_REPEAT, episode_length < 1, reset_all not 0 or 1, speed outside [0, 2] or NaN, frame not 16-byte
+ *   aligned, a float / int array not 4-byte aligned.
+ * drq_vec_walker_render: the frames of the states as they are, by the frame rule above (the same device function): every
+ *   byte of frame, nothing else; phys is only read.  DRQ_EARG, nothing launched: a null pointer, N < 1 or > INT32_MAX,
+ *   frame not 16-byte aligned, phys not 4-byte aligned. */
+int drq_vec_walker_step(float* phys, int* t, unsigned* episode, uint8_t* over, long N, int A, const float* action,
+                        unsigned seed, int episode_length, int repeat, int reset_all, float speed, uint8_t* frame,
+                        float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
+int drq_vec_walker_render(const float* phys, long N, uint8_t* frame, drq_stream_t stream);
+
 /* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
  * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
  * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep

@@ -1,6 +1,6 @@
 """The "Vectorised collection" loop of INTEGRATION.md, run as written, on the built-in environment:
 
-  VecReach, VecPointMass, VecCartpole, VecReacher, VecMaze or VecCatch (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
+  VecReach, VecPointMass, VecCartpole, VecReacher, VecMaze, VecCatch or VecWalker (N environments stepped by one launch) -> VecFrameReplay.add() -> VecEpisodeStats.step()
   VecFrameReplay.observation() -> DrQV2Agent.act_batch() -> the next step; one DrQV2Agent.update() per step after a warm-up
 
 Nothing in the loop waits for the GPU but the statistics read-out once per reporting interval.  It prints the mean episode
@@ -8,7 +8,7 @@ return (and length) of the episodes that finished in every interval, from VecEpi
 uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small|catch|catch_hard]
+  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small|catch|catch_hard|walker_stand|walker_walk|walker_run]
                                  [--reward sparse|dense] [--action-repeat 1]
                                  [--maze-layouts K] [--maze-loops Q] [--maze-eval-layout-seed S]
                                  [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
@@ -40,6 +40,9 @@ and --eval-every STEPS;
 --task catch and catch_hard train on VecCatch (cup_width 0.3 / 0.18): a ball on a tether must be swung up and caught in a
 driven cup, 1 for every simulator step with the ball in the cup, else 0 (the reference configures episodes of 1,000
 simulator steps for its cup_catch); --reward dense swaps in the shaping by the distance to the cup's interior;
+--task walker_stand, walker_walk and walker_run train on VecWalker at speed 0, 0.3 and 0.6: a planar legged runner paid
+for standing, and for standing and moving forward at that speed (the reference configures episodes of 1,000 simulator
+steps for its walker and cheetah tasks); --action-dim defaults to the columns the task reads, at least 2: 4 there;
 --action-repeat K holds every action for up to K simulator steps inside the step launch.  All of these apply to the training
 environment, the evaluation environment and the random baseline alike.  --episode-length counts simulator steps; the
 lengths that are printed count rows, i.e. agent steps.
@@ -120,7 +123,7 @@ import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch  # noqa: E402
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
-from drqv2_amd.envs import VecCartpole, VecCatch, VecMaze, VecPointMass, VecReach, VecReacher  # noqa: E402
+from drqv2_amd.envs import VecCartpole, VecCatch, VecMaze, VecPointMass, VecReach, VecReacher, VecWalker  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import KnnBonus, RandomFeatures, SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
@@ -129,7 +132,9 @@ from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  #
 TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_balance": (VecCartpole, {"swing_up": False}),
          "cartpole_swingup": (VecCartpole, {"swing_up": True}), "reacher_easy": (VecReacher, {"target_radius": 0.15}),
          "reacher_hard": (VecReacher, {"target_radius": 0.05}), "maze": (VecMaze, {"size": 6}), "maze_small": (VecMaze, {"size": 4}),
-         "catch": (VecCatch, {"cup_width": 0.3}), "catch_hard": (VecCatch, {"cup_width": 0.18})}
+         "catch": (VecCatch, {"cup_width": 0.3}), "catch_hard": (VecCatch, {"cup_width": 0.18}),
+         "walker_stand": (VecWalker, {"speed": 0.0}), "walker_walk": (VecWalker, {"speed": VecWalker.WALK_SPEED}),
+         "walker_run": (VecWalker, {"speed": VecWalker.RUN_SPEED})}
 REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: the two forms of VecReacher, VecMaze and VecCatch
 
 
@@ -194,7 +199,7 @@ def main():
     ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per action, 1 .. 16")
     ap.add_argument("--steps", type=int, default=20000, help="environment steps (each of all N environments)")
     ap.add_argument("--envs", type=int, default=16)
-    ap.add_argument("--action-dim", type=int, default=2)
+    ap.add_argument("--action-dim", type=int, default=None, help="columns of an action (what the task reads, at least 2)")
     ap.add_argument("--episode-length", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=1000, help="steps of uniform-random actions before the first update")
     ap.add_argument("--report", type=int, default=2000, help="steps per reporting interval")
@@ -237,6 +242,8 @@ def main():
     ap.add_argument("--svea-alpha", type=float, default=None, metavar="A", help="weight of the overlaid image, 0 .. 1 (0.5)")
     ap.add_argument("--svea-bank", type=int, default=None, metavar="M", help="images of the procedural overlay bank (64)")
     args = ap.parse_args()
+    if args.action_dim is None:
+        args.action_dim = max(2, getattr(TASKS[args.task][0], "_MIN_ACTION_DIM", 2))
     if args.reward and TASKS[args.task][0] not in (VecReacher, VecMaze, VecCatch):
         raise SystemExit("--reward needs --task reacher_easy, reacher_hard, maze, maze_small, catch or catch_hard")
     if TASKS[args.task][0] is not VecMaze and (args.maze_layouts or args.maze_loops or args.maze_eval_layout_seed is not None):
