@@ -126,6 +126,8 @@ PROTOTYPES = {
     "drq_vec_catch_render": (I, [P, L, F, P, P]),
     "drq_vec_walker_step": (I, [P, P, P, P, L, I, P, C.c_uint, I, I, I, F, P, P, P, P, P, P]),
     "drq_vec_walker_render": (I, [P, L, P, P]),
+    "drq_vec_finger_step": (I, [P, P, P, P, P, L, I, P, C.c_uint, I, I, I, I, F, I, P, P, P, P, P, P]),
+    "drq_vec_finger_render": (I, [P, P, L, I, F, P, P]),
     "drq_vec_maze_step": (I, [P, P, P, P, P, P, L, I, P, C.c_uint, I, I, I, I, I, I, C.c_uint, I, P, P, P, P, P, P]),
     "drq_vec_maze_render": (I, [P, P, P, L, I, P, P]),
     "drq_vec_maze_geodesic": (I, [P, P, P, L, I, P, P]),

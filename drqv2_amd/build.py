@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdrqv2_hip.so")
-SOURCES = ["conv.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv1aug.hip", "conv_bf16.hip", "gemm.hip", "gemm2.hip", "gemm3.hip", "rowblock.hip", "skinny.hip", "aug.hip", "layernorm.hip", "losses.hip", "qout.hip", "policy_out.hip", "optim.hip", "dormant.hip", "per.hip", "vecreplay.hip", "vecframes.hip", "vecepisodes.hip", "vecrender.hip", "vecstats.hip", "vecenv.hip", "veccartpole.hip", "vecreacher.hip", "vecmaze.hip", "veccatch.hip", "vecwalker.hip", "vecdistract.hip", "strongaug.hip", "veceval.hip", "explore.hip", "knn.hip", "rng.hip", "step.hip", "autograd.hip", "act.hip"]
+SOURCES = ["conv.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv1aug.hip", "conv_bf16.hip", "gemm.hip", "gemm2.hip", "gemm3.hip", "rowblock.hip", "skinny.hip", "aug.hip", "layernorm.hip", "losses.hip", "qout.hip", "policy_out.hip", "optim.hip", "dormant.hip", "per.hip", "vecreplay.hip", "vecframes.hip", "vecepisodes.hip", "vecrender.hip", "vecstats.hip", "vecenv.hip", "veccartpole.hip", "vecreacher.hip", "vecmaze.hip", "veccatch.hip", "vecwalker.hip", "vecfinger.hip", "vecdistract.hip", "strongaug.hip", "veceval.hip", "explore.hip", "knn.hip", "rng.hip", "step.hip", "autograd.hip", "act.hip"]
 # per-file additions.  conv_wino.hip: hipcc's SLP vectoriser packs the transform adds into v_pk_add_f32 plus the
 # v_mov shuffles that feed them -- more VALU issue slots beside the MFMAs, not fewer (136 moves per unit)
 # rng.hip: hipRAND's Box-Muller (logf, sincosf, the scaling multiply-adds) must round like the copy inside torch's
@@ -25,6 +25,8 @@ SOURCES = ["conv.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv1aug.hip", "
 # rounded: the cartpole's two flags
 # vecwalker.hip: the walker, under the same contract: every constraint of every sweep takes a square root and divides twice,
 # all correctly rounded: the cartpole's two flags
+# vecfinger.hip: the finger, under the same contract: the drive, the impulse, the separation and every renormalised unit
+# vector divide and take square roots, all correctly rounded: the cartpole's two flags
 # strongaug.hip: the random convolution is 27 multiplies and adds in the written order and one division per output byte,
 # under the same contract and a numpy oracle of its own: the cartpole's two flags
 # explore.hip: the bonus is beta / sqrt(count) with both operations correctly rounded (a numpy oracle holds it to the bit);
@@ -38,6 +40,7 @@ FILE_FLAGS = {"conv_wino.hip": ["-fno-slp-vectorize"], "conv_wino_wgrad.hip": ["
               "vecmaze.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
               "veccatch.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
               "vecwalker.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+              "vecfinger.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
               "strongaug.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
               "knn.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",

@@ -1,7 +1,7 @@
 // The skeleton of a device environment (contract: include/drqv2_hip.h, "device environment"): what a task does not decide.
 // A task (vecenv.hip: the square of reach and the point mass; veccartpole.hip: the cartpole; vecreacher.hip: the reacher;
-// vecmaze.hip: the maze; veccatch.hip: the catch; vecwalker.hip: the walker) is a class of static device
-// functions over Args (its state pointers and flags), State (one environment, in registers) and Action (what a sub-step
+// vecmaze.hip: the maze; veccatch.hip: the catch; vecwalker.hip: the walker; vecfinger.hip: the finger) is a class of static
+// device functions over Args (its state pointers and flags), State (one environment, in registers) and Action (what a sub-step
 // reads of an action row):
 //   State  load(const Args&, long e)
 //   void   reset(const Args&, State&, unsigned seed, unsigned e, unsigned episode)      the draws of a new episode

@@ -41,6 +41,11 @@ under position-based dynamics, with four muscles and a ground with friction, in 
 walker_walk, walker_run and cheetah_run -- the one locomotion task here: ground contact, four actuators, an unbounded
 coordinate that the camera follows, and a reward on speed.  Specified in include/drqv2_hip.h ("Walker"), restated by
 tests/vec_walker_oracle.py, which also holds a scripted open-loop gait that makes it run.
+
+VecFinger is an eighth (csrc/vecfinger.hip, drq_vec_finger_step): the reacher's arm above a rod that turns freely on a hinge,
+in the image of the reference's finger_spin, finger_turn_easy and finger_turn_hard -- the one manipulation task here: the
+agent drives one body and is paid for the motion of another, which it can only influence through contact.  Specified in
+include/drqv2_hip.h ("Finger"), restated by tests/vec_finger_oracle.py, which also holds a scripted controller per mode.
 """
 import torch
 
@@ -473,6 +478,66 @@ class VecWalker(_VecTask):
 
     def _config(self):
         return dict(super()._config(), speed=self.speed)
+
+
+class VecFinger(_VecTask):
+    """N environments of the finger on the device: in the world [-1, 1]^2 without gravity a finger -- the reacher's arm, links
+    of 0.4 and 0.3 rooted at (0, 0.2), a fingertip disc of radius 0.06 -- hangs above a spinner, a rod of length 0.3 and
+    radius 0.05 that turns freely on a hinge at (0, -0.2) and loses 3 % of its angular velocity per simulator step.
+    action[:, 0] in [-1, 1] is the torque at the shoulder and action[:, 1] the torque at the elbow, each times 2 (NaN counts
+    as 0; further columns are ignored).  Only the fingertip collides, and only with the rod, without restitution: the
+    agent is paid for the motion of a body it can only push.  task="spin" pays 1 for every simulator step on which the rod
+    turns anticlockwise at SPIN_SPEED or faster (sparse=False: clamp(ws / SPIN_SPEED, 0, 1)); a velocity, so it shows
+    only across stacked frames.  task="turn" pays 1 while the rod's tip is inside a target disc of radius target_radius
+    centred on the rod's circle (sparse=False: 1 / (1 + 4 d^2) of the distance d between the two, the reacher's shaping):
+    TURN_EASY_RADIUS and TURN_HARD_RADIUS are the reference's finger_turn_easy and finger_turn_hard.  It is a task in the
+    image of DMC's finger, not a port of it, and nothing it scores says anything about DMC.  The rule is in
+    include/drqv2_hip.h ("Finger") to the bit and restated in numpy by tests/vec_finger_oracle.py, whose flick() and
+    turn_to() solve the two modes.
+
+        env = VecFinger(num_envs=N, device="cuda", action_dim=2, episode_length=1000, seed=0, action_repeat=1,
+                        task="spin", target_radius=VecFinger.TURN_EASY_RADIUS, sparse=True)
+
+    The discount is 1 on every row and only the time limit (t == episode_length, in simulator steps) ends an episode, so
+    a macro step's sparse reward is an exact small integer.  A reset draws both joint angles, the rod's angle and a
+    target angle at least 45 degrees from the rod's; no episode starts in contact.  The frame is the world at 42 pixels per
+    unit: the target (green, turn only), the hinge and the rod's tip (blue), the rod (magenta), the upper link (red), the
+    forearm (cyan) and the fingertip (yellow); no velocity is in a frame, so the policy needs the frame stack.  Same
+    methods and guarantees as VecReach (_VecTask holds them).  The state words are "phys", float32 [N, 9] = (c1, s1, w1,
+    c2, s2, w2, cs, ss, ws) -- the shoulder's unit vector and angular velocity, the elbow's, the rod's -- "target", float32
+    [N, 2], the unit vector of the target's angle (drawn in both modes), and t, episode, over; the config of a state dict
+    carries mode, target_radius and sparse."""
+    TASK = "finger"
+    _STATE = ("phys", "target", "t", "episode", "over")
+    _STATE_SPEC = dict(_VecTask._STATE_SPEC, phys=((9,), torch.float32))
+    MODES = ("spin", "turn")
+    MIN_TARGET_RADIUS, MAX_TARGET_RADIUS = 0.02, 0.2
+    TURN_EASY_RADIUS, TURN_HARD_RADIUS, SPIN_SPEED = 0.1, 0.04, 2.0
+
+    def __init__(self, num_envs, device, action_dim=2, episode_length=1000, seed=0, action_repeat=1, task="spin",
+                 target_radius=TURN_EASY_RADIUS, sparse=True):
+        if not isinstance(task, str) or task not in self.MODES:
+            raise ValueError(f"task must be one of {self.MODES}, got {task!r}")
+        if isinstance(target_radius, bool) or not isinstance(target_radius, (int, float)) \
+                or not self.MIN_TARGET_RADIUS <= target_radius <= self.MAX_TARGET_RADIUS:
+            raise ValueError(f"target_radius must be a number in {self.MIN_TARGET_RADIUS} .. {self.MAX_TARGET_RADIUS}, "
+                             f"got {target_radius!r}")
+        if not isinstance(sparse, (bool, int)) or sparse not in (0, 1):
+            raise ValueError(f"sparse must be True or False, got {sparse!r}")
+        self.mode, self.target_radius, self.sparse = task, float(target_radius), bool(sparse)
+        super().__init__(num_envs, device, action_dim, episode_length, seed, action_repeat)
+
+    def _step_launch(self, action, reset_all, out):
+        launch("drq_vec_finger_step", ptr(self.phys), ptr(self.target), ptr(self.t), ptr(self.episode), ptr(self.over),
+               self.N, self.A, ptr(action), self.seed, self.episode_length, self.action_repeat, int(reset_all),
+               self.MODES.index(self.mode), self.target_radius, int(self.sparse), *(ptr(o) for o in out), device=self.device)
+
+    def _render_launch(self, frame):
+        launch("drq_vec_finger_render", ptr(self.phys), ptr(self.target), self.N, self.MODES.index(self.mode),
+               self.target_radius, ptr(frame), device=self.device)
+
+    def _config(self):
+        return dict(super()._config(), mode=self.mode, target_radius=self.target_radius, sparse=self.sparse)
 
 
 class VecMaze(_VecTask):

@@ -1076,6 +1076,104 @@ int drq_vec_walker_step(float* phys, int* t, unsigned* episode, uint8_t* over, l
                         float* reward, float* discount, uint8_t* first, int* substeps, drq_stream_t stream);
 int drq_vec_walker_render(const float* phys, long N, uint8_t* frame, drq_stream_t stream);
 
+/* Finger.  An eighth task of the device environment, with entries of its own: the reacher's arm of two links above a rod
+ * that turns freely on a hinge.  The agent drives the finger and is paid for the motion of the rod (the spinner), which it
+ * can only influence through contact -- in the image of the reference's finger_spin / finger_turn_easy /
+ * finger_turn_hard (cfgs/task/, DMC's finger), not a port of them.  The one task here of manipulation.  These definitions
+ * are the contract; they are exact to the bit.  Every float operation below is ONE correctly rounded IEEE float32
+ * operation (+, -, *, / or sqrt), in the written order (a + b * c + d * e is (a + b * c) + d * e), never fused.  The draws
+ * v_k, the sanitising, normalise() and direction() are those above ("Cartpole", "Reacher").
+ * World: [-1, 1]^2, y upwards, no gravity, dt = 0.01.  The finger: links of 0.4 and 0.3 with unit point masses at the elbow
+ *   and the tip, rooted at (0, 0.2); the fingertip is a disc of radius 0.06.  The spinner: a rod of length 0.3 and radius
+ *   0.05 on a hinge at (0, -0.2), inertia 0.05.  Touching is a distance of 0.11 between the fingertip's centre and the
+ *   rod's axis (the segment from the hinge to the rod's tip).  Only the fingertip collides, and only with the rod: the
+ *   finger's two links pass over the rod, the hinge and each other.  Skin: after a sub-step the fingertip's centre is no
+ *   closer to the axis than 0.11 - 0.011.
+ * State per environment e: phys f32 [N][9] = (c1, s1, w1, c2, s2, w2, cs, ss, ws) -- the shoulder's unit vector and angular
+ *   velocity, the elbow's (relative to the upper link), the rod's; target f32 [N][2], the unit vector (gx, gy) of the
+ *   target's angle, drawn in both modes; t i32 [N], episode u32 [N], over u8 [N] as above.  mode (0 spin, 1 turn),
+ *   target_radius and sparse are launch arguments.
+ * Geometry of a state (what the reset, the impulse and the separation read):
+ *   c12 = c1 * c2 - s1 * s2;  s12 = s1 * c2 + c1 * s2;  fx = 0.3f * c12;  fy = 0.3f * s12        (the forearm)
+ *   tx = 0.4f * c1 + fx;  ty = 0.4f * s1 + fy                                   (the fingertip's centre from the root)
+ *   qx = tx;  qy = ty + 0.4f                                                    (... from the hinge)
+ *   proj = qx * cs + qy * ss;  u = clamp(proj, 0, 0.3f);  rx = cs * u;  ry = ss * u     (the closest point of the axis)
+ *   dx = qx - rx;  dy = qy - ry;  e2 = dx * dx + dy * dy
+ *   normal:  e2 == 0: e = 0, (nx, ny) = (0, 1)   (a fixed normal);  otherwise e = sqrt(e2);  nx = dx / e;  ny = dy / e
+ *   levers:  j1 = ny * tx - nx * ty;  j2 = ny * fx - nx * fy;  js = rx * ny - ry * nx
+ *   rotate(c, s, k):  k == 0: (c, s) stay as they are;  otherwise c' = c - s * k;  s' = s + c * k;  (c, s) = normalise(c', s')
+ * Reset of e (reset_all = 1, or over[e] == 1): episode += 1 (mod 2^32), t = 0, over = 0; four draws v_0 .. v_3:
+ *   (c1, s1) = direction(v_0);  (c2, s2) = direction(v_1);  (cs, ss) = direction(v_2);  w1 = w2 = ws = 0;
+ *   the geometry;  e2 < 0.0169f  (closer than 0.13):  qx * qx + qy * qy >= 0.0169f: (cs, ss) = normalise(-qx, -qy)  (the rod
+ *   points away from the fingertip);  otherwise (c1, s1, c2, s2) = (0, 1, 1, 0)  (the finger straight up).  So no episode
+ *   starts in penetration.  v = v_3;  v < 0: v = v * 0.75f - 0.225f;  otherwise v = v * 0.75f + 0.225f;  (ax, ay) =
+ *   direction(v);  (gx, gy) = normalise(cs * ax - ss * ay, ss * ax + cs * ay): the rod's direction turned by 45 degrees or more.
+ *   Outputs first = 1, reward = 0, discount = 1, substeps = 0, the frame of the new state.  The action is not read.
+ * Sub-step, (a1, a2) the sanitised action (action[e][0] the shoulder's torque, action[e][1] the elbow's, each NaN to 0,
+ *   then the clamp to [-1, 1]; columns 2 .. A-1 are not read), in this order:
+ *   1. the drive (the reacher's, with these links; torque 2 per unit of action, damping 0.5):
+ *      M11 = 0.41f + 0.24f * c2;  M12 = 0.09f + 0.12f * c2;  h = 0.12f * s2                             (M22 = 0.09)
+ *      cor = (2 * w1) * w2 + w2 * w2;  tau1 = (a1 * 2 - 0.5f * w1) + h * cor;  tau2 = (a2 * 2 - 0.5f * w2) - h * (w1 * w1)
+ *      det = M11 * 0.09f - M12 * M12                                     (= 0.0288 - 0.0144 c2^2 >= 0.0144: never near 0)
+ *      al1 = (0.09f * tau1 - M12 * tau2) / det;  al2 = (M11 * tau2 - M12 * tau1) / det
+ *      w1 = clamp(w1 + al1 * 0.01f, -6, 6);  w2 = clamp(w2 + al2 * 0.01f, -6, 6);  ws = ws * 0.97f
+ *   2. the impulse, at the positions as they are: the geometry;  e2 < 0.0441f  (within 0.21): the normal and the levers;
+ *      gap = e - 0.11f;  lim = -(max(gap, 0) * 100);  vn = (j1 * w1 + j2 * w2) - js * ws
+ *      u1 = (0.09f * j1 - M12 * j2) / det;  u2 = (M11 * j2 - M12 * j1) / det;  den = (j1 * u1 + j2 * u2) + (js * js) * 20
+ *      vn < lim and den > 0:  lam = (lim - vn) / den;  w1 = w1 + u1 * lam;  w2 = w2 + u2 * lam;  ws = ws - (js * 20) * lam
+ *      One impulse along the normal, shared by effective mass (the arm's n^T J M^-1 J^T n, the rod's js^2 / I), leaves
+ *      the two no more approaching speed than closes the gap in this step; touching, it removes all of it (restitution
+ *      0).  At the hinge end js = 0: the finger alone is stopped, by the same formula.  It never adds kinetic energy.
+ *   3. the clamps:  w1 = clamp(w1, -6, 6);  w2 = clamp(w2, -6, 6);  ws = clamp(ws, -10, 10)
+ *   4. the advance:  rotate(c1, s1, w1 * 0.01f);  rotate(c2, s2, w2 * 0.01f);  rotate(cs, ss, ws * 0.01f)
+ *      (a body at rest keeps its vector to the bit)
+ *   5. the separation, at the new positions: the geometry;  e2 < 0.0121f: the normal and the levers;
+ *      den = (j1 * j1) * 2.5f + (js * js) * 20;  den >= 0.01f:  mu = (0.11f - e) / den;  rotate(c1, s1, (j1 * 2.5f) * mu);
+ *      rotate(cs, ss, -((js * 20) * mu)).   The shoulder and the rod turn until the two touch again; the elbow does not,
+ *      so the mass matrix and the kinetic energy stay as they are.  Without a lever (den < 0.01f) nothing is turned.
+ *   t += 1;  over = 1 only when t == episode_length;  d_i = 1 always: the task never ends an episode itself.
+ *   Reward r_i of the new state.  mode 0 (spin):  sparse: r_i = ws >= 2 ? 1 : 0;  dense: r_i = clamp(ws / 2, 0, 1).
+ *   mode 1 (turn):  dx = 0.3f * cs - 0.3f * gx;  dy = 0.3f * ss - 0.3f * gy;  d2 = dx * dx + dy * dy  (the rod's tip from the
+ *   target's centre G = hinge + 0.3 (gx, gy));  sparse: r_i = d2 <= target_radius * target_radius ? 1 : 0;  dense:
+ *   r_i = 1 / (1 + 4 * d2).   finger_turn_easy is target_radius 0.1, finger_turn_hard 0.04.
+ * Macro step: the one of "Tasks and action repeat" with every d_i = 1; in the sparse forms the reward is an exact small
+ *   integer, 0 .. repeat.
+ * Frame of a state, u8 [3][84][84].  Coordinates are integers in 1/16 pixel; pixel (i, j) has its centre at
+ *   (16 j + 8, 16 i + 8).  672 units (42 pixels) are one unit of length, y points up, the world's origin is at (672, 672):
+ *   the root at (672, 538), the hinge at (672, 806).  The finger (0.2 + 0.7 + 0.06), the rod (0.2 + 0.3 + 0.05) and the
+ *   target's disc (0.2 + 0.3 + 0.2) stay inside the frame.  Each coordinate is rounded once:
+ *   ax = c1 * 268.8f;  ay = s1 * 268.8f;  EX = (int)floorf(ax + 672.5f);  EY = (int)floorf(672.5f - (ay + 134.4f))     (the elbow)
+ *   TX = (int)floorf((ax + c12 * 201.6f) + 672.5f);  TY = (int)floorf(672.5f - ((ay + s12 * 201.6f) + 134.4f))      (the fingertip)
+ *   SX = (int)floorf(cs * 201.6f + 672.5f);  SY = (int)floorf(672.5f - (ss * 201.6f - 134.4f))                     (the rod's tip)
+ *   GX = (int)floorf(gx * 201.6f + 672.5f);  GY = (int)floorf(672.5f - (gy * 201.6f - 134.4f))                     (the target)
+ *   GR = (int)floorf(target_radius * 672 + 0.5f)
+ *   Everything after that is integer arithmetic.  Per pixel, with P = (16 j + 8, 16 i + 8), later rules drawn over earlier:
+ *   background 32 + ((i + j) >> 2) in all three channels;
+ *   the target, mode 1 only, |P - G|^2 <= GR * GR, in (64, 255, 64);
+ *   the hinge, |P - (672, 806)|^2 <= 44 * 44, in (64, 64, 255);
+ *   the rod, the capsule of radius 34 around the segment hinge -- S, in (255, 64, 255);
+ *   the rod's tip, |P - S|^2 <= 34 * 34, in (64, 64, 255);
+ *   the upper link, the capsule of radius 20 around the segment root -- E, in (255, 64, 64);
+ *   the forearm, the capsule of radius 20 around the segment E -- T, in (64, 255, 255);
+ *   the fingertip, |P - T|^2 <= 40 * 40, in (255, 255, 64).
+ *   A capsule is the cartpole's (the cross product squared in int64; a segment of length 0 is a disc).
+ *   No velocity is in a frame.  A shape pixel holds 64 and 255 only and never three equal channels.
+ *
+ * drq_vec_finger_step: one launch, N workgroups of 256 threads with the shape of drq_vec_cartpole_step.  Writes every byte
+ *   of frame, reward, discount, first, substeps and the state (phys and target), nothing else.  No LDS, no atomics.
+ *   DRQ_EARG, nothing launched: a null pointer (action only without reset_all), N < 1 or > INT32_MAX, A < 2, repeat < 1
+ *   or > DRQ_TASK_MAX_REPEAT, episode_length < 1, reset_all, mode or sparse not 0 or 1, target_radius outside [0.02, 0.2]
+ *   or NaN, frame not 16-byte aligned, a float / int array not 4-byte aligned.
+ * drq_vec_finger_render: the frames of the states as they are, by the frame rule above (the same device function): every
+ *   byte of frame, nothing else; phys and target are only read.  DRQ_EARG, nothing launched: a null pointer, N < 1 or
+ *   > INT32_MAX, mode and target_radius as for the step, frame not 16-byte aligned, phys or target not 4-byte aligned. */
+int drq_vec_finger_step(float* phys, float* target, int* t, unsigned* episode, uint8_t* over, long N, int A,
+                        const float* action, unsigned seed, int episode_length, int repeat, int reset_all, int mode,
+                        float target_radius, int sparse, uint8_t* frame, float* reward, float* discount, uint8_t* first,
+                        int* substeps, drq_stream_t stream);
+int drq_vec_finger_render(const float* phys, const float* target, long N, int mode, float target_radius, uint8_t* frame,
+                          drq_stream_t stream);
+
 /* ---- exploration bonus.  New functionality: the reference explores by the noise of its policy alone (drqv2.py:164-175)
  * and every reward its replay sees is the environment's.  This is the count-based bonus of "#Exploration" (Tang et al.
  * 2017) -- a SimHash of the frame, a table of visit counts, bonus = beta / sqrt(count) -- on the frames of N lockstep

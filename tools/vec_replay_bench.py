@@ -53,13 +53,13 @@ float32 means half to even, so its frames are not add_render()'s everywhere; the
 
   python tools/vec_replay_bench.py --render [--steps 2000] [--repeats 3] [--envs 16,256,1024] [--sizes 84,128,168]
 
---env reach | pointmass | cartpole | reacher | maze | catch | walker measures the built-in environment (drqv2_amd.envs.VecReach / VecPointMass:
-drq_vec_task_step; VecCartpole, swing-up: drq_vec_cartpole_step; VecReacher, sparse: drq_vec_reacher_step; VecMaze, size 6, sparse, a fresh maze per episode: drq_vec_maze_step; VecCatch, cup_width 0.3, sparse: drq_vec_catch_step; VecWalker, the walk speed: drq_vec_walker_step; one launch per step of all N; --action-repeat K sub-steps
+--env reach | pointmass | cartpole | reacher | maze | catch | walker | finger measures the built-in environment (drqv2_amd.envs.VecReach / VecPointMass:
+drq_vec_task_step; VecCartpole, swing-up: drq_vec_cartpole_step; VecReacher, sparse: drq_vec_reacher_step; VecMaze, size 6, sparse, a fresh maze per episode: drq_vec_maze_step; VecCatch, cup_width 0.3, sparse: drq_vec_catch_step; VecWalker, the walk speed: drq_vec_walker_step; VecFinger, spin, sparse: drq_vec_finger_step; one launch per step of all N; --action-repeat K sub-steps
 inside it, 1 by default)
 next to the single-frame ring it feeds: env.step(), ring.add() of one step's outputs, and the two together, alternated
 inside every repeat of one process.  Same steps, repeats and the same two figures per line as above.
 
-  python tools/vec_replay_bench.py --env reach|pointmass|cartpole|reacher|maze|catch|walker [--action-repeat 1] [--steps 2000] [--repeats 3] [--envs 16,256,1024]
+  python tools/vec_replay_bench.py --env reach|pointmass|cartpole|reacher|maze|catch|walker|finger [--action-repeat 1] [--steps 2000] [--repeats 3] [--envs 16,256,1024]
 
 --eval-stack measures the evaluation pieces (drqv2_amd.evaluate): VecFrameStack.push() -- drq_vec_stack_push, one launch --
 beside what an evaluation loop used before it, VecFrameReplay.add() + observation() (two launches), and add() alone, the
@@ -315,11 +315,11 @@ def render(N, S, args):
 
 
 def device_env(N, args):
-    """step() of the built-in environment (--env reach | pointmass | cartpole | reacher | maze | catch | walker at --action-repeat K), VecFrameReplay.add() of one
+    """step() of the built-in environment (--env reach | pointmass | cartpole | reacher | maze | catch | walker | finger at --action-repeat K), VecFrameReplay.add() of one
     step's outputs, and both, alternated per repeat"""
-    from drqv2_amd.envs import VecCartpole, VecCatch, VecMaze, VecPointMass, VecReach, VecReacher, VecWalker
+    from drqv2_amd.envs import VecCartpole, VecCatch, VecFinger, VecMaze, VecPointMass, VecReach, VecReacher, VecWalker
     cls = {"reach": VecReach, "pointmass": VecPointMass, "cartpole": VecCartpole, "reacher": VecReacher, "maze": VecMaze,
-           "catch": VecCatch, "walker": VecWalker}[args.env]
+           "catch": VecCatch, "walker": VecWalker, "finger": VecFinger}[args.env]
     env = cls(N, "cuda", action_dim=A, episode_length=250, seed=1, action_repeat=args.action_repeat)
     ring = VecFrameReplay(max(32, SLOTS // N), N, A, NSTEP, 0.99, "cuda", seed=1)
     g = torch.Generator(device="cuda")
@@ -552,7 +552,7 @@ def main():
     ap.add_argument("--render", action="store_true",
                     help="measure add_render() against the torch resize chain in front of add(), and add() alone")
     ap.add_argument("--sizes", default="84,128,168", help="image sizes of --render")
-    ap.add_argument("--env", choices=["reach", "pointmass", "cartpole", "reacher", "maze", "catch", "walker"], default=None,
+    ap.add_argument("--env", choices=["reach", "pointmass", "cartpole", "reacher", "maze", "catch", "walker", "finger"], default=None,
                     help="measure the built-in environment's step() next to the single-frame ring's add()")
     ap.add_argument("--action-repeat", type=int, default=1, metavar="K", help="simulator steps per step() of --env, 1 .. 16")
     ap.add_argument("--eval-stack", action="store_true",

@@ -8,7 +8,7 @@ return (and length) of the episodes that finished in every interval, from VecEpi
 uniform-random actions over the SAME number of episodes on a second environment of the same seed, measured in the same
 process: that is the baseline the training curve is read against, not a constant written down in advance.
 
-  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small|catch|catch_hard|walker_stand|walker_walk|walker_run]
+  python tools/vec_train_demo.py [--task reach|pointmass|cartpole_balance|cartpole_swingup|reacher_easy|reacher_hard|maze|maze_small|catch|catch_hard|walker_stand|walker_walk|walker_run|finger_spin|finger_turn_easy|finger_turn_hard]
                                  [--reward sparse|dense] [--action-repeat 1]
                                  [--maze-layouts K] [--maze-loops Q] [--maze-eval-layout-seed S]
                                  [--steps 20000] [--envs 16] [--episode-length 50] [--warmup 1000] [--report 2000]
@@ -40,6 +40,8 @@ and --eval-every STEPS;
 --task catch and catch_hard train on VecCatch (cup_width 0.3 / 0.18): a ball on a tether must be swung up and caught in a
 driven cup, 1 for every simulator step with the ball in the cup, else 0 (the reference configures episodes of 1,000
 simulator steps for its cup_catch); --reward dense swaps in the shaping by the distance to the cup's interior;
+--task finger_spin, finger_turn_easy and finger_turn_hard train on VecFinger: a finger that must spin a hinged rod, or turn
+its tip into a target disc of radius 0.1 or 0.04, by contact alone; --reward dense swaps in the shapings of the two modes;
 --task walker_stand, walker_walk and walker_run train on VecWalker at speed 0, 0.3 and 0.6: a planar legged runner paid
 for standing, and for standing and moving forward at that speed (the reference configures episodes of 1,000 simulator
 steps for its walker and cheetah tasks); --action-dim defaults to the columns the task reads, at least 2: 4 there;
@@ -123,7 +125,7 @@ import utils  # noqa: E402
 from drqv2_amd import checkpoint  # noqa: E402
 from drqv2_amd.augment import RandomConv, RandomOverlay, noise_bank, svea_batch  # noqa: E402
 from drqv2_amd.distract import FrameDistractor, VecDistract, parse_spec  # noqa: E402
-from drqv2_amd.envs import VecCartpole, VecCatch, VecMaze, VecPointMass, VecReach, VecReacher, VecWalker  # noqa: E402
+from drqv2_amd.envs import VecCartpole, VecCatch, VecFinger, VecMaze, VecPointMass, VecReach, VecReacher, VecWalker  # noqa: E402
 from drqv2_amd.evaluate import VecFrameStack, VecVideo, evaluate  # noqa: E402
 from drqv2_amd.explore import KnnBonus, RandomFeatures, SimHashBonus  # noqa: E402
 from drqv2_amd.replay import VecDeviceReplay, VecEpisodeStats, VecFrameReplay  # noqa: E402
@@ -134,8 +136,11 @@ TASKS = {"reach": (VecReach, {}), "pointmass": (VecPointMass, {}), "cartpole_bal
          "reacher_hard": (VecReacher, {"target_radius": 0.05}), "maze": (VecMaze, {"size": 6}), "maze_small": (VecMaze, {"size": 4}),
          "catch": (VecCatch, {"cup_width": 0.3}), "catch_hard": (VecCatch, {"cup_width": 0.18}),
          "walker_stand": (VecWalker, {"speed": 0.0}), "walker_walk": (VecWalker, {"speed": VecWalker.WALK_SPEED}),
-         "walker_run": (VecWalker, {"speed": VecWalker.RUN_SPEED})}
-REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: the two forms of VecReacher, VecMaze and VecCatch
+         "walker_run": (VecWalker, {"speed": VecWalker.RUN_SPEED}),
+         "finger_spin": (VecFinger, {"task": "spin"}),
+         "finger_turn_easy": (VecFinger, {"task": "turn", "target_radius": VecFinger.TURN_EASY_RADIUS}),
+         "finger_turn_hard": (VecFinger, {"task": "turn", "target_radius": VecFinger.TURN_HARD_RADIUS})}
+REWARDS = {None: {}, "sparse": {"sparse": True}, "dense": {"sparse": False}}       # --reward: the two forms of VecReacher, VecMaze, VecCatch and VecFinger
 
 
 def make_env(args, seed, role="train"):
@@ -191,7 +196,7 @@ def random_baseline(args, episodes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=sorted(TASKS), default="reach")
-    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher, maze and catch tasks (sparse)")
+    ap.add_argument("--reward", choices=("sparse", "dense"), default=None, help="the reward of the reacher, maze, catch and finger tasks (sparse)")
     ap.add_argument("--maze-layouts", type=int, default=0, metavar="K", help="the mazes come from a pool of K layouts (0: a fresh maze per episode)")
     ap.add_argument("--maze-loops", type=int, default=0, metavar="Q", help="open every remaining wall with probability Q / 256, 0 .. 255")
     ap.add_argument("--maze-eval-layout-seed", type=int, default=None, metavar="S",
@@ -244,8 +249,8 @@ def main():
     args = ap.parse_args()
     if args.action_dim is None:
         args.action_dim = max(2, getattr(TASKS[args.task][0], "_MIN_ACTION_DIM", 2))
-    if args.reward and TASKS[args.task][0] not in (VecReacher, VecMaze, VecCatch):
-        raise SystemExit("--reward needs --task reacher_easy, reacher_hard, maze, maze_small, catch or catch_hard")
+    if args.reward and TASKS[args.task][0] not in (VecReacher, VecMaze, VecCatch, VecFinger):
+        raise SystemExit("--reward needs --task reacher_easy, reacher_hard, maze, maze_small, catch, catch_hard or a finger task")
     if TASKS[args.task][0] is not VecMaze and (args.maze_layouts or args.maze_loops or args.maze_eval_layout_seed is not None):
         raise SystemExit("--maze-layouts, --maze-loops and --maze-eval-layout-seed need --task maze or maze_small")
     if not 0 <= args.maze_layouts <= VecMaze.MAX_LAYOUTS or not 0 <= args.maze_loops <= VecMaze.MAX_LOOPS:
