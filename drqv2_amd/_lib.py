@@ -44,6 +44,8 @@ I, L, F, D, P, SZ = C.c_int, C.c_long, C.c_float, C.c_double, C.c_void_p, C.c_si
 # name -> (restype, argtypes); mirrors include/drqv2_hip.h one to one
 PROTOTYPES = {
     "drq_abi_version": (I, []),
+    "drq_num_cus_in_effect": (I, []),
+    "drq_set_num_cus": (I, [I]),
     "drq_aug_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "drq_aug_fwd_f32": (I, [P, P, P, P, I, I, I, I, P]),
     "drq_conv1_aug_fwd": (I, [P, P, P, P, P, P, P, P, P, I, I, P]),
@@ -180,7 +182,7 @@ STEP_OVERLAP_ACTOR = 16   # DRQ_STEP_OVERLAP_ACTOR (DrqStep.flags)
 PARAM_LAYOUT_LEN = 59   # DRQ_PARAM_LAYOUT_LEN: the offsets drq_param_layout writes
 
 # the entries without a trailing drq_stream_t: they launch nothing, or their DrqStep carries the stream
-NO_STREAM = frozenset({"drq_abi_version", "drq_conv3x3_wgrad_ws_bytes", "drq_param_layout", "drq_step_ws_bytes",
+NO_STREAM = frozenset({"drq_abi_version", "drq_num_cus_in_effect", "drq_set_num_cus", "drq_conv3x3_wgrad_ws_bytes", "drq_param_layout", "drq_step_ws_bytes",
                        "drq_step_ws_offset", "drq_update_phase", "drq_update_phase_overlap", "drq_update_phase_bc", "drq_update_phase_per",
                        "drq_update_phase_frames", "drq_act_forward", "drq_act_ws_bytes", "drq_explore_knn_ws_bytes"})
 
@@ -201,7 +203,10 @@ def load():
                        "(hipcc --offload-arch=gfx950).  The DrQ-v2 update path has no fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)       # AttributeError = ABI mismatch, also loud
+        if not hasattr(lib, name):    # additive changes keep the ABI version: a library built before one lacks the entry
+            raise DrqError(f"{LIB_PATH} does not export {name}: it was built from older sources; rebuild it with "
+                           "`python -m drqv2_amd.build --force`")
+        fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     if lib.drq_abi_version() != 7:

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdrqv2_hip.so")
-SOURCES = ["conv.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv1aug.hip", "conv_bf16.hip", "gemm.hip", "gemm2.hip", "gemm3.hip", "rowblock.hip", "skinny.hip", "aug.hip", "layernorm.hip", "losses.hip", "qout.hip", "policy_out.hip", "optim.hip", "dormant.hip", "per.hip", "vecreplay.hip", "vecframes.hip", "vecepisodes.hip", "vecrender.hip", "vecstats.hip", "vecenv.hip", "veccartpole.hip", "vecreacher.hip", "vecmaze.hip", "veccatch.hip", "vecwalker.hip", "vecfinger.hip", "vecdistract.hip", "strongaug.hip", "veceval.hip", "explore.hip", "knn.hip", "rng.hip", "step.hip", "autograd.hip", "act.hip"]
+SOURCES = ["conv.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv1aug.hip", "conv_bf16.hip", "gemm.hip", "gemm2.hip", "gemm3.hip", "rowblock.hip", "skinny.hip", "aug.hip", "layernorm.hip", "losses.hip", "qout.hip", "policy_out.hip", "optim.hip", "dormant.hip", "per.hip", "vecreplay.hip", "vecframes.hip", "vecepisodes.hip", "vecrender.hip", "vecstats.hip", "vecenv.hip", "veccartpole.hip", "vecreacher.hip", "vecmaze.hip", "veccatch.hip", "vecwalker.hip", "vecfinger.hip", "vecdistract.hip", "strongaug.hip", "veceval.hip", "explore.hip", "knn.hip", "rng.hip", "step.hip", "autograd.hip", "act.hip", "device.hip"]
 # per-file additions.  conv_wino.hip: hipcc's SLP vectoriser packs the transform adds into v_pk_add_f32 plus the
 # v_mov shuffles that feed them -- more VALU issue slots beside the MFMAs, not fewer (136 moves per unit)
 # rng.hip: hipRAND's Box-Muller (logf, sincosf, the scaling multiply-adds) must round like the copy inside torch's

@@ -35,16 +35,9 @@ static inline int drq_device() {
   return dev;
 }
 
-static inline int drq_num_cus() {
-  static int n[kMaxDevices] = {};
-  const int dev = drq_device();
-  if (n[dev] == 0) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
-    n[dev] = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  return n[dev];
-}
+// The CU count of the current device as every planner sees it: the override of drq_set_num_cus() where one is set, else
+// the hardware's.  ONE definition and one cache for the whole library (device.hip), hidden like every internal function.
+int drq_num_cus();
 
 // raises Kernel's dynamic LDS limit to `bytes`, once per device (every instantiation has its own flags): 0 or the hipError_t
 template <auto Kernel>

@@ -8,7 +8,8 @@
  *   - every call is enqueued on `stream` (a hipStream_t, passed as void*), nothing synchronises;
  *   - return 0 = ok, <0 = argument/shape/workspace error, >0 = hipError_t of the launch;
  *   - no allocation and no state that outlives a call, except two host-side caches indexed by the current HIP
- *     device: the CU count, and "dynamic-LDS attribute already set" flags of the weight-gradient kernels;
+ *     device: the CU count (with the test override of drq_set_num_cus), and "dynamic-LDS attribute already set" flags
+ *     of the weight-gradient kernels;
  *   - the library is built with -fvisibility=hidden: the functions declared here are ALL it exports
  *     (tests/test_cpu_interface.py checks both directions);
  *   - tensors are fp32 row-major / NCHW unless stated.
@@ -29,6 +30,23 @@ typedef void* drq_stream_t; /* hipStream_t */
 #define DRQ_EWS (-2)
 
 int drq_abi_version(void);
+
+/* ---- The CU count the library plans with.  Every launch sizes its grid from the CU count of the current HIP device,
+ * and so do the XCD-aware workgroup orders, the shares of a merged grid, the split-K factors and the grid-stride caps.
+ * drq_num_cus_in_effect(): the count every planner sees on the current device: the override below where one is set,
+ * else the hardware's (hipDeviceProp_t::multiProcessorCount, asked once per device).
+ * drq_set_num_cus(n): a per-device override for tests, which makes a whole device plan like a partition of it (an
+ * MI355X in CPX / QPX / DPX mode shows 32 / 64 / 128 CUs).  n == 0 clears the override of the current device;
+ * 1 <= n <= the hardware count sets it; anything else returns DRQ_EARG and changes nothing.  Returns DRQ_OK or DRQ_EARG.
+ * A count above the hardware's is refused on purpose: a smaller count only shrinks grids, a larger one could enlarge
+ * them past what is resident at once.  The workspace-size entries (drq_conv3x3_wgrad_ws_bytes, drq_step_ws_bytes,
+ * drq_explore_knn_ws_bytes, drq_act_ws_bytes) do not depend on the count, so a workspace sized under an override serves
+ * the launches made under it and under any smaller one.  Both entries launch nothing and take no stream.  The
+ * override is plain process-wide state per device, NOT thread-safe against concurrent launches: set it while no other
+ * thread is inside the library, and restore it (n = 0) before anything else runs.  Results under an override are as correct as without one; only grids (and with them the
+ * summation order of the kernels that leave per-workgroup partial sums) change. */
+int drq_num_cus_in_effect(void);
+int drq_set_num_cus(int n);
 
 /* ---- RandomShiftsAug.forward (drqv2.py:19-45) [+ Encoder's obs/255-0.5, drqv2.py:64, if fuse_norm]
  * obs u8 [n][c][hw][hw]; shift_xy f32 [n][2] = the torch.randint(0,2*pad+1,(n,1,1,2)) draw (x,y);

@@ -273,7 +273,9 @@ DECISIONS = (
 # decision -> the side no batch 1..4096 takes on a 256-CU device.  The branches stay in the code: other CU counts (a
 # partitioned device) take the overshoot loop (32 CUs) and the remap (8, 16, 64, 128 CUs); the other two guard the
 # arithmetic (fewer than 3 CUs; a share that rounds to zero).  tests/test_cpu_conv_variants.py asserts that each entry is still true, and that
-# nothing else is one-sided over the audit rows.
+# nothing else is one-sided over the audit rows.  The far sides run on the device all the same: tests/cu_rows.py lists the
+# rows tests/test_hip_cu_counts.py runs under an override of the CU count (32 CUs: overshoot and remap; 8, 64, 128: the
+# remap; 2: the fallback), and which far side no count reaches (STILL_UNREACHABLE: ww3.share<1).
 UNREACHABLE_AT_256 = {
     "ww3.fallback": True,       # tot = 273 steps at B = 1 already
     "ww3.share<1": True,        # the three layers' steps are within 25 % of each other: every share is about cus / 3

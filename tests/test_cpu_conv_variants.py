@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from tests import conv_variants as cv
+from tests import cu_rows
 
 ISSUE_BATCHES = {"fp32": [1, 2, 3, 5, 32], "bf16": [2, 32]}      # the audit may add rows, never lose one of these
 SECOND_UPDATE = [2, 32]
@@ -201,3 +202,112 @@ def test_the_planner_sizes_and_refuses_workspaces(plan_dump):
                _line("ww3", 2, 8, ws=0)]) == [(0, 94 * PART[32]), (-2, 94 * PART[32]), (-1, 0)]
     assert rc([_line("wgrad_bf16", 256, 2, 41, ws=20 * PART[32]), _line("wgrad_bf16", 256, 2, 41, ws=20 * PART[32] - 1),
                _line("wgrad_bf16", 256, 2, 43, ws=0)]) == [(0, 20 * PART[32]), (-2, 20 * PART[32]), (-1, 0)]
+
+
+# ------------------------------------------------------- the rows run under an override of the CU count (tests/cu_rows.py)
+def test_the_override_rows_hold_the_rows_asked_for():
+    rows = {(r.cus, r.B, r.dtype) for r in cu_rows.CU_ROWS}
+    assert {(32, 1, "fp32"), (32, 2, "fp32"), (32, 8, "fp32"), (8, 2, "fp32"), (8, 3, "fp32"), (64, 2, "fp32"),
+            (128, 2, "fp32"), (2, 1, "fp32"), (3, 1, "fp32"), (32, 2, "bf16")} <= rows
+    assert len(rows) == len(cu_rows.CU_ROWS) and all(1 <= r.cus <= cv.CUS for r in cu_rows.CU_ROWS + cu_rows.OP_ROWS)
+    at = lambda cus, B: dict(cu_rows.row_launches(cu_rows.CuRow(cus, B, "fp32", 1)))
+    for B in (1, 2, 8):                             # 32 CUs: the overshoot and the remap, a grid of exactly 32
+        w = at(32, B)["dW2-4"]
+        assert w.decisions["ww3.overshoot"] and w.decisions["ww3.xcd_remap"] and w.grid == 32 == sum(w.records)
+    f = at(32, 8)["ACT2"]
+    assert f.grid == 64 and f.decisions["wino.blocks>cap"] and f.decisions["wino.xcd_remap"]
+    for B in (2, 3):                                # 8 CUs: forward grids of 16 (remap on), a weight-gradient grid of 8
+        la = at(8, B)
+        assert [la[s].grid for s in ("ACT2", "ACT3", "FEAT")] == [16] * 3 and la["ACT2"].decisions["wino.xcd_remap"]
+        assert la["dW2-4"].grid == 8 and la["dW2-4"].decisions["ww3.xcd_remap"]
+    assert at(8, 3)["ACT2"].decisions["wino.full_rounds"] and [at(8, 3)[s].grid for s in ("DY3", "DY2", "DY1")] == [16] * 3
+    for cus in (64, 128):
+        w = at(cus, 2)["dW2-4"]
+        assert w.decisions["ww3.xcd_remap"] and w.grid == cus
+    assert at(2, 1)["dW2-4"].kernel == cv.EARG and [at(2, 1)["dW%d" % l].grid for l in (2, 3, 4)] == [2, 2, 2]
+    assert at(3, 1)["dW2-4"].records == [1, 1, 1]
+    # the fused aug+conv1 rows at 8 CUs: the shift table is full at 103 and 110 frames (grid = ceil(10 n / 64)), not at 3
+    aug = {r.args[0]: cu_rows.row_launches(r)[0][1] for r in cu_rows.OP_ROWS if r.fn == "launch_conv1_aug"}
+    assert {n: (la.grid, la.decisions["conv1_aug.table_full"]) for n, la in aug.items()} == \
+        {103: (17, True), 110: (18, True), 3: (16, False)}
+    first = lambda f: next(n for n in range(1, 4097) if f(n))
+    assert first(lambda n: cv.launch_conv1_aug(n, 0, 8).decisions["conv1_aug.table_full"]) == 103
+    assert first(lambda n: cv.launch_conv1_aug(n, 0, 256).decisions["conv1_aug.table_full"]) == 3277
+    assert all(cu_rows.describe(r) for r in cu_rows.CU_ROWS)
+
+
+def test_every_far_side_of_the_unreachable_table_is_taken_under_an_override():
+    """... by a row of cu_rows, unless no CU count of the sweep takes it at any batch 1..4096: those are listed in
+    STILL_UNREACHABLE with the reason, and the list is held true"""
+    seen = cv.decisions_of(cu_rows.override_launches())
+    swept = {}
+    for cus in SWEEP_CUS:
+        if cus <= cv.CUS:
+            for B in range(1, 4097):
+                for k, v in cv.wgrad_partial_wino3(B, cus).decisions.items():
+                    swept.setdefault(k, set()).add(v)
+    assert set(cu_rows.STILL_UNREACHABLE) <= set(cv.UNREACHABLE_AT_256)
+    for k, side in cv.UNREACHABLE_AT_256.items():
+        if k in cu_rows.STILL_UNREACHABLE:
+            assert side not in swept[k] and side not in seen[k], "%s is reachable: it needs a row" % k
+        else:
+            assert side in seen[k], "no override row takes %s = %s" % (k, side)
+
+
+def test_what_is_one_sided_at_256_is_two_sided_with_the_override_rows():
+    names = cv.DECISIONS + cv.OP_DECISIONS + cu_rows.AUG_DECISIONS + cu_rows.BF16_DECISIONS
+    old = cv.decisions_of(cu_rows.launches_at_256())
+    both = cv.decisions_of(cu_rows.launches_at_256() + cu_rows.override_launches())
+    assert set(both) == set(names)
+    one_sided = sorted(k for k in names if old.get(k, set()) != {True, False})
+    assert one_sided == sorted(list(cv.UNREACHABLE_AT_256) + ["conv1_aug.table_full"])
+    left = {k: sorted(both[k]) for k in one_sided if both[k] != {True, False}}
+    assert set(left) == set(cu_rows.STILL_UNREACHABLE), left
+    # every fp32 update row but the 3-CU one (the same sides at the smallest merged grid) adds a side of its own
+    assert [r.cus for r in cu_rows.CU_ROWS if r.dtype == "fp32" and not cu_rows.new_sides(r, old)] == [3]
+
+
+def test_the_planner_agrees_with_the_mirror_on_the_override_rows(plan_dump):
+    """the sweep covers them; this guards the table: every launch of every row, through the library's own planner"""
+    kinds = {"launch_conv_v": lambda nb, hin, s: _line("conv_v", 0, nb, hin, s, 9 if hin == 84 else 32),
+             "launch_wino": lambda nb, hin: _line("wino", 0, nb, hin),
+             "launch_ww": lambda nb, hin: _line("ww", 0, nb, hin),
+             "launch_wgrad": lambda nb, cin, hin, s: _line("wgrad", 0, nb, hin, s, cin),
+             "launch_conv_bf16": lambda nb, hin, lay: _line("conv_bf16", 0, nb, hin, lay=lay),
+             "launch_wgrad_bf16": lambda nb, hin: _line("wgrad_bf16", 0, nb, hin),
+             "launch_conv1_aug": lambda n, riders: _line("conv1_aug", 0, n, lay=riders)}
+    cases = []
+    for r in cu_rows.OP_ROWS:
+        kind, rest = kinds[r.fn](*r.args).split(" ", 1)
+        cases.append(("%s %d %s" % (kind, r.cus, rest.split(" ", 1)[1]), cu_rows.row_launches(r)[0][1]))
+    for r in cu_rows.CU_ROWS:
+        cases.append((_line("ww3", r.cus, r.B), cv.wgrad_partial_wino3(r.B, r.cus)))
+        cases.append((_line("wgrad", r.cus, r.B, 84, 2, 9), cv.launch_wgrad(r.B, 9, 84, 2, r.cus)))
+        for l in (1, 2, 3):
+            cases.append((_line("wino", r.cus, 2 * r.B, cv.ENC_H[l]), cv.launch_wino(2 * r.B, cv.ENC_H[l], r.cus)))
+            cases.append((_line("wino", r.cus, r.B, cv.ENC_H[l + 1] + 4), cv.launch_wino(r.B, cv.ENC_H[l + 1] + 4, r.cus)))
+            cases.append((_line("ww", r.cus, r.B, cv.ENC_H[l]), cv.launch_ww(r.B, cv.ENC_H[l], r.cus)))
+            cases.append((_line("wgrad_bf16", r.cus, r.B, cv.ENC_H[l]), cv.launch_wgrad_bf16(r.B, cv.ENC_H[l], r.cus)))
+        for riders in (0, 6):
+            cases.append((_line("conv1_aug", r.cus, r.B, lay=riders), cv.launch_conv1_aug(r.B, riders, r.cus)))
+    got = plan_dump([c[0] for c in cases])
+    assert len(got) == len(cases) > 200
+    for (line, la), (rc, grid, grid_y, r0, r1, r2, merged, _) in zip(cases, got):
+        if la.kernel == cv.EARG:
+            assert rc == -1 and not merged, line
+        else:
+            assert rc == 0 and (grid, grid_y) == (la.grid, 1) and [r0, r1, r2] == (list(la.records or []) + [0] * 3)[:3], (line, la)
+
+
+def test_the_baseline_at_256_is_the_shapes_the_guarded_tests_run():
+    """cu_rows reads the 256-CU launches of the fused aug+conv1 and bf16 kernels off these lines of
+    tests/test_hip_guarded.py: each still stands there, the parametrize lines right in front of their tests"""
+    with open(os.path.join(os.path.dirname(__file__), "test_hip_guarded.py")) as f:
+        src = f.read()
+    for test, line in cu_rows.GUARDED_ROWS.values():
+        at = src.index("def %s(" % test)
+        if line.startswith("@"):
+            assert line in src[src.rindex("\n\n", 0, at):at], test
+        else:
+            assert src.count(line) == 1 and line.split(" = ")[0] in src[src.rindex("\n\n", 0, at):at], test
+    assert cu_rows.AUG_N_AT_256 == (3, 200, 7, 200) and len(cu_rows.BF16_AT_256) == 10

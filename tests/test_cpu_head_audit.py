@@ -52,6 +52,19 @@ def test_each_rows_expected_decisions_are_the_planners(plan_dump):
         assert r.expect <= set(hv.DECISIONS)
 
 
+def test_the_rows_run_under_a_cu_override_keep_their_decisions(plan_dump):
+    """tests/test_hip_cu_counts.py runs the smallest row of each mode at 32 and 8 CUs with the row's own `expect`: the
+    planner takes the same ten decisions there, and leaves fewer split-K records per trunk product than at 256 CUs"""
+    from tests import cu_rows
+    rows = cu_rows.head_rows()
+    assert sorted(r.mode for r in rows) == ["bc", "bf16", "fp32", "per"]
+    at_hw = plan_dump([hv.dump_line(r) for r in rows])
+    for cus in cu_rows.FAMILY_CUS:
+        for r, values, hw in zip(rows, plan_dump([hv.dump_line(r, cus=cus) for r in rows]), at_hw):
+            assert min(values) >= 0 and hv.decisions_of(values) == hv.expected(r), (cus, hv.row_id(r), values)
+            assert 1 < values[5] < hw[5] and 1 < values[6] < hw[6], (cus, hv.row_id(r), values, hw)
+
+
 def test_the_trunk_records_are_the_ones_the_gemm_mirror_predicts(plan_dump):
     """"trunk forward leaves records" read from tests/gemm_variants.py (held to the planner by its own CPU test) agrees
     with the dump, split count included, for the fp32 rows (the mirror restates the fp32 rules only)"""
